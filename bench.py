@@ -16,6 +16,7 @@ time of the K timed steps (max over ranks), inputs resident in HBM.  See DESIGN.
 from __future__ import annotations
 
 import argparse
+import hashlib
 import json
 import os
 import socket
@@ -53,7 +54,12 @@ def parse():
     ap.add_argument("--force-exchange", action="store_true", help="rehearsal: run the N>1 code path (RCCL exchange) with a world of 1")
     ap.add_argument("--list-cap", type=int, default=0, help="views per m_images / m_vimages list = which engine library (16, 32, 64); 0 = the smallest that holds --views")
     ap.add_argument("--scene-cache", default=os.path.join("/tmp", "mvskit_scene_cache"))
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (its counters, the thresholds and a fixed sample of the pool) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -100,7 +106,10 @@ def load_scene(args, rank):
 
     from mvskit_amd import synth
 
-    tag = f"v{args.views}_{args.width}x{args.height}_s{args.seed_stride}"
+    # the cache file is named after the generator's source too: a scene that another version of synth.py made is never read back
+    with open(synth.__file__, "rb") as f:
+        src = hashlib.blake2b(f.read(), digest_size=6).hexdigest()
+    tag = f"v{args.views}_{args.width}x{args.height}_s{args.seed_stride}_{src}"
     path = os.path.join(args.scene_cache, tag + ".npz")
     if os.path.exists(path):
         z = np.load(path)
@@ -111,11 +120,60 @@ def load_scene(args, rank):
     sc.points = None
     sc.normals = None
     if rank == 0:
-        os.makedirs(args.scene_cache, exist_ok=True)
         tmp = path + f".tmp{os.getpid()}.npz"
-        np.savez(tmp, P=sc.P, images=sc.images, centers=sc.centers, seeds=seeds.view(np.uint8))
-        os.replace(tmp, path)
+        try:  # the cache is shared by whoever runs on this host: a directory this user cannot write only costs the regeneration
+            os.makedirs(args.scene_cache, exist_ok=True)
+            np.savez(tmp, P=sc.P, images=sc.images, centers=sc.centers, seeds=seeds.view(np.uint8))
+            os.replace(tmp, path)
+        except OSError as err:
+            log(f"scene cache not written: {err}")
     return sc, seeds
+
+
+# --dump-outputs: at most 64 MB in all; the pool is the bulk of it
+DUMP_POOL_BYTES = 48 << 20
+DUMP_SAMPLE_SEED = 20240607
+COUNTER_NAMES = ("candidates", "prefiltered", "patches", "fail0", "fail1", "inserted", "replaced", "evals", "view_evals", "trimmed")
+
+
+def dump_outputs(out_dir, pool, counters, thresholds, list_cap):
+    """What the last timed step gave its caller, as float32 / float64 .npy files in `out_dir`:
+      counters.npy        float64 [10]  the step's counters in COUNTER_NAMES order (+ filter_removed.npy [4] with --filter)
+      thresholds.npy      float64 [3]   nccThreshold, nccThresholdBefore, m_depth after the step's updateThreshold
+      pool_size.npy       float64 [1]   patches alive after the step
+      pool_rows.npy       float64 [k]   the rows of the downloaded pool (pool order) kept below: all of them, or a fixed seeded
+                                        sample of k when the pool is larger than DUMP_POOL_BYTES allows
+      pool_<field>.npy    the record fields of those rows; images / vimages hold the first list_cap slots, -1 past nimages / nvimages.
+    Returns the names written."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(pool.shape[0])
+    row_bytes = 4 * (4 + 4 + 7 + 2 * list_cap) + 8 + 8  # float32 coord, normal, 7 scalars, lists; float64 id and row
+    k = min(n, DUMP_POOL_BYTES // row_bytes)
+    rows = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+    p = pool[rows]
+    arrays = {
+        "counters": np.array([counters[name] for name in COUNTER_NAMES], dtype=np.float64),
+        "thresholds": np.array(thresholds, dtype=np.float64),
+        "pool_size": np.array([n], dtype=np.float64),
+        "pool_rows": rows.astype(np.float64),
+        "pool_coord": p["coord"].astype(np.float32),
+        "pool_normal": p["normal"].astype(np.float32),
+        "pool_id": p["id"].astype(np.float64),
+    }
+    if "filter_removed" in counters:
+        arrays["filter_removed"] = np.array([counters["filter_removed"][key] for key in ("outside", "exact", "neighbor", "groups")], dtype=np.float64)
+    for name in ("ncc", "dscale", "ascale", "tmp", "nimages", "nvimages", "flags"):
+        arrays["pool_" + name] = p[name].astype(np.float32)
+    slot = np.arange(list_cap)
+    for name, count in (("images", "nimages"), ("vimages", "nvimages")):
+        lists = p[name][:, :list_cap].astype(np.float32)
+        lists[slot[None, :] >= p[count][:, None]] = -1.0
+        arrays["pool_" + name] = lists
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def cpu_baseline(args, sc, seeds, pool_after_iter0, gpu_patches_by_iter):
@@ -396,6 +454,10 @@ def main():
             fstats[k] = fstats.get(k, 0) + v
         if it == 0 and pool_after_iter0 is None and world == 1 and args.cpu_seconds > 0 and not args.filter:
             pool_after_iter0 = e.patches()  # for the CPU baseline's sample B (untimed: after the closing barrier)
+        if args.dump_outputs and s == args.steps - 1 and rank == 0:
+            # untimed, after the closing barrier; every rank holds the same pool, rank 0 writes it with its own counters
+            dumped = dump_outputs(args.dump_outputs, e.patches(), c, e.thresholds(), e.list_cap)
+            log(f"outputs of step {s} written to {args.dump_outputs}: {', '.join(dumped)}")
         if world > 1 and it == SCHEDULE_ITERS - 1:
             # self-validation of a multi-rank run (untimed): every rank hashes the pool it holds at the end of a repetition; the hashes
             # are all-gathered below.  The result does not depend on the sharding, so all ranks must hold the SAME pool -- and `patches`
