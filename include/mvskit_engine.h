@@ -88,6 +88,28 @@ typedef struct mvs_config {
     int64_t max_patches;     /* patch pool capacity (0 = 4 * total cells, at most a sixth of the device's memory per pool buffer) */
 } mvs_config;
 
+/* The refiner of Optim::refinePatch (optim.cpp:470-547).  The reference minimises cost_func over (depth, angle1, angle2) with NLopt
+ * LN_BOBYQA, at most TIME = 500 evaluations (optim.cpp:471) and xtol_rel 1e-7 (optim.cpp:511-524).  mvs_config has no room left, so
+ * the choice is a call of its own, mvs_engine_set_refiner; it takes effect at the next mvs_engine_pass / propagate / probe.
+ *   HALVING   (default, the engine's own search): refine_steps steps of four proposals, 1 + 4 * refine_steps evaluations, ranges
+ *             refine_rd0 / refine_ra0 of mvs_config halved at every step.
+ *   CONVERGED a bounded Nelder-Mead (one four-proposal pass per iteration) run until the tolerance holds or the budget is spent:
+ *             start simplex x, x + refine_rd0 e0, x + refine_ra0 e1, x + refine_ra0 e2 from the clamped start x; the angle coordinates
+ *             of every trial are clamped into [-23.99999, 23.99999] (optim.cpp:496-506), the depth coordinate is unbounded.
+ *             Convergence: every coordinate's spread over the four vertices <= xtol * max(1, |x_best,i|); the patch then takes the
+ *             best vertex.  Budget: every evaluated proposal counts, the first evaluation at the start included (so do the
+ *             evals / view_evals counters); when the next pass would take the count beyond max_evals the run stops as NLopt's
+ *             MAXEVAL_REACHED, which refinePatch treats as a failure (optim.cpp:530-545): the patch keeps its starting coordinate,
+ *             normal and m_ncc, and the sweep carries on to postProcess as after a converged run.
+ * Every rank of a multi-rank job must set the same refiner: the engine does not check it. */
+typedef enum mvs_refine_mode { MVS_REFINE_HALVING = 0, MVS_REFINE_CONVERGED = 1 } mvs_refine_mode;
+typedef struct mvs_refiner {
+    int32_t mode;      /* mvs_refine_mode; HALVING = the search of refine_steps, refine_rd0 / refine_ra0 of mvs_config */
+    int32_t max_evals; /* CONVERGED: cost evaluations per candidate, the first one included; default 500 (optim.cpp:471) */
+    float xtol;        /* CONVERGED: stop when every coordinate's spread over the simplex <= xtol * max(1, |x_best,i|); default 1e-4, not
+                        * the reference's relative 1e-7 (optim.cpp:513): that is about one float32 ulp of the engine's variables */
+} mvs_refiner;
+
 /* One view: PhotoSet::m_photos[i] (image/photoSet.hpp:62).  P is the row-major 3x4 level-0 projection
  * (`CONTOUR` camera text, image/camera.cpp:110-116); rgb is the level-0 image as Image::m_images[0]
  * holds it, interleaved uint8 RGB, H rows of W pixels (image/image.hpp:76); mask is H*W uint8 or NULL. */
@@ -124,6 +146,7 @@ int mvs_device_count(void);
 int mvs_list_cap(void);
 int mvs_patch_bytes(void); /* sizeof(mvs_patch) in this build of the library: 128, or 192 in libmvskit_engine_cap64.so -- a caller checks it against its own */
 void mvs_default_config(mvs_config* cfg); /* Option::Option, option.cpp:19-33 */
+void mvs_default_refiner(mvs_refiner* r); /* HALVING, max_evals 500, xtol 1e-4 */
 
 /* PmMvps::init (pmmvps.cpp:18-68): thresholds, tau = min(2*minImageNum, nviews), maxLevel = level+3.
  * LIMITS -- Option::init (pmmvps/option.cpp:53-116) takes any value; the engine returns MVS_ERR_ARG outside these:
@@ -138,6 +161,9 @@ void mvs_default_config(mvs_config* cfg); /* Option::Option, option.cpp:19-33 */
  * records start at 0x40000000), and 14336 distinct patches / 4064 neighbours around one patch in Optim::check / filterNeighbor. */
 int mvs_engine_create(const mvs_config* cfg, mvs_engine** out);
 int mvs_engine_destroy(mvs_engine* e);
+/* the refiner of every later pass / propagate / probe (see mvs_refiner); MVS_ERR_ARG on an unknown mode, max_evals outside 5..4096,
+ * or xtol not finite or <= 0.  An engine that never calls it runs HALVING. */
+int mvs_engine_set_refiner(mvs_engine* e, const mvs_refiner* r);
 
 /* PhotoSet::init + Image::buildImagePyramid + Camera::updateCamera + Optim::setAxesScales +
  * PatchManager::init: uploads level 0, builds pyramids, cameras and grids on the device. */
@@ -241,10 +267,14 @@ int mvs_engine_depth_normal_map(mvs_engine* e, int view, int kind, float* depth,
 typedef enum mvs_probe_op {
     MVS_PROBE_NCC = 0,        /* PatchManager::computeNcc      -> out_f[n] */
     MVS_PROBE_PREPROCESS = 1, /* Optim::preProcess             -> out_rec[n], out_i[n] = flag */
-    MVS_PROBE_REFINE = 2,     /* Optim::refinePatch            -> out_rec[n]; key = (0,0,i,0) */
+    MVS_PROBE_REFINE = 2,     /* Optim::refinePatch            -> out_rec[n]; key = (0,0,i,0); with the engine's refiner */
     MVS_PROBE_POSTPROCESS = 3,/* Optim::postProcess            -> out_rec[n], out_i[n] = flag */
     MVS_PROBE_COST = 4,       /* Optim::cost_func at encode(p) -> out_f[n] */
-    MVS_PROBE_MATH = 5        /* in_f[n] -> out_f[5n]: sin, cos, asin, acos, atan of each input */
+    MVS_PROBE_MATH = 5,       /* in_f[n] -> out_f[5n]: sin, cos, asin, acos, atan of each input */
+    MVS_PROBE_REFINE_X = 6    /* Optim::refinePatch (optim.cpp:480-547) with the CONVERGED refiner (MVS_ERR_STATE under HALVING) -> out_rec[n]
+                               * as MVS_PROBE_REFINE; out_f[4n] = the final (x0, x1, x2) -- the best vertex, in the input's encode frame --
+                               * and the cost there; out_i[n] = cost evaluations used, negated when the budget ran out (out_rec[i] is
+                               * then the input) */
 } mvs_probe_op;
 int mvs_engine_probe(mvs_engine* e, int op, int64_t n, const mvs_patch* in_rec, const float* in_f,
                      mvs_patch* out_rec, float* out_f, int32_t* out_i);

@@ -1331,19 +1331,20 @@ DEV double cost_of_group(const DParams& prm, const WaveCtx& wc, unsigned okm, fl
     if (denom < minimum - 1) return 2.0;
     return ans / (double)denom;
 }
+// rows (four proposals): bit g = proposal g is evaluated; a proposal left out samples nothing, costs 2 and is not counted.
 DEV void cost_func4(const DParams& prm, WaveCtx& wc, const RefineCtx& rc, int imgx, int n, bool four, float x0, float x1, float x2,
-                    double (&fv)[4], float* piv = nullptr, const ClsConst* cc = nullptr) {
+                    double (&fv)[4], float* piv = nullptr, const ClsConst* cc = nullptr, unsigned rows = 0xFu) {
     F4 coord, normal, px, py;
     decode(prm, rc, x0, x1, x2, coord, normal);
     get_paxes(prm, prm.views + rc.ref, coord, normal, px, py);
     const int sz = min(prm.tau, n);
     const int minimum = min(prm.minImageNum, sz);
     const int g = wc.lane >> 4, i = wc.lane & 15;
-    const Frame f = make_frame(prm, coord, px, py, normal, imgx, g < (four ? 4 : 1) && i < sz);
+    const Frame f = make_frame(prm, coord, px, py, normal, imgx, (four ? ((rows >> g) & 1u) != 0u : g < 1) && i < sz);
     float incc_l;
     fv[1] = fv[2] = fv[3] = 2.0;
     if (four) {
-        wc.evals += 4;
+        wc.evals += (unsigned)__popc(rows);
         unsigned okm[4];
         eval_steps4(prm, wc, *cc, f, sz, okm, incc_l);
         const float val_l = robustincc(incc_l);
@@ -1426,6 +1427,123 @@ STAGE void refine_patch(const DParams& prm, WaveCtx& wc, Cand& c, uint32_t k0, u
     c.normal.w = 0.0f;
     if (w_out) *w_out = w;
     else c.ncc = 1.0f - unrobustincc(compute_incc(prm, wc, c.coord, c.normal, c.img, c.nimg, w, 1));
+}
+
+// Optim::refinePatch run to convergence (mvs_refiner CONVERGED): a bounded Nelder-Mead over the same three
+// variables.  A simplex in three variables has four vertices, one per proposal row: row g holds vertex g (vx0..vx2, its cost vf)
+// and every decision is taken on values read back from lanes 0, 16, 32, 48 -- wave-uniform.  One pass per iteration evaluates
+// the four trials for the worst vertex w: reflection, expansion, outside and inside contraction, c + k d with k = 1, 2, 1/2, -1/2,
+// c = ((v_a + v_b) + v_c) / 3 over the other three vertices in ascending slot order, d = c - v_w (float32, no fused operations;
+// tests/refiner_restatement.py restates it in this order).  If no trial is accepted the other three vertices shrink towards the
+// best one, v_j = v_b + 0.5 (v_j - v_b): one more pass, three rows.  Angle coordinates are clamped to the bounds of
+// optim.cpp:496-506 after every step.  Stop: every coordinate's spread over the simplex <= xtol * max(1, |x_best,i|) (converged),
+// or the next pass would take the evaluations beyond max_evals (NLopt's MAXEVAL_REACHED: the reference counts that a failure and
+// leaves the patch as it was, optim.cpp:530-545).  Returns the evaluations made, negated when the budget ran out; x_out / f_out:
+// the best vertex and its cost.  w_out as refine_patch.
+STAGE int refine_patch_simplex(const DParams& prm, WaveCtx& wc, Cand& c, int max_evals, float xtol, float* w_out = nullptr,
+                               float* x_out = nullptr, double* f_out = nullptr) {
+    RefineCtx rc;
+    rc.center = c.coord;
+    rc.ref = rli(c.img, 0);
+    rc.ray = nrm4(sub4(c.coord, ld4((prm.views + rc.ref)->center)));
+    rc.dscale = c.dscale;
+    rc.ascale = prm.ascaleConst;
+    const float w = compute_weights(prm, wc, c.coord, c.normal, c.img, c.nimg);
+    const int imgx = __shfl(c.img, wc.lane & 15);
+    float x[3];
+    encode(prm, rc, c.coord, c.normal, x);
+    const float amin = -23.99999f, amax = 23.99999f;
+    x[1] = fmaxf(fminf(x[1], amax), amin);
+    x[2] = fmaxf(fminf(x[2], amax), amin);
+    double fv[4];
+    float piv[3] = {128.0f, 128.0f, 128.0f};  // as refine_patch: the first evaluation publishes the class-lane pivots
+    cost_func4(prm, wc, rc, imgx, c.nimg, false, x[0], x[1], x[2], fv, piv);
+    __syncthreads();
+    if (wc.lane < 16) mvs_dyn_lds4[MVS_PIVOT_LDS4 + wc.lane] = make_float4(piv[0], piv[1], piv[2], 0.0f);
+    __syncthreads();
+    const double f0 = fv[0];
+    const ClsConst cc = wc.cc;
+    const int g = wc.lane >> 4;
+    // the start simplex: x, x + rd0 e0, x + ra0 e1, x + ra0 e2 (rows 1..3 in one pass, row 0 idle)
+    float vx0 = g == 1 ? x[0] + prm.rd0 : x[0];
+    float vx1 = g == 2 ? fmaxf(fminf(x[1] + prm.ra0, amax), amin) : x[1];
+    float vx2 = g == 3 ? fmaxf(fminf(x[2] + prm.ra0, amax), amin) : x[2];
+    cost_func4(prm, wc, rc, imgx, c.nimg, true, vx0, vx1, vx2, fv, nullptr, &cc, 0xEu);
+    double vf = g == 0 ? f0 : (g == 1 ? fv[1] : (g == 2 ? fv[2] : fv[3]));
+    int evals = 4;
+    bool ok = false;
+    int b = 0;
+    for (;;) {
+        double f[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) f[j] = rld(vf, 16 * j);
+        b = 0;
+        int wv = 0;  // best: lowest cost, lowest slot on a tie; worst: highest cost, highest slot on a tie
+#pragma unroll
+        for (int j = 1; j < 4; ++j) {
+            if (f[j] < (b == 1 ? f[1] : (b == 2 ? f[2] : f[0]))) b = j;
+            if (f[j] >= (wv == 1 ? f[1] : (wv == 2 ? f[2] : f[0]))) wv = j;
+        }
+        const float b0 = rlf(vx0, 16 * b), b1 = rlf(vx1, 16 * b), b2 = rlf(vx2, 16 * b);
+        {
+            float lo0 = rlf(vx0, 0), hi0 = lo0, lo1 = rlf(vx1, 0), hi1 = lo1, lo2 = rlf(vx2, 0), hi2 = lo2;
+#pragma unroll
+            for (int j = 1; j < 4; ++j) {
+                const float a0 = rlf(vx0, 16 * j), a1 = rlf(vx1, 16 * j), a2 = rlf(vx2, 16 * j);
+                lo0 = fminf(lo0, a0); hi0 = fmaxf(hi0, a0);
+                lo1 = fminf(lo1, a1); hi1 = fmaxf(hi1, a1);
+                lo2 = fminf(lo2, a2); hi2 = fmaxf(hi2, a2);
+            }
+            if (hi0 - lo0 <= xtol * fmaxf(1.0f, fabsf(b0)) && hi1 - lo1 <= xtol * fmaxf(1.0f, fabsf(b1)) &&
+                hi2 - lo2 <= xtol * fmaxf(1.0f, fabsf(b2))) { ok = true; break; }
+        }
+        if (evals + 4 > max_evals) break;
+        const double fb = rld(vf, 16 * b), fw = rld(vf, 16 * wv);
+        double fsw = wv == 0 ? f[1] : f[0];  // the highest cost of the other three
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (j != wv) fsw = fmax(fsw, f[j]);
+        const int r0 = wv == 0 ? 1 : 0, r1 = wv <= 1 ? 2 : 1, r2 = wv <= 2 ? 3 : 2;
+        const float c0 = ((rlf(vx0, 16 * r0) + rlf(vx0, 16 * r1)) + rlf(vx0, 16 * r2)) / 3.0f;
+        const float c1 = ((rlf(vx1, 16 * r0) + rlf(vx1, 16 * r1)) + rlf(vx1, 16 * r2)) / 3.0f;
+        const float c2 = ((rlf(vx2, 16 * r0) + rlf(vx2, 16 * r1)) + rlf(vx2, 16 * r2)) / 3.0f;
+        const float d0 = c0 - rlf(vx0, 16 * wv), d1 = c1 - rlf(vx1, 16 * wv), d2 = c2 - rlf(vx2, 16 * wv);
+        const float k = g == 0 ? 1.0f : (g == 1 ? 2.0f : (g == 2 ? 0.5f : -0.5f));  // this row's trial
+        const float t0 = c0 + k * d0;
+        const float t1 = fmaxf(fminf(c1 + k * d1, amax), amin);
+        const float t2 = fmaxf(fminf(c2 + k * d2, amax), amin);
+        cost_func4(prm, wc, rc, imgx, c.nimg, true, t0, t1, t2, fv, nullptr, &cc);
+        evals += 4;
+        int acc = -1;  // Nelder-Mead's sequential rules on the four costs
+        if (fv[0] < fb) acc = fv[1] < fv[0] ? 1 : 0;
+        else if (fv[0] < fsw) acc = 0;
+        else if (fv[0] < fw) acc = fv[2] <= fv[0] ? 2 : -1;
+        else acc = fv[3] < fw ? 3 : -1;
+        if (acc >= 0) {
+            const float a0 = rlf(t0, 16 * acc), a1 = rlf(t1, 16 * acc), a2 = rlf(t2, 16 * acc);
+            const double fa = acc == 0 ? fv[0] : (acc == 1 ? fv[1] : (acc == 2 ? fv[2] : fv[3]));
+            if (g == wv) { vx0 = a0; vx1 = a1; vx2 = a2; vf = fa; }
+            continue;
+        }
+        if (evals + 3 > max_evals) break;
+        if (g != b) {  // shrink towards the best vertex
+            vx0 = b0 + 0.5f * (vx0 - b0);
+            vx1 = fmaxf(fminf(b1 + 0.5f * (vx1 - b1), amax), amin);
+            vx2 = fmaxf(fminf(b2 + 0.5f * (vx2 - b2), amax), amin);
+        }
+        cost_func4(prm, wc, rc, imgx, c.nimg, true, vx0, vx1, vx2, fv, nullptr, &cc, 0xFu & ~(1u << b));
+        evals += 3;
+        if (g != b) vf = g == 0 ? fv[0] : (g == 1 ? fv[1] : (g == 2 ? fv[2] : fv[3]));
+    }
+    const float xb0 = rlf(vx0, 16 * b), xb1 = rlf(vx1, 16 * b), xb2 = rlf(vx2, 16 * b);
+    if (x_out) { x_out[0] = xb0; x_out[1] = xb1; x_out[2] = xb2; }
+    if (f_out) *f_out = rld(vf, 16 * b);
+    if (ok) {
+        decode(prm, rc, xb0, xb1, xb2, c.coord, c.normal);
+        c.normal.w = 0.0f;
+        if (!w_out) c.ncc = 1.0f - unrobustincc(compute_incc(prm, wc, c.coord, c.normal, c.img, c.nimg, w, 1));
+    }
+    if (w_out) *w_out = w;
+    return ok ? evals : -evals;
 }
 
 // ------------------------------------------------------------------ post-processing

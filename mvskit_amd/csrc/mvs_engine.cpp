@@ -143,6 +143,7 @@ struct Range {
 
 struct mvs_engine {
     mvs_config cfg{};
+    mvs_refiner refiner{MVS_REFINE_HALVING, 500, 1e-4f};  // mvs_engine_set_refiner
     DParams prm{};
     hipStream_t stream = nullptr;
     bool have_views = false;
@@ -215,6 +216,10 @@ struct mvs_engine {
 namespace {
 
 int64_t total_cells_of(const mvs_engine* e) { return e->total_cells; }
+
+RefineSel refine_sel(const mvs_engine* e) {
+    return RefineSel{e->refiner.mode == MVS_REFINE_CONVERGED ? 1 : 0, e->refiner.max_evals, e->refiner.xtol};
+}
 
 void derive_params(mvs_engine* e) {  // PmMvps::init, pmmvps.cpp:32-36,54-67
     const mvs_config& c = e->cfg;
@@ -706,6 +711,22 @@ int mvs_device_count(void) {
     return n;
 }
 
+void mvs_default_refiner(mvs_refiner* r) {  // HALVING; CONVERGED's budget as Optim::refinePatch (optim.cpp:471)
+    if (!r) return;
+    r->mode = MVS_REFINE_HALVING; r->max_evals = 500; r->xtol = 1e-4f;
+}
+
+int mvs_engine_set_refiner(mvs_engine* e, const mvs_refiner* r) {
+    if (!e || !r) { g_err = "mvs_engine_set_refiner: null argument"; return MVS_ERR_ARG; }
+    if ((r->mode != MVS_REFINE_HALVING && r->mode != MVS_REFINE_CONVERGED) || r->max_evals < 5 || r->max_evals > 4096 ||
+        !std::isfinite(r->xtol) || !(r->xtol > 0.0f)) {
+        g_err = "mvs_engine_set_refiner: unknown mode, max_evals outside 5..4096, or xtol not finite and > 0";
+        return MVS_ERR_ARG;
+    }
+    e->refiner = *r;
+    return MVS_OK;
+}
+
 void mvs_default_config(mvs_config* c) {  // Option::Option, option.cpp:19-33
     memset(c, 0, sizeof *c);
     c->level = 1; c->csize = 2; c->wsize = 7; c->minImageNum = 3; c->max_propag = 2;
@@ -1095,14 +1116,15 @@ static int pass_impl(mvs_engine* e, int iter, int pass, mvs_counters* out) {
     HIPCHK(hipMemsetAsync(e->counters.p, 0, MVS_COUNTER_SLOTS * sizeof(DCounters), st));
     HIPCHK(hipMemsetAsync(e->error_flag.p, 0, sizeof(int32_t), st));
     const DParams p = current_params(e);
-    mvsk_sweep(p, a, st);
+    const RefineSel rs = refine_sel(e);
+    mvsk_sweep(p, a, rs, st);
     e->pass_retried = 0;
     if (want_vgrid(e)) {  // cells whose Optim::check outgrew the wave's LDS run again on the second tier (normally none)
         int32_t nretry = 0;
         HIPCHK(hipMemcpyAsync(&nretry, a.nretry, sizeof nretry, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         e->pass_retried = nretry;
-        if (nretry > 0) { mvsk_sweep_retry(p, a, nretry, st); e->retried_cells += nretry; }
+        if (nretry > 0) { mvsk_sweep_retry(p, a, nretry, rs, st); e->retried_cells += nretry; }
     }
     HIPCHK(hipEventRecord(e->ev[2], st));
     DCounters hc;
@@ -1616,12 +1638,14 @@ int mvs_engine_depth_normal_map(mvs_engine* e, int view, int kind, float* depth,
 }
 
 int mvs_engine_probe(mvs_engine* e, int op, int64_t n, const mvs_patch* in_rec, const float* in_f, mvs_patch* out_rec, float* out_f, int32_t* out_i) {
-    if (!e || !e->have_views || n < 0 || op < 0 || op > 5) { g_err = "mvs_engine_probe: bad argument / views not set"; return MVS_ERR_ARG; }
+    if (!e || !e->have_views || n < 0 || op < 0 || op > 6) { g_err = "mvs_engine_probe: bad argument / views not set"; return MVS_ERR_ARG; }
+    const RefineSel rs = refine_sel(e);
+    if (op == MVS_PROBE_REFINE_X && !rs.simplex) { g_err = "mvs_engine_probe: MVS_PROBE_REFINE_X needs the CONVERGED refiner"; return MVS_ERR_STATE; }
     if (n == 0) return MVS_OK;
     HIPCHK(hipSetDevice(e->cfg.device));
     hipStream_t st = e->stream;
     if (op == MVS_PROBE_POSTPROCESS && e->prm.depth > 0) if (int r = build_index(e, nullptr)) return r;  // setVImagesVGrids reads m_dpgrids
-    const int64_t nf_out = op == MVS_PROBE_MATH ? 5 * n : n;
+    const int64_t nf_out = op == MVS_PROBE_MATH ? 5 * n : ((op == MVS_PROBE_REFINE || op == MVS_PROBE_REFINE_X) && rs.simplex ? 4 * n : n);
     if (e->tmp_rec_in.ensure(n) || e->tmp_rec_out.ensure(n) || e->tmp_f_in.ensure(n) || e->tmp_f_out.ensure(nf_out) || e->tmp_i.ensure(n + 1)) return MVS_ERR_HIP;
     if (op == MVS_PROBE_MATH) {
         if (!in_f || !out_f) return MVS_ERR_ARG;
@@ -1632,10 +1656,10 @@ int mvs_engine_probe(mvs_engine* e, int op, int64_t n, const mvs_patch* in_rec, 
     }
     HIPCHK(hipMemsetAsync(e->tmp_i.p, 0, (size_t)(n + 1) * sizeof(int32_t), st));
     const DParams p = current_params(e);
-    mvsk_probe(p, op, n, e->tmp_rec_in.p, e->tmp_f_in.p, e->tmp_rec_out.p, e->tmp_f_out.p, e->tmp_i.p, st);
-    if (out_rec && (op == MVS_PROBE_PREPROCESS || op == MVS_PROBE_REFINE || op == MVS_PROBE_POSTPROCESS))
+    mvsk_probe(p, op, n, e->tmp_rec_in.p, e->tmp_f_in.p, e->tmp_rec_out.p, e->tmp_f_out.p, e->tmp_i.p, rs, st);
+    if (out_rec && (op == MVS_PROBE_PREPROCESS || op == MVS_PROBE_REFINE || op == MVS_PROBE_POSTPROCESS || op == MVS_PROBE_REFINE_X))
         HIPCHK(hipMemcpyAsync(out_rec, e->tmp_rec_out.p, (size_t)n * sizeof(mvs_patch), hipMemcpyDeviceToHost, st));
-    if (out_f && (op == MVS_PROBE_NCC || op == MVS_PROBE_COST || op == MVS_PROBE_MATH))
+    if (out_f && (op == MVS_PROBE_NCC || op == MVS_PROBE_COST || op == MVS_PROBE_MATH || op == MVS_PROBE_REFINE_X))
         HIPCHK(hipMemcpyAsync(out_f, e->tmp_f_out.p, (size_t)nf_out * sizeof(float), hipMemcpyDeviceToHost, st));
     if (out_i) HIPCHK(hipMemcpyAsync(out_i, e->tmp_i.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));

@@ -22,9 +22,12 @@ void mvsk_depth_mark_dirty(const DParams& prm, const uint8_t* kill, unsigned lon
 void mvsk_best_ncc_map(const DParams& prm, int view, unsigned long long* best, hipStream_t st);
 void mvsk_map_extract(const DParams& prm, int view, int kind, const unsigned long long* sel, float* depth, float* normal, int32_t* ids, int ncells, hipStream_t st);
 void mvsk_fill_ncc(const DParams& prm, unsigned long long* evals, hipStream_t st);
+// the refiner of a sweep / refine probe (mvs_engine_set_refiner): simplex = 0 is the halving search of the default kernels,
+// simplex = 1 the CONVERGED refiner (k_sweep_simplex, k_sweep_retry_simplex, k_probe_refine_simplex) with these two arguments
+struct RefineSel { int simplex; int max_evals; float xtol; };
 size_t mvsk_sweep_lds_bytes(const DParams& prm);
-void mvsk_sweep(const DParams& prm, const SweepArgs& a, hipStream_t st);
-void mvsk_sweep_retry(const DParams& prm, const SweepArgs& a, int nretry, hipStream_t st);
+void mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hipStream_t st);
+void mvsk_sweep_retry(const DParams& prm, const SweepArgs& a, int nretry, const RefineSel& rs, hipStream_t st);
 void mvsk_job_work(const DParams& prm, const SweepArgs& a, int mode, int shift, int32_t* work, hipStream_t st);
 void mvsk_job_cuts(const int32_t* scan, int64_t njobs, int n, int32_t* cuts, hipStream_t st);
 void mvsk_commit_count(const SweepArgs& a, int32_t* cnt, hipStream_t st);
@@ -47,4 +50,6 @@ void mvsk_groups_literal_edges(const DParams& prm, int* parent, int* size, int* 
 void mvsk_gather_i32(const int32_t* src, const int32_t* idx, int32_t* out, int64_t n, hipStream_t st);
 void mvsk_scatter_i32(int32_t* dst, const int32_t* idx, const int32_t* val, int64_t n, hipStream_t st);
 void mvsk_groups_kill(const DParams& prm, const int* parent, const int* size, int threshold, uint8_t* kill, hipStream_t st);
-void mvsk_probe(const DParams& prm, int op, int64_t n, const DPatch* in, const float* in_f, DPatch* out, float* out_f, int32_t* out_i, hipStream_t st);
+// op 6 needs rs.simplex (the engine checks it); op 2 follows rs
+void mvsk_probe(const DParams& prm, int op, int64_t n, const DPatch* in, const float* in_f, DPatch* out, float* out_f, int32_t* out_i, const RefineSel& rs,
+                hipStream_t st);

@@ -442,8 +442,11 @@ __global__ void k_job_cuts(const int32_t* __restrict__ scan, int64_t njobs, int 
 #ifndef MVS_XCD_CHUNK
 #define MVS_XCD_CHUNK 128
 #endif
-template <bool BIG>
-DEV void sweep_cell(const DParams& prm, const SweepArgs& a, const int64_t job, int* s_scratch, float* s_texs, int* big_table) {
+// SIMPLEX = true: the refinement is refine_patch_simplex with max_evals / xtol (k_sweep_simplex, k_sweep_retry_simplex: the CONVERGED
+// refiner of mvs_engine_set_refiner); the default kernels keep the halving search and never see the two arguments.
+template <bool BIG, bool SIMPLEX = false>
+DEV void sweep_cell(const DParams& prm, const SweepArgs& a, const int64_t job, int* s_scratch, float* s_texs, int* big_table,
+                    int max_evals = 0, float xtol = 0.0f) {
 #ifdef MVS_STAGE_TIMING
     unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const unsigned long long st_begin = ST_NOW();
@@ -540,7 +543,8 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, const int64_t job, i
                 ST_ADD(2, st_t)
                 if (pre_r == -1) { ++n_f0; continue; }
                 float keep_w;  // computeWeights of refinePatch, for the m_ncc postProcess takes from its first evaluation
-                refine_patch(prm, wc, c, k0, k1, k2, k3, &keep_w);
+                if constexpr (SIMPLEX) (void)refine_patch_simplex(prm, wc, c, max_evals, xtol, &keep_w);
+                else refine_patch(prm, wc, c, k0, k1, k2, k3, &keep_w);
                 ST_ADD(3, st_t)
                 const int post_r = post_process(prm, wc, s_scratch, s_texs, tstride, c, keep_w, true);
                 ST_ADD(4, st_t)
@@ -620,6 +624,18 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, const int64_t job, i
     }
 }
 
+// the job of this block in k_sweep_simplex: k_sweep's job order, restated below (k_sweep keeps it inline: through this helper it
+// spills one SGPR more)
+DEV int64_t sweep_job(const SweepArgs& a) {
+#if MVS_XCD_CHUNK > 0
+    const int64_t bi = blockIdx.x >> 3;
+    const int64_t job = a.job_lo + (bi / MVS_XCD_CHUNK) * (8 * MVS_XCD_CHUNK) + (int64_t)(blockIdx.x & 7u) * MVS_XCD_CHUNK + (bi % MVS_XCD_CHUNK);
+#else
+    const int64_t chunk = (a.job_hi - a.job_lo + 7) / 8;
+    const int64_t job = a.job_lo + (int64_t)(blockIdx.x & 7u) * chunk + (blockIdx.x >> 3);
+#endif
+    return job;
+}
 __global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep(DParams prm, SweepArgs a) {
     __shared__ int s_scratch[192];
     extern __shared__ float s_texs[];
@@ -638,6 +654,13 @@ __global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep(DParams prm, Swee
     if (job >= a.job_hi) return;
     sweep_cell<false>(prm, a, job, s_scratch, s_texs, nullptr);
 }
+__global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep_simplex(DParams prm, SweepArgs a, int max_evals, float xtol) {
+    __shared__ int s_scratch[192];
+    extern __shared__ float s_texs[];
+    const int64_t job = sweep_job(a);
+    if (job >= a.job_hi) return;
+    sweep_cell<false, true>(prm, a, job, s_scratch, s_texs, nullptr, max_evals, xtol);
+}
 // the second tier: block b runs the cells retry_jobs[b], retry_jobs[b + gridDim.x], ... with big_tables slot b
 __global__ __launch_bounds__(64, 1) void k_sweep_retry(DParams prm, SweepArgs a, int nretry) {
     __shared__ int s_scratch[192];
@@ -646,6 +669,15 @@ __global__ __launch_bounds__(64, 1) void k_sweep_retry(DParams prm, SweepArgs a,
     for (int k = blockIdx.x; k < nretry; k += gridDim.x) {
         __syncthreads();
         sweep_cell<true>(prm, a, (int64_t)a.retry_jobs[k], s_scratch, s_texs, big_table);
+    }
+}
+__global__ __launch_bounds__(64, 1) void k_sweep_retry_simplex(DParams prm, SweepArgs a, int nretry, int max_evals, float xtol) {
+    __shared__ int s_scratch[192];
+    extern __shared__ float s_texs[];
+    int* big_table = a.big_tables + (size_t)blockIdx.x * MVS_FILTER2_HASH_CAP;
+    for (int k = blockIdx.x; k < nretry; k += gridDim.x) {
+        __syncthreads();
+        sweep_cell<true, true>(prm, a, (int64_t)a.retry_jobs[k], s_scratch, s_texs, big_table, max_evals, xtol);
     }
 }
 
@@ -1189,6 +1221,24 @@ __global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_probe_refine(DParams pr
     refine_patch(prm, wc, c, 0u, 0u, (uint32_t)i, 0u);
     store_cand(out + i, wc, c, 1, (int)i);
 }
+// refinePatch with the CONVERGED refiner (probe ops 2 and 6): out_f[4 i ..] = the best vertex and its cost, out_i[i] = evaluations
+// (negative: the budget ran out and the record is the input)
+__global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_probe_refine_simplex(DParams prm, int64_t n, const DPatch* __restrict__ in, DPatch* __restrict__ out,
+                                                                              float* __restrict__ out_f, int32_t* __restrict__ out_i, int max_evals, float xtol) {
+    const int64_t i = blockIdx.x;
+    if (i >= n) return;
+    WaveCtx wc = make_wave_ctx(prm);
+    Cand c;
+    load_cand(in + i, wc, c);
+    float x[3];
+    double f;
+    const int r = refine_patch_simplex(prm, wc, c, max_evals, xtol, nullptr, x, &f);
+    store_cand(out + i, wc, c, 1, (int)i);
+    if (wc.lane == 0) {
+        out_f[4 * i] = x[0]; out_f[4 * i + 1] = x[1]; out_f[4 * i + 2] = x[2]; out_f[4 * i + 3] = (float)f;
+        out_i[i] = r;
+    }
+}
 
 // =================================================================== host-callable launchers
 static inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
@@ -1254,7 +1304,7 @@ size_t mvsk_sweep_lds_bytes(const DParams& prm) {
     const size_t need = texs > chk ? texs : chk;
     return need > (size_t)MVS_FRAME_LDS_BYTES ? need : (size_t)MVS_FRAME_LDS_BYTES;  // the frames + pivots of a refinement step
 }
-void mvsk_sweep(const DParams& prm, const SweepArgs& a, hipStream_t st) {
+void mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hipStream_t st) {
     const int64_t nloc = a.job_hi - a.job_lo;
     if (nloc <= 0) return;
     const int64_t chunk = (nloc + 7) / 8;
@@ -1265,7 +1315,8 @@ void mvsk_sweep(const DParams& prm, const SweepArgs& a, hipStream_t st) {
 #else
     const int64_t nblocks = chunk * 8;
 #endif
-    hipLaunchKernelGGL(k_sweep, dim3((unsigned)nblocks), dim3(64), mvsk_sweep_lds_bytes(prm) + pad, st, prm, a);
+    if (rs.simplex) hipLaunchKernelGGL(k_sweep_simplex, dim3((unsigned)nblocks), dim3(64), mvsk_sweep_lds_bytes(prm) + pad, st, prm, a, rs.max_evals, rs.xtol);
+    else hipLaunchKernelGGL(k_sweep, dim3((unsigned)nblocks), dim3(64), mvsk_sweep_lds_bytes(prm) + pad, st, prm, a);
 }
 void mvsk_job_work(const DParams& prm, const SweepArgs& a, int mode, int shift, int32_t* work, hipStream_t st) {
     if (a.njobs > 0) hipLaunchKernelGGL(k_job_work, dim3(nblk(a.njobs, 256)), dim3(256), 0, st, prm, a, mode, shift, work);
@@ -1273,9 +1324,11 @@ void mvsk_job_work(const DParams& prm, const SweepArgs& a, int mode, int shift, 
 void mvsk_job_cuts(const int32_t* scan, int64_t njobs, int n, int32_t* cuts, hipStream_t st) {
     if (njobs > 0) hipLaunchKernelGGL(k_job_cuts, dim3(nblk(njobs, 256)), dim3(256), 0, st, scan, njobs, n, cuts);
 }
-void mvsk_sweep_retry(const DParams& prm, const SweepArgs& a, int nretry, hipStream_t st) {
+void mvsk_sweep_retry(const DParams& prm, const SweepArgs& a, int nretry, const RefineSel& rs, hipStream_t st) {
     if (nretry <= 0) return;
-    hipLaunchKernelGGL(k_sweep_retry, dim3((unsigned)std::min(nretry, MVS_BIG_SLOTS)), dim3(64), mvsk_sweep_lds_bytes(prm), st, prm, a, nretry);
+    const dim3 grid((unsigned)std::min(nretry, MVS_BIG_SLOTS));
+    if (rs.simplex) hipLaunchKernelGGL(k_sweep_retry_simplex, grid, dim3(64), mvsk_sweep_lds_bytes(prm), st, prm, a, nretry, rs.max_evals, rs.xtol);
+    else hipLaunchKernelGGL(k_sweep_retry, grid, dim3(64), mvsk_sweep_lds_bytes(prm), st, prm, a, nretry);
 }
 void mvsk_commit_count(const SweepArgs& a, int32_t* cnt, hipStream_t st) { hipLaunchKernelGGL(k_commit_count, dim3(nblk(a.njobs, 256)), dim3(256), 0, st, a, cnt); }
 void mvsk_commit_copy(const SweepArgs& a, const int32_t* base, DPatch* dst, int64_t dst_cap, int32_t* per_view, int keep_key, hipStream_t st) {
@@ -1365,7 +1418,12 @@ void mvsk_scatter_i32(int32_t* dst, const int32_t* idx, const int32_t* val, int6
 void mvsk_groups_kill(const DParams& prm, const int* parent, const int* size, int threshold, uint8_t* kill, hipStream_t st) {
     if (prm.pool_n > 0) hipLaunchKernelGGL(k_groups_kill, dim3(nblk(prm.pool_n, 256)), dim3(256), 0, st, prm, parent, size, threshold, kill);
 }
-void mvsk_probe(const DParams& prm, int op, int64_t n, const DPatch* in, const float* in_f, DPatch* out, float* out_f, int32_t* out_i, hipStream_t st) {
+void mvsk_probe(const DParams& prm, int op, int64_t n, const DPatch* in, const float* in_f, DPatch* out, float* out_f, int32_t* out_i, const RefineSel& rs,
+                hipStream_t st) {
+    if (n > 0 && (op == 2 || op == 6) && rs.simplex) {
+        hipLaunchKernelGGL(k_probe_refine_simplex, dim3((unsigned)n), dim3(64), MVS_FRAME_LDS_BYTES, st, prm, n, in, out, out_f, out_i, rs.max_evals, rs.xtol);
+        return;
+    }
     if (n > 0 && op == 2) { hipLaunchKernelGGL(k_probe_refine, dim3((unsigned)n), dim3(64), MVS_FRAME_LDS_BYTES, st, prm, n, in, out); return; }
     if (n > 0) hipLaunchKernelGGL(k_probe, dim3((unsigned)n), dim3(64), mvsk_sweep_lds_bytes(prm), st, prm, op, n, in, in_f, out, out_f, out_i);
 }

@@ -12,7 +12,8 @@ from . import build
 from . import synth
 from .synth import MAX_IMAGES, PATCH_DTYPE  # noqa: F401  (PATCH_DTYPE mirrors mvs_patch at 32 list slots)
 
-PROBE_NCC, PROBE_PREPROCESS, PROBE_REFINE, PROBE_POSTPROCESS, PROBE_COST, PROBE_MATH = range(6)
+PROBE_NCC, PROBE_PREPROCESS, PROBE_REFINE, PROBE_POSTPROCESS, PROBE_COST, PROBE_MATH, PROBE_REFINE_X = range(7)
+REFINE_HALVING, REFINE_CONVERGED = 0, 1  # mvs_refine_mode
 
 #: every symbol include/mvskit_engine.h declares
 EXPORTS = [
@@ -24,6 +25,7 @@ EXPORTS = [
     "mvs_engine_commit_local", "mvs_engine_depth_normal_map", "mvs_engine_probe", "mvs_engine_last_timing",
     "mvs_engine_filter", "mvs_comm_unique_id", "mvs_engine_comm_init", "mvs_engine_comm_attach", "mvs_engine_comm_release",
     "mvs_engine_exchange", "mvs_list_cap", "mvs_engine_filter_stats", "mvs_patch_bytes", "mvs_engine_reserve", "mvs_engine_comm_info",
+    "mvs_default_refiner", "mvs_engine_set_refiner",
 ]
 
 
@@ -35,6 +37,11 @@ class Config(C.Structure):
                 ("enable_check", C.c_int32), ("view_begin", C.c_int32), ("view_stride", C.c_int32),
                 ("device", C.c_int32), ("view_propagation", C.c_int32), ("shard_index", C.c_int32), ("shard_count", C.c_int32),
                 ("literal_groups", C.c_int32), ("max_patches", C.c_int64)]
+
+
+class Refiner(C.Structure):
+    """mvs_refiner: which refiner Optim::refinePatch runs (mvs_engine_set_refiner)."""
+    _fields_ = [("mode", C.c_int32), ("max_evals", C.c_int32), ("xtol", C.c_float)]
 
 
 class ViewDesc(C.Structure):
@@ -124,6 +131,10 @@ def load_library(cap32: bool = False, cap: int = 0):
     L.mvs_patch_bytes.restype = C.c_int
     L.mvs_engine_reserve.argtypes = [vp, C.c_int64]
     L.mvs_engine_filter_stats.argtypes = [vp, C.POINTER(FilterStats)]
+    if hasattr(L, "mvs_engine_set_refiner"):  # absent from a build of an older revision (tools/build_variant.sh, A/B timing)
+        L.mvs_default_refiner.argtypes = [C.POINTER(Refiner)]
+        L.mvs_default_refiner.restype = None
+        L.mvs_engine_set_refiner.argtypes = [vp, C.POINTER(Refiner)]
     _libs[LIB_PATH] = L
     return L
 
@@ -200,6 +211,15 @@ class Engine:
         out = np.empty((h.value, w.value, 3), dtype=np.uint8)
         self._check(self.L.mvs_engine_get_pyramid(self.h, v, level, _ptr(out), C.byref(w), C.byref(h)))
         return out
+
+    def set_refiner(self, mode="halving", max_evals=500, xtol=1e-4):
+        """Optim::refinePatch's refiner for the passes and probes that follow: "halving" (the default search) or "converged"
+        (Nelder-Mead until xtol or max_evals evaluations; include/mvskit_engine.h, mvs_refiner)."""
+        modes = {"halving": REFINE_HALVING, "converged": REFINE_CONVERGED}
+        if mode not in modes:
+            raise ValueError(f"refiner mode {mode!r}: 'halving' or 'converged'")
+        r = Refiner(modes[mode], int(max_evals), float(xtol))
+        self._check(self.L.mvs_engine_set_refiner(self.h, C.byref(r)))
 
     def set_thresholds(self, ncc, before, depth):
         self._check(self.L.mvs_engine_set_thresholds(self.h, ncc, before, depth))
@@ -325,7 +345,7 @@ class Engine:
         recs = synth.convert_records(recs, self.dtype)
         n = recs.shape[0]
         out_rec = np.zeros(n, dtype=self.dtype)
-        out_f = np.zeros(n, np.float32)
+        out_f = np.zeros((n, 4) if op == PROBE_REFINE_X else n, np.float32)  # PROBE_REFINE_X: (x0, x1, x2, cost) per record
         out_i = np.zeros(n, np.int32)
         self._check(self.L.mvs_engine_probe(self.h, op, n, _ptr(recs), None, _ptr(out_rec), _ptr(out_f), _ptr(out_i)))
         return out_rec, out_f, out_i

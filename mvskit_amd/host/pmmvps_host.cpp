@@ -623,6 +623,7 @@ int PmMvps::createEngine(float maxAngle, float quad) {
         return MVS_ERR_ARG;
     }
     int r = mvs_engine_create(&cfg, &m_engine);
+    if (r == 0) r = mvs_engine_set_refiner(m_engine, &m_refiner);
     if (r != 0) { cerr << "PmMvps::init: " << mvs_last_error() << endl; return r; }
     vector<mvs_view_desc> views(m_nimages);
     for (int i = 0; i < m_nimages; ++i) {
@@ -759,6 +760,9 @@ extern "C" void mvshost_set_ranks(int rank, int world, const char* id_file, int 
     g_ranks.rank = rank; g_ranks.world = world; g_ranks.device = device; g_ranks.id_file = id_file ? id_file : "";
 }
 extern "C" void mvshost_set_filter(int on) { g_run_filter = on != 0; }
+// the refiner of the next mvshost_run's PmMvps (m_refiner): mvs_refiner's mode, max_evals, xtol
+static mvs_refiner g_refiner{MVS_REFINE_HALVING, 500, 1e-4f};
+extern "C" void mvshost_set_refiner(int mode, int max_evals, float xtol) { g_refiner = mvs_refiner{mode, max_evals, xtol}; }
 extern "C" int mvshost_run(int nviews, int width, int height, const float* P /*[n][12]*/, const unsigned char* rgb /*[n][H][W][3]*/,
                            int level, int csize, int wsize, int minImageNum, float nccThreshold, unsigned seed, int iters,
                            long long nseeds, const mvs_patch* seeds, long long cap, mvs_patch* out, long long* nout, long long* patches_total) {
@@ -775,6 +779,7 @@ extern "C" int mvshost_run(int nviews, int width, int height, const float* P /*[
     }
     PmMvps pmmvps;
     pmmvps.m_seed = seed; pmmvps.ITER = iters; pmmvps.m_writeFiles = false;
+    pmmvps.m_refiner = g_refiner;
     if (g_ranks.world > 0) pmmvps.setRanks(g_ranks.rank, g_ranks.world, g_ranks.id_file, g_ranks.device);
     pmmvps.init(option, ps);
     if (pmmvps.m_status) return pmmvps.m_status;

@@ -237,6 +237,7 @@ public:
     mvs_engine* m_engine = nullptr;  // Optim + the PatchManager grids live behind this handle
     unsigned m_seed = 1;
     int m_refineSteps = 6;
+    mvs_refiner m_refiner{MVS_REFINE_HALVING, 500, 1e-4f};  // Optim::refinePatch's refiner (mvs_engine_set_refiner; CONVERGED + 500 = optim.cpp:471)
     int m_viewPropagation = 0;  // 1 = the branch propagate.cpp:110-120 keeps commented out
     int m_literalGroups = 0;    // 1 = Filter::filterSmallGroups labels breadth-first in patch order, as filter.cpp:432-524 does
     bool m_writeFiles = true;

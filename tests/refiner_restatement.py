@@ -1,0 +1,83 @@
+"""A numpy restatement, in float32, of the engine's CONVERGED refiner (refine_patch_simplex, mvskit_amd/csrc/mvs_device.cuh):
+a bounded Nelder-Mead over Optim::refinePatch's three variables whose iterations make one four-proposal pass each.
+
+`cost(x)` is Optim::cost_func at x (float32[3]) -> float (double); the tests pass the oracle's orc_cost.  Every vertex update
+below is written in the kernel's operation order (no fused operations: the engine builds with -ffp-contract=off):
+    centroid  c = ((v_a + v_b) + v_c) / 3   over the three vertices other than the worst, in ascending slot order
+    d = c - v_w;  trial g = c + k_g * d     k = (1, 2, 1/2, -1/2): reflection, expansion, outside / inside contraction
+    shrink    v_j = v_b + 0.5 * (v_j - v_b)
+The multiplications by k_g and 0.5 are exact, so the kernel's and this file's trajectories agree wherever the costs agree."""
+from __future__ import annotations
+
+import numpy as np
+
+F = np.float32
+AMIN, AMAX = F(-23.99999), F(23.99999)  # optim.cpp:496-506
+COEF = (F(1.0), F(2.0), F(0.5), F(-0.5))
+
+
+def clamp_angles(x):
+    x = np.array(x, dtype=F)
+    x[1] = np.minimum(np.maximum(x[1], AMIN), AMAX)  # fmaxf(fminf(x, amax), amin), as the kernel
+    x[2] = np.minimum(np.maximum(x[2], AMIN), AMAX)
+    return x
+
+
+def converged(V, b, xtol):
+    """every coordinate's spread over the simplex <= xtol * max(1, |x_best,i|)"""
+    for i in range(3):
+        col = np.array([V[j][i] for j in range(4)], dtype=F)
+        spread = F(col.max() - col.min())
+        if spread > F(F(xtol) * max(F(1.0), F(abs(V[b][i])))):
+            return False
+    return True
+
+
+def refine_converged(cost, x_start, rd0, ra0, max_evals=500, xtol=1e-4):
+    """-> (x_best float32[3], f_best, evals, ok).  ok = False: the budget ran out (the engine then leaves the patch as it was)."""
+    x = clamp_angles(x_start)
+    V = [x.copy() for _ in range(4)]
+    V[1][0] = F(x[0] + F(rd0))
+    V[2][1] = F(x[1] + F(ra0))
+    V[3][2] = F(x[2] + F(ra0))
+    V = [V[0]] + [clamp_angles(v) for v in V[1:]]
+    fv = [float(cost(V[0]))]
+    fv += [float(cost(V[j])) for j in (1, 2, 3)]
+    evals = 4
+    ok = False
+    while True:
+        b = min(range(4), key=lambda j: (fv[j], j))      # lowest cost, lowest slot on a tie
+        w = max(range(4), key=lambda j: (fv[j], j))      # highest cost, highest slot on a tie
+        if converged(V, b, xtol):
+            ok = True
+            break
+        if evals + 4 > max_evals:
+            break
+        fsw = max(fv[j] for j in range(4) if j != w)
+        rest = [j for j in range(4) if j != w]
+        c = F(F(F(V[rest[0]] + V[rest[1]]) + V[rest[2]]) / F(3.0))
+        d = F(c - V[w])
+        T = [clamp_angles(F(c + F(k * d))) for k in COEF]
+        ft = [float(cost(t)) for t in T]
+        evals += 4
+        acc = -1
+        if ft[0] < fv[b]:
+            acc = 1 if ft[1] < ft[0] else 0
+        elif ft[0] < fsw:
+            acc = 0
+        elif ft[0] < fv[w]:
+            acc = 2 if ft[2] <= ft[0] else -1
+        else:
+            acc = 3 if ft[3] < fv[w] else -1
+        if acc >= 0:
+            V[w], fv[w] = T[acc], ft[acc]
+            continue
+        if evals + 3 > max_evals:
+            break
+        for j in range(4):
+            if j != b:
+                V[j] = clamp_angles(F(V[b] + F(F(0.5) * F(V[j] - V[b]))))
+                fv[j] = float(cost(V[j]))
+        evals += 3
+    b = min(range(4), key=lambda j: (fv[j], j))
+    return V[b].copy(), fv[b], evals, ok
