@@ -187,6 +187,21 @@ int mvs_engine_reserve(mvs_engine* e, int64_t list_entries);
 int mvs_engine_num_patches(mvs_engine* e, int64_t* n_alive);
 int mvs_engine_download_patches(mvs_engine* e, int64_t cap, mvs_patch* out, int64_t* n); /* collectPatches */
 
+/* PatchManager::writePly (patch_manager.cpp:542-633): the whole PLY file of the alive pool, header included, vertices in the order of
+ * mvs_engine_download_patches.  Per vertex: x y z nx ny nz (coord, normal) and diffuse_red / green / blue, the mean over m_images of a
+ * bilinear sample of the level-`level` pyramid at the patch's projection; a listed view the point lies behind or projects outside of
+ * [0, W-1) x [0, H-1) counts in the mean but adds nothing; 128 grey for an empty list.
+ *   MVS_PLY_ASCII       "format ascii 1.0", one line "x y z nx ny nz r g b\n" per vertex with the floats as printf("%g", (double)v)
+ *                       writes them -- byte for byte what std::ostream writes;
+ *   MVS_PLY_BINARY_LE   "format binary_little_endian 1.0", 27 bytes per vertex: 6 float32, 3 uint8; the same numbers.
+ * out == NULL or cap < the size: *nbytes = the exact size (MVS_ERR_CAPACITY when out != NULL; out is then not written).  The size of an
+ * ASCII file costs one pass over the pool on the device; a call whose cap holds 90 bytes per vertex skips it.  The call only reads:
+ * pool, indexes, thresholds and RNG state stay as they were; not a collective (every rank holds the whole pool).  Device memory: fixed
+ * buffers of ~110 MB for the call, whatever the pool's size.  MVS_ERR_ARG: bad format, nbytes NULL, no engine (checked in that order,
+ * before the handle is read); MVS_ERR_STATE: views not set, or a pass waiting for its commit. */
+typedef enum mvs_ply_format { MVS_PLY_ASCII = 0, MVS_PLY_BINARY_LE = 1 } mvs_ply_format;
+int mvs_engine_export_ply(mvs_engine* e, int format, int64_t cap, uint8_t* out, int64_t* nbytes);
+
 /* Propagate::run(iter), propagate.cpp:28-64: two colour passes, each = index build + sweep + commit */
 int mvs_engine_propagate(mvs_engine* e, int iter, mvs_counters* out);
 

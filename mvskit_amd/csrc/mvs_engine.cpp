@@ -1022,6 +1022,97 @@ int mvs_engine_download_patches(mvs_engine* e, int64_t cap, mvs_patch* out, int6
     return MVS_OK;
 }
 
+// PatchManager::writePly (patch_manager.cpp:542-633) of the alive pool, on the device (mvs_ply.hip).  The pool is walked in chunks of
+// PLY_CHUNK slots, each through fixed buffers (~110 MB: the pool indices, colours, line lengths and offsets and at most 90 bytes of text
+// per slot), and every chunk is copied into `out` as soon as it is formatted.  Nothing of the engine's state changes: kill_cnt /
+// kill_base are scratch that every user fills first (mvs_engine_num_patches), the scan's block sums go to scan_tmp.
+#define PLY_CHUNK ((int64_t)1 << 20)
+#define PLY_ASCII_LINE_MAX 90  // mvs_plyfmt.h: six numbers of at most 12 characters, three of 3, 8 blanks and the newline
+static void ply_header(int64_t n, bool ascii, std::string* out) {
+    char head[512];
+    snprintf(head, sizeof head,
+             "ply\nformat %s 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\n"
+             "property float ny\nproperty float nz\nproperty uchar diffuse_red\nproperty uchar diffuse_green\nproperty uchar diffuse_blue\n"
+             "end_header\n",
+             ascii ? "ascii" : "binary_little_endian", (long long)n);
+    *out = head;
+}
+struct PlyBufs {
+    DevBuf<int32_t> idx, len;
+    DevBuf<int64_t> off;
+    DevBuf<uint32_t> rgb;
+    DevBuf<uint8_t> bytes;
+    ~PlyBufs() { idx.release(); len.release(); off.release(); rgb.release(); bytes.release(); }
+};
+
+int mvs_engine_export_ply(mvs_engine* e, int format, int64_t cap, uint8_t* out, int64_t* nbytes) {
+    // the arguments first, the handle after them
+    if (format != MVS_PLY_ASCII && format != MVS_PLY_BINARY_LE) { g_err = "mvs_engine_export_ply: format must be MVS_PLY_ASCII or MVS_PLY_BINARY_LE"; return MVS_ERR_ARG; }
+    if (!nbytes || cap < 0) { g_err = "mvs_engine_export_ply: nbytes is null or cap negative"; return MVS_ERR_ARG; }
+    if (!e) { g_err = "mvs_engine_export_ply: no engine"; return MVS_ERR_ARG; }
+    if (!e->have_views) { g_err = "mvs_engine_export_ply: views not set"; return MVS_ERR_STATE; }
+    if (e->staged) { g_err = "mvs_engine_export_ply: a pass is waiting for its commit"; return MVS_ERR_STATE; }
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:export_ply");
+    hipStream_t st = e->stream;
+    const bool ascii = format == MVS_PLY_ASCII;
+    int64_t alive = 0;
+    if (int r = mvs_engine_num_patches(e, &alive)) return r;  // leaves kill_base = exclusive scan of the alive flags
+    std::string head;
+    ply_header(alive, ascii, &head);
+    const int64_t chunk = std::min<int64_t>(PLY_CHUNK, std::max<int64_t>(e->pool_n, 1));
+    PlyBufs b;
+    if (alive > 0 && (b.idx.ensure(chunk) || b.rgb.ensure(chunk) || (ascii && (b.len.ensure(chunk + 1) || b.off.ensure(chunk + 1))))) return MVS_ERR_HIP;
+    // one chunk of pool slots [i0, i1): its nv alive vertices listed, coloured and (ASCII) measured; *cb = the chunk's bytes
+    auto measure = [&](int64_t i0, int64_t i1, int64_t* nv, int64_t* cb) -> int {
+        int32_t ends[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(&ends[0], e->kill_base.p + i0, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&ends[1], e->kill_base.p + i1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        *nv = ends[1] - ends[0];
+        *cb = 27 * *nv;
+        if (*nv == 0) return MVS_OK;
+        mvsk_ply_select(e->pool.p, e->kill_base.p, i0, i1, b.idx.p, st);
+        mvsk_ply_colour(e->pool.p, b.idx.p, *nv, e->dviews.p, e->cfg.nviews, e->cfg.level, ascii ? 1 : 0, b.rgb.p, b.len.p, st);
+        if (!ascii) return MVS_OK;
+        mvsk_exclusive_scan_off(b.len.p, b.off.p, *nv, reinterpret_cast<csr_off_t*>(e->scan_tmp.p), st);
+        HIPCHK(hipMemcpyAsync(cb, b.off.p + *nv, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return MVS_OK;
+    };
+    // the size: header + 27 bytes a vertex, or (ASCII) one length pass -- skipped when `out` holds the longest file N vertices can make
+    const int64_t upper = (int64_t)head.size() + (ascii ? PLY_ASCII_LINE_MAX : 27) * alive;
+    if (!out || cap < upper) {
+        int64_t total = (int64_t)head.size() + 27 * alive;
+        if (ascii) {
+            total = (int64_t)head.size();
+            for (int64_t i0 = 0; i0 < e->pool_n; i0 += chunk) {
+                int64_t nv = 0, cb = 0;
+                if (int r = measure(i0, std::min(e->pool_n, i0 + chunk), &nv, &cb)) return r;
+                total += cb;
+            }
+        }
+        *nbytes = total;
+        if (!out) return MVS_OK;
+        if (cap < total) { g_err = "mvs_engine_export_ply: cap is smaller than the file (*nbytes)"; return MVS_ERR_CAPACITY; }
+    }
+    if (alive > 0 && b.bytes.ensure(chunk * (ascii ? PLY_ASCII_LINE_MAX : 27))) return MVS_ERR_HIP;
+    memcpy(out, head.data(), head.size());
+    int64_t pos = (int64_t)head.size();
+    for (int64_t i0 = 0; i0 < e->pool_n; i0 += chunk) {
+        int64_t nv = 0, cb = 0;
+        if (int r = measure(i0, std::min(e->pool_n, i0 + chunk), &nv, &cb)) return r;
+        if (nv == 0) continue;
+        if (pos + cb > cap || cb > b.bytes.cap) { g_err = "mvs_engine_export_ply: a chunk outgrew its bound"; return MVS_ERR_CAPACITY; }
+        mvsk_ply_emit(e->pool.p, b.idx.p, nv, b.rgb.p, ascii ? b.off.p : nullptr, b.bytes.p, st);
+        HIPCHK(hipMemcpyAsync(out + pos, b.bytes.p, (size_t)cb, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        pos += cb;
+    }
+    *nbytes = pos;
+    return MVS_OK;
+}
+
 // A pass that failed (staging or Optim::check capacity in this rank's shard, a HIP error) leaves its status in the engine:
 // with a communicator attached the next mvs_engine_exchange hands it to every rank, so that all of them give the pass up
 // together instead of waiting in a collective for a rank that has already returned.

@@ -53,3 +53,9 @@ void mvsk_groups_kill(const DParams& prm, const int* parent, const int* size, in
 // op 6 needs rs.simplex (the engine checks it); op 2 follows rs
 void mvsk_probe(const DParams& prm, int op, int64_t n, const DPatch* in, const float* in_f, DPatch* out, float* out_f, int32_t* out_i, const RefineSel& rs,
                 hipStream_t st);
+// mvs_engine_export_ply (mvs_ply.hip): the alive pool slots of [i0, i1) -> idx (base = exclusive scan of the alive flags); the
+// colour (and ASCII line length) of each listed vertex; the vertex records into out at off[k] (ASCII) or 27 k (binary: off null)
+void mvsk_ply_select(const DPatch* pool, const int32_t* base, int64_t i0, int64_t i1, int32_t* idx, hipStream_t st);
+void mvsk_ply_colour(const DPatch* pool, const int32_t* idx, int64_t n, const DView* views, int nviews, int level, int ascii, uint32_t* rgb, int32_t* len,
+                     hipStream_t st);
+void mvsk_ply_emit(const DPatch* pool, const int32_t* idx, int64_t n, const uint32_t* rgb, const int64_t* off, uint8_t* out, hipStream_t st);

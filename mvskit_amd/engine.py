@@ -25,8 +25,11 @@ EXPORTS = [
     "mvs_engine_commit_local", "mvs_engine_depth_normal_map", "mvs_engine_probe", "mvs_engine_last_timing",
     "mvs_engine_filter", "mvs_comm_unique_id", "mvs_engine_comm_init", "mvs_engine_comm_attach", "mvs_engine_comm_release",
     "mvs_engine_exchange", "mvs_list_cap", "mvs_engine_filter_stats", "mvs_patch_bytes", "mvs_engine_reserve", "mvs_engine_comm_info",
-    "mvs_default_refiner", "mvs_engine_set_refiner",
+    "mvs_default_refiner", "mvs_engine_set_refiner", "mvs_engine_export_ply",
 ]
+PLY_ASCII, PLY_BINARY_LE = 0, 1  # mvs_ply_format
+#: one vertex of the binary PLY file (mvs_engine_export_ply): 27 packed bytes
+PLY_VERTEX_DTYPE = np.dtype([("xyz", "<f4", (3,)), ("normal", "<f4", (3,)), ("rgb", "u1", (3,))])
 
 
 class Config(C.Structure):
@@ -135,6 +138,8 @@ def load_library(cap32: bool = False, cap: int = 0):
         L.mvs_default_refiner.argtypes = [C.POINTER(Refiner)]
         L.mvs_default_refiner.restype = None
         L.mvs_engine_set_refiner.argtypes = [vp, C.POINTER(Refiner)]
+    if hasattr(L, "mvs_engine_export_ply"):
+        L.mvs_engine_export_ply.argtypes = [vp, C.c_int, C.c_int64, vp, C.POINTER(C.c_int64)]
     _libs[LIB_PATH] = L
     return L
 
@@ -258,6 +263,24 @@ class Engine:
         if n.value:
             self._check(self.L.mvs_engine_download_patches(self.h, n.value, _ptr(out), C.byref(n)))
         return out
+
+    def export_ply(self, binary=False):
+        """PatchManager::writePly of the alive pool as the bytes of a PLY file: ASCII (what std::ostream wrote) or, with binary=True,
+        binary_little_endian with the same numbers (include/mvskit_engine.h, mvs_engine_export_ply)."""
+        fmt = PLY_BINARY_LE if binary else PLY_ASCII
+        n = C.c_int64()
+        self._check(self.L.mvs_engine_export_ply(self.h, fmt, 0, None, C.byref(n)))
+        buf = C.create_string_buffer(max(n.value, 1))
+        self._check(self.L.mvs_engine_export_ply(self.h, fmt, n.value, buf, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def points(self):
+        """The alive pool as PLY vertices: a structured array with xyz (f4 x 3), normal (f4 x 3) and rgb (u1 x 3), parsed from the
+        binary file of export_ply(binary=True), in the order of patches()."""
+        data = self.export_ply(binary=True)
+        end = data.index(b"end_header\n") + len(b"end_header\n")
+        n = int(data[:end].split(b"element vertex ")[1].split(b"\n")[0])
+        return np.frombuffer(data, dtype=PLY_VERTEX_DTYPE, count=n, offset=end).copy()
 
     # ---- the hot path
     def propagate(self, it):

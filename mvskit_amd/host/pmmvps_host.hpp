@@ -115,7 +115,7 @@ public:
     int readPatches(const int iter);
     void addPatches(const vector<Ppatch>& seeds);  // in-memory seeds
     void writePatches(const string prefix, bool bExportPLY, bool bExportPatch, bool bExportPSet);  // :499-540
-    void writePly(const vector<Ppatch>& ppatches, const string filename);                           // :542-633, colour = mean of the views' samples
+    int writePly(const string filename);  // :542-633, the alive pool as the engine writes it (mvs_engine_export_ply); 0 or an mvs_status
     vector<int> m_gheights, m_gwidths;
     vector<Ppatch> m_ppatches;
 

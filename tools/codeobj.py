@@ -10,21 +10,26 @@ import tempfile
 lib = sys.argv[1]
 want = sys.argv[2] if len(sys.argv) > 2 else ""
 data = open(lib, "rb").read()
+# one offload bundle per HIP source of the library, each with its own gfx950 code object
+out = ""
 i = data.find(b"__CLANG_OFFLOAD_BUNDLE__")
-n = struct.unpack_from("<Q", data, i + 24)[0]
-off = i + 32
-co = None
-for _ in range(n):
-    o, s, tl = struct.unpack_from("<QQQ", data, off)
-    off += 24
-    t = data[off:off + tl]
-    off += tl
-    if b"gfx950" in t:
-        co = data[i + o:i + o + s]
-with tempfile.NamedTemporaryFile(suffix=".co") as f:
-    f.write(co)
-    f.flush()
-    out = subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", f.name], text=True)
+while i >= 0:
+    n = struct.unpack_from("<Q", data, i + 24)[0]
+    off = i + 32
+    co = None
+    for _ in range(n):
+        o, s, tl = struct.unpack_from("<QQQ", data, off)
+        off += 24
+        t = data[off:off + tl]
+        off += tl
+        if b"gfx950" in t:
+            co = data[i + o:i + o + s]
+    if co is not None:
+        with tempfile.NamedTemporaryFile(suffix=".co") as f:
+            f.write(co)
+            f.flush()
+            out += subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", f.name], text=True)
+    i = data.find(b"__CLANG_OFFLOAD_BUNDLE__", i + 24)
 cur = {}
 rows = []
 for line in out.splitlines():
