@@ -9,7 +9,12 @@ and the schedule starts over -- so any --steps measures BASELINE.json configs[1]
 leave [0.6, 0.7].  `value` = patches (candidates that reached Optim::preProcess, propagate.cpp:182) of all ranks /
 time of the K timed steps (max over ranks), inputs resident in HBM.  See DESIGN.md "Measurement".
 
+A plain run does what `value` needs and nothing more: set-up, warm-up, the timed steps, --dump-outputs, the JSON line.
+--full adds what takes work of its own after the timed steps: the config5 and config4 blocks, the CPU baseline, the
+host-transfer figures and, with --gpus N, the ranks' pool hashes.
+
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
     python bench.py --gpus N ...              (spawns N rank processes itself)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 """
@@ -47,13 +52,17 @@ def parse():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--seed-stride", type=int, default=2, help="one seed patch per stride x stride cells per view")
     ap.add_argument("--refine-steps", type=int, default=6)  # four proposals per step: 1 + 4 * 6 = 25 cost evaluations per candidate
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target duration of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: the config5 and config4 blocks, the CPU "
+                         "baseline, the host transfers (a download of the final pool) and, with --gpus N, the ranks' pool hashes")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="with --full: target duration of the CPU baseline sample (0 = skip)")
     ap.add_argument("--filter", action="store_true", help="BASELINE config 5: run Filter::run (filter.cpp:25-49) after every iteration, inside the timed region")
-    ap.add_argument("--no-config5", dest="config5", action="store_false", help="skip the extra repetition with Filter::run that fills the `config5` block")
-    ap.add_argument("--no-config4", dest="config4", action="store_false", help="skip the BASELINE configs[3] block (48 views of 3840x2160, five iterations with Filter::run, the 64-view library)")
+    ap.add_argument("--no-config5", dest="config5", action="store_false", help="with --full: skip the extra repetition with Filter::run that fills the `config5` block")
+    ap.add_argument("--no-config4", dest="config4", action="store_false", help="with --full: skip the BASELINE configs[3] block (48 views of 3840x2160, five iterations with Filter::run, the 64-view library)")
     ap.add_argument("--force-exchange", action="store_true", help="rehearsal: run the N>1 code path (RCCL exchange) with a world of 1")
     ap.add_argument("--list-cap", type=int, default=0, help="views per m_images / m_vimages list = which engine library (16, 32, 64); 0 = the smallest that holds --views")
-    ap.add_argument("--scene-cache", default=os.path.join("/tmp", "mvskit_scene_cache"))
+    ap.add_argument("--scene-cache", metavar="DIR", default=None,
+                    help="keep the generated scene in DIR and read it back when a later run asks for the same one (default: every run generates its own)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (its counters, the thresholds and a fixed sample of the pool) as DIR/<name>.npy")
     args = ap.parse_args()
@@ -101,17 +110,20 @@ def spawn_ranks(args) -> int:
 
 
 def load_scene(args, rank):
-    """Synthetic cfg2 scene + seeds; cached on local disk so that N ranks do not all render it."""
+    """Synthetic cfg2 scene + seeds, generated in this process; with args.scene_cache set, kept on local disk for later runs
+    (tools that load the same scene many times), and read back from there."""
     import numpy as np
 
     from mvskit_amd import synth
 
-    # the cache file is named after the generator's source too: a scene that another version of synth.py made is never read back
-    with open(synth.__file__, "rb") as f:
-        src = hashlib.blake2b(f.read(), digest_size=6).hexdigest()
-    tag = f"v{args.views}_{args.width}x{args.height}_s{args.seed_stride}_{src}"
-    path = os.path.join(args.scene_cache, tag + ".npz")
-    if os.path.exists(path):
+    path = None
+    if args.scene_cache:
+        # the cache file is named after the generator's source too: a scene that another version of synth.py made is never read back
+        with open(synth.__file__, "rb") as f:
+            src = hashlib.blake2b(f.read(), digest_size=6).hexdigest()
+        tag = f"v{args.views}_{args.width}x{args.height}_s{args.seed_stride}_{src}"
+        path = os.path.join(args.scene_cache, tag + ".npz")
+    if path and os.path.exists(path):
         z = np.load(path)
         sc = synth.Scene(W=args.width, H=args.height, P=z["P"], images=z["images"], centers=z["centers"])
         return sc, z["seeds"].view(synth.PATCH_DTYPE).reshape(-1)
@@ -119,7 +131,7 @@ def load_scene(args, rank):
     seeds = synth.make_seeds(sc, level=0, csize=2, stride=args.seed_stride, seed=777)
     sc.points = None
     sc.normals = None
-    if rank == 0:
+    if path and rank == 0:
         tmp = path + f".tmp{os.getpid()}.npz"
         try:  # the cache is shared by whoever runs on this host: a directory this user cannot write only costs the regeneration
             os.makedirs(args.scene_cache, exist_ok=True)
@@ -348,11 +360,13 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    if rank == 0:
-        sc, seeds = load_scene(args, rank)
-    if world > 1:
+    if args.scene_cache and world > 1:  # rank 0 writes the cache, the others read it back
+        if rank == 0:
+            sc, seeds = load_scene(args, rank)
         dist.barrier()
-    if rank != 0:
+        if rank != 0:
+            sc, seeds = load_scene(args, rank)
+    else:
         sc, seeds = load_scene(args, rank)
 
     e = eng.Engine(args.views, list_cap=args.list_cap or None, level=0, csize=2, wsize=7, minImageNum=3, enable_check=1, seed=1, refine_steps=args.refine_steps,
@@ -452,13 +466,13 @@ def main():
         local_view_evals += c["view_evals"]
         for k, v in c.get("filter_stats", {}).items():
             fstats[k] = fstats.get(k, 0) + v
-        if it == 0 and pool_after_iter0 is None and world == 1 and args.cpu_seconds > 0 and not args.filter:
+        if it == 0 and pool_after_iter0 is None and world == 1 and args.full and args.cpu_seconds > 0 and not args.filter:
             pool_after_iter0 = e.patches()  # for the CPU baseline's sample B (untimed: after the closing barrier)
         if args.dump_outputs and s == args.steps - 1 and rank == 0:
             # untimed, after the closing barrier; every rank holds the same pool, rank 0 writes it with its own counters
             dumped = dump_outputs(args.dump_outputs, e.patches(), c, e.thresholds(), e.list_cap)
             log(f"outputs of step {s} written to {args.dump_outputs}: {', '.join(dumped)}")
-        if world > 1 and it == SCHEDULE_ITERS - 1:
+        if world > 1 and args.full and it == SCHEDULE_ITERS - 1:
             # self-validation of a multi-rank run (untimed): every rank hashes the pool it holds at the end of a repetition; the hashes
             # are all-gathered below.  The result does not depend on the sharding, so all ranks must hold the SAME pool -- and `patches`
             # of the whole job must equal the one-GPU run's for the same --steps.
@@ -472,7 +486,7 @@ def main():
         dist.all_reduce(sm, op=dist.ReduceOp.SUM)
         dt = float(mx[0]); patches = int(sm[1]); view_evals = int(sm[2])
     validation = None
-    if world > 1:
+    if world > 1 and args.full:
         info = e.comm_info() if ex is not None else {"world": 0, "comm_count": -1}
         mine = torch.tensor((pool_hashes + [0] * 64)[:64] + [len(pool_hashes), info["world"], info["comm_count"]], dtype=torch.int64, device="cpu" if shared_gpu else device)
         allh = [torch.zeros_like(mine) for _ in range(world)]
@@ -487,7 +501,7 @@ def main():
     # repetition of the 3-iteration schedule with Filter::run (filter.cpp:25-49) after every iteration, as PmMvps::run has it
     # (pmmvps.cpp:95-105), on its own clock -- the headline `value` above is not touched by it.
     cfg5 = None
-    if not args.filter and args.config5:
+    if args.full and not args.filter and args.config5:
         f5 = {}
         p5 = 0
         t5 = 0.0
@@ -514,11 +528,12 @@ def main():
         cfg5 = (p5, t5, f5, f5_ms)
 
     n_alive = e.num_patches()
-    t_d0 = time.perf_counter()
-    final_pool = e.patches()  # what a caller takes back over PCIe after the last iteration
-    host_ms["download_patches_ms"] = 1000.0 * (time.perf_counter() - t_d0)
-    host_ms["downloaded_patches"] = int(final_pool.shape[0])
-    del final_pool
+    if args.full:
+        t_d0 = time.perf_counter()
+        final_pool = e.patches()  # what a caller takes back over PCIe after the last iteration
+        host_ms["download_patches_ms"] = 1000.0 * (time.perf_counter() - t_d0)
+        host_ms["downloaded_patches"] = int(final_pool.shape[0])
+        del final_pool
 
     if rank == 0:
         reps, extra = divmod(args.steps, SCHEDULE_ITERS)
@@ -614,7 +629,7 @@ def main():
                               "metric": "patches/s (propagate+optim iteration + Filter::run), 12-view 1080p", "value": p5 / t5 if t5 > 0 else 0.0, "unit": "patches/s",
                               "steps": SCHEDULE_ITERS, "ms_per_step": 1000.0 * t5 / SCHEDULE_ITERS, "patches": p5,
                               "filter_ms_per_call_host_clock": f5_ms / SCHEDULE_ITERS, "roofline_filter": filter_roofline(f5, SCHEDULE_ITERS)}
-        if world == 1 and reps >= 1:
+        if world == 1 and reps >= 1 and args.full:
             # what a caller that hands over host buffers sees for ONE 3-iteration job: images and seeds in over PCIe (pyramids built on
             # the device), the three iterations, the patches back out.  Never `value` (inputs resident), reported beside it.
             per_job = dt / reps if extra == 0 else dt * SCHEDULE_ITERS / max(args.steps, 1)
@@ -622,15 +637,15 @@ def main():
             out["host_transfers"] = dict(host_ms, patches_per_job=patches / max(args.steps, 1) * SCHEDULE_ITERS,
                                          pcie_inclusive_value=(patches / max(args.steps, 1) * SCHEDULE_ITERS) / (per_job + host_s), unit="patches/s",
                                          note="one job = set_views (host RGB in, pyramids on the device) + upload_patches + 3 iterations + download of the pool")
-        if world == 1 and args.config4 and not args.filter and args.views == 12 and args.width == 1920:
-            # BASELINE configs[3] in the driver's own line: the 12-view engine goes first (its memory is the card's), then the 48 x 4K run
+        if world == 1 and args.full and args.config4 and not args.filter and args.views == 12 and args.width == 1920:
+            # BASELINE configs[3] in the --full line: the 12-view engine goes first (its memory is the card's), then the 48 x 4K run
             e.close()
             e = None
             try:
                 out["config4"] = run_config4(log)
             except Exception as err:  # the headline must not be lost to the extra block
                 out["config4"] = {"error": f"{type(err).__name__}: {err}"}
-        if world == 1 and args.cpu_seconds > 0:
+        if world == 1 and args.full and args.cpu_seconds > 0:
             log("cpu baseline ...")
             out["cpu_baseline"] = cpu_baseline(args, sc, seeds, pool_after_iter0, patches_by_iter if patches_by_iter[0] else [1, 0, 0])
             out["cpu_baseline_all_cores"] = out["cpu_baseline"]["all_cores"]
