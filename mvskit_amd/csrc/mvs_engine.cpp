@@ -32,10 +32,17 @@ thread_local std::string g_err;
         }                                                                                                  \
     } while (0)
 
+// Device memory owned by the engine: freed by the destructor, with whatever device is current (the engine's: every entry point
+// sets it first).  Not copyable; a move (the view pyramids' vectors) or a swap of the storage is.
 template <typename T> struct DevBuf {
     T* p = nullptr;
     int64_t cap = 0;
     bool headroom = false;  // the cell indexes only: a buffer that has to grow a second time takes half as much again
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap), headroom(o.headroom) { o.p = nullptr; o.cap = 0; }
+    ~DevBuf() { release(); }
+    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); }  // the storage only: `headroom` belongs to the member
     int ensure(int64_t n) {
         if (n <= cap) return MVS_OK;
         // (headroom) The cell indexes of a pool that grows from iteration to iteration: freeing and allocating 10 GB costs ~100 ms, and an
@@ -43,9 +50,8 @@ template <typename T> struct DevBuf {
         // up front: mvs_engine_reserve.)  Every other buffer gets exactly what it asks for.
         const int64_t exact = std::max<int64_t>(n, 16);
         int64_t want = (p && headroom) ? exact + exact / 2 : exact;
-        // The contents are never needed across a growth.  The new buffer is allocated BEFORE the old one is freed where both fit, so
-        // that a failure leaves the old buffer in place (a failed mvs_engine_reserve must not take the indexes away); if they do not
-        // fit side by side the old one goes first.
+        // The contents are never needed across a growth.  The new buffer is allocated before the old one is freed where both fit; if
+        // they do not fit side by side, the old one is freed first, and a failure then leaves the buffer empty (cap 0).
         T* q = nullptr;
         hipError_t e = hipMalloc((void**)&q, (size_t)want * sizeof(T));
         if (e != hipSuccess && want > exact) { (void)hipGetLastError(); want = exact; e = hipMalloc((void**)&q, (size_t)want * sizeof(T)); }  // no room for the headroom
@@ -61,6 +67,26 @@ template <typename T> struct DevBuf {
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
+
+// The scratch words of mvs_engine::misc (unsigned long long; a count that a kernel keeps as int32 uses the low half of its word)
+namespace misc {
+constexpr int stage_counter = 0;   // the sweep's staging counter (SweepArgs::stage_counter)
+constexpr int fill_evals = 1;      // [2] mvsk_fill_ncc: evaluations and view evaluations spent on seeds whose m_ncc was < 0
+constexpr int neighbor_retry = 4;  // filterNeighbor: the number of patches for its retry launch
+constexpr int sweep_retry = 5;     // the sweep: the number of cells for Optim::check's second tier (SweepArgs::nretry)
+constexpr int geo_bad = 6;         // pack_geometry: a record that cannot be packed
+constexpr int group_edges = 7;     // the literal filterSmallGroups: the number of one-way edges between sets
+constexpr int trim_parts = 8;      // [trim_nparts] the MAX_NUM_OF_PATCHES trim's count as partial sums
+constexpr int trim_nparts = 256;   // (k_index_sort_trim: one per block index mod 256)
+constexpr int words = trim_parts + trim_nparts;
+}  // namespace misc
+// The words of mvs_engine::fstat_buf (Filter::run's statistics).  k_filter_neighbor fixes the first two ranges itself.
+namespace fstat {
+constexpr int neighbor_parts = 0;      // [1024][4] partial sums of filterNeighbor's work counts
+constexpr int neighbor_cycles = 4096;  // [16] filterNeighbor's stage cycles (-DMVS_STAGE_TIMING)
+constexpr int exact_evals = 4112;      // [1024][2] partial sums of filterExact's evaluations and view evaluations
+constexpr int words = exact_evals + 2048;
+}  // namespace fstat
 
 // RCCL, opened at run time.  A process that has loaded torch already holds torch's own librccl: that copy is reused
 // (one RCCL per process); otherwise the ROCm installation's is opened.  Nothing here is needed on one GPU.
@@ -149,8 +175,8 @@ struct mvs_engine {
     bool have_views = false;
     std::vector<DView> hviews;
     DevBuf<DView> dviews;
-    std::vector<uint32_t*> img_bufs;
-    std::vector<uint8_t*> mask_bufs;
+    std::vector<DevBuf<uint32_t>> img_bufs;  // the pyramid levels (DView::img)
+    std::vector<DevBuf<uint8_t>> mask_bufs;  // and masks (DView::mask) of the views
     int total_cells = 0;
     // pool
     DevBuf<DPatch> pool, pool_alt;  // pool_alt: target of the stable compaction done at every commit
@@ -170,7 +196,6 @@ struct mvs_engine {
     DevBuf<int32_t> group_edges;         // its literal labelling: (root, root) pairs of the one-way edges between sets
     DevBuf<int32_t> cnt_alive, vcnt_alive;
     DevBuf<unsigned long long> dpgrid, best;
-    bool index_valid = false;
     DevBuf<uint32_t> dirty;      // Filter::run: one bit per depth-map cell whose nearest patch the last stage removed
     bool dirty_marked = false;
     DevBuf<float4> geo;            // Filter::run: the packed geometry of the pool (DParams::geo), 2 words per patch
@@ -179,8 +204,8 @@ struct mvs_engine {
     bool lists_dense[2] = {false, false};  // m_pgrids / m_vpgrids index built without the trim: the lists of neighbouring cells lie end to end
     // sweep / staging
     DevBuf<DPatch> staging;
-    DevBuf<int32_t> job_stage, job_nstage, job_cnt, job_base_scan, kill_cnt, kill_base, per_view;
-    DevBuf<unsigned long long> misc;  // [0] stage_counter, [1..2] fill_ncc evals, [4..7] small counters of the stages, [8..264) the trim's count in 256 parts
+    DevBuf<int32_t> job_stage, job_nstage, job_cnt, job_base_scan, kill_cnt, kill_base;
+    DevBuf<unsigned long long> misc;  // scratch words: namespace misc
     DevBuf<DCounters> counters;
     DevBuf<int32_t> error_flag;
     DevBuf<int32_t> big_tables, retry_jobs;  // Optim::check's second tier (k_sweep_retry): 256 id sets of 16384 ints, the cells to run again
@@ -200,7 +225,7 @@ struct mvs_engine {
     mvs_timing timing{};
     mvs_filter_stats fstats{};
     int64_t fstats_exchange_bytes = 0;  // bytes this rank received in the last Filter::run's exchanges
-    DevBuf<unsigned long long> fstat_buf;  // [1024][4] partial sums of Filter::filterNeighbor's work counts
+    DevBuf<unsigned long long> fstat_buf;  // Filter::run's statistics: namespace fstat
     hipEvent_t fev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // multi-GPU (mvs_engine_comm_*): one RCCL communicator over the engines of the job
     ncclComm_t comm = nullptr;
@@ -214,8 +239,6 @@ struct mvs_engine {
 };
 
 namespace {
-
-int64_t total_cells_of(const mvs_engine* e) { return e->total_cells; }
 
 RefineSel refine_sel(const mvs_engine* e) {
     return RefineSel{e->refiner.mode == MVS_REFINE_CONVERGED ? 1 : 0, e->refiner.max_evals, e->refiner.xtol};
@@ -302,13 +325,6 @@ void setup_camera(const mvs_engine* e, DView& vw, const float* P0) {
     vw.ipscale = hdot4(&vw.P[0][0], x4) + hdot4(&vw.P[0][4], y4);
 }
 
-void free_views(mvs_engine* e) {
-    for (uint32_t* p : e->img_bufs) if (p) (void)hipFree(p);
-    for (uint8_t* p : e->mask_bufs) if (p) (void)hipFree(p);
-    e->img_bufs.clear(); e->mask_bufs.clear();
-    e->have_views = false;
-}
-
 DParams current_params(mvs_engine* e) {
     DParams p = e->prm;
     p.views = e->dviews.p;
@@ -355,8 +371,7 @@ int build_list(mvs_engine* e, bool vgrid, bool trim, bool unordered = false) {
     HIPCHK(hipMemsetAsync(cursor.p, 0, (size_t)(nc + 1) * sizeof(int32_t), st));
     if (direct) {
         mvsk_index_fill_direct(p, vgrid ? 1 : 0, start.p, cursor.p, id32.p, st);
-        std::swap(cnt.p, cnt_alive.p);  // every entry is alive: the counts ARE the alive counts (two buffers of one size; the next build clears its own)
-        std::swap(cnt.cap, cnt_alive.cap);
+        cnt.swap(cnt_alive);  // every entry is alive: the counts ARE the alive counts (two buffers of one size; the next build clears its own)
         e->lists_dense[vgrid ? 1 : 0] = true;
         return MVS_OK;
     }
@@ -364,7 +379,7 @@ int build_list(mvs_engine* e, bool vgrid, bool trim, bool unordered = false) {
     // packed end to end (a second scan, over the alive counts), so that every index the engine builds is dense
     if (int r = e->id32_raw.ensure(tot + 16)) return r;
     mvsk_index_fill(p, vgrid ? 1 : 0, raw.p, cursor.p, ids.p, st);
-    mvsk_index_sort_trim(p, raw.p, ids.p, trim ? 1 : 0, e->misc.p + 8, st);  // [8 .. 264): the trim's count as 256 partial sums
+    mvsk_index_sort_trim(p, raw.p, ids.p, trim ? 1 : 0, e->misc.p + misc::trim_parts, st);
     mvsk_index_finalize(p, vgrid ? 1 : 0, raw.p, ids.p, e->id32_raw.p, cnt_alive.p, st);
     mvsk_exclusive_scan_off(cnt_alive.p, start.p, nc, reinterpret_cast<csr_off_t*>(e->scan_tmp.p), st);
     mvsk_index_pack(p, raw.p, start.p, cnt_alive.p, ids.p, e->id32_raw.p, vgrid ? nullptr : e->key.p, id32.p, st);
@@ -382,25 +397,24 @@ int build_depth(mvs_engine* e) {  // m_dpgrids from the alive pool
 int build_index(mvs_engine* e, unsigned long long* trimmed_out) {
     hipStream_t st = e->stream;
     const DParams p = current_params(e);
-    HIPCHK(hipMemsetAsync(e->misc.p + 1, 0, 3 * sizeof(unsigned long long), st));
-    HIPCHK(hipMemsetAsync(e->misc.p + 8, 0, 256 * sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(e->misc.p + misc::fill_evals, 0, 2 * sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(e->misc.p + misc::trim_parts, 0, misc::trim_nparts * sizeof(unsigned long long), st));
     // PatchManager::sortPatches re-scores every patch whose m_ncc < 0 each time it meets it
     // (patch_manager.cpp:411-415); a wave that finds m_ncc >= 0 exits at once.
-    mvsk_fill_ncc(p, e->misc.p + 1, st);
+    mvsk_fill_ncc(p, e->misc.p + misc::fill_evals, st);
     e->ncc_dirty = false;
     if (int r = build_list(e, false, true)) return r;
     // m_vpgrids: no reader depends on the order inside its lists (findNeighbors' set, filterSmallGroups' unions): written without keys and sort
     if (want_vgrid(e)) if (int r = build_list(e, true, false, true)) return r;
     if (int r = build_depth(e)) return r;
     if (trimmed_out) {
-        unsigned long long part[256];
-        HIPCHK(hipMemcpyAsync(part, e->misc.p + 8, sizeof part, hipMemcpyDeviceToHost, st));
+        unsigned long long part[misc::trim_nparts];
+        HIPCHK(hipMemcpyAsync(part, e->misc.p + misc::trim_parts, sizeof part, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         *trimmed_out = 0;
         for (unsigned long long v : part) *trimmed_out += v;
     }
     HIPCHK(hipGetLastError());
-    e->index_valid = true;
     return MVS_OK;
 }
 // Filter::setDepthMapsVGridsVPGridsAddPatchV, filter.cpp:628-655
@@ -483,29 +497,34 @@ int filter_agree(FilterRun& fr) {
     }
     return fr.agreed;
 }
-// in-place broadcasts of every rank's share of the kill bytes and / or records (an all-gather-v without staging); returns != 0 when
-// the call is given up
+// An all-gather-v without staging: every rank's blocks broadcast in place from that rank, all in one group.  blocks(r, send) calls
+// send(ptr, count, type) for each block of rank r; empty blocks are skipped.  An error inside the group still closes it (a group left
+// open would swallow every later call of this thread); the first error is returned.
+template <typename Blocks> ncclResult_t broadcast_blocks(mvs_engine* e, Blocks&& blocks) {
+    const Rccl& R = rccl();
+    ncclResult_t first = R.GroupStart();
+    for (int r = 0; r < e->comm_world && first == ncclSuccess; ++r)
+        blocks(r, [&](void* p, int64_t n, ncclDataType_t type) {
+            if (n > 0 && first == ncclSuccess) first = R.Broadcast(p, p, (size_t)n, type, r, e->comm, e->stream);
+        });
+    const ncclResult_t end = R.GroupEnd();
+    return first == ncclSuccess ? end : first;
+}
+// in-place broadcasts of every rank's share of the kill bytes and / or records; returns != 0 when the call is given up
 int filter_exchange(FilterRun& fr, bool kills, bool records) {
     mvs_engine* e = fr.e;
     if (!fr.multi()) return filter_agree(fr);
     if (int a = filter_agree(fr)) return a;
     if (e->pool_n == 0) return MVS_OK;
-    const Rccl& R = rccl();
-    hipStream_t st = e->stream;
     const int N = e->comm_world;
-    ncclResult_t first_err = R.GroupStart();
-    for (int r = 0; r < N && first_err == ncclSuccess; ++r) {
+    const ncclResult_t first_err = broadcast_blocks(e, [&](int r, auto&& send) {
         const int64_t lo = e->pool_n * r / N, hi = e->pool_n * (r + 1) / N;
-        if (hi <= lo) continue;
-        if (kills) first_err = R.Broadcast(e->kill.p + lo, e->kill.p + lo, (size_t)(hi - lo), ncclUint8, r, e->comm, st);
-        if (records && first_err == ncclSuccess)
-            first_err = R.Broadcast(e->pool.p + lo, e->pool.p + lo, (size_t)(hi - lo) * sizeof(DPatch), ncclUint8, r, e->comm, st);
+        if (kills) send(e->kill.p + lo, hi - lo, ncclUint8);
+        if (records) send(e->pool.p + lo, (hi - lo) * (int64_t)sizeof(DPatch), ncclUint8);
         e->fstats_exchange_bytes += (r == e->comm_rank) ? 0 : (kills ? (hi - lo) : 0) + (records ? (hi - lo) * (int64_t)sizeof(DPatch) : 0);
-    }
-    const ncclResult_t end = R.GroupEnd();
-    if (first_err == ncclSuccess) first_err = end;
+    });
     if (first_err != ncclSuccess) {  // the transport itself: nothing can be agreed on any more
-        g_err = std::string("Filter::run exchange: ") + R.GetErrorString(first_err);
+        g_err = std::string("Filter::run exchange: ") + rccl().GetErrorString(first_err);
         fr.note(MVS_ERR_HIP); fr.agreed = MVS_ERR_HIP;
         return fr.agreed;
     }
@@ -523,7 +542,7 @@ int literal_small_groups(mvs_engine* e, int threshold) {
     const DParams p = current_params(e);
     const int cap = 8 << 20;  // (root, root) pairs
     if (int r = e->group_edges.ensure(2 * (int64_t)cap)) return r;
-    int32_t* nedges = reinterpret_cast<int32_t*>(e->misc.p + 7);
+    int32_t* nedges = reinterpret_cast<int32_t*>(e->misc.p + misc::group_edges);
     HIPCHK(hipMemsetAsync(nedges, 0, sizeof(unsigned long long), st));
     mvsk_groups_literal_edges(p, e->uf_parent.p, e->uf_size.p, e->group_edges.p, nedges, cap, st);
     int32_t ne = 0;
@@ -601,7 +620,7 @@ int pack_geometry(mvs_engine* e) {
 #endif
     if (e->geo.ensure(2 * e->pool_n) != MVS_OK || e->geo_ref.ensure(e->pool_n) != MVS_OK) { (void)hipGetLastError(); return MVS_OK; }
     hipStream_t st = e->stream;
-    int32_t* bad = reinterpret_cast<int32_t*>(e->misc.p + 5);
+    int32_t* bad = reinterpret_cast<int32_t*>(e->misc.p + misc::geo_bad);
     HIPCHK(hipMemsetAsync(bad, 0, sizeof(unsigned long long), st));
     mvsk_geo_pack(e->pool.p, e->pool_n, e->geo.p, e->geo_ref.p, bad, st);
     int32_t hbad = 1;
@@ -619,6 +638,27 @@ int filter_rebuild(FilterRun& fr, int additive, bool need_pgrid, bool need_vpgri
     FR(rebuild_tail(fr.e, need_vpgrid));
     return MVS_OK;
 }
+// What count_pool counts: the alive records, the kill flags, or the kill flags that are then applied (mvsk_apply_kill_flags, queued
+// in front of the wait so that the device does not idle between the read-back and the apply)
+enum class Count { alive, kills, apply_kills };
+// Count, exclusive scan, total over the pool's slots: kill_cnt[i] = 1 where slot i holds an alive record (Count::alive) or carries a
+// kill flag (the other two), kill_base = the exclusive scan of kill_cnt, and *total = kill_base[pool_n], read back after a
+// synchronisation.  Until the next call kill_base[i] is the number of counted slots before slot i: mvsk_kill_export reads it after
+// a count of the kill flags, the gathers of mvs_engine_download_patches and mvs_engine_export_ply after one of the alive records.
+int count_pool(mvs_engine* e, Count what, int64_t* total) {
+    hipStream_t st = e->stream;
+    *total = 0;
+    if (e->pool_n == 0) return MVS_OK;
+    if (what == Count::alive) mvsk_alive_count(e->pool.p, e->pool_n, e->kill_cnt.p, st);
+    else mvsk_kill_count(e->kill.p, e->pool_n, e->kill_cnt.p, st);
+    mvsk_exclusive_scan(e->kill_cnt.p, e->kill_base.p, e->pool_n, reinterpret_cast<int32_t*>(e->scan_tmp.p), st);
+    int32_t n = 0;
+    HIPCHK(hipMemcpyAsync(&n, e->kill_base.p + e->pool_n, sizeof n, hipMemcpyDeviceToHost, st));
+    if (what == Count::apply_kills) mvsk_apply_kill_flags(e->pool.p, e->kill.p, e->pool_n, st);
+    HIPCHK(hipStreamSynchronize(st));
+    *total = n;
+    return MVS_OK;
+}
 // counts and applies the kill flags a filter stage has set
 // `mark` (inside Filter::run, the depth maps being those of the pool as it stands): the cells that name a patch about to be
 // removed are emptied and marked, for filter_rebuild's incremental passes
@@ -634,14 +674,7 @@ int apply_kills(mvs_engine* e, int64_t* removed, bool mark = false) {
         mvsk_depth_mark_dirty(current_params(e), e->kill.p, e->dpgrid.p, e->dirty.p, st);
         e->dirty_marked = true;
     }
-    mvsk_kill_count(e->kill.p, e->pool_n, e->kill_cnt.p, st);
-    mvsk_exclusive_scan(e->kill_cnt.p, e->kill_base.p, e->pool_n, reinterpret_cast<int32_t*>(e->scan_tmp.p), st);
-    int32_t nk = 0;
-    HIPCHK(hipMemcpyAsync(&nk, e->kill_base.p + e->pool_n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    mvsk_apply_kill_flags(e->pool.p, e->kill.p, e->pool_n, st);
-    HIPCHK(hipStreamSynchronize(st));
-    *removed = nk;
-    return MVS_OK;
+    return count_pool(e, Count::apply_kills, removed);
 }
 
 int ensure_counts(mvs_engine* e) {  // commit_count + scans for the staged pass
@@ -661,14 +694,7 @@ int ensure_counts(mvs_engine* e) {  // commit_count + scans for the staged pass
         e->n_new = bounds[e->sa.nsweep_views];
         for (int s = 0; s < e->sa.nsweep_views; ++s) e->h_per_view[e->sa.sweep_views[s]] = bounds[s + 1] - bounds[s];
     }
-    if (e->pool_n > 0) {
-        mvsk_kill_count(e->kill.p, e->pool_n, e->kill_cnt.p, st);
-        mvsk_exclusive_scan(e->kill_cnt.p, e->kill_base.p, e->pool_n, reinterpret_cast<int32_t*>(e->scan_tmp.p), st);
-        int32_t nk = 0;
-        HIPCHK(hipMemcpyAsync(&nk, e->kill_base.p + e->pool_n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        e->n_kill = nk;
-    }
+    if (int r = count_pool(e, Count::kills, &e->n_kill)) return r;
     e->counted = true;
     return MVS_OK;
 }
@@ -676,22 +702,36 @@ int ensure_counts(mvs_engine* e) {  // commit_count + scans for the staged pass
 // Stable compaction of the pool: dead records (evicted, trimmed) are dropped, the relative order of the
 // survivors -- the only thing ids are used for -- is kept.  Runs at every commit, on every rank alike.
 int compact_pool(mvs_engine* e) {
-    hipStream_t st = e->stream;
-    if (e->pool_n == 0) return MVS_OK;
-    mvsk_alive_count(e->pool.p, e->pool_n, e->kill_cnt.p, st);
-    mvsk_exclusive_scan(e->kill_cnt.p, e->kill_base.p, e->pool_n, reinterpret_cast<int32_t*>(e->scan_tmp.p), st);
-    int32_t alive = 0;
-    HIPCHK(hipMemcpyAsync(&alive, e->kill_base.p + e->pool_n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    int64_t alive = 0;
+    if (int r = count_pool(e, Count::alive, &alive)) return r;
     if (alive == e->pool_n) return MVS_OK;
-    mvsk_alive_gather(e->pool.p, e->pool_n, e->kill_base.p, e->pool_alt.p, e->pool_alt.cap, st);
-    std::swap(e->pool.p, e->pool_alt.p);
-    std::swap(e->pool.cap, e->pool_alt.cap);
+    mvsk_alive_gather(e->pool.p, e->pool_n, e->kill_base.p, e->pool_alt.p, e->pool_alt.cap, e->stream);
+    e->pool.swap(e->pool_alt);
     e->pool_n = alive;
     return MVS_OK;
 }
 
-void add_counters(mvs_counters& a, const mvs_counters& b) {
+// The tail of every commit (mvs_engine_commit_device, mvs_engine_commit_local, and mvs_engine_exchange for the union of the ranks):
+// apply(&n_new) evicts the pass's patches, leaves the kill bytes clear and puts the n_new new records behind the pool; the pool then
+// takes them in and is compacted.  The whole is timed as commit_ms.
+template <typename Apply> int commit_pool(mvs_engine* e, Apply&& apply) {
+    hipStream_t st = e->stream;
+    HIPCHK(hipEventRecord(e->ev[2], st));
+    int64_t n_new = 0;
+    if (int r = apply(&n_new)) return r;
+    e->pool_n += n_new;
+    if (int r = compact_pool(e)) return r;
+    HIPCHK(hipEventRecord(e->ev[3], st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, e->ev[2], e->ev[3]);
+    e->timing.commit_ms = ms;
+    e->staged = false; e->counted = false;
+    return MVS_OK;
+}
+
+// a += b over the ten counters (b: another mvs_counters, or one of the sweep's DCounters partial sums)
+template <typename C> void add_counters(mvs_counters& a, const C& b) {
     a.candidates += b.candidates; a.prefiltered += b.prefiltered; a.patches += b.patches; a.fail0 += b.fail0; a.fail1 += b.fail1;
     a.inserted += b.inserted; a.replaced += b.replaced; a.evals += b.evals; a.view_evals += b.view_evals; a.trimmed += b.trimmed;
 }
@@ -756,8 +796,8 @@ int mvs_engine_create(const mvs_config* cfg, mvs_engine** out) {
     if (he != hipSuccess) { g_err = std::string("hipStreamCreate: ") + hipGetErrorString(he); delete e; return MVS_ERR_HIP; }
     for (auto& ev : e->ev) (void)hipEventCreate(&ev);
     for (auto& ev : e->fev) (void)hipEventCreate(&ev);
-    if (e->misc.ensure(8 + 256) || e->counters.ensure(MVS_COUNTER_SLOTS) || e->error_flag.ensure(1)) { delete e; return MVS_ERR_HIP; }
-    (void)hipMemset(e->misc.p, 0, (8 + 256) * sizeof(unsigned long long));
+    if (e->misc.ensure(misc::words) || e->counters.ensure(MVS_COUNTER_SLOTS) || e->error_flag.ensure(1)) { delete e; return MVS_ERR_HIP; }
+    (void)hipMemset(e->misc.p, 0, misc::words * sizeof(unsigned long long));
     (void)hipMemset(e->error_flag.p, 0, sizeof(int32_t));
     *out = e;
     return MVS_OK;
@@ -768,22 +808,10 @@ int mvs_engine_destroy(mvs_engine* e) {
     (void)hipSetDevice(e->cfg.device);
     (void)hipStreamSynchronize(e->stream);
     (void)mvs_engine_comm_release(e);
-    e->comm_counts.release(); e->comm_kill_ids.release();
-    e->geo.release(); e->geo_ref.release();
-    free_views(e);
-    e->dviews.release(); e->pool.release(); e->pool_alt.release(); e->kill.release();
-    e->cnt.release(); e->start.release(); e->cursor.release(); e->ids.release(); e->vcnt.release(); e->vstart.release();
-    e->uf_parent.release(); e->uf_size.release(); e->group_edges.release(); e->dirty.release();
-    e->vcursor.release(); e->key.release(); e->start_raw.release(); e->id32_raw.release(); e->id32.release(); e->vid32.release(); e->cnt_alive.release(); e->vcnt_alive.release(); e->scan_tmp.release(); e->dpgrid.release(); e->best.release();
-    e->staging.release(); e->job_stage.release(); e->job_nstage.release(); e->job_cnt.release(); e->job_base_scan.release();
-    e->kill_cnt.release(); e->kill_base.release(); e->per_view.release(); e->misc.release(); e->counters.release(); e->error_flag.release();
-    e->big_tables.release(); e->retry_jobs.release();
-    e->tmp_rec_in.release(); e->tmp_rec_out.release(); e->tmp_f_in.release(); e->tmp_f_out.release(); e->tmp_i.release(); e->tmp_bytes.release();
     for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : e->fev) if (ev) (void)hipEventDestroy(ev);
-    e->fstat_buf.release();
     (void)hipStreamDestroy(e->stream);
-    delete e;
+    delete e;  // the device memory goes with its DevBufs, the engine's device current
     return MVS_OK;
 }
 
@@ -792,7 +820,8 @@ int mvs_engine_set_views(mvs_engine* e, int nviews, const mvs_view_desc* views) 
     HIPCHK(hipSetDevice(e->cfg.device));
     hipStream_t st = e->stream;
     Range rg("mvs:set_views (upload + pyramids)");
-    free_views(e);
+    e->img_bufs.clear(); e->mask_bufs.clear();
+    e->have_views = false;
     const int maxLevel = e->cfg.level + 3;
     e->hviews.assign(nviews, DView{});
     int cell_base = 0;
@@ -810,9 +839,9 @@ int mvs_engine_set_views(mvs_engine* e, int nviews, const mvs_view_desc* views) 
         const size_t n0 = (size_t)vw.W[0] * vw.H[0];
         HIPCHK(hipMemcpyAsync(e->tmp_bytes.p, views[v].rgb, n0 * 3, hipMemcpyHostToDevice, st));
         for (int l = 0; l < maxLevel; ++l) {
-            uint32_t* buf = nullptr;
-            HIPCHK(hipMalloc((void**)&buf, std::max<size_t>((size_t)vw.W[l] * vw.H[l], 1) * sizeof(uint32_t)));
-            e->img_bufs.push_back(buf);
+            e->img_bufs.emplace_back();
+            if (int r = e->img_bufs.back().ensure(std::max<int64_t>((int64_t)vw.W[l] * vw.H[l], 1))) return r;
+            uint32_t* buf = e->img_bufs.back().p;
             vw.img[l] = buf;
             if (l == 0) mvsk_rgb_to_rgba(e->tmp_bytes.p, buf, (int64_t)n0, st);
             else mvsk_pyr_down(vw.img[l - 1], vw.W[l - 1], vw.H[l - 1], buf, vw.W[l], vw.H[l], st);
@@ -822,9 +851,9 @@ int mvs_engine_set_views(mvs_engine* e, int nviews, const mvs_view_desc* views) 
             HIPCHK(hipStreamSynchronize(st));
             uint8_t* prev = nullptr;
             for (int l = 0; l <= e->cfg.level; ++l) {
-                uint8_t* m = nullptr;
-                HIPCHK(hipMalloc((void**)&m, std::max<size_t>((size_t)vw.W[l] * vw.H[l], 1)));
-                e->mask_bufs.push_back(m);
+                e->mask_bufs.emplace_back();
+                if (int r = e->mask_bufs.back().ensure(std::max<int64_t>((int64_t)vw.W[l] * vw.H[l], 1))) return r;
+                uint8_t* m = e->mask_bufs.back().p;
                 if (l == 0) {
                     HIPCHK(hipMemcpyAsync(m, views[v].mask, n0, hipMemcpyHostToDevice, st));
                     mvsk_mask_binarise(m, (int64_t)n0, st);
@@ -872,7 +901,7 @@ int mvs_engine_set_views(mvs_engine* e, int nviews, const mvs_view_desc* views) 
     for (int v = 0; v < nviews; ++v) njobs_max += (int64_t)((e->hviews[v].gw + 1) / 2) * e->hviews[v].gh;
     const int maxstage = (e->prm.view_propagation ? 3 : 2) * e->prm.cap * e->prm.max_propag;
     if (e->job_stage.ensure(njobs_max * maxstage) || e->job_nstage.ensure(njobs_max + 2) || e->job_cnt.ensure(njobs_max + 2) ||
-        e->job_base_scan.ensure(njobs_max + 2) || e->per_view.ensure(MVS_MAXVIEWS))
+        e->job_base_scan.ensure(njobs_max + 2))
         return MVS_ERR_HIP;
     const int64_t scan_n = std::max<int64_t>(std::max<int64_t>(nc, pool_cap), njobs_max);
     if (e->scan_tmp.ensure(scan_n / 256 + 4096)) return MVS_ERR_HIP;
@@ -880,13 +909,12 @@ int mvs_engine_set_views(mvs_engine* e, int nviews, const mvs_view_desc* views) 
     // first pass with check, so that no pass allocates
     if (e->big_tables.ensure((int64_t)256 * 16384) || e->retry_jobs.ensure(std::max<int64_t>(njobs_max, 16))) return MVS_ERR_HIP;
     // likewise what Filter::run needs per patch and per cell (union-find, retry list, the bit per depth-map cell)
-    if (e->uf_parent.ensure(pool_cap) || e->uf_size.ensure(pool_cap) || e->dirty.ensure((nc + 31) / 32 + 1) || e->fstat_buf.ensure(4096)) return MVS_ERR_HIP;
+    if (e->uf_parent.ensure(pool_cap) || e->uf_size.ensure(pool_cap) || e->dirty.ensure((nc + 31) / 32 + 1) || e->fstat_buf.ensure(fstat::words)) return MVS_ERR_HIP;
     if (e->staging.ensure(std::max<int64_t>(pool_cap / 2, 1024))) return MVS_ERR_HIP;
     if (e->tmp_rec_out.ensure(16)) return MVS_ERR_HIP;
     HIPCHK(hipStreamSynchronize(st));
     e->pool_n = 0;
     e->have_views = true;
-    e->index_valid = false;
     e->staged = false;
     return MVS_OK;
 }
@@ -957,32 +985,27 @@ int mvs_engine_upload_patches(mvs_engine* e, int64_t n, const mvs_patch* patches
     HIPCHK(hipStreamSynchronize(e->stream));
     e->pool_n += (int64_t)recs.size();
     e->ncc_dirty = true;
-    e->index_valid = false;
     return MVS_OK;
 }
 
 // Sizes the buffers of both cell indexes for `list_entries` memberships each (0: MAX_NUM_OF_PATCHES per cell of every view, what
 // m_pgrids holds after the trim), so that Propagate::run / Filter::run allocate nothing while the lists stay below that: the first
-// iterations of a run otherwise grow them inside the call (free + allocate, gigabytes at a time).
+// iterations of a run otherwise grow them inside the call (free + allocate, gigabytes at a time).  A reserve that fails may leave
+// some of these buffers replaced or emptied; nothing reads the lists across calls (every pass and Filter::run builds its own index).
 int mvs_engine_reserve(mvs_engine* e, int64_t list_entries) {
     if (!e || !e->have_views || list_entries < 0) { g_err = "mvs_engine_reserve: views not set, or a negative size"; return MVS_ERR_ARG; }
     HIPCHK(hipSetDevice(e->cfg.device));
     int64_t n = list_entries > 0 ? list_entries : e->total_cells * (int64_t)(e->cfg.max_propag * e->cfg.csize * e->cfg.csize);
     // a buffer that is allocated here is also written once: the first use of fresh device memory is slow in a process that has just
     // come up (the first m_vpgrids build of the first process on a box took 95 ms instead of 21), and this call is the set-up
-    bool fresh = false;
     auto take = [&](auto& buf, int64_t want) -> int {
         const int64_t before = buf.cap;
         if (int r = buf.ensure(want)) return r;
-        if (buf.cap != before) {
-            fresh = true;
-            if (hipMemsetAsync(buf.p, 0, (size_t)buf.cap * sizeof(*buf.p), e->stream) != hipSuccess) { (void)hipGetLastError(); return MVS_ERR_HIP; }
-        }
+        if (buf.cap != before && hipMemsetAsync(buf.p, 0, (size_t)buf.cap * sizeof(*buf.p), e->stream) != hipSuccess) { (void)hipGetLastError(); return MVS_ERR_HIP; }
         return MVS_OK;
     };
     if (take(e->ids, n + 16) || take(e->key, n + 16) || take(e->id32, n + 16) || take(e->id32_raw, n + 16) || take(e->vid32, n + 16)) return MVS_ERR_HIP;
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (fresh) e->index_valid = false;  // the lists lived in the buffers that were replaced
     return MVS_OK;
 }
 
@@ -990,28 +1013,20 @@ int mvs_engine_clear_patches(mvs_engine* e) {
     if (!e) return MVS_ERR_ARG;
     HIPCHK(hipSetDevice(e->cfg.device));
     if (e->kill.p) HIPCHK(hipMemsetAsync(e->kill.p, 0, (size_t)e->kill.cap, e->stream));
-    e->pool_n = 0; e->staged = false; e->counted = false; e->index_valid = false;
+    e->pool_n = 0; e->staged = false; e->counted = false;
     return MVS_OK;
 }
 
 int mvs_engine_num_patches(mvs_engine* e, int64_t* n_alive) {
     if (!e || !n_alive) return MVS_ERR_ARG;
     HIPCHK(hipSetDevice(e->cfg.device));
-    *n_alive = 0;
-    if (e->pool_n == 0) return MVS_OK;
-    mvsk_alive_count(e->pool.p, e->pool_n, e->kill_cnt.p, e->stream);
-    mvsk_exclusive_scan(e->kill_cnt.p, e->kill_base.p, e->pool_n, reinterpret_cast<int32_t*>(e->scan_tmp.p), e->stream);
-    int32_t tot = 0;
-    HIPCHK(hipMemcpyAsync(&tot, e->kill_base.p + e->pool_n, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    *n_alive = tot;
-    return MVS_OK;
+    return count_pool(e, Count::alive, n_alive);
 }
 
 int mvs_engine_download_patches(mvs_engine* e, int64_t cap, mvs_patch* out, int64_t* n) {
     if (!e || !n) return MVS_ERR_ARG;
     int64_t alive = 0;
-    if (int r = mvs_engine_num_patches(e, &alive)) return r;  // leaves kill_base = exclusive scan of the alive flags
+    if (int r = mvs_engine_num_patches(e, &alive)) return r;  // count_pool: kill_base = the scan of the alive flags
     *n = alive;
     if (!out || alive == 0) return MVS_OK;
     const int64_t m = std::min(cap, alive);
@@ -1025,7 +1040,7 @@ int mvs_engine_download_patches(mvs_engine* e, int64_t cap, mvs_patch* out, int6
 // PatchManager::writePly (patch_manager.cpp:542-633) of the alive pool, on the device (mvs_ply.hip).  The pool is walked in chunks of
 // PLY_CHUNK slots, each through fixed buffers (~110 MB: the pool indices, colours, line lengths and offsets and at most 90 bytes of text
 // per slot), and every chunk is copied into `out` as soon as it is formatted.  Nothing of the engine's state changes: kill_cnt /
-// kill_base are scratch that every user fills first (mvs_engine_num_patches), the scan's block sums go to scan_tmp.
+// kill_base are scratch that every user fills first (count_pool), the scan's block sums go to scan_tmp.
 #define PLY_CHUNK ((int64_t)1 << 20)
 #define PLY_ASCII_LINE_MAX 90  // mvs_plyfmt.h: six numbers of at most 12 characters, three of 3, 8 blanks and the newline
 static void ply_header(int64_t n, bool ascii, std::string* out) {
@@ -1042,7 +1057,6 @@ struct PlyBufs {
     DevBuf<int64_t> off;
     DevBuf<uint32_t> rgb;
     DevBuf<uint8_t> bytes;
-    ~PlyBufs() { idx.release(); len.release(); off.release(); rgb.release(); bytes.release(); }
 };
 
 int mvs_engine_export_ply(mvs_engine* e, int format, int64_t cap, uint8_t* out, int64_t* nbytes) {
@@ -1057,7 +1071,7 @@ int mvs_engine_export_ply(mvs_engine* e, int format, int64_t cap, uint8_t* out, 
     hipStream_t st = e->stream;
     const bool ascii = format == MVS_PLY_ASCII;
     int64_t alive = 0;
-    if (int r = mvs_engine_num_patches(e, &alive)) return r;  // leaves kill_base = exclusive scan of the alive flags
+    if (int r = mvs_engine_num_patches(e, &alive)) return r;  // count_pool: kill_base = the scan of the alive flags
     std::string head;
     ply_header(alive, ascii, &head);
     const int64_t chunk = std::min<int64_t>(PLY_CHUNK, std::max<int64_t>(e->pool_n, 1));
@@ -1127,7 +1141,7 @@ int mvs_engine_pass(mvs_engine* e, int iter, int pass, mvs_counters* out) {
 static void discard_pass(mvs_engine* e) {
     if (e->kill.p && e->pool_n > 0) (void)hipMemsetAsync(e->kill.p, 0, (size_t)e->pool_n, e->stream);
     (void)hipStreamSynchronize(e->stream);
-    e->staged = false; e->counted = false; e->index_valid = false;
+    e->staged = false; e->counted = false;
 }
 static int pass_impl(mvs_engine* e, int iter, int pass, mvs_counters* out) {
     if (!e || !e->have_views) { g_err = "mvs_engine_pass: views not set"; return MVS_ERR_STATE; }
@@ -1191,7 +1205,7 @@ static int pass_impl(mvs_engine* e, int iter, int pass, mvs_counters* out) {
         HIPCHK(hipMemsetAsync(e->job_nstage.p, 0, (size_t)nj * sizeof(int32_t), st));  // jobs of other shards stage nothing
     }
     a.staging = e->staging.p; a.staging_cap = e->staging.cap;
-    a.stage_counter = e->misc.p;
+    a.stage_counter = e->misc.p + misc::stage_counter;
     a.job_stage = e->job_stage.p; a.job_nstage = e->job_nstage.p;
     a.maxstage = (e->prm.view_propagation ? 3 : 2) * e->prm.cap * e->prm.max_propag;
     a.kill = e->kill.p;
@@ -1201,9 +1215,9 @@ static int pass_impl(mvs_engine* e, int iter, int pass, mvs_counters* out) {
         if (int r = e->big_tables.ensure((int64_t)256 * 16384)) return r;
         if (int r = e->retry_jobs.ensure(std::max<int64_t>(nj, 16))) return r;
     }
-    a.big_tables = e->big_tables.p; a.retry_jobs = e->retry_jobs.p; a.nretry = reinterpret_cast<int32_t*>(e->misc.p + 5);
-    HIPCHK(hipMemsetAsync(e->misc.p + 5, 0, sizeof(unsigned long long), st));
-    HIPCHK(hipMemsetAsync(e->misc.p, 0, sizeof(unsigned long long), st));
+    a.big_tables = e->big_tables.p; a.retry_jobs = e->retry_jobs.p; a.nretry = reinterpret_cast<int32_t*>(e->misc.p + misc::sweep_retry);
+    HIPCHK(hipMemsetAsync(e->misc.p + misc::sweep_retry, 0, sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(e->misc.p + misc::stage_counter, 0, sizeof(unsigned long long), st));
     HIPCHK(hipMemsetAsync(e->counters.p, 0, MVS_COUNTER_SLOTS * sizeof(DCounters), st));
     HIPCHK(hipMemsetAsync(e->error_flag.p, 0, sizeof(int32_t), st));
     const DParams p = current_params(e);
@@ -1218,41 +1232,36 @@ static int pass_impl(mvs_engine* e, int iter, int pass, mvs_counters* out) {
         if (nretry > 0) { mvsk_sweep_retry(p, a, nretry, rs, st); e->retried_cells += nretry; }
     }
     HIPCHK(hipEventRecord(e->ev[2], st));
-    DCounters hc;
     std::vector<DCounters> hcs(MVS_COUNTER_SLOTS);
     int32_t herr = 0;
     unsigned long long fill[2] = {0, 0};  // evaluations spent on seeds whose m_ncc was < 0 (sortPatches)
-    HIPCHK(hipMemcpyAsync(fill, e->misc.p + 1, sizeof fill, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(fill, e->misc.p + misc::fill_evals, sizeof fill, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(hcs.data(), e->counters.p, hcs.size() * sizeof(DCounters), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&herr, e->error_flag.p, sizeof herr, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
-    memset(&hc, 0, sizeof hc);
-    for (const DCounters& c : hcs) {
-        hc.candidates += c.candidates; hc.prefiltered += c.prefiltered; hc.patches += c.patches; hc.fail0 += c.fail0; hc.fail1 += c.fail1;
-        hc.inserted += c.inserted; hc.replaced += c.replaced; hc.evals += c.evals; hc.view_evals += c.view_evals; hc.trimmed += c.trimmed;
-        for (int k = 0; k < 16; ++k) hc.stage[k] = (k == 12 || k == 13) ? std::max(hc.stage[k], c.stage[k]) : hc.stage[k] + c.stage[k];
-    }
+    mvs_counters sum{};
+    for (const DCounters& c : hcs) add_counters(sum, c);
+    sum.evals += fill[0]; sum.view_evals += fill[1]; sum.trimmed = (int64_t)trimmed;
     float ms = 0.0f;
     (void)hipEventElapsedTime(&ms, e->ev[0], e->ev[1]); e->timing.index_ms = ms;
     (void)hipEventElapsedTime(&ms, e->ev[1], e->ev[2]); e->timing.sweep_ms = ms;
     e->timing.commit_ms = 0.0f; e->timing.sweep_launches = 1; e->timing.exchange_ms = 0.0f; e->timing.exchange_bytes = 0;
     e->timing.check_retried_cells = e->pass_retried;
     e->staged = true; e->counted = false;
-    if (out) {
-        out->candidates = (int64_t)hc.candidates; out->prefiltered = (int64_t)hc.prefiltered; out->patches = (int64_t)hc.patches;
-        out->fail0 = (int64_t)hc.fail0; out->fail1 = (int64_t)hc.fail1; out->inserted = (int64_t)hc.inserted; out->replaced = (int64_t)hc.replaced;
-        out->evals = (int64_t)(hc.evals + fill[0]); out->view_evals = (int64_t)(hc.view_evals + fill[1]); out->trimmed = (int64_t)trimmed;
-    }
+    if (out) *out = sum;
 #ifdef MVS_STAGE_TIMING
     {
+        unsigned long long stage[16] = {0};
+        for (const DCounters& c : hcs)
+            for (int k = 0; k < 16; ++k) stage[k] = (k == 12 || k == 13) ? std::max(stage[k], c.stage[k]) : stage[k] + c.stage[k];
         static const char* nm[8] = {"wave", "generate", "pre", "refine", "post", "check", "stage", "prologue"};
         fprintf(stderr, "[stage cycles]");
-        for (int k = 0; k < 8; ++k) fprintf(stderr, " %s %.1f%%", nm[k], 100.0 * (double)hc.stage[k] / (double)(hc.stage[0] ? hc.stage[0] : 1));
+        for (int k = 0; k < 8; ++k) fprintf(stderr, " %s %.1f%%", nm[k], 100.0 * (double)stage[k] / (double)(stage[0] ? stage[0] : 1));
         static const char* nm2[4] = {"gain", "search", "sort", "quad"};
-        for (int k = 0; k < 4; ++k) fprintf(stderr, " %s %.1f%%", nm2[k], 100.0 * (double)hc.stage[8 + k] / (double)(hc.stage[0] ? hc.stage[0] : 1));
-        fprintf(stderr, " setRefImage pairs %.1f%% choice %.1f%%", 100.0 * (double)hc.stage[14] / (double)(hc.stage[0] ? hc.stage[0] : 1), 100.0 * (double)hc.stage[15] / (double)(hc.stage[0] ? hc.stage[0] : 1));
-        fprintf(stderr, "  (wave cycles %.3e; max visited %llu, max neighbours %llu)\n", (double)hc.stage[0], hc.stage[12], hc.stage[13]);
+        for (int k = 0; k < 4; ++k) fprintf(stderr, " %s %.1f%%", nm2[k], 100.0 * (double)stage[8 + k] / (double)(stage[0] ? stage[0] : 1));
+        fprintf(stderr, " setRefImage pairs %.1f%% choice %.1f%%", 100.0 * (double)stage[14] / (double)(stage[0] ? stage[0] : 1), 100.0 * (double)stage[15] / (double)(stage[0] ? stage[0] : 1));
+        fprintf(stderr, "  (wave cycles %.3e; max visited %llu, max neighbours %llu)\n", (double)stage[0], stage[12], stage[13]);
     }
 #endif
     // Fault injection: MVS_FAULT_PASS=<shard>:<iter>:<pass> makes that one pass of that shard report a
@@ -1301,18 +1310,13 @@ int mvs_engine_commit_device(mvs_engine* e, const void* d_new, int64_t n_new, co
     HIPCHK(hipSetDevice(e->cfg.device));
     hipStream_t st = e->stream;
     if (e->pool_n + n_new > e->pool.cap) { g_err = "mvs_engine_commit_device: patch pool capacity exceeded (raise mvs_config.max_patches)"; return MVS_ERR_CAPACITY; }
-    HIPCHK(hipEventRecord(e->ev[2], st));
-    mvsk_apply_kill_ids(e->pool.p, (const int32_t*)d_kill, n_kill, e->pool_n, st);
-    mvsk_append_records(e->pool.p, e->pool_n, (const DPatch*)d_new, n_new, st);
-    if (e->pool_n > 0) HIPCHK(hipMemsetAsync(e->kill.p, 0, (size_t)e->pool_n, st));
-    e->pool_n += n_new;
-    if (int r = compact_pool(e)) return r;
-    HIPCHK(hipEventRecord(e->ev[3], st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, e->ev[2], e->ev[3]); e->timing.commit_ms = ms;
-    e->staged = false; e->counted = false; e->index_valid = false;
-    return MVS_OK;
+    return commit_pool(e, [&](int64_t* added) -> int {  // the caller's kill ids and records
+        mvsk_apply_kill_ids(e->pool.p, (const int32_t*)d_kill, n_kill, e->pool_n, st);
+        mvsk_append_records(e->pool.p, e->pool_n, (const DPatch*)d_new, n_new, st);
+        if (e->pool_n > 0) HIPCHK(hipMemsetAsync(e->kill.p, 0, (size_t)e->pool_n, st));
+        *added = n_new;
+        return MVS_OK;
+    });
 }
 
 int mvs_engine_commit_local(mvs_engine* e) {
@@ -1320,19 +1324,14 @@ int mvs_engine_commit_local(mvs_engine* e) {
     HIPCHK(hipSetDevice(e->cfg.device));
     hipStream_t st = e->stream;
     Range rg("mvs:commit");
-    HIPCHK(hipEventRecord(e->ev[2], st));
-    if (int r = ensure_counts(e)) return r;
-    if (e->pool_n + e->n_new > e->pool.cap) { g_err = "mvs_engine_commit_local: patch pool capacity exceeded (raise mvs_config.max_patches)"; return MVS_ERR_CAPACITY; }
-    if (e->n_new > 0) mvsk_commit_copy(e->sa, e->job_base_scan.p, e->pool.p + e->pool_n, e->pool.cap - e->pool_n, nullptr, 0, st);
-    mvsk_apply_kill_flags(e->pool.p, e->kill.p, e->pool_n, st);
-    e->pool_n += e->n_new;
-    if (int r = compact_pool(e)) return r;
-    HIPCHK(hipEventRecord(e->ev[3], st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, e->ev[2], e->ev[3]); e->timing.commit_ms = ms;
-    e->staged = false; e->counted = false; e->index_valid = false;
-    return MVS_OK;
+    return commit_pool(e, [&](int64_t* added) -> int {  // this engine's kill flags and staged records
+        if (int r = ensure_counts(e)) return r;
+        if (e->pool_n + e->n_new > e->pool.cap) { g_err = "mvs_engine_commit_local: patch pool capacity exceeded (raise mvs_config.max_patches)"; return MVS_ERR_CAPACITY; }
+        if (e->n_new > 0) mvsk_commit_copy(e->sa, e->job_base_scan.p, e->pool.p + e->pool_n, e->pool.cap - e->pool_n, nullptr, 0, st);
+        mvsk_apply_kill_flags(e->pool.p, e->kill.p, e->pool_n, st);
+        *added = e->n_new;
+        return MVS_OK;
+    });
 }
 
 // ---- multi-GPU: RCCL communicator + the per-pass exchange (include/mvskit_engine.h, "multi-GPU through the C ABI")
@@ -1432,9 +1431,11 @@ int mvs_engine_exchange(mvs_engine* e) {
     if (hipMemcpyAsync(e->comm_counts.p, mine, sizeof mine, hipMemcpyHostToDevice, st) != hipSuccess) {
         (void)hipGetLastError();
         g_err = "mvs_engine_exchange: host-to-device copy of the count words failed"; fail_local(MVS_ERR_HIP);
-        // {0, 0, MVS_ERR_HIP (all ones in the low word, sign-extended by the second), 0, 0}: zero the words, then the status
+        // {0, 0, MVS_ERR_HIP, 0, 0}: zero the words, then the status as an int64 -- low word MVS_ERR_HIP, high word all ones
         (void)hipMemsetAsync(e->comm_counts.p, 0, sizeof mine, st);
-        (void)hipMemsetD32Async((hipDeviceptr_t)(e->comm_counts.p + 2), (int)(uint32_t)MVS_ERR_HIP, 2, st);
+        int32_t* status = reinterpret_cast<int32_t*>(e->comm_counts.p + 2);
+        (void)hipMemsetD32Async((hipDeviceptr_t)status, (int)MVS_ERR_HIP, 1, st);
+        (void)hipMemsetD32Async((hipDeviceptr_t)(status + 1), -1, 1, st);
     }
     NCCLCHK(R.AllGather(e->comm_counts.p, e->comm_counts.p + MVS_XCHG_WORDS, MVS_XCHG_WORDS, ncclInt64, e->comm, st));
     HIPCHK(hipMemcpyAsync(all.data(), e->comm_counts.p + MVS_XCHG_WORDS, all.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -1471,36 +1472,27 @@ int mvs_engine_exchange(mvs_engine* e) {
     DPatch* tail = e->pool.p + e->pool_n;
     if (e->n_new > 0) mvsk_commit_copy(e->sa, e->job_base_scan.p, tail + off_new[rank], e->n_new, nullptr, 0, st);
     if (e->n_kill > 0) mvsk_kill_export(e->kill.p, e->pool_n, e->kill_base.p, e->comm_kill_ids.p + off_kill[rank], e->n_kill, st);
-    {
-        // an error inside the group still closes it (a group left open would swallow every later call of this thread)
-        ncclResult_t first = R.GroupStart();
-        for (int r = 0; r < world && first == ncclSuccess; ++r) {
-            const int64_t nn = all[MVS_XCHG_WORDS * (size_t)r], nk = all[MVS_XCHG_WORDS * (size_t)r + 1];
-            if (nn > 0) first = R.Broadcast(tail + off_new[r], tail + off_new[r], (size_t)nn * sizeof(DPatch), ncclUint8, r, e->comm, st);
-            if (nk > 0 && first == ncclSuccess) first = R.Broadcast(e->comm_kill_ids.p + off_kill[r], e->comm_kill_ids.p + off_kill[r], (size_t)nk, ncclInt32, r, e->comm, st);
-        }
-        const ncclResult_t end = R.GroupEnd();
-        if (first == ncclSuccess) first = end;
-        if (first != ncclSuccess) { g_err = std::string("mvs_engine_exchange: record / kill-id broadcast: ") + R.GetErrorString(first); return MVS_ERR_HIP; }
-    }
+    const ncclResult_t bc = broadcast_blocks(e, [&](int r, auto&& send) {
+        send(tail + off_new[r], all[MVS_XCHG_WORDS * (size_t)r] * (int64_t)sizeof(DPatch), ncclUint8);
+        send(e->comm_kill_ids.p + off_kill[r], all[MVS_XCHG_WORDS * (size_t)r + 1], ncclInt32);
+    });
+    if (bc != ncclSuccess) { g_err = std::string("mvs_engine_exchange: record / kill-id broadcast: ") + R.GetErrorString(bc); return MVS_ERR_HIP; }
     HIPCHK(hipEventRecord(e->ev[5], st));
-    // commit of the union (the same on every rank)
     {
         Range rc("mvs:commit");
-        HIPCHK(hipEventRecord(e->ev[2], st));
-        mvsk_apply_kill_ids(e->pool.p, e->comm_kill_ids.p, tot_kill, e->pool_n, st);
-        if (e->pool_n > 0) HIPCHK(hipMemsetAsync(e->kill.p, 0, (size_t)e->pool_n, st));
-        e->pool_n += tot_new;
-        if (int r = compact_pool(e)) return r;
-        HIPCHK(hipEventRecord(e->ev[3], st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
+        // the union of the ranks' kill ids and records (the same on every rank)
+        if (int r = commit_pool(e, [&](int64_t* added) -> int {
+                mvsk_apply_kill_ids(e->pool.p, e->comm_kill_ids.p, tot_kill, e->pool_n, st);
+                if (e->pool_n > 0) HIPCHK(hipMemsetAsync(e->kill.p, 0, (size_t)e->pool_n, st));
+                *added = tot_new;
+                return MVS_OK;
+            }))
+            return r;
     }
+    HIPCHK(hipGetLastError());
     float ms = 0.0f;
     (void)hipEventElapsedTime(&ms, e->ev[4], e->ev[5]); e->timing.exchange_ms = ms;
-    (void)hipEventElapsedTime(&ms, e->ev[2], e->ev[3]); e->timing.commit_ms = ms;
     e->timing.exchange_bytes = (tot_new - e->n_new) * (int64_t)sizeof(DPatch) + (tot_kill - e->n_kill) * 4 + 8 * MVS_XCHG_WORDS * (int64_t)(world - 1);
-    e->staged = false; e->counted = false; e->index_valid = false;
     return MVS_OK;
 }
 
@@ -1541,8 +1533,7 @@ int mvs_engine_filter(mvs_engine* e, int64_t* removed4) {  // Filter::run, filte
     FRHIP(hipMemsetAsync(e->error_flag.p, 0, sizeof(int32_t), st));
     if (e->pool_n > 0) FRHIP(hipMemsetAsync(e->kill.p, 0, (size_t)e->pool_n, st));
     e->fstats = mvs_filter_stats{};
-    FR(e->fstat_buf.ensure(4096 + 16 + 2048));  // [4096..]: k_filter_neighbor's stage cycles (-DMVS_STAGE_TIMING); [4112..]: k_filter_exact's [1024][2] work counts
-    FRHIP(hipMemsetAsync(e->fstat_buf.p, 0, (4096 + 16 + 2048) * sizeof(unsigned long long), st));
+    FRHIP(hipMemsetAsync(e->fstat_buf.p, 0, fstat::words * sizeof(unsigned long long), st));  // sized by set_views
     FR(mvs_engine_num_patches(e, &e->fstats.patches_in));
     e->fstats_exchange_bytes = 0;
     int64_t first = 0, last = 0;  // this rank's share of the pool (everything on one GPU)
@@ -1561,13 +1552,12 @@ int mvs_engine_filter(mvs_engine* e, int64_t* removed4) {  // Filter::run, filte
         // a stage that removed nothing leaves the depth maps, hence m_vimages (additive pass) and both grids, as they are
         if (rem[0] > 0) { if (filter_rebuild(fr, 1, false, false, 2)) break; }
         e->fstats.exact_patches = e->fstats.patches_in - rem[0];
-        FRHIP(hipMemsetAsync(e->misc.p + 1, 0, 2 * sizeof(unsigned long long), st));
         FRHIP(hipEventRecord(e->fev[2], st));
         filter_range(e, first, last);
 #ifdef MVS_STAGE_TIMING
         FRHIP(hipMemsetAsync(e->counters.p, 0, sizeof(DCounters), st));
         if (fr.live()) {
-            mvsk_filter_exact(current_params(e), e->kill.p, e->fstat_buf.p + 4112, e->counters.p->stage, first, last, st);
+            mvsk_filter_exact(current_params(e), e->kill.p, e->fstat_buf.p + fstat::exact_evals, e->counters.p->stage, first, last, st);
             DCounters hc;
             (void)hipMemcpyAsync(&hc, e->counters.p, sizeof hc, hipMemcpyDeviceToHost, st);
             (void)hipStreamSynchronize(st);
@@ -1577,12 +1567,12 @@ int mvs_engine_filter(mvs_engine* e, int64_t* removed4) {  // Filter::run, filte
             fprintf(stderr, " (wave cycles %.3e)\n", (double)hc.stage[0]);
         }
 #else
-        if (fr.live()) mvsk_filter_exact(current_params(e), e->kill.p, e->fstat_buf.p + 4112, nullptr, first, last, st);  // filterExact
+        if (fr.live()) mvsk_filter_exact(current_params(e), e->kill.p, e->fstat_buf.p + fstat::exact_evals, nullptr, first, last, st);  // filterExact
 #endif
         FRHIP(hipEventRecord(e->fev[3], st));
         {
-            std::vector<unsigned long long> ev(2048, 0ull);
-            FRHIP(hipMemcpyAsync(ev.data(), e->fstat_buf.p + 4112, ev.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            std::vector<unsigned long long> ev(fstat::words - fstat::exact_evals, 0ull);
+            FRHIP(hipMemcpyAsync(ev.data(), e->fstat_buf.p + fstat::exact_evals, ev.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
             FRHIP(hipStreamSynchronize(st));
             unsigned long long ev2[2] = {0, 0};
             for (size_t k = 0; k < ev.size(); ++k) ev2[k & 1] += ev[k];
@@ -1595,24 +1585,24 @@ int mvs_engine_filter(mvs_engine* e, int64_t* removed4) {  // Filter::run, filte
         e->fstats.neighbor_patches = e->fstats.exact_patches - rem[1];
         {                                                                              // filterNeighbor(1)
             FR(e->uf_parent.ensure(e->pool.cap));                                      // reused as the retry list
-            FRHIP(hipMemsetAsync(e->misc.p + 4, 0, sizeof(unsigned long long), st));
-            int32_t* nretry = reinterpret_cast<int32_t*>(e->misc.p + 4);
+            FRHIP(hipMemsetAsync(e->misc.p + misc::neighbor_retry, 0, sizeof(unsigned long long), st));
+            int32_t* nretry = reinterpret_cast<int32_t*>(e->misc.p + misc::neighbor_retry);
             FRHIP(hipEventRecord(e->fev[4], st));
             if (fr.live() && (!e->lists_dense[0] || !e->lists_dense[1])) { g_err = "Filter::filterNeighbor: the grid indexes must come from a rebuild without the trim"; fr.note(MVS_ERR_ARG); }
             filter_range(e, first, last);
             int32_t nr = 0;
-            if (fr.live()) mvsk_filter_neighbor(current_params(e), e->kill.p, e->uf_parent.p, nretry, e->error_flag.p, e->fstat_buf.p, first, last, st);
+            if (fr.live()) mvsk_filter_neighbor(current_params(e), e->kill.p, e->uf_parent.p, nretry, e->error_flag.p, e->fstat_buf.p + fstat::neighbor_parts, first, last, st);
             FRHIP(hipMemcpyAsync(&nr, nretry, sizeof nr, hipMemcpyDeviceToHost, st));
             FRHIP(hipStreamSynchronize(st));
             FRHIP(hipGetLastError());
             e->fstats.neighbor_retried = nr;
-            if (fr.live()) mvsk_filter_neighbor_retry(current_params(e), e->kill.p, e->uf_parent.p, nr, e->error_flag.p, e->fstat_buf.p, st);
+            if (fr.live()) mvsk_filter_neighbor_retry(current_params(e), e->kill.p, e->uf_parent.p, nr, e->error_flag.p, e->fstat_buf.p + fstat::neighbor_parts, st);
             FRHIP(hipGetLastError());  // a refused launch (LDS request) must not pass for "nothing to filter"
             FRHIP(hipEventRecord(e->fev[5], st));
 #ifdef MVS_STAGE_TIMING
             if (fr.live()) {
                 unsigned long long hc[16] = {0};
-                (void)hipMemcpyAsync(hc, e->fstat_buf.p + 4096, sizeof hc, hipMemcpyDeviceToHost, st);
+                (void)hipMemcpyAsync(hc, e->fstat_buf.p + fstat::neighbor_cycles, sizeof hc, hipMemcpyDeviceToHost, st);
                 (void)hipStreamSynchronize(st);
                 const double w = (double)(hc[0] ? hc[0] : 1);
                 fprintf(stderr, "[filterNeighbor cycles] load + grids %.1f%% set build %.1f%% gather + predicate %.1f%% filterQuad %.1f%% (wave cycles %.3e)\n",
@@ -1653,7 +1643,6 @@ int mvs_engine_filter(mvs_engine* e, int64_t* removed4) {  // Filter::run, filte
         }
     } while (0);
     const int status = filter_agree(fr);  // the closing agreement (one GPU: this rank's own status)
-    e->index_valid = false;
     e->geo_valid = false;  // compact_pool renumbers the patches
     if (status != MVS_OK) {
         // given up: what the unfinished stage marked is forgotten.  The stages that completed stand (on every rank alike); a stage that
@@ -1678,10 +1667,10 @@ int mvs_engine_filter(mvs_engine* e, int64_t* removed4) {  // Filter::run, filte
         (void)hipEventElapsedTime(&f.neighbor_ms, e->fev[4], e->fev[5]);
         (void)hipEventElapsedTime(&f.groups_ms, e->fev[6], e->fev[7]);
         f.rebuild_ms = f.total_ms - f.outside_ms - f.exact_ms - f.neighbor_ms - f.groups_ms;  // rebuilds + the scans between the stages
-        std::vector<unsigned long long> part(4096);
-        HIPCHK(hipMemcpy(part.data(), e->fstat_buf.p, part.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        std::vector<unsigned long long> part(fstat::neighbor_cycles - fstat::neighbor_parts);
+        HIPCHK(hipMemcpy(part.data(), e->fstat_buf.p + fstat::neighbor_parts, part.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         unsigned long long sum4[4] = {0, 0, 0, 0};
-        for (int b = 0; b < 1024; ++b) for (int k = 0; k < 4; ++k) sum4[k] += part[4 * b + k];
+        for (size_t k = 0; k < part.size(); ++k) sum4[k & 3] += part[k];
         f.neighbor_tasks = (int64_t)sum4[0]; f.neighbor_entries = (int64_t)sum4[1]; f.neighbor_visited = (int64_t)sum4[2]; f.neighbor_accepted = (int64_t)sum4[3];
     }
     e->fstats.exchange_bytes = e->fstats_exchange_bytes;
@@ -1713,7 +1702,6 @@ int mvs_engine_depth_normal_map(mvs_engine* e, int view, int kind, float* depth,
         HIPCHK(hipMemsetAsync(e->dpgrid.p, 0xff, (size_t)e->total_cells * sizeof(unsigned long long), st));
         mvsk_depth_maps(p, e->dpgrid.p, nullptr, st);
         sel = e->dpgrid.p + vw.cell_base;
-        e->index_valid = false;
     } else {
         HIPCHK(hipMemsetAsync(e->best.p, 0, (size_t)ncells * sizeof(unsigned long long), st));
         mvsk_best_ncc_map(p, view, e->best.p, st);
