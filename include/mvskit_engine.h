@@ -179,6 +179,33 @@ int mvs_engine_update_threshold(mvs_engine* e); /* PmMvps::updateThreshold + ++m
 /* PatchManager::readPatches tail (patch_manager.cpp:450-463): seeds -> pool */
 int mvs_engine_upload_patches(mvs_engine* e, int64_t n, const mvs_patch* patches);
 int mvs_engine_clear_patches(mvs_engine* e);
+/* DepthNormInit::createPatches with isTest = 0 (pmmvps/depth_normal_init.cpp:34-91): the seed patches from a depth point cloud and one
+ * photometric-stereo normal map per view, built on the device and appended to the pool in point order.  Per point: project into
+ * every view at level 0 (PhotoSet::project), take the pixel floorf(x + 0.5f); a view takes part when that pixel lies inside the image
+ * and its mask byte is foreground (> 127, the rule of mvs_engine_set_views); the views' normals at those pixels are summed in view
+ * order, divided by the number of views, then by the norm (depth_normal_init.cpp:66-73), normal.w = -coord . n; the views are ordered
+ * by Optim::sortImages(patch, 0) (optim.cpp:221-258).  No patch for a point with fewer than two views, a zero sum, or -- unlike the
+ * reference, which keeps such a patch with an empty m_images in no grid cell -- fewer than two views left by sortImages.  A map pixel
+ * outside the image is never read (the reference reads out of bounds there).  The record is what mvs_engine_upload_patches makes of
+ * the mirror's: list cut to mvs_list_cap() after the sort, m_vimages empty, m_ncc = -1, m_tmp = score2, alive.
+ *   xyz     3 * npoints float32, world coordinates (DepthNormInit::readDepths)
+ *   views   one mvs_seed_view per view of mvs_engine_set_views, in that order, with that view's width and height:
+ *           normals  H*W*3 float32 in world axes (what DepthNormInit::readNormals leaves: R * n), (0, 0, 0) = no normal there: the view
+ *                    still counts; NULL: the view takes no part
+ *           mask     H*W level-0 mask bytes as mvs_view_desc.mask (the engine itself keeps masks at Option::m_level only); NULL: the
+ *                    view takes no part (PhotoSet::getMask = -1)
+ *   n_added the number of patches appended (may be NULL)
+ * LIMITS: npoints <= 2^31 - 4097 per call.  Device memory for the call, released before it returns: 44 bytes per point and 13 bytes
+ * per pixel of the largest view (the views stream through one buffer, whatever their number).  Two calls on the same input give the
+ * same pool bytes (positions come from a scan, not from atomics).  A second call appends.
+ * MVS_ERR_ARG: npoints negative, xyz (with npoints > 0) or views NULL, no engine (checked in that order, before the handle is read);
+ * MVS_ERR_STATE: views not set, or a pass waiting for its commit; MVS_ERR_HIP: an allocation or copy failed; MVS_ERR_CAPACITY: the
+ * patches do not fit the pool.  After any error the pool is what it was. */
+typedef struct mvs_seed_view {
+    const float* normals;
+    const uint8_t* mask;
+} mvs_seed_view;
+int mvs_engine_seed_patches(mvs_engine* e, int64_t npoints, const float* xyz, const mvs_seed_view* views, int64_t* n_added);
 /* Optional: sizes the two cell indexes (PatchManager::m_pgrids / m_vpgrids as lists, patch_manager.hpp) for `list_entries` memberships
  * each up front -- 0 = MAX_NUM_OF_PATCHES per cell of every view -- so that the calls below allocate nothing while the lists stay
  * below that.  Without it the buffers grow inside the first iterations of a run.  A buffer that the call allocates is written once

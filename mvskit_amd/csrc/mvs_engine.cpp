@@ -988,6 +988,103 @@ int mvs_engine_upload_patches(mvs_engine* e, int64_t n, const mvs_patch* patches
     return MVS_OK;
 }
 
+// DepthNormInit::createPatches with isTest = 0 (depth_normal_init.cpp:34-91) on the device: mvs_seed.hip.  The views stream one at a
+// time through one map and one mask buffer (13 bytes per pixel of the largest view), so the float sum of a point's normals runs in the
+// reference's order (image 0, 1, 2 ...) and the memory does not grow with the view count; per point 44 bytes (coordinates, sum,
+// membership word, keep flag and its scan).  All of it is released on return.  The pool is written only after the count is known to fit.
+namespace {
+// The camera constants Optim::sortImages reads, as the host mirror's DepthNormInit derives them from the level-0 projection (Camera::
+// getCameraCenter, camera.cpp:295-308; Optim::setAxesScales, optim.cpp:43-65): plain products and sums, each element of the inverse
+// divided by the determinant before the sum.  DView::center / ipscale hold the same quantities in the sweep's fmaf-chain arithmetic,
+// which can differ in the last bit; a seed record is to have the bits of the mirror's.
+SeedCam seed_camera(const float* P) {
+    SeedCam c;
+    const double m[9] = {P[0], P[1], P[2], P[4], P[5], P[6], P[8], P[9], P[10]};
+    const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
+    const double inv[9] = {(m[4] * m[8] - m[5] * m[7]) / det, (m[2] * m[7] - m[1] * m[8]) / det, (m[1] * m[5] - m[2] * m[4]) / det,
+                           (m[5] * m[6] - m[3] * m[8]) / det, (m[0] * m[8] - m[2] * m[6]) / det, (m[2] * m[3] - m[0] * m[5]) / det,
+                           (m[3] * m[7] - m[4] * m[6]) / det, (m[1] * m[6] - m[0] * m[7]) / det, (m[0] * m[4] - m[1] * m[3]) / det};
+    const double q[3] = {P[3], P[7], P[11]};
+    for (int r = 0; r < 3; ++r) c.center[r] = (float)-(inv[3 * r] * q[0] + inv[3 * r + 1] * q[1] + inv[3 * r + 2] * q[2]);
+    c.center[3] = 1.0f;
+    const float on = sqrtf(P[8] * P[8] + P[9] * P[9] + P[10] * P[10]);
+    const float z[3] = {P[8] / on, P[9] / on, P[10] / on};
+    float x[3] = {P[0], P[1], P[2]};
+    float y[3] = {z[1] * x[2] - z[2] * x[1], z[2] * x[0] - z[0] * x[2], z[0] * x[1] - z[1] * x[0]};
+    const float yn = sqrtf(y[0] * y[0] + y[1] * y[1] + y[2] * y[2]);
+    for (int k = 0; k < 3; ++k) y[k] /= yn;
+    x[0] = y[1] * z[2] - y[2] * z[1]; x[1] = y[2] * z[0] - y[0] * z[2]; x[2] = y[0] * z[1] - y[1] * z[0];
+    c.ipscale = (P[0] * x[0] + P[1] * x[1] + P[2] * x[2]) + (P[4] * y[0] + P[5] * y[1] + P[6] * y[2]);
+    return c;
+}
+}  // namespace
+
+int mvs_engine_seed_patches(mvs_engine* e, int64_t npoints, const float* xyz, const mvs_seed_view* views, int64_t* n_added) {
+    // the arguments first, the handle after them
+    if (npoints < 0 || (npoints > 0 && !xyz) || !views) { g_err = "mvs_engine_seed_patches: negative npoints, or xyz / views null"; return MVS_ERR_ARG; }
+    if (npoints > (int64_t)INT32_MAX - 4096) { g_err = "mvs_engine_seed_patches: more than 2^31 - 4097 points in one call"; return MVS_ERR_ARG; }
+    if (!e) { g_err = "mvs_engine_seed_patches: no engine"; return MVS_ERR_ARG; }
+    if (!e->have_views) { g_err = "mvs_engine_seed_patches: views not set"; return MVS_ERR_STATE; }
+    if (e->staged) { g_err = "mvs_engine_seed_patches: a pass is waiting for its commit"; return MVS_ERR_STATE; }
+    if (n_added) *n_added = 0;
+    if (npoints == 0) return MVS_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:seed_patches");
+    hipStream_t st = e->stream;
+    const int nviews = e->cfg.nviews;
+    const int64_t n = npoints;
+    int64_t max_pix = 0;
+    for (int v = 0; v < nviews; ++v)
+        if (views[v].normals && views[v].mask) max_pix = std::max(max_pix, (int64_t)e->hviews[v].W[0] * e->hviews[v].H[0]);
+    DevBuf<float> d_xyz, d_sum, d_map;
+    DevBuf<unsigned long long> d_bits;
+    DevBuf<int32_t> d_keep, d_base, d_scan;
+    DevBuf<uint8_t> d_mask;
+    DevBuf<SeedCam> d_cams;
+    if (d_xyz.ensure(3 * n) || d_sum.ensure(3 * n) || d_bits.ensure(n) || d_keep.ensure(n + 1) || d_base.ensure(n + 1) || d_scan.ensure(n / 256 + 4096) ||
+        d_cams.ensure(nviews) || (max_pix > 0 && (d_map.ensure(3 * max_pix) || d_mask.ensure(max_pix))))
+        return MVS_ERR_HIP;
+    std::vector<SeedCam> cams((size_t)nviews);
+    for (int v = 0; v < nviews; ++v) cams[(size_t)v] = seed_camera(e->hviews[v].P[0]);
+    HIPCHK(hipMemcpyAsync(d_cams.p, cams.data(), sizeof(SeedCam) * (size_t)nviews, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_xyz.p, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_sum.p, 0, sizeof(float) * 3 * (size_t)n, st));
+    HIPCHK(hipMemsetAsync(d_bits.p, 0, sizeof(unsigned long long) * (size_t)n, st));
+    for (int v = 0; v < nviews; ++v) {
+        // a view without a mask is skipped (PhotoSet::getMask = -1); one without a map has nothing to add
+        if (!views[v].normals || !views[v].mask) continue;
+        const DView& vw = e->hviews[v];
+        const size_t pix = (size_t)vw.W[0] * vw.H[0];
+        SeedView sv;
+        memcpy(sv.P, vw.P[0], sizeof sv.P);
+        sv.W = vw.W[0]; sv.H = vw.H[0]; sv.view = v;
+        HIPCHK(hipMemcpyAsync(d_map.p, views[v].normals, sizeof(float) * 3 * pix, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_mask.p, views[v].mask, pix, hipMemcpyHostToDevice, st));
+        mvsk_seed_accumulate(sv, d_map.p, d_mask.p, d_xyz.p, n, d_sum.p, d_bits.p, st);
+        HIPCHK(hipStreamSynchronize(st));  // the two buffers are reused by the next view
+    }
+    mvsk_seed_flags(d_cams.p, e->cfg.level, d_xyz.p, d_sum.p, d_bits.p, n, d_keep.p, st);
+    mvsk_exclusive_scan(d_keep.p, d_base.p, n, d_scan.p, st);
+    int32_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, d_base.p + n, sizeof total, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    if (e->pool_n + (int64_t)total > e->pool.cap) { g_err = "mvs_engine_seed_patches: patch pool capacity exceeded (raise mvs_config.max_patches)"; return MVS_ERR_CAPACITY; }
+    if (total > 0) {
+        // Optim::sortImages' threshold as the mirror writes it (optim.cpp:222), in float; Patch::m_ncc = -1 in mvs_engine_upload_patches' score2
+        volatile float deg10 = 10.0f * (float)M_PI / 180.0f;
+        const float thr = 1.0f - cosf(deg10);
+        const float tmp_unit = std::max(0.0f, -1.0f - e->prm.nccThreshold);
+        mvsk_seed_emit(d_cams.p, nviews, e->cfg.level, thr, tmp_unit, d_xyz.p, d_sum.p, d_bits.p, d_keep.p, d_base.p, n, e->pool.p + e->pool_n, st);
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        e->pool_n += (int64_t)total;
+        e->ncc_dirty = true;
+    }
+    if (n_added) *n_added = (int64_t)total;
+    return MVS_OK;
+}
+
 // Sizes the buffers of both cell indexes for `list_entries` memberships each (0: MAX_NUM_OF_PATCHES per cell of every view, what
 // m_pgrids holds after the trim), so that Propagate::run / Filter::run allocate nothing while the lists stay below that: the first
 // iterations of a run otherwise grow them inside the call (free + allocate, gigabytes at a time).  A reserve that fails may leave

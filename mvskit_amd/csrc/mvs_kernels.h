@@ -59,3 +59,15 @@ void mvsk_ply_select(const DPatch* pool, const int32_t* base, int64_t i0, int64_
 void mvsk_ply_colour(const DPatch* pool, const int32_t* idx, int64_t n, const DView* views, int nviews, int level, int ascii, uint32_t* rgb, int32_t* len,
                      hipStream_t st);
 void mvsk_ply_emit(const DPatch* pool, const int32_t* idx, int64_t n, const uint32_t* rgb, const int64_t* off, uint8_t* out, hipStream_t st);
+// mvs_engine_seed_patches (mvs_seed.hip): DepthNormInit::createPatches' PLY branch.  SeedView: what the accumulate launch of one view
+// needs by value; SeedCam: the camera centre and pixel scale Optim::sortImages reads, one per view in device memory.
+struct SeedView { float P[12]; int32_t W, H, view; };
+struct SeedCam { float center[4]; float ipscale; };
+// one view's pass over the points: sum[3 i ..] += map[pixel], bits[i] |= 1 << view where the point projects onto a foreground pixel
+void mvsk_seed_accumulate(const SeedView& sv, const float* map, const uint8_t* mask, const float* xyz, int64_t n, float* sum, unsigned long long* bits,
+                          hipStream_t st);
+// keep[i] = 1 where point i gives a patch; then, with base = the exclusive scan of keep, the records at dst[base[i]]
+void mvsk_seed_flags(const SeedCam* cams, int level, const float* xyz, const float* sum, const unsigned long long* bits, int64_t n, int32_t* keep,
+                     hipStream_t st);
+void mvsk_seed_emit(const SeedCam* cams, int nviews, int level, float thr, float tmp_unit, const float* xyz, const float* sum, const unsigned long long* bits,
+                    const int32_t* keep, const int32_t* base, int64_t n, DPatch* dst, hipStream_t st);

@@ -1,0 +1,173 @@
+// mvs_seed.hip -- DepthNormInit::createPatches with isTest = 0 (depth_normal_init.cpp:34-91) on the device: a depth point cloud and one
+// world-space normal map per view -> the seed patches, appended to the pool in point order (mvs_engine_seed_patches in mvs_engine.cpp
+// drives it).
+//   k_seed_accumulate  one lane per point, one launch per view in view order: level-0 projection, the pixel's mask byte, the gather of
+//                      the map's normal into the point's float sum, the view's membership bit
+//   k_seed_flags       one lane per point: the two-step normalisation, then how many member views see the front of the patch
+//                      (Optim::computeUnits' dot > 0): keep = at least two members, a non-zero sum, at least two such views
+//   k_seed_emit        one wave per kept point, one lane per view: Optim::sortImages with isFixed = 0, the record written at
+//                      pool_n + base[point] (base = the exclusive scan of the keep flags: no atomic decides a position)
+// The arithmetic is the host mirror's (DepthNormInit::buildPatches / sortImages in mvskit_amd/host/pmmvps_host.cpp), operation for
+// operation: plain fp32 products and sums from left to right (no fmaf chains: -ffp-contract=off keeps them apart), IEEE `/` and sqrtf
+// (correctly rounded over the whole range, zero sums and far-away points included, where the engine's div_rn / sqrt_rn helpers are
+// specified for the sweep's lengths and depths only), Optim::getUnit's division in double.  A record therefore has the mirror's bits.
+#include <hip/hip_runtime.h>
+
+#include "mvs_device.cuh"
+#include "mvs_kernels.h"
+
+using namespace mvsdev;
+
+#define SEED_BLOCK 256
+
+// PhotoSet::project at level 0 (camera.cpp:310-326) as the mirror computes it, then the pixel floorf(x + 0.5f).  False: behind the
+// camera (the mirror's -65535 lies outside every image) or outside the image.  The bounds are tested on the floats, so that a
+// coordinate no int holds is outside too.
+DEV bool seed_pixel(const float (&P)[12], int W, int H, float X0, float X1, float X2, int& px, int& py) {
+    float v[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        float a = 0.0f;
+        a += P[4 * r] * X0; a += P[4 * r + 1] * X1; a += P[4 * r + 2] * X2; a += P[4 * r + 3] * 1.0f;
+        v[r] = a;
+    }
+    if (v[2] <= 0.0f) return false;
+    const float fx = floorf(v[0] / v[2] + 0.5f), fy = floorf(v[1] / v[2] + 0.5f);
+    if (!(fx >= 0.0f && fx < (float)W && fy >= 0.0f && fy < (float)H)) return false;
+    px = (int)fx; py = (int)fy;
+    return true;
+}
+
+__global__ __launch_bounds__(SEED_BLOCK) void k_seed_accumulate(SeedView sv, const float* __restrict__ map, const uint8_t* __restrict__ mask,
+                                                               const float* __restrict__ xyz, int64_t n, float* __restrict__ sum,
+                                                               unsigned long long* __restrict__ bits) {
+    const int64_t i = (int64_t)blockIdx.x * SEED_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    int px, py;
+    if (!seed_pixel(sv.P, sv.W, sv.H, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], px, py)) return;
+    const size_t pix = (size_t)py * sv.W + px;
+    if (!(mask[pix] > 127)) return;  // PhotoSet::getMask <= 0
+    sum[3 * i] += map[3 * pix]; sum[3 * i + 1] += map[3 * pix + 1]; sum[3 * i + 2] += map[3 * pix + 2];
+    bits[i] |= 1ull << sv.view;
+}
+
+// depth_normal_init.cpp:62-73: false when fewer than two views took part or the summed normal is zero; else the sum divided by the
+// count, then by its norm, and the plane offset
+DEV bool seed_normal(const float* __restrict__ sum, unsigned long long b, F4 coord, F4& normal) {
+    float n0 = sum[0], n1 = sum[1], n2 = sum[2];
+    const int cnt = __popcll(b);
+    float norm = sqrtf(n0 * n0 + n1 * n1 + n2 * n2);
+    if (cnt < 2 || norm == 0.0f) return false;
+    const float fc = (float)cnt;
+    n0 = n0 / fc; n1 = n1 / fc; n2 = n2 / fc;
+    norm = sqrtf(n0 * n0 + n1 * n1 + n2 * n2);
+    n0 = n0 / norm; n1 = n1 / norm; n2 = n2 / norm;
+    normal = {n0, n1, n2, -(coord.x * n0 + coord.y * n1 + coord.z * n2)};
+    return true;
+}
+
+// Optim::computeUnits for one view (optim.cpp:86-107, getUnit 34-41): the unit ray towards the camera and pixel size / cosine;
+// false when the patch faces away
+DEV bool seed_unit(const SeedCam& c, F4 coord, F4 normal, int level, F4& ray, float& unit) {
+    F4 r{c.center[0] - coord.x, c.center[1] - coord.y, c.center[2] - coord.z, c.center[3] - coord.w};
+    const float fz = sqrtf(r.x * r.x + r.y * r.y + r.z * r.z + r.w * r.w);
+    r = {r.x / fz, r.y / fz, r.z / fz, r.w / fz};
+    const float dot = r.x * normal.x + r.y * normal.y + r.z * normal.z + r.w * normal.w;
+    ray = r;
+    if (dot <= 0.0f) return false;
+    const float scale = c.ipscale == 0.0f ? 1.0f : (float)(2.0 * (double)fz * (double)(1 << level) / (double)c.ipscale);
+    unit = scale / dot;
+    return true;
+}
+
+__global__ __launch_bounds__(SEED_BLOCK) void k_seed_flags(const SeedCam* __restrict__ cams, int level, const float* __restrict__ xyz,
+                                                          const float* __restrict__ sum, const unsigned long long* __restrict__ bits, int64_t n,
+                                                          int32_t* __restrict__ keep) {
+    const int64_t i = (int64_t)blockIdx.x * SEED_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const F4 coord{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], 1.0f};
+    unsigned long long b = bits[i];
+    F4 normal;
+    int facing = 0;
+    if (seed_normal(sum + 3 * i, b, coord, normal)) {
+        while (b) {
+            const int v = __ffsll((long long)b) - 1;
+            b &= b - 1;
+            F4 ray;
+            float unit;
+            facing += seed_unit(cams[v], coord, normal, level, ray, unit) ? 1 : 0;
+        }
+    }
+    keep[i] = facing >= 2 ? 1 : 0;  // sortImages empties a list of fewer than two views: the pool holds no such patch
+}
+
+// Optim::sortImages(patch, 0), optim.cpp:221-258, in the wave-wide form of mvsdev::sort_images: lane v is view v, the minimum of the
+// remaining units by wave_min + ballot, the lowest lane among equals (std::min_element on the shrinking arrays, which stay in view order)
+__global__ __launch_bounds__(SEED_BLOCK) void k_seed_emit(const SeedCam* __restrict__ cams, int nviews, int level, float thr, float tmp_unit,
+                                                         const float* __restrict__ xyz, const float* __restrict__ sum,
+                                                         const unsigned long long* __restrict__ bits, const int32_t* __restrict__ keep,
+                                                         const int32_t* __restrict__ base, int64_t n, DPatch* __restrict__ dst) {
+    const int lane = lane_id();
+    const int64_t stride = (int64_t)gridDim.x * (SEED_BLOCK / MVS_WAVE);
+    for (int64_t i = (int64_t)blockIdx.x * (SEED_BLOCK / MVS_WAVE) + (threadIdx.x >> 6); i < n; i += stride) {
+        if (!keep[i]) continue;  // wave-uniform
+        const F4 coord{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], 1.0f};
+        const unsigned long long b = bits[i];
+        F4 normal;
+        if (!seed_normal(sum + 3 * i, b, coord, normal)) continue;
+        const bool in = (b >> lane) & 1ull;
+        F4 ray;
+        float unit = 0.0f;
+        const bool valid = seed_unit(cams[in && lane < nviews ? lane : 0], coord, normal, level, ray, unit) && in;
+        unsigned long long active = ballot(valid);
+        int out = 0, k = 0;
+        while (active) {
+            const bool act = (active >> lane) & 1ull;
+            const float m = wave_min(act ? unit : __int_as_float(0x7f800000));
+            const unsigned long long eq = ballot(act && unit == m);
+            const int sel = eq ? __ffsll((long long)eq) - 1 : __ffsll((long long)active) - 1;  // NaN guard: first remaining
+            if (lane == k) out = sel;
+            const F4 rsel{rlf(ray.x, sel), rlf(ray.y, sel), rlf(ray.z, sel), rlf(ray.w, sel)};
+            active &= ~(1ull << sel);
+            if (act && lane != sel) {
+                float d = 0.0f;
+                d += rsel.x * ray.x; d += rsel.y * ray.y; d += rsel.z * ray.z; d += rsel.w * ray.w;
+                const float ftmp = fminf(thr, fmaxf(thr / 2.0f, 1.0f - d));
+                unit = unit * thr / ftmp;
+            }
+            ++k;
+        }
+        // the record as mvs_engine_upload_patches leaves one: the list cut to MVS_LISTCAP after the sort, m_vimages empty, m_ncc = -1
+        // (Patch::Patch), m_tmp = score2, alive
+        const int nimg = min(k, MVS_LISTCAP);
+        DPatch* rec = dst + base[i];
+        if (lane < MVS_MAXI) {
+            rec->images[lane] = lane < nimg ? (uint8_t)out : (uint8_t)0;
+            rec->vimages[lane] = 0;
+        }
+        if (lane == 0) {
+            rec->coord[0] = coord.x; rec->coord[1] = coord.y; rec->coord[2] = coord.z; rec->coord[3] = 1.0f;
+            rec->normal[0] = normal.x; rec->normal[1] = normal.y; rec->normal[2] = normal.z; rec->normal[3] = normal.w;
+            rec->ncc = -1.0f; rec->dscale = 0.0f; rec->ascale = 0.0f; rec->tmp = tmp_unit * (float)nimg;
+            rec->nimages = nimg; rec->nvimages = 0; rec->flags = MVS_FLAG_ALIVE; rec->id = 0;
+        }
+    }
+}
+
+static inline unsigned seed_blocks(int64_t n) { return (unsigned)((n + SEED_BLOCK - 1) / SEED_BLOCK); }
+
+void mvsk_seed_accumulate(const SeedView& sv, const float* map, const uint8_t* mask, const float* xyz, int64_t n, float* sum, unsigned long long* bits,
+                          hipStream_t st) {
+    if (n > 0) hipLaunchKernelGGL(k_seed_accumulate, dim3(seed_blocks(n)), dim3(SEED_BLOCK), 0, st, sv, map, mask, xyz, n, sum, bits);
+}
+void mvsk_seed_flags(const SeedCam* cams, int level, const float* xyz, const float* sum, const unsigned long long* bits, int64_t n, int32_t* keep,
+                     hipStream_t st) {
+    if (n > 0) hipLaunchKernelGGL(k_seed_flags, dim3(seed_blocks(n)), dim3(SEED_BLOCK), 0, st, cams, level, xyz, sum, bits, n, keep);
+}
+void mvsk_seed_emit(const SeedCam* cams, int nviews, int level, float thr, float tmp_unit, const float* xyz, const float* sum, const unsigned long long* bits,
+                    const int32_t* keep, const int32_t* base, int64_t n, DPatch* dst, hipStream_t st) {
+    if (n <= 0) return;
+    const int64_t per = SEED_BLOCK / MVS_WAVE;
+    const unsigned nb = (unsigned)std::min<int64_t>((n + per - 1) / per, (int64_t)1 << 20);
+    hipLaunchKernelGGL(k_seed_emit, dim3(nb), dim3(SEED_BLOCK), 0, st, cams, nviews, level, thr, tmp_unit, xyz, sum, bits, keep, base, n, dst);
+}

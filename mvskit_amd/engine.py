@@ -25,7 +25,7 @@ EXPORTS = [
     "mvs_engine_commit_local", "mvs_engine_depth_normal_map", "mvs_engine_probe", "mvs_engine_last_timing",
     "mvs_engine_filter", "mvs_comm_unique_id", "mvs_engine_comm_init", "mvs_engine_comm_attach", "mvs_engine_comm_release",
     "mvs_engine_exchange", "mvs_list_cap", "mvs_engine_filter_stats", "mvs_patch_bytes", "mvs_engine_reserve", "mvs_engine_comm_info",
-    "mvs_default_refiner", "mvs_engine_set_refiner", "mvs_engine_export_ply",
+    "mvs_default_refiner", "mvs_engine_set_refiner", "mvs_engine_export_ply", "mvs_engine_seed_patches",
 ]
 PLY_ASCII, PLY_BINARY_LE = 0, 1  # mvs_ply_format
 #: one vertex of the binary PLY file (mvs_engine_export_ply): 27 packed bytes
@@ -50,6 +50,11 @@ class Refiner(C.Structure):
 class ViewDesc(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("P", C.c_float * 12), ("rgb", C.c_void_p),
                 ("mask", C.c_void_p)]
+
+
+class SeedView(C.Structure):
+    """mvs_seed_view: one view's world-space normal map and level-0 mask (mvs_engine_seed_patches)."""
+    _fields_ = [("normals", C.c_void_p), ("mask", C.c_void_p)]
 
 
 class Counters(C.Structure):
@@ -140,6 +145,8 @@ def load_library(cap32: bool = False, cap: int = 0):
         L.mvs_engine_set_refiner.argtypes = [vp, C.POINTER(Refiner)]
     if hasattr(L, "mvs_engine_export_ply"):
         L.mvs_engine_export_ply.argtypes = [vp, C.c_int, C.c_int64, vp, C.POINTER(C.c_int64)]
+    if hasattr(L, "mvs_engine_seed_patches"):
+        L.mvs_engine_seed_patches.argtypes = [vp, C.c_int64, vp, C.POINTER(SeedView), C.POINTER(C.c_int64)]
     _libs[LIB_PATH] = L
     return L
 
@@ -204,6 +211,7 @@ class Engine:
                 keep.append(m)
                 descs[v].mask = m.ctypes.data
         self._check(self.L.mvs_engine_set_views(self.h, n, descs))
+        self._view_shape = (scene.H, scene.W)
 
     def grid_dims(self, v):
         gw, gh = C.c_int(), C.c_int()
@@ -243,6 +251,36 @@ class Engine:
         self._check(self.L.mvs_engine_upload_patches(self.h, recs.shape[0], _ptr(recs)))
 
     add_patches = upload_patches
+
+    def seed_patches(self, points, normal_maps, masks=None):
+        """DepthNormInit::createPatches' PLY branch on the device (include/mvskit_engine.h, mvs_engine_seed_patches): appends the seed
+        patches of `points` (N x 3 world coordinates) to the pool, in point order, and returns how many.  normal_maps[v]: H x W x 3
+        float32 in world axes, zero where the view has no normal, or None; masks[v]: H x W uint8 level-0 mask (> 127 = foreground) or
+        None.  A view without a mask takes no part (the reference's rule), so masks=None seeds nothing."""
+        n = self.cfg.nviews
+        if len(normal_maps) != n or (masks is not None and len(masks) != n):
+            raise ValueError(f"seed_patches: {n} views, one normal map (and mask) each")
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        shape = getattr(self, "_view_shape", None)
+        views = (SeedView * n)()
+        keep = [pts]
+        for v in range(n):
+            views[v].normals = views[v].mask = None
+            if normal_maps[v] is not None:
+                m = np.ascontiguousarray(normal_maps[v], dtype=np.float32)
+                if shape is not None and m.shape != shape + (3,):
+                    raise ValueError(f"seed_patches: normal map {v} has shape {m.shape}, the view is {shape + (3,)}")
+                keep.append(m)
+                views[v].normals = m.ctypes.data
+            if masks is not None and masks[v] is not None:
+                k = np.ascontiguousarray(masks[v], dtype=np.uint8)
+                if shape is not None and k.shape != shape:
+                    raise ValueError(f"seed_patches: mask {v} has shape {k.shape}, the view is {shape}")
+                keep.append(k)
+                views[v].mask = k.ctypes.data
+        added = C.c_int64()
+        self._check(self.L.mvs_engine_seed_patches(self.h, pts.shape[0], _ptr(pts), views, C.byref(added)))
+        return added.value
 
     def reserve(self, list_entries=0):
         """Sizes the cell indexes up front (0: MAX_NUM_OF_PATCHES per cell of every view): no allocation inside the iterations."""

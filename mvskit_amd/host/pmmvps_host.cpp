@@ -507,6 +507,10 @@ int DepthNormInit::buildPatches(vector<Ppatch>& ppatches) {  // depth_normal_ini
     if (readDepths(coords) != 0) return -1;
     vector<vector<std::array<float, 3> > > normals((size_t)std::max(0, m_nplys - 1));
     if (readNormals(normals) != 0) return -1;
+    return buildPatches(coords, normals, ppatches);
+}
+// the loop of depth_normal_init.cpp:46-85 on arrays already read: the CPU yardstick of mvs_engine_seed_patches
+int DepthNormInit::buildPatches(const vector<std::array<float, 3> >& coords, const vector<vector<std::array<float, 3> > >& normals, vector<Ppatch>& ppatches) {
     const PhotoSet& ps = m_pmmvps.m_photoSet;
     for (size_t i = 0; i < coords.size(); ++i) {
         Ppatch ppatch(new Patch());
@@ -543,9 +547,21 @@ void DepthNormInit::createPatches() {  // depth_normal_init.cpp:29-91
         if (m_pmmvps.m_patchManager.readPatches() != 0) cerr << "DepthNormInit::createPatches: no ply/00000000.patch under " << m_pmmvps.m_prefix << endl;
         return;
     }
-    vector<Ppatch> pp;
-    if (buildPatches(pp) != 0) { m_pmmvps.m_status = MVS_ERR_ARG; return; }
-    m_pmmvps.m_patchManager.addPatches(pp);
+    // the PLY branch: the files are read and the maps scattered here (readNormals: the last vertex of a pixel wins, in file order);
+    // the patches themselves are built on the device (mvs_engine_seed_patches), from the level-0 masks PhotoSet holds
+    if (m_nplys <= 0) init(m_pmmvps.m_prefix, m_pmmvps.m_nimages + 1);  // pmmvps.cpp:45
+    vector<std::array<float, 3> > coords;
+    vector<vector<std::array<float, 3> > > normals((size_t)std::max(0, m_nplys - 1));
+    if (readDepths(coords) != 0 || readNormals(normals) != 0) { m_pmmvps.m_status = MVS_ERR_ARG; return; }
+    const PhotoSet& ps = m_pmmvps.m_photoSet;
+    vector<mvs_seed_view> views((size_t)m_pmmvps.m_nimages, mvs_seed_view{nullptr, nullptr});
+    for (int i = 0; i < m_pmmvps.m_nimages && i < (int)normals.size(); ++i) {
+        views[i].normals = normals[i].empty() ? nullptr : normals[i][0].data();
+        views[i].mask = ps.m_photos[i].m_mask.empty() ? nullptr : ps.m_photos[i].m_mask.data();
+    }
+    int64_t added = 0;
+    const int r = mvs_engine_seed_patches(m_pmmvps.m_engine, (int64_t)coords.size(), coords.empty() ? nullptr : coords[0].data(), views.data(), &added);
+    if (r != 0) { cerr << "DepthNormInit::createPatches: " << mvs_last_error() << endl; m_pmmvps.m_status = r; }
 }
 
 // ------------------------------------------------------------------ Filter
@@ -885,4 +901,41 @@ extern "C" long long mvshost_seeds_from_plys(const char* prefix, long long cap, 
     if (pmmvps.m_dnInit.buildPatches(pp) != 0) return -3;
     for (long long i = 0; i < std::min<long long>(cap, (long long)pp.size()); ++i) out[i] = to_record(*pp[i]);
     return (long long)pp.size();
+}
+// The parent path of DepthNormInit::createPatches on arrays (tools/seed_probe.py): DepthNormInit::buildPatches' loop and
+// PatchManager::addPatches (conversion to records + mvs_engine_upload_patches into a fresh engine) on nviews views of one size with
+// level-0 masks (or null), world-space normal maps [n][H][W][3] and npoints points.  Returns the number of patches in the pool or a
+// negative status; mvshost_seed_cpu_ms() then gives the wall time of the loop and of addPatches in milliseconds (std::chrono).
+static double g_seed_cpu_ms[2] = {0.0, 0.0};
+extern "C" void mvshost_seed_cpu_ms(double* loop_ms, double* add_ms) { if (loop_ms) *loop_ms = g_seed_cpu_ms[0]; if (add_ms) *add_ms = g_seed_cpu_ms[1]; }
+extern "C" long long mvshost_seed_cpu_probe(int nviews, int width, int height, const float* P, const unsigned char* rgb, const unsigned char* masks /*[n][H][W] or null*/,
+                                            const float* normals, long long npoints, const float* xyz, int level) {
+    using namespace mvshost;
+    Option option;
+    option.m_nimages = nviews; option.m_nillums = 1; option.m_level = level; option.m_csize = 2; option.m_wsize = 7;
+    option.m_minImageNum = 2; option.m_nccThreshold = 0.7f; option.m_flag = -1;
+    for (int i = 0; i < nviews; ++i) option.m_images.push_back(i);
+    PhotoSet ps;
+    ps.m_images = option.m_images;
+    const size_t pix = (size_t)width * height;
+    for (int i = 0; i < nviews; ++i) { ps.m_dict[i] = i; ps.setPhoto(i, width, height, P + 12 * i, rgb + (size_t)i * pix * 3, masks ? masks + (size_t)i * pix : nullptr); }
+    PmMvps pmmvps;
+    pmmvps.m_writeFiles = false;
+    pmmvps.init(option, ps);
+    if (pmmvps.m_status) return pmmvps.m_status;
+    vector<std::array<float, 3> > coords((size_t)npoints);
+    if (npoints > 0) memcpy(coords[0].data(), xyz, sizeof(float) * 3 * (size_t)npoints);
+    vector<vector<std::array<float, 3> > > maps((size_t)nviews);
+    for (int i = 0; i < nviews; ++i) { maps[i].resize(pix); memcpy(maps[i][0].data(), normals + (size_t)i * pix * 3, sizeof(float) * 3 * pix); }
+    vector<Ppatch> pp;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (pmmvps.m_dnInit.buildPatches(coords, maps, pp) != 0) return -1;
+    const auto t1 = std::chrono::steady_clock::now();
+    pmmvps.m_patchManager.addPatches(pp);
+    const auto t2 = std::chrono::steady_clock::now();
+    g_seed_cpu_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    g_seed_cpu_ms[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    int64_t n = 0;
+    if (int r = mvs_engine_num_patches(pmmvps.m_engine, &n)) return r;
+    return (long long)n;
 }

@@ -168,6 +168,7 @@ public:
     void createPatches();
     // the host part of the PLY branch: the patches createPatches() then hands to PatchManager (no engine involved)
     int buildPatches(vector<Ppatch>& ppatches);
+    int buildPatches(const vector<std::array<float, 3> >& coords, const vector<vector<std::array<float, 3> > >& normals, vector<Ppatch>& ppatches);
     int m_isTest = 1;
 
 protected:
