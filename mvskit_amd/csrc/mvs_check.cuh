@@ -225,12 +225,6 @@ DEV int wave_max_scan(int x) {
     x = max(x, __builtin_amdgcn_update_dpp(-1, x, 0x143, 0xc, 0xf, false));
     return x;
 }
-#ifndef MVS_FN_MARKS
-#define MVS_FN_MARKS 1
-#endif
-#ifndef MVS_FN_JOINT_PROBE
-#define MVS_FN_JOINT_PROBE 1
-#endif
 // `marks` (MK): 64 ints of LDS outside the table -- the run of an id by marks and a running maximum instead of a binary search, see below
 // JP: the probe sequences of a lane's four keys side by side (see below) -- fewer waits, more instructions: the sweep, three waves per
 // SIMD and waiting, gains 0.4 % from it; Filter::filterNeighbor, whose vector ALU is 89 % busy, loses 6 %
@@ -351,22 +345,6 @@ DEV int find_neighbors(const DParams& prm, const WaveCtx& wc, const CheckCtx& cx
                     const int k = k0 + 64 * q + wc.lane;
                     const unsigned lo = (unsigned)__builtin_amdgcn_ds_bpermute(run[q] << 2, (int)blo), hi = (unsigned)__builtin_amdgcn_ds_bpermute(run[q] << 2, (int)bhi);
                     int v_id = MVS_SET_EMPTY;
-#if MVS_FN_MARKS == 2  // debugging: the address by the search as well; loads through that one and reports a difference
-                    {
-                        int lo2 = 0;
-                        for (int step = 32; step >= 1; step >>= 1) { const int pc = __shfl(P, lo2 + step); if (pc <= k) lo2 += step; }
-                        const csr_off_t bb = __shfl(b, lo2);
-                        const int pl = __shfl(P, lo2), sr = __shfl(src, lo2);
-                        if (k < total) {
-                            const int32_t* want = sr == 2 ? nullptr : (sr == 1 ? prm.vcsr_id32 : prm.csr_id32) + (bb + (k - pl));
-                            const int32_t* got = reinterpret_cast<const int32_t*>(((unsigned long long)hi << 32) | lo) + k;
-                            const bool livegot = live_i >= 0 && hi == 0x7fffffffu;
-                            if ((sr == 2) != livegot || (sr == 2 ? ((int)lo + k != k - pl) : (want != got)))
-                                printf("[marks] block %d lane %d k %d total %d run %d search %d sr %d hi %08x lo %08x want %p got %p live_i %d nrow_all %d r0 %d k0 %d\n", (int)blockIdx.x, wc.lane, k, total, run[q], lo2, sr, hi, lo, want, got, live_i, nrow_all, r0, k0);
-                            v_id = sr == 2 ? cx.live_ids[k - pl] : *want;
-                        }
-                    }
-#else
                     // Two loads in their own address spaces.  As ONE generic pointer the compiler folds the "+ 64 q" of k into the flat
                     // instruction's offset field, and the address without it lies below the LDS aperture for the first ids of the live list
                     // (k - 64 q < P): the hardware picks the aperture before it adds the offset -- a memory aperture violation.
@@ -376,7 +354,6 @@ DEV int find_neighbors(const DParams& prm, const WaveCtx& wc, const CheckCtx& cx
                         if (live_i >= 0 && hi == 0x7fffffffu) v_id = ((lptr_i32)cx.live_ids)[(int)lo + k];
                         else v_id = ((gptr_i32)(((unsigned long long)hi << 32) | lo))[k];
                     }
-#endif
                     id[q] = v_id;
                 }
             } else
@@ -720,7 +697,7 @@ MVS_CHECK_FN int check_patch(const DParams& prm, const WaveCtx& wc, const CheckC
     if (MVS_CHECK_STAGES < 2) return 0;
     int* table = reinterpret_cast<int*>(lds);
     static_assert(MVS_HASH_CAP + 64 <= MVS_CHECK_LDS_FLOATS, "the marks of the row walk sit behind the id set");
-    int n = find_neighbors<MVS_HASH_CAP, false, false, MVS_FN_MARKS != 0, MVS_FN_JOINT_PROBE != 0>(prm, wc, cx, c, table, 4.0f, 2, nullptr, table + MVS_HASH_CAP);
+    int n = find_neighbors<MVS_HASH_CAP, false, false, true, true>(prm, wc, cx, c, table, 4.0f, 2, nullptr, table + MVS_HASH_CAP);
     if (n < 0 || n > MVS_ROW_CAP) {
         if (!BIG) return -1;
         n = find_neighbors<MVS_FILTER2_HASH_CAP, true>(prm, wc, cx, c, big_table, 4.0f, 2);

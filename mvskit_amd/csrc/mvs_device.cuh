@@ -25,23 +25,6 @@ struct F3 { float x, y, z; };
 struct F4 { float x, y, z, w; };
 
 #define DEV __device__ __forceinline__
-// The stages around the refinement loop can be compiled as real calls (MVS_OUTLINE=1): their register live ranges
-// then do not interfere with the hot loop.
-#ifndef MVS_OUTLINE
-#define MVS_OUTLINE 0
-#endif
-// how far the texel loads run ahead of their use (1 = the next round / view only)
-#ifndef MVS_EV_DEPTH
-#define MVS_EV_DEPTH 1  // rounds of a single evaluation whose loads are in flight beyond the current one
-#endif
-#ifndef MVS_ST_DEPTH
-#define MVS_ST_DEPTH 1  // views of a refinement step whose loads are in flight beyond the current one
-#endif
-#if MVS_OUTLINE
-#define STAGE __device__ __noinline__
-#else
-#define STAGE __device__ __forceinline__
-#endif
 
 DEV int lane_id() { return (int)(threadIdx.x & 63u); }
 DEV float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
@@ -81,24 +64,13 @@ DEV float sqrt_rn(float x) {
 // float with 2^-120 <= |x| < 2^121 (4.04 * 10^9 inputs: no difference) and div_rn against `a / b` on 1.18 * 10^10 pairs (none) --
 // profiles/r04_div_exact.txt.  Outside that range (zero, subnormal, infinite or NaN divisors, quotients that over- or underflow) they
 // differ from IEEE division; they are used only where the divisor is a length, a depth, a focal scale or 1 + 3 incc of this path.
-#ifndef MVS_FASTDIV
-#define MVS_FASTDIV 1
-#endif
 DEV float rcp_rn(float x) {
-#if MVS_FASTDIV
     const float r = __builtin_amdgcn_rcpf(x);
     return __builtin_fmaf(__builtin_fmaf(-x, r, 1.0f), r, r);
-#else
-    return 1.0f / x;
-#endif
 }
 DEV float div_rn(float a, float b) {
-#if MVS_FASTDIV
     const float y = rcp_rn(b), q = a * y;
     return __builtin_fmaf(__builtin_fmaf(-b, q, a), y, q);
-#else
-    return a / b;
-#endif
 }
 DEV float norm4(F4 a) { return sqrt_rn(dot4(a, a)); }
 DEV float norm3(F3 a) { return sqrt_rn(dot3(a, a)); }
@@ -314,10 +286,6 @@ DEV void get_paxes(const DParams& prm, const DView* vw, F4 coord, F4 normal, F4&
     F3 x3 = cross3(y3, n3);
     px = {x3.x * pscale, x3.y * pscale, x3.z * pscale, 0.0f};
     py = {y3.x * pscale, y3.y * pscale, y3.z * pscale, 0.0f};
-#ifndef MVS_PAXES_SPREAD
-#define MVS_PAXES_SPREAD 1
-#endif
-#if MVS_PAXES_SPREAD
     const int j = lane_id() & 15;
     const float a = j == 1 ? 1.0f : 0.0f, b = j == 2 ? 1.0f : 0.0f;
     const F4 X{fma_(b, py.x, fma_(a, px.x, coord.x)), fma_(b, py.y, fma_(a, px.y, coord.y)), fma_(b, py.z, fma_(a, px.z, coord.z)), coord.w};
@@ -326,13 +294,6 @@ DEV void get_paxes(const DParams& prm, const DView* vw, F4 coord, F4 normal, F4&
     const float inv = rcp_rn(norm3(sub3(ic, c0)));  // lane 1: 1 / xdis, lane 2: 1 / ydis (lane 0 and the rest: 1 / 0, never read)
     px = scl4(px, row_bcast_f<1>(inv));
     py = scl4(py, row_bcast_f<2>(inv));
-#else
-    const F3 c0 = project_regs(P, coord);
-    const float xdis = norm3(sub3(project_regs(P, add4(coord, px)), c0));
-    const float ydis = norm3(sub3(project_regs(P, add4(coord, py)), c0));
-    px = scl4(px, rcp_rn(xdis));
-    py = scl4(py, rcp_rn(ydis));
-#endif
 }
 DEV float robustincc(float incc) { return div_rn(incc, 1 + 3 * incc); }
 DEV float unrobustincc(float r) { return div_rn(r, 1 - 3 * r); }
@@ -352,27 +313,13 @@ struct Frame {
 // pick").  Those six thresholds are ONE float mantissa (that of sqrt 2, 0x3504F3) under six exponents, so for ratio = 2^e * 1.m the
 // largest k with ratio >= 2^(k - .5) is e + (m >= 0x3504F3): adding 0x800000 - 0x3504F3 to the bits carries into the exponent exactly
 // then -- three integer instructions for six compares and selects; the clamp to [-4, 2] takes care of zero, tiny and huge ratios as
-// the chain of comparisons did (a NaN ratio, which only a degenerate frame that is rejected anyway can produce, read -4 there and
-// reads 2 here).
-#ifndef MVS_FS1
-#define MVS_FS1 1
-#endif
+// the chain of comparisons does (a NaN ratio, which only a degenerate frame that is rejected anyway can produce, reads -4 there and
+// 2 here).
 DEV int level_diff(const DParams& prm, float ratio) {
-#if MVS_FS1
     static_assert(0x3504F3 == (0x3FB504F3 & 0x7FFFFF), "mantissa of 1.414213562373095f");
     const int k = ((__float_as_int(ratio) + (0x800000 - 0x3504F3)) >> 23) - 127;
     const int ld = max(-4, min(2, k));
     return max(-prm.level, min(2, ld));
-#else
-    int ld = -4;
-    if (ratio >= 0.088388347648318f) ld = -3;
-    if (ratio >= 0.176776695296637f) ld = -2;
-    if (ratio >= 0.353553390593274f) ld = -1;
-    if (ratio >= 0.707106781186548f) ld = 0;
-    if (ratio >= 1.414213562373095f) ld = 1;
-    if (ratio >= 2.828427124746190f) ld = 2;
-    return max(-prm.level, min(2, ld));
-#endif
 }
 DEV float pow2_level(int ld) { return __int_as_float((127 + ld) << 23); }  // Optim::myPow2, exact powers of two
 // Straight-line: every load of the view's constants is issued at the top (one wait instead of one per early exit --
@@ -403,19 +350,10 @@ DEV Frame make_frame(const DParams& prm, F4 coord, F4 px, F4 py, F4 pz, int v, b
     // combinations.  Rounding is monotone, so the smallest of the four is (c - |a|) - |b| and the largest (c + |a|) + |b| -- the very
     // values the reference's min / max over the corners pick (optim.cpp:902-912), without forming the other three corners.
     const float m = (float)(prm.wsize / 2);
-#if MVS_FS1
     const float ax = dx.x * m, bx = dy.x * m, ay = dx.y * m, by = dy.y * m;
     const float tlx = (center.x - ax) - bx, tly = (center.y - ay) - by;
     const float minx = (center.x - fabsf(ax)) - fabsf(bx), maxx = (center.x + fabsf(ax)) + fabsf(bx);
     const float miny = (center.y - fabsf(ay)) - fabsf(by), maxy = (center.y + fabsf(ay)) + fabsf(by);
-#else
-    const float tlx = (center.x - dx.x * m) - dy.x * m, trx = (center.x + dx.x * m) - dy.x * m;
-    const float blx = (center.x - dx.x * m) + dy.x * m, brx = (center.x + dx.x * m) + dy.x * m;
-    const float tly = (center.y - dx.y * m) - dy.y * m, try_ = (center.y + dx.y * m) - dy.y * m;
-    const float bly = (center.y - dx.y * m) + dy.y * m, bry = (center.y + dx.y * m) + dy.y * m;
-    const float minx = fminf(tlx, fminf(trx, fminf(blx, brx))), maxx = fmaxf(tlx, fmaxf(trx, fmaxf(blx, brx)));
-    const float miny = fminf(tly, fminf(try_, fminf(bly, bry))), maxy = fmaxf(tly, fmaxf(try_, fmaxf(bly, bry)));
-#endif
     const int margin2 = 2;
     const int W = W0 >> newLevel, H = H0 >> newLevel;  // the pyramid halves (rounding down) at every level
     const bool inside = !(minx < margin2 || W - 1 - margin2 <= maxx || miny < margin2 || H - 1 - margin2 <= maxy);
@@ -576,35 +514,23 @@ DEV void eval_steps4(const DParams& prm, WaveCtx& wc, const ClsConst& cc, const 
     const int lc = wc.lane & 15;
     float c0[3][3];
     ClsPend pend[3];
-#if MVS_ST_DEPTH > 1
-    ClsPend ahead[3];  // the loads of the view after next (many-view builds: one or two waves per SIMD hide no latency)
-#endif
     float P1r, P1g, P1b, P2, P01 = 0.0f;
     const int vlast = max(n - 1, 0);
     {
         const ClsFrame fr = cls_frame(fb);
 #pragma unroll
         for (int j = 0; j < 3; ++j) pend[j] = cls_issue(fr, cls_opaque(cc.cs[j]));
-#if MVS_ST_DEPTH > 1
-        const ClsFrame f1 = cls_frame(fb + min(1, vlast));
-#pragma unroll
-        for (int j = 0; j < 3; ++j) ahead[j] = cls_issue(f1, cls_opaque(cc.cs[j]));
-#endif
     }
     {   // the reference view
         const float4 pv = mvs_dyn_lds4[MVS_PIVOT_LDS4];
-        const ClsFrame fn = cls_frame(fb + min(MVS_ST_DEPTH, vlast));
+        const ClsFrame fn = cls_frame(fb + min(1, vlast));
         float s1r = 0.0f, s1g = 0.0f, s1b = 0.0f, s2 = 0.0f;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const unsigned cs = cls_opaque(cc.cs[j]);
             float r, g, b;
             cls_colour(pend[j], cs, pv.x, pv.y, pv.z, r, g, b);
-#if MVS_ST_DEPTH > 1
-            pend[j] = ahead[j]; ahead[j] = cls_issue(fn, cs);
-#else
             pend[j] = cls_issue(fn, cs);
-#endif
             c0[j][0] = r; c0[j][1] = g; c0[j][2] = b;
             s1r += r; s1g += g; s1b += b;
             s2 = fma_(r, r, s2); s2 = fma_(g, g, s2); s2 = fma_(b, b, s2);
@@ -614,18 +540,14 @@ DEV void eval_steps4(const DParams& prm, WaveCtx& wc, const ClsConst& cc, const 
     }
     for (int k = 1; k < n; ++k) {
         const float4 pv = mvs_dyn_lds4[MVS_PIVOT_LDS4 + k];
-        const ClsFrame fn = cls_frame(fb + min(k + MVS_ST_DEPTH, vlast));
+        const ClsFrame fn = cls_frame(fb + min(k + 1, vlast));
         float s1r = 0.0f, s1g = 0.0f, s1b = 0.0f, s2 = 0.0f, s01 = 0.0f;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const unsigned cs = cls_opaque(cc.cs[j]);
             float r, g, b;
             cls_colour(pend[j], cs, pv.x, pv.y, pv.z, r, g, b);
-#if MVS_ST_DEPTH > 1
-            pend[j] = ahead[j]; ahead[j] = cls_issue(fn, cs);
-#else
             pend[j] = cls_issue(fn, cs);
-#endif
             s1r += r; s1g += g; s1b += b;
             s2 = fma_(r, r, s2); s2 = fma_(g, g, s2); s2 = fma_(b, b, s2);
             s01 = fma_(r, c0[j][0], s01); s01 = fma_(g, c0[j][1], s01); s01 = fma_(b, c0[j][2], s01);
@@ -687,13 +609,8 @@ DEV void cls_raw(const ClsPend& p, unsigned cs, float& r, float& g, float& b) { 
 }
 #define MVS_ROW_STEP3(C) { const float t0 = dpp0_f<C>(s1r), t1 = dpp0_f<C>(s1g), t2 = dpp0_f<C>(s1b); s1r = s1r + t0; s1g = s1g + t1; s1b = s1b + t2; }
 #define MVS_ROW_STEP2(C) { const float t0 = dpp0_f<C>(sq), t1 = dpp0_f<C>(dt); sq = sq + t0; dt = dt + t1; }
-#ifndef MVS_EV_PREFETCH
-#define MVS_EV_PREFETCH 1
-#endif
 
-#ifndef MVS_PAIR_MFMA
 #define MVS_PAIR_MFMA (MVS_LISTCAP > 16)  // setRefImage's pair sums on the matrix cores (the 32- and 64-view builds)
-#endif
 #if MVS_PAIR_MFMA
 // The Gram matrix G[a][b] = sum(k) t_a[k] t_b[k] of the kept textures is taken WHILE the views are sampled, in chunks of 16 views, so
 // that only one chunk of textures lies in LDS at a time (the textures of a whole 32- or 64-view list were what held these builds at one
@@ -709,11 +626,9 @@ DEV void cls_raw(const ClsPend& p, unsigned cs, float& r, float& g, float& b) { 
 // Rounds 3-4 kept chunk A (half the list) in 37 / 74 registers while chunk B was sampled: the 64-view build then needed the 256 VGPRs
 // and the 22 KB of LDS of two waves per SIMD and ran at 11.5 M patches/s on 48 x 540p; 13.6 M with form 1, 14.5 M with form 2
 // (gpurun_out/r04l, r04m); the 32-view build 17.4 M either way, 16.6 M with form 2.
-#ifndef MVS_GRAM_SCRATCH
 #define MVS_GRAM_SCRATCH (MVS_LISTCAP > 32 ? 2 : 1)
-#endif
 #define MVS_GRAM_CH 16
-#define MVS_GRAM_NCH (MVS_LISTCAP / 16)                          // chunks at most: 2 or 4 (1 in an experimental 16-view build)
+#define MVS_GRAM_NCH (MVS_LISTCAP / 16)                          // chunks at most: 2 or 4
 #define MVS_GRAM_NT (MVS_GRAM_NCH * (MVS_GRAM_NCH + 1) / 2)     // tiles (p <= c): 3 or 10
 #define MVS_GRAM_KSP 40                                         // MVS_GRAM_KS rounded up to groups of 8 k-steps
 #define MVS_GRAM_T(p, c) ((c) * ((c) + 1) / 2 + (p))
@@ -736,7 +651,7 @@ DEV void eval_views(const DParams& prm, WaveCtx& wc, const Frame& f, int n, vmas
     float gops[MVS_GRAM_NCH * MVS_GRAM_KSP];           // private memory: the MFMA operands of ALL chunks (lane l: t_{l % 16}[4 s + l / 16])
 #elif MVS_GRAM_SCRATCH
     gram_acc_t gacc[MVS_GRAM_NT];                      // tile (p, c), p <= c, at MVS_GRAM_T(p, c)
-    float gops[(MVS_GRAM_NCH > 1 ? MVS_GRAM_NCH - 1 : 1) * MVS_GRAM_KSP];  // private memory: the MFMA operands of the finished chunks (lane l: t_{l % 16}[4 s + l / 16]); unused with one chunk
+    float gops[(MVS_GRAM_NCH - 1) * MVS_GRAM_KSP];     // private memory: the MFMA operands of the finished chunks (lane l: t_{l % 16}[4 s + l / 16])
 #pragma unroll
     for (int q = 0; q < MVS_GRAM_NT; ++q)
 #pragma unroll
@@ -765,46 +680,24 @@ DEV void eval_views(const DParams& prm, WaveCtx& wc, const Frame& f, int n, vmas
     float d0[3][3], d0x[3] = {0.0f, 0.0f, 0.0f};
     float ssd_l = 1.0f, dot_l = 0.0f, mr_l = 128.0f, mg_l = 128.0f, mb_l = 128.0f;
     ClsPend pend[3];
-#if MVS_EV_DEPTH > 1
-    ClsPend ahead[MVS_EV_DEPTH - 1][3];  // the loads of the rounds t + 1 .. t + MVS_EV_DEPTH - 1 (many-view builds: one or two waves per SIMD hide no latency)
-#endif
     {
         const int last = max(n - 1, 0);  // an empty list never reaches this point; the clamps below stay inside the frames all the same
         const ClsFrame fr = cls_frame(min(row, last));
 #pragma unroll
         for (int j = 0; j < 3; ++j) pend[j] = cls_issue(fr, cls_opaque(cc.cs[j]));
-#if MVS_EV_DEPTH > 1
-#pragma unroll
-        for (int d = 0; d < MVS_EV_DEPTH - 1; ++d) {
-            const ClsFrame fd = cls_frame(min(row + 4 * (d + 1), last));
-#pragma unroll
-            for (int j = 0; j < 3; ++j) ahead[d][j] = cls_issue(fd, cls_opaque(cc.cs[j]));
-        }
-#endif
     }
     if (cc.nx > 0) cls_raw(pe, xcs, fxr, fxg, fxb);
     const int rounds = (n + 3) >> 2;
     auto round_body = [&](const int t) {
         const int v = 4 * t + row, vq = min(v, max(n - 1, 0));
-#if MVS_EV_PREFETCH
-        const ClsFrame fn = cls_frame(min(v + 4 * MVS_EV_DEPTH, max(n - 1, 0)));
-#endif
+        const ClsFrame fn = cls_frame(min(v + 4, max(n - 1, 0)));
         float cr[3], cg[3], cb[3];
         float s1r = 0.0f, s1g = 0.0f, s1b = 0.0f;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const unsigned cs = cls_opaque(cc.cs[j]);
             cls_raw(pend[j], cs, cr[j], cg[j], cb[j]);
-#if MVS_EV_PREFETCH
-#if MVS_EV_DEPTH > 1
-            pend[j] = ahead[0][j];
-#pragma unroll
-            for (int d = 0; d + 1 < MVS_EV_DEPTH - 1; ++d) ahead[d][j] = ahead[d + 1][j];
-            ahead[MVS_EV_DEPTH - 2][j] = cls_issue(fn, cs);
-#else
             pend[j] = cls_issue(fn, cs);
-#endif
-#endif
             s1r += cr[j]; s1g += cg[j]; s1b += cb[j];
         }
         MVS_ROW_STEP3(0xB1) MVS_ROW_STEP3(0x4E) MVS_ROW_STEP3(0x141) MVS_ROW_STEP3(0x140)
@@ -839,13 +732,6 @@ DEV void eval_views(const DParams& prm, WaveCtx& wc, const Frame& f, int n, vmas
             dt += fma_(d0x[2], exb, fma_(d0x[1], exg, d0x[0] * exr));
         }
         if (lc == t) { ssd_l = sq; dot_l = dt; if (PIV) { mr_l = mr; mg_l = mg; mb_l = mb; } }
-#if !MVS_EV_PREFETCH
-        if (t + 1 < rounds) {
-            const ClsFrame fn = cls_frame(min(v + 4, max(n - 1, 0)));
-#pragma unroll
-            for (int j = 0; j < 3; ++j) pend[j] = cls_issue(fn, cls_opaque(cc.cs[j]));
-        }
-#endif
 #if MVS_PAIR_MFMA
         if (texs) {  // sample-major: element 3 q + channel of the view's row of 3 * tstride floats (the k order of the pair sums); slot = view % CH
             float* tv = texs + (3 * (v & (MVS_GRAM_CH - 1))) * tstride;
@@ -953,7 +839,7 @@ DEV void eval_views(const DParams& prm, WaveCtx& wc, const Frame& f, int n, vmas
             }
             if (C < MVS_GRAM_NCH - 1) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) gops[(C < MVS_GRAM_NCH - 1 ? C : 0) * MVS_GRAM_KSP + s0 + j] = tb[j];
+                for (int j = 0; j < 8; ++j) gops[C * MVS_GRAM_KSP + s0 + j] = tb[j];
             }
         }
         __syncthreads();
@@ -966,9 +852,7 @@ DEV void eval_views(const DParams& prm, WaveCtx& wc, const Frame& f, int n, vmas
                 const int rc = (t & 3) + 1;
                 switch (ch) {
                     case 0: chunk_done(GramIC<0>{}, rc); break;
-#if MVS_GRAM_NCH > 1
                     case 1: chunk_done(GramIC<1>{}, rc); break;
-#endif
 #if MVS_GRAM_NCH > 2
                     case 2: chunk_done(GramIC<2>{}, rc); break;
                     default: chunk_done(GramIC<3>{}, rc); break;
@@ -1258,7 +1142,7 @@ DEV int check_angles(const DParams& prm, const WaveCtx& wc, const Cand& c) {
 }
 
 // Optim::preProcess, optim.cpp:137-163
-STAGE int pre_process(const DParams& prm, WaveCtx& wc, int* scratch, Cand& c) {
+DEV int pre_process(const DParams& prm, WaveCtx& wc, int* scratch, Cand& c) {
     add_images(prm, wc, scratch, c);
     constraint_images(prm, wc, scratch, c, prm.nccThresholdBefore);
     sort_images(prm, wc, c);
@@ -1375,7 +1259,7 @@ DEV void cost_func4(const DParams& prm, WaveCtx& wc, const RefineCtx& rc, int im
 }
 // Optim::refinePatch, optim.cpp:480-547, BOBYQA replaced by the halving random search
 // w_out != nullptr (inside the sweep): the weights go out and the final m_ncc is left to postProcess
-STAGE void refine_patch(const DParams& prm, WaveCtx& wc, Cand& c, uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3, float* w_out = nullptr) {
+DEV void refine_patch(const DParams& prm, WaveCtx& wc, Cand& c, uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3, float* w_out = nullptr) {
     RefineCtx rc;
     rc.center = c.coord;
     rc.ref = rli(c.img, 0);
@@ -1440,7 +1324,7 @@ STAGE void refine_patch(const DParams& prm, WaveCtx& wc, Cand& c, uint32_t k0, u
 // or the next pass would take the evaluations beyond max_evals (NLopt's MAXEVAL_REACHED: the reference counts that a failure and
 // leaves the patch as it was, optim.cpp:530-545).  Returns the evaluations made, negated when the budget ran out; x_out / f_out:
 // the best vertex and its cost.  w_out as refine_patch.
-STAGE int refine_patch_simplex(const DParams& prm, WaveCtx& wc, Cand& c, int max_evals, float xtol, float* w_out = nullptr,
+DEV int refine_patch_simplex(const DParams& prm, WaveCtx& wc, Cand& c, int max_evals, float xtol, float* w_out = nullptr,
                                float* x_out = nullptr, double* f_out = nullptr) {
     RefineCtx rc;
     rc.center = c.coord;
@@ -1745,7 +1629,7 @@ DEV int get_mask_all(const DParams& prm, const WaveCtx& wc, const Cand& c) {
 DEV float score2(const Cand& c, float thr) { return fmaxf(0.0f, c.ncc - thr) * (float)c.nimg; }
 
 // Optim::postProcess, optim.cpp:260-298 (Optim::check is applied by the caller, which owns the cell lists)
-STAGE int post_process(const DParams& prm, WaveCtx& wc, int* scratch, float* texs, int tstride, Cand& c, float keep_w = 0.0f, bool keep = false) {
+DEV int post_process(const DParams& prm, WaveCtx& wc, int* scratch, float* texs, int tstride, Cand& c, float keep_w = 0.0f, bool keep = false) {
     if (c.nimg < prm.minImageNum) return -1;
     if (get_mask_all(prm, wc, c) == 0) return -1;
     const int keep_n = keep ? c.nimg : 0;
@@ -1809,7 +1693,7 @@ DEV WaveCtx make_wave_ctx(const DParams& prm) {
 // (optim.cpp:385-395) makes that view the reference.
 // need_ncc = false (engine schedule, destination cell not full): the initial score is only ever read by the
 // replace-worst pre-filter (propagate.cpp:170); refinePatch overwrites it, so it is not computed when nothing reads it.
-STAGE bool generate_patch(const DParams& prm, WaveCtx& wc, int* scratch, const Cand& src, F3 icoord, Cand& out, int as_view = -1, bool need_ncc = true) {
+DEV bool generate_patch(const DParams& prm, WaveCtx& wc, int* scratch, const Cand& src, F3 icoord, Cand& out, int as_view = -1, bool need_ncc = true) {
     int simg = src.img;
     if (as_view >= 0 && rli(src.img, 0) != as_view) {
         const unsigned long long hit = ballot(0 < wc.lane && wc.lane < src.nimg && src.img == as_view);

@@ -627,30 +627,20 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, const int64_t job, i
 // the job of this block in k_sweep_simplex: k_sweep's job order, restated below (k_sweep keeps it inline: through this helper it
 // spills one SGPR more)
 DEV int64_t sweep_job(const SweepArgs& a) {
-#if MVS_XCD_CHUNK > 0
     const int64_t bi = blockIdx.x >> 3;
     const int64_t job = a.job_lo + (bi / MVS_XCD_CHUNK) * (8 * MVS_XCD_CHUNK) + (int64_t)(blockIdx.x & 7u) * MVS_XCD_CHUNK + (bi % MVS_XCD_CHUNK);
-#else
-    const int64_t chunk = (a.job_hi - a.job_lo + 7) / 8;
-    const int64_t job = a.job_lo + (int64_t)(blockIdx.x & 7u) * chunk + (blockIdx.x >> 3);
-#endif
     return job;
 }
 __global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep(DParams prm, SweepArgs a) {
     __shared__ int s_scratch[192];
     extern __shared__ float s_texs[];
     // XCD-aware job order: blocks are dealt round-robin over the 8 XCDs (block b runs on XCD b % 8).
-#if MVS_XCD_CHUNK > 0
     // chunks of MVS_XCD_CHUNK consecutive jobs (a stretch of one grid row) go to one XCD, consecutive chunks to
     // consecutive XCDs: the destination and its source cells share an L2, and every XCD gets the same mix of cheap and
     // expensive regions.  (One contiguous band of cells per XCD left XCDs idle for a quarter of the launch: the bands
     // -- one and a half views each -- differ in work; measured 770 -> 603 ms per iteration.)
     const int64_t bi = blockIdx.x >> 3;
     const int64_t job = a.job_lo + (bi / MVS_XCD_CHUNK) * (8 * MVS_XCD_CHUNK) + (int64_t)(blockIdx.x & 7u) * MVS_XCD_CHUNK + (bi % MVS_XCD_CHUNK);
-#else
-    const int64_t chunk = (a.job_hi - a.job_lo + 7) / 8;
-    const int64_t job = a.job_lo + (int64_t)(blockIdx.x & 7u) * chunk + (blockIdx.x >> 3);
-#endif
     if (job >= a.job_hi) return;
     sweep_cell<false>(prm, a, job, s_scratch, s_texs, nullptr);
 }
@@ -1008,7 +998,7 @@ __global__ __launch_bounds__(64) void k_filter_neighbor(DParams prm, uint8_t* ki
     const bool pk = prm.geo != nullptr;
     // the first launch keeps the marks of the row walk behind its set (64 dwords more than the set needs); the second launch's table
     // fills the 64 KB a block may have, and it walks its rows by the binary search
-    constexpr bool MK = MVS_FN_MARKS != 0 && HCAP == MVS_FILTER_HASH_CAP;
+    constexpr bool MK = HCAP == MVS_FILTER_HASH_CAP;
     int* const marks = reinterpret_cast<int*>(s_lds) + MVS_SET_LDS_FLOATS(HCAP, RCAP);
     const int n = pk ? find_neighbors<HCAP, false, true, MK>(prm, wc, cx, c, table, 4.0f, 2, st4, marks) : find_neighbors<HCAP, false, false, MK>(prm, wc, cx, c, table, 4.0f, 2, st4, marks);
     if (n < 0 || n > RCAP) {
@@ -1307,14 +1297,9 @@ size_t mvsk_sweep_lds_bytes(const DParams& prm) {
 void mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hipStream_t st) {
     const int64_t nloc = a.job_hi - a.job_lo;
     if (nloc <= 0) return;
-    const int64_t chunk = (nloc + 7) / 8;
     // development knob: MVS_SWEEP_LDS_PAD=<bytes> raises the block's LDS allocation, i.e. lowers the waves per SIMD
     static const size_t pad = getenv("MVS_SWEEP_LDS_PAD") ? (size_t)atol(getenv("MVS_SWEEP_LDS_PAD")) : 0;
-#if MVS_XCD_CHUNK > 0
     const int64_t nblocks = (nloc + 8 * MVS_XCD_CHUNK - 1) / (8 * MVS_XCD_CHUNK) * (8 * MVS_XCD_CHUNK);
-#else
-    const int64_t nblocks = chunk * 8;
-#endif
     if (rs.simplex) hipLaunchKernelGGL(k_sweep_simplex, dim3((unsigned)nblocks), dim3(64), mvsk_sweep_lds_bytes(prm) + pad, st, prm, a, rs.max_evals, rs.xtol);
     else hipLaunchKernelGGL(k_sweep, dim3((unsigned)nblocks), dim3(64), mvsk_sweep_lds_bytes(prm) + pad, st, prm, a);
 }
