@@ -193,25 +193,28 @@ class Engine:
             pass
 
     # ---- views
-    def set_scene(self, scene, masks=None):
+    def set_scene(self, scene, masks=None, sizes=None):
+        """sizes: one (width, height) per view -- the view is the top-left crop of the scene's image (and mask) to that size, which
+        leaves its projection valid; default: every view at scene.W x scene.H."""
         n = scene.nviews
         descs = (ViewDesc * n)()
         keep = []
         for v in range(n):
-            img = np.ascontiguousarray(scene.images[v], dtype=np.uint8)
+            w, h = (scene.W, scene.H) if sizes is None else sizes[v]
+            img = np.ascontiguousarray(np.asarray(scene.images[v], dtype=np.uint8)[:h, :w])
             keep.append(img)
-            descs[v].width, descs[v].height = scene.W, scene.H
+            descs[v].width, descs[v].height = w, h
             P = np.ascontiguousarray(scene.P[v], dtype=np.float32).ravel()
             for k in range(12):
                 descs[v].P[k] = float(P[k])
             descs[v].rgb = img.ctypes.data
             descs[v].mask = None
             if masks is not None:
-                m = np.ascontiguousarray(masks[v], dtype=np.uint8)
+                m = np.ascontiguousarray(np.asarray(masks[v], dtype=np.uint8)[:h, :w])
                 keep.append(m)
                 descs[v].mask = m.ctypes.data
         self._check(self.L.mvs_engine_set_views(self.h, n, descs))
-        self._view_shape = (scene.H, scene.W)
+        self._view_shapes = [(scene.H, scene.W)] * n if sizes is None else [(h, w) for w, h in sizes]
 
     def grid_dims(self, v):
         gw, gh = C.c_int(), C.c_int()
@@ -261,11 +264,12 @@ class Engine:
         if len(normal_maps) != n or (masks is not None and len(masks) != n):
             raise ValueError(f"seed_patches: {n} views, one normal map (and mask) each")
         pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
-        shape = getattr(self, "_view_shape", None)
+        shapes = getattr(self, "_view_shapes", None)
         views = (SeedView * n)()
         keep = [pts]
         for v in range(n):
             views[v].normals = views[v].mask = None
+            shape = shapes[v] if shapes is not None else None
             if normal_maps[v] is not None:
                 m = np.ascontiguousarray(normal_maps[v], dtype=np.float32)
                 if shape is not None and m.shape != shape + (3,):

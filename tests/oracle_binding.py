@@ -194,12 +194,15 @@ class Oracle:
             pass
 
     # ---- scene
-    def set_scene(self, scene, masks=None):
+    def set_scene(self, scene, masks=None, sizes=None):
+        """sizes: one (width, height) per view -- the top-left crop of the scene's image and mask (P stays valid), as
+        Engine.set_scene; default: every view at scene.W x scene.H."""
         for v in range(scene.nviews):
-            img = np.ascontiguousarray(scene.images[v])
+            w, h = (scene.W, scene.H) if sizes is None else sizes[v]
+            img = np.ascontiguousarray(np.asarray(scene.images[v], dtype=np.uint8)[:h, :w])
             P = np.ascontiguousarray(scene.P[v], dtype=np.float32)
-            m = None if masks is None else np.ascontiguousarray(masks[v], dtype=np.uint8)
-            if self.L.orc_set_view(self.h, v, scene.W, scene.H, _ptr(P), _ptr(img), _ptr(m)) != 0:
+            m = None if masks is None else np.ascontiguousarray(np.asarray(masks[v], dtype=np.uint8)[:h, :w])
+            if self.L.orc_set_view(self.h, v, w, h, _ptr(P), _ptr(img), _ptr(m)) != 0:
                 raise RuntimeError(self.L.orc_last_error().decode())
         if self.L.orc_finalize_views(self.h) != 0:
             raise RuntimeError(self.L.orc_last_error().decode())

@@ -68,14 +68,16 @@ def restate_ply(recs, P_level, pyr, binary=False):
     return head + "".join(lines).encode()
 
 
-def level_inputs(e, sc, level):
+def level_inputs(e, sc, level, sizes=None):
+    """sizes: the per-view (width, height) given to Engine.set_scene (top-left crops), default every view at sc.W x sc.H"""
     P = []
     for v in range(sc.nviews):
         p = np.asarray(sc.P[v], F).ravel().copy()
         for _ in range(level):
             p[:8] = p[:8] / F(2)
         P.append(p)
-    pyr = [np.asarray(sc.images[v], np.uint8) if level == 0 else e.pyramid(v, level) for v in range(sc.nviews)]
+    wh = [(sc.W, sc.H)] * sc.nviews if sizes is None else sizes
+    pyr = [np.asarray(sc.images[v], np.uint8)[:wh[v][1], :wh[v][0]] if level == 0 else e.pyramid(v, level) for v in range(sc.nviews)]
     return P, pyr
 
 

@@ -56,22 +56,27 @@ def members(ds, X, views=None):
         if ds["masks"][v] is None:
             continue
         px = pixel_of(ds["P"][v], X)
-        if px is None or not (0 <= px[0] < W and 0 <= px[1] < H) or ds["masks"][v][px[1], px[0]] <= 127:
+        w, h = ds["sizes"][v]
+        if px is None or not (0 <= px[0] < w and 0 <= px[1] < h) or ds["masks"][v][px[1], px[0]] <= 127:
             continue
         out.append((v, px))
     return out
 
 
-def make_dataset(root, host, nv, pts, no_mask=(), near=(), holes_for=(), arc=(-15.0, 15.0), seed=5):
+def make_dataset(root, host, nv, pts, no_mask=(), near=(), holes_for=(), arc=(-15.0, 15.0), seed=5, sizes=None):
     """A dataset directory in the layout of tests/test_seed_plys.py: CONTOUR2 cameras on an arc 4 units from a plane through the origin
     (`near`: 1 unit), the 40 x 30 JPEG as every image, PGM masks with a background band and sub-threshold greys (`no_mask`: no file),
     the point cloud, one binary normal-map PLY per view with holes.  holes_for: points whose pixels carry no normal in any view.
-    Returns the projections the mirror derives, the level-0 masks as stored, and the maps readNormals leaves (R * n in float32)."""
+    sizes: one (width, height) per view instead of 40 x 30 -- a binary PPM of that size as the view's image (PhotoSet::init takes
+    <name>.ppm before <name>.jpg), masks and maps of that size; the cameras share the intrinsics of sizes[0], so a smaller view is a
+    top-left crop.  Returns the projections the mirror derives, the level-0 masks as stored, and the maps readNormals leaves (R * n in float32)."""
     for d in ("txt", "image", "mask", "ply"):
         os.makedirs(root / d)
     (root / "option").write_text(f"level 0\ncsize 2\nthreshold 0.7\nwsize 7\nminImageNum 2\nimages -1 0 {nv}\n")
     rng = np.random.RandomState(seed)
-    ds = dict(root=root, P=[], R=[], masks=[], maps=[], pts=pts.astype(F), nv=nv)
+    ds = dict(root=root, P=[], R=[], masks=[], maps=[], pts=pts.astype(F), nv=nv, sizes=[(W, H)] * nv if sizes is None else list(sizes))
+    w0, h0 = ds["sizes"][0]
+    intr = dict(fx=60.0 * w0 / W, fy=60.0 * w0 / W, cx=w0 / 2.0, cy=h0 / 2.0)
     for v in range(nv):
         ang = arc[0] + (arc[1] - arc[0]) * v / max(nv - 1, 1)
         th = math.radians(ang)
@@ -80,20 +85,24 @@ def make_dataset(root, host, nv, pts, no_mask=(), near=(), holes_for=(), arc=(-1
         angles = (3.0 * (v % 7) - 4.0, ang, 2.0 * (v % 3))
         _, R = euler_camera(*angles, (0.0, 0.0, 0.0))
         t = -R @ centre
-        text, _ = euler_camera(*angles, t)
+        text, _ = euler_camera(*angles, t, **intr)
         ds["P"].append(probe_camera(host, root / "txt" / f"{v:08d}.txt", text))
         # Photo::m_R itself: with K = identity the projection the mirror derives is [R | t] exactly
         unit_k, _ = euler_camera(*angles, t, fx=1.0, fy=1.0, cx=0.0, cy=0.0)
         ds["R"].append(probe_camera(host, root / "ply" / "unit_k.txt", unit_k)[:, :3].copy())
-        shutil.copy(GOLDEN_JPG, root / "image" / f"{v:04d}0000.jpg")
+        w, h = ds["sizes"][v]
+        if sizes is None:
+            shutil.copy(GOLDEN_JPG, root / "image" / f"{v:04d}0000.jpg")
+        else:
+            (root / "image" / f"{v:04d}0000.ppm").write_bytes(b"P6\n%d %d\n255\n" % (w, h) + rng.randint(0, 255, (h, w, 3)).astype(np.uint8).tobytes())
         if v in no_mask:
             ds["masks"].append(None)
         else:
-            m = np.full((H, W), 255, np.uint8)
+            m = np.full((h, w), 255, np.uint8)
             m[:, : 6 + 3 * (v % 4)] = 0
             m[10:14, 20:26] = 100  # below the 127 threshold: background
             m[2:4, 30:34] = 200    # above it: foreground, though not 255
-            (root / "mask" / f"{v:08d}.pgm").write_bytes(b"P5\n%d %d\n255\n" % (W, H) + m.tobytes())
+            (root / "mask" / f"{v:08d}.pgm").write_bytes(b"P5\n%d %d\n255\n" % (w, h) + m.tobytes())
             ds["masks"].append(m)
     os.remove(root / "ply" / "unit_k.txt")
     write_ply(root / "ply" / "00000000.ply", "ascii", pts)
@@ -103,8 +112,9 @@ def make_dataset(root, host, nv, pts, no_mask=(), near=(), holes_for=(), arc=(-1
             hole_px[v].add(px)
     n_world = np.array([0.1, -0.05, -1.0])
     n_world /= np.linalg.norm(n_world)
-    ys, xs = np.mgrid[0:H, 0:W]
     for v in range(nv):
+        w, h = ds["sizes"][v]
+        ys, xs = np.mgrid[0:h, 0:w]
         keep = (xs + 2 * ys + v) % 7 != 0  # pixels without a normal: zero vectors in the map
         for (x, y) in hole_px[v]:
             keep[y, x] = False
@@ -112,7 +122,7 @@ def make_dataset(root, host, nv, pts, no_mask=(), near=(), holes_for=(), arc=(-1
         nrm = (ds["R"][v].astype(np.float64).T @ (n_world[None] + rng.normal(0, 0.05, (len(xy), 3))).T).T
         write_ply(root / "ply" / f"{v + 1:08d}.ply", "binary_little_endian", xy, nrm, extra_colour=v % 2 == 1)
         n32, R = nrm.astype(F), ds["R"][v]
-        m = np.zeros((H, W, 3), F)
+        m = np.zeros((h, w, 3), F)
         for k in range(3):  # readNormals: R[3k] * v0 + R[3k + 1] * v1 + R[3k + 2] * v2, float32, left to right
             m[ys[keep], xs[keep], k] = (R[k, 0] * n32[:, 0] + R[k, 1] * n32[:, 1]) + R[k, 2] * n32[:, 2]
         ds["maps"].append(m)
@@ -128,17 +138,18 @@ def plane_points(n, seed=5):
 
 def scene_of(ds):
     rng = np.random.RandomState(11)
-    base = rng.randint(0, 255, (H // 2 + 1, W // 2 + 1, 3)).astype(np.float64)
-    img = np.kron(base, np.ones((2, 2, 1)))[:H, :W]
+    w, h = ds["sizes"][0]  # the largest view: the others are its top-left crops (Engine.set_scene(sizes=))
+    base = rng.randint(0, 255, (h // 2 + 1, w // 2 + 1, 3)).astype(np.float64)
+    img = np.kron(base, np.ones((2, 2, 1)))[:h, :w]
     images = np.stack([np.clip(img + 3.0 * v, 0, 255).astype(np.uint8) for v in range(ds["nv"])])
-    return synth.Scene(W=W, H=H, P=np.stack(ds["P"]).astype(F), images=images, centers=np.zeros((ds["nv"], 3)))
+    return synth.Scene(W=w, H=h, P=np.stack(ds["P"]).astype(F), images=images, centers=np.zeros((ds["nv"], 3)))
 
 
 def new_engine(ds, cap=None, **kw):
     args = dict(level=0, csize=2, wsize=7, minImageNum=2, nccThreshold=0.7, enable_check=0, seed=3)
     args.update(kw)
     e = engine.Engine(ds["nv"], list_cap=cap, **args)
-    e.set_scene(scene_of(ds))
+    e.set_scene(scene_of(ds), sizes=ds["sizes"])
     return e
 
 
@@ -302,3 +313,32 @@ def test_case5_same_bytes_from_two_engines():
         if j == 2000:
             break
     assert j == min(2000, len(coords))
+
+
+@pytest.mark.parametrize("sizes", [[(321, 243)] * 4, [(321, 243), (320, 243), (301, 220), (321, 236)]], ids=["odd", "unequal"])
+def test_case7_odd_and_unequal_view_sizes(tmp_path, sizes):
+    """Views of 321 x 243 (odd both ways: level-0 pixel tests against W and H, maps and masks with an odd row pitch), and four views
+    of unequal size (every view's own W, H, map and mask in the kernel and in Engine.seed_patches' per-view shape check): records
+    byte for byte against the mirror's loop.  Points near the right and bottom borders make sure the per-view bounds decide: the
+    view lists of the unequal case differ from those the same points get when every view has the full size."""
+    host = host_lib(16)
+    rng = np.random.RandomState(9)
+    edge = np.stack([rng.uniform(0.9, 1.45, 200), rng.uniform(-0.95, 0.95, 200), 0.02 * rng.normal(size=200)], 1)   # right border
+    low = np.stack([rng.uniform(-1.4, 1.4, 200), rng.uniform(0.6, 1.1, 200), 0.02 * rng.normal(size=200)], 1)       # bottom border
+    pts = np.vstack([plane_points(300), edge, low])
+    ds = make_dataset(tmp_path / "d", host, 4, pts, sizes=sizes)
+    assert [m.shape for m in ds["masks"]] == [(h, w) for w, h in sizes] and [m.shape for m in ds["maps"]] == [(h, w, 3) for w, h in sizes]
+    e, o, got, exp = device_and_mirror(ds, 16)
+    assert 300 < len(got) < len(pts) - 5
+    lists = [tuple(r["images"][: r["nimages"]].tolist()) for r in got]
+    assert len(set(lists)) > 4
+    if len(set(sizes)) > 1:
+        full = dict(ds, sizes=[sizes[0]] * 4, masks=[np.pad(m, ((0, sizes[0][1] - m.shape[0]), (0, sizes[0][0] - m.shape[1])), constant_values=255)
+                                                    for m in ds["masks"]])
+        cut = sum(len(members(full, X)) != len(members(ds, X)) for X in ds["pts"])
+        assert cut > 20, cut  # points some view sees only beyond its own, smaller size
+        with pytest.raises(ValueError):
+            e.seed_patches(ds["pts"], [ds["maps"][0]] * 4, ds["masks"])  # view 2's map must have view 2's shape
+    ce, co = e.propagate(0), o.propagate(0)
+    assert ce == co, (ce, co)
+    assert_same_pool(e.patches(), o.patches())

@@ -231,6 +231,109 @@ def test_pyramid_second_reading(setup):
             np.testing.assert_array_equal(o.pyramid(v, level), pyrs[v][level])
 
 
+def test_pyramid_second_reading_odd_sizes():
+    """Image::alloc halves with W / 2 rounded down (image.cpp:135-138): below an odd parent the last output pixel's 2x + 2 tap is
+    the parent's last column (kept), below an even parent it lies outside (dropped).  The fixture above has even parents only.
+    Two views of unequal size: 97x75 -> 48x37 -> 24x18 -> 12x9 and 91x70 -> 45x35 -> 22x17 -> 11x8, so both kinds of parent occur
+    in both directions and at more than one level."""
+    sc = synth.make_scene(nviews=2, W=97, H=75, arc_deg=20.0, radius=4.0, kind="plane")
+    sizes = [(97, 75), (91, 70)]
+    o = ob.Oracle(2, level=1, csize=2, wsize=7, minImageNum=2, schedule=ob.SCHEDULE_ENGINE, sum_mode=ob.SUM_SEQ, enable_check=0, nthreads=1)
+    o.set_scene(sc, sizes=sizes)
+    odd_parents = 0
+    for v, (w, h) in enumerate(sizes):
+        img = np.ascontiguousarray(sc.images[v][:h, :w])
+        for level in range(1, 4):
+            odd_parents += (img.shape[1] & 1) + (img.shape[0] & 1)
+            img = ref_pyr_down(img)
+            got = o.pyramid(v, level)
+            assert got.shape == (h >> level, w >> level, 3)
+            np.testing.assert_array_equal(got, img, err_msg=f"view {v} level {level}")
+    assert odd_parents >= 6
+    assert o.grid_dims(0) == (24, 19) and o.grid_dims(1) == (23, 18)  # ceil(48 / 2) x ceil(37 / 2), ceil(45 / 2) x ceil(35 / 2)
+    o.close()
+
+
+def ref_mask_down(mask):
+    """Image::buildMaskPyramid, image.cpp:717-747: a pixel of the next level is 255 if any of the four pixels (2x, 2x + 1) x (2y, 2y + 1)
+    of the level above is set.  The reference bounds 2x + 1 by the width itself, not by width - 1; with w = W / 2 rounded down
+    2x + 1 <= W - 1 for every x < w, so the bound never acts and an odd parent's last column and row are never read."""
+    H, W = mask.shape
+    h, w = H // 2, W // 2
+    out = np.zeros((h, w), np.uint8)
+    for y in range(h):
+        ys = (2 * y, min(H, 2 * y + 1))
+        for x in range(w):
+            xs = (2 * x, min(W, 2 * x + 1))
+            inside = sum(1 for j in range(2) for i in range(2) if mask[ys[j], xs[i]])
+            out[y, x] = 255 if inside > 0 else 0
+    return out
+
+
+def ref_get_mask_all(cams, masks, X, level):
+    """PhotoSet::getMask(coord, level), photoSet.cpp:223-233, over Image::getMask, image.cpp:749-781: 0 if the point projects onto
+    a zero mask pixel of any view, else -1 (a projection outside a view's image does not count against it)."""
+    for cam, m in zip(cams, masks):
+        ic = ref_project(cam.P[level], X)
+        ix, iy = int(np.floor(ic[0] + F(0.5))), int(np.floor(ic[1] + F(0.5)))
+        H, W = m[level].shape
+        if ix < 0 or W <= ix or iy < 0 or H <= iy:
+            continue
+        if m[level][iy, ix] == 0:
+            return 0
+    return -1
+
+
+def test_mask_pyramid_second_reading_odd_sizes():
+    """The oracle has no accessor for its mask pyramid, so it is read through the one place that uses it, Optim::postProcess
+    (optim.cpp:260-298: `if (m_pmmvps.m_photoSets.getMask(patch.m_coord, m_pmmvps.m_level) == 0) return -1`): the same records go
+    through an oracle with masks and one without.  Where the numpy reading of the level-1 masks says "masked", the masked oracle
+    must refuse the record; everywhere else it must return what the unmasked one returns.  Level 1 of a 97x75 scene (48x37), masks
+    binarised at 127 (image.cpp:149-156) with a zero band between the odd columns 41 and 47, a zero last column and last row
+    (never read at level 1: 2 * 48 < 97, 2 * 37 < 75) and a sub-threshold block."""
+    sc = synth.make_scene(nviews=3, W=97, H=75, arc_deg=25.0, radius=4.0, kind="plane")
+    nv, level = sc.nviews, 1
+    raw = np.full((nv, sc.H, sc.W), 255, np.uint8)
+    raw[:, :, 41:48] = 0
+    raw[:, :, sc.W - 1] = 0
+    raw[:, sc.H - 1, :] = 0
+    raw[1, 20:31, 60:71] = 127  # not above 127: background
+    raw[2, 40:51, 10:21] = 128  # above: foreground
+    kw = dict(level=level, csize=1, wsize=5, minImageNum=2, schedule=ob.SCHEDULE_ENGINE, sum_mode=ob.SUM_SEQ, enable_check=0, nthreads=1, seed=1)
+    om, o0 = ob.Oracle(nv, **kw), ob.Oracle(nv, **kw)
+    om.set_scene(sc, masks=raw)
+    o0.set_scene(sc)
+    cams = [RefCam(sc.P[v], level) for v in range(nv)]
+    masks = []
+    for v in range(nv):
+        m0 = np.where(raw[v] > 127, 255, 0).astype(np.uint8)
+        masks.append([m0, ref_mask_down(m0)])
+        assert masks[v][1].shape == (37, 48)
+    assert masks[2][1][20:25, 5:10].all() and not masks[1][1][11:15, 31:35].any()
+    assert masks[0][1][:, 47].all() and masks[0][1][36, :20].all()  # the zero last column and row of level 0 left no trace
+    seeds = synth.make_seeds(sc, level=level, csize=1, stride=2, seed=4)
+    masked = plain = passed = 0
+    for i, s in enumerate(seeds):
+        f, rec = o0.preprocess(s)
+        if f != 0:
+            continue
+        _, rec = o0.refine(rec, (0, 0, i, 0))
+        f0, r0 = o0.postprocess(rec)
+        fm, rm = om.postprocess(rec)
+        if ref_get_mask_all(cams, masks, rec["coord"].astype(F), level) == 0:
+            assert fm != 0, rec["coord"]
+            masked += 1
+        else:
+            assert fm == f0, (rec["coord"], fm, f0)
+            if f0 == 0:
+                assert rm.tobytes() == r0.tobytes()
+                passed += 1
+            plain += 1
+    assert masked > 30 and passed > 100 and plain > masked, (masked, plain, passed)
+    om.close()
+    o0.close()
+
+
 def test_camera_second_reading(setup):
     sc, o, cams, _, seeds = setup
     for v in range(sc.nviews):
