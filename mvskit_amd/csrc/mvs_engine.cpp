@@ -78,7 +78,10 @@ constexpr int geo_bad = 6;         // pack_geometry: a record that cannot be pac
 constexpr int group_edges = 7;     // the literal filterSmallGroups: the number of one-way edges between sets
 constexpr int trim_parts = 8;      // [trim_nparts] the MAX_NUM_OF_PATCHES trim's count as partial sums
 constexpr int trim_nparts = 256;   // (k_index_sort_trim: one per block index mod 256)
-constexpr int words = trim_parts + trim_nparts;
+// the sweep's queue cursors (SweepArgs::cursors, uint32 each): eight 128-byte lines, the first on a line boundary of the buffer
+constexpr int sweep_cursors = (trim_parts + trim_nparts + 15) / 16 * 16;
+constexpr int sweep_cursor_words = MVS_SWEEP_QUEUES * MVS_SWEEP_CURSOR_STRIDE * (int)sizeof(uint32_t) / (int)sizeof(unsigned long long);
+constexpr int words = sweep_cursors + sweep_cursor_words;
 }  // namespace misc
 // The words of mvs_engine::fstat_buf (Filter::run's statistics).  k_filter_neighbor fixes the first two ranges itself.
 namespace fstat {
@@ -1315,6 +1318,8 @@ static int pass_impl(mvs_engine* e, int iter, int pass, mvs_counters* out) {
     a.big_tables = e->big_tables.p; a.retry_jobs = e->retry_jobs.p; a.nretry = reinterpret_cast<int32_t*>(e->misc.p + misc::sweep_retry);
     HIPCHK(hipMemsetAsync(e->misc.p + misc::sweep_retry, 0, sizeof(unsigned long long), st));
     HIPCHK(hipMemsetAsync(e->misc.p + misc::stage_counter, 0, sizeof(unsigned long long), st));
+    a.cursors = reinterpret_cast<uint32_t*>(e->misc.p + misc::sweep_cursors);
+    HIPCHK(hipMemsetAsync(e->misc.p + misc::sweep_cursors, 0, misc::sweep_cursor_words * sizeof(unsigned long long), st));
     HIPCHK(hipMemsetAsync(e->counters.p, 0, MVS_COUNTER_SLOTS * sizeof(DCounters), st));
     HIPCHK(hipMemsetAsync(e->error_flag.p, 0, sizeof(int32_t), st));
     const DParams p = current_params(e);

@@ -363,7 +363,7 @@ __global__ __launch_bounds__(64) void k_fill_ncc(DParams prm, unsigned long long
 }
 
 // =================================================================== K4: the sweep
-// One wavefront per destination cell of the pass colour.  Propagate::propagatePmImage (propagate.cpp:72-124)
+// One wavefront at a time per destination cell of the pass colour.  Propagate::propagatePmImage (propagate.cpp:72-124)
 // turned inside out: the cell gathers from the cell above/below and the cell beside it, in the order the
 // raster sweep would reach them, and runs Propagate::propagatePatch (propagate.cpp:126-218) on its own list.
 DEV bool rank_before(float na, int a, float nb, int b) { return (na != nb) ? (na > nb) : (a < b); }
@@ -376,6 +376,23 @@ DEV void job_cell(const DParams& prm, const SweepArgs& a, int64_t job, int& v, i
     const int local = (int)(job - a.job_base[s]);
     cy = local / halfw;
     cx = 2 * (local % halfw) + ((a.colour + cy) & 1);
+}
+// Has the job a destination cell (not the ghost job at cx == gw of an odd-width grid) with any source at all?  A lane per job.
+DEV bool job_has_source(const DParams& prm, const SweepArgs& a, int64_t job) {
+    int v, cx, cy;
+    job_cell(prm, a, job, v, cx, cy);
+    const DView* vw = prm.views + v;
+    const int gw = vw->gw, gh = vw->gh;
+    if (cx >= gw || cy >= gh) return false;
+    const int sxs[2] = {cx, cx - a.inc}, sys[2] = {cy - a.inc, cy};
+    bool has = false;
+    for (int k = 0; k < 2; ++k) {
+        if (sxs[k] < 0 || gw <= sxs[k] || sys[k] < 0 || gh <= sys[k]) continue;
+        const int g = vw->cell_base + sys[k] * gw + sxs[k];
+        has |= prm.csr_cnt[g] > 0;
+    }
+    if (prm.view_propagation) has |= prm.csr_cnt[vw->cell_base + cy * gw + cx] > 0;
+    return has;
 }
 // Work proxy of a job, for cutting the job sequence into ranges of equal WORK (multi-GPU: every rank holds the same index,
 // computes the same proxy and finds the same cuts).  A job runs max_propag trials per source entry whose reference view is
@@ -442,35 +459,62 @@ __global__ void k_job_cuts(const int32_t* __restrict__ scan, int64_t njobs, int 
 #ifndef MVS_XCD_CHUNK
 #define MVS_XCD_CHUNK 128
 #endif
+// The work counts of a wave, summed over its cells (wave-uniform: scalar registers) and added into one counter slot before it exits
+struct SweepAcc {
+    unsigned cand, pref, patch, f0, f1, ins, rep;
+    unsigned long long evals, view_evals;
+#ifdef MVS_STAGE_TIMING
+    unsigned long long stage[16];
+#endif
+};
+DEV SweepAcc sweep_acc_zero() {
+    SweepAcc acc;
+    acc.cand = acc.pref = acc.patch = acc.f0 = acc.f1 = acc.ins = acc.rep = 0u;
+    acc.evals = acc.view_evals = 0ull;
+#ifdef MVS_STAGE_TIMING
+    for (int k = 0; k < 16; ++k) acc.stage[k] = 0ull;
+#endif
+    return acc;
+}
+DEV void sweep_acc_flush(const SweepArgs& a, const SweepAcc& acc, unsigned slot) {  // one lane
+    DCounters* C = a.counters + slot;  // partial sums, added up by the host: the waves of a launch on ONE cache line queue up
+    if (acc.cand) atomicAdd(&C->candidates, (unsigned long long)acc.cand);
+    if (acc.pref) atomicAdd(&C->prefiltered, (unsigned long long)acc.pref);
+    if (acc.patch) atomicAdd(&C->patches, (unsigned long long)acc.patch);
+    if (acc.f0) atomicAdd(&C->fail0, (unsigned long long)acc.f0);
+    if (acc.f1) atomicAdd(&C->fail1, (unsigned long long)acc.f1);
+    if (acc.ins) atomicAdd(&C->inserted, (unsigned long long)acc.ins);
+    if (acc.rep) atomicAdd(&C->replaced, (unsigned long long)acc.rep);
+    if (acc.evals) atomicAdd(&C->evals, acc.evals);
+    if (acc.view_evals) atomicAdd(&C->view_evals, acc.view_evals);
+#ifdef MVS_STAGE_TIMING
+    for (int k = 0; k < 12; ++k) if (acc.stage[k]) atomicAdd(&C->stage[k], acc.stage[k]);
+    atomicMax(&C->stage[12], acc.stage[12]); atomicMax(&C->stage[13], acc.stage[13]);
+    atomicAdd(&C->stage[14], acc.stage[14]); atomicAdd(&C->stage[15], acc.stage[15]);  // inside postProcess: setRefImage's pair sums and choice
+#endif
+}
+// One destination cell: `job` has a cell and a source (job_has_source), job_nstage[job] is 0.  The wave comes here cell after cell
+// (the LDS of the previous cell is dead: the caller puts a barrier in between): everything a cell keeps is set up here, and what it
+// counted goes into `acc` when it is done -- nothing of a cell that gives up.
 // SIMPLEX = true: the refinement is refine_patch_simplex with max_evals / xtol (k_sweep_simplex, k_sweep_retry_simplex: the CONVERGED
 // refiner of mvs_engine_set_refiner); the default kernels keep the halving search and never see the two arguments.
 template <bool BIG, bool SIMPLEX = false>
-DEV void sweep_cell(const DParams& prm, const SweepArgs& a, const int64_t job, int* s_scratch, float* s_texs, int* big_table,
-                    int max_evals = 0, float xtol = 0.0f) {
+DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WaveCtx& wc, SweepAcc* acc, const int64_t job, int* s_scratch, float* s_texs,
+                    int* big_table, int max_evals = 0, float xtol = 0.0f) {
 #ifdef MVS_STAGE_TIMING
     unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const unsigned long long st_begin = ST_NOW();
     unsigned long long st_t = st_begin;
+    for (int k = 0; k < 8; ++k) wc.st_acc[k] = 0;
 #endif
     int v, cx, cy;
     job_cell(prm, a, job, v, cx, cy);
     const DView* vw = prm.views + v;
     const int gw = vw->gw, gh = vw->gh;
-    WaveCtx wc = make_wave_ctx(prm);
-    if (wc.lane == 0) a.job_nstage[job] = 0;
-    if (cx >= gw || cy >= gh) return;
+    wc.evals = 0; wc.view_evals = 0;
     const int cell = cy * gw + cx;
     const int inc = a.inc;
     const int sxs[2] = {cx, cx - inc}, sys[2] = {cy - inc, cy};
-    // any source at all?
-    bool has = false;
-    for (int k = 0; k < 2; ++k) {
-        if (sxs[k] < 0 || gw <= sxs[k] || sys[k] < 0 || gh <= sys[k]) continue;
-        const int g = vw->cell_base + sys[k] * gw + sxs[k];
-        has |= prm.csr_cnt[g] > 0;
-    }
-    if (prm.view_propagation) has |= prm.csr_cnt[vw->cell_base + cy * gw + cx] > 0;
-    if (!has) return;
 
     const int tstride = prm.wsz;  // odd for 7x7 / 5x5 windows: the lane-per-pair reads of setRefImage fall in distinct banks
     unsigned n_cand = 0, n_pref = 0, n_patch = 0, n_f0 = 0, n_f1 = 0, n_ins = 0, n_rep = 0;
@@ -603,62 +647,99 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, const int64_t job, i
         if (wc.lane == 0) { a.job_nstage[job] = 0; a.retry_jobs[atomicAdd(a.nretry, 1)] = (int32_t)job; }
         return;
     }
-    if (wc.lane == 0) {
-        a.job_nstage[job] = ns;
-        DCounters* C = a.counters + (job & (MVS_COUNTER_SLOTS - 1));  // partial sums, added up by the host: a million waves on ONE cache line queue up
-        if (n_cand) atomicAdd(&C->candidates, (unsigned long long)n_cand);
-        if (n_pref) atomicAdd(&C->prefiltered, (unsigned long long)n_pref);
-        if (n_patch) atomicAdd(&C->patches, (unsigned long long)n_patch);
-        if (n_f0) atomicAdd(&C->fail0, (unsigned long long)n_f0);
-        if (n_f1) atomicAdd(&C->fail1, (unsigned long long)n_f1);
-        if (n_ins) atomicAdd(&C->inserted, (unsigned long long)n_ins);
-        if (n_rep) atomicAdd(&C->replaced, (unsigned long long)n_rep);
-        if (wc.evals) atomicAdd(&C->evals, (unsigned long long)wc.evals);
-        if (wc.view_evals) atomicAdd(&C->view_evals, (unsigned long long)wc.view_evals);
+    if (wc.lane == 0) a.job_nstage[job] = ns;
+    {  // wave-uniform sums: scalar registers, the caller's SweepAcc being a local
+        acc->cand += n_cand; acc->pref += n_pref; acc->patch += n_patch; acc->f0 += n_f0; acc->f1 += n_f1; acc->ins += n_ins; acc->rep += n_rep;
+        acc->evals += wc.evals; acc->view_evals += wc.view_evals;
 #ifdef MVS_STAGE_TIMING
         st_acc[0] = ST_NOW() - st_begin;
-        for (int k = 0; k < 12; ++k) if (st_acc[k]) atomicAdd(&C->stage[k], st_acc[k]);
-        atomicMax(&C->stage[12], st_acc[12]); atomicMax(&C->stage[13], st_acc[13]);
-        atomicAdd(&C->stage[14], wc.st_acc[3]); atomicAdd(&C->stage[15], wc.st_acc[4]);  // inside postProcess: setRefImage's pair sums and choice
+        for (int k = 0; k < 12; ++k) acc->stage[k] += st_acc[k];
+        acc->stage[12] = max(acc->stage[12], st_acc[12]); acc->stage[13] = max(acc->stage[13], st_acc[13]);
+        acc->stage[14] += wc.st_acc[3]; acc->stage[15] += wc.st_acc[4];
 #endif
     }
 }
 
-// the job of this block in k_sweep_simplex: k_sweep's job order, restated below (k_sweep keeps it inline: through this helper it
-// spills one SGPR more)
-DEV int64_t sweep_job(const SweepArgs& a) {
-    const int64_t bi = blockIdx.x >> 3;
-    const int64_t job = a.job_lo + (bi / MVS_XCD_CHUNK) * (8 * MVS_XCD_CHUNK) + (int64_t)(blockIdx.x & 7u) * MVS_XCD_CHUNK + (bi % MVS_XCD_CHUNK);
-    return job;
+// The sweep's launch form: a grid of RESIDENT waves (as many 64-thread blocks as the device holds at MVS_SWEEP_WAVES per SIMD, or
+// fewer) that pull work until none is left.  The launch's job range [job_lo, job_hi) is cut into chunks of MVS_XCD_CHUNK consecutive
+// jobs (a stretch of one grid row); chunk c is in queue c % 8.  Blocks are dealt round-robin over the 8 XCDs (block b runs on XCD
+// b % 8), and a wave serves queue blockIdx.x & 7 first: a stretch of cells goes to one XCD and consecutive stretches to consecutive
+// XCDs, so a destination and its source cells share an L2 and every XCD gets the same mix of cheap and expensive regions.  (One
+// contiguous band of cells per XCD left XCDs idle for a quarter of the launch: the bands -- one and a half views each -- differ in
+// work; measured 770 -> 603 ms per iteration.)  A wave takes the next MVS_SWEEP_TAKE jobs of its queue with one atomicAdd WITH
+// return on the queue's cursor (a cache line each, zero before the launch) -- in the middle of its work, like the staging-slot
+// counter, never as its last instruction -- and when its queue is drained it takes from the others, in the order q + 1, q + 2, ...;
+// when all eight are drained it adds its work counts into its counter slot and exits.  No grid barrier, no co-residency assumption:
+// a block that starts late finds less work, a grid of one wave drains everything.
+// Of a take every job gets a lane (job_has_source) that clears its job_nstage -- jobs beyond job_hi and the ghost jobs of an
+// odd-width grid end here --; the wave then runs the cells with work in job order.
+// MVS_SWEEP_TAKE is 1: the waves of an XCD must work on NEIGHBOURING cells at any one time, as the blocks of a one-block-per-cell
+// launch do -- neighbours sample the same texels and read the same lists, and L1 / L2 serve them.  A wave that keeps a whole
+// chunk to itself spreads the 384 waves of an XCD over 384 chunks: sweep 333 ms per step against 281 for one block per cell;
+// takes of 64 / 16 / 4 / 1 jobs: 309 / 285 / 273.5 / 270.4 ms (profiles/r09_resident_ab.txt).  The cursor's atomic is one per
+// job then, 390 k per queue and launch: a round trip in ~430 us of work per cell.
+#ifndef MVS_SWEEP_TAKE
+#define MVS_SWEEP_TAKE 1
+#endif
+static_assert(MVS_SWEEP_TAKE <= 64 && MVS_XCD_CHUNK % MVS_SWEEP_TAKE == 0, "a take is a part of one chunk, a lane per job");
+template <bool SIMPLEX>
+DEV void sweep_resident(const DParams& prm, const SweepArgs& a, int* s_scratch, float* s_texs, int max_evals, float xtol) {
+    WaveCtx wc = make_wave_ctx(prm);
+    SweepAcc acc = sweep_acc_zero();
+    const int nchunks = (int)((a.job_hi - a.job_lo + MVS_XCD_CHUNK - 1) / MVS_XCD_CHUNK);
+    constexpr unsigned per = MVS_XCD_CHUNK / MVS_SWEEP_TAKE;  // takes per chunk
+    for (unsigned step = 0; step < MVS_SWEEP_QUEUES; ++step) {
+        const unsigned q = (blockIdx.x + step) & (MVS_SWEEP_QUEUES - 1u);
+        // queue q holds the chunks q, q + 8, ...: (nchunks - q + 7) / 8 of them, none if q >= nchunks
+        const unsigned ntake = (unsigned)((nchunks - (int)q + MVS_SWEEP_QUEUES - 1) / MVS_SWEEP_QUEUES) * per;
+        for (;;) {
+            unsigned k = 0;
+            if (wc.lane == 0) k = atomicAdd(a.cursors + q * MVS_SWEEP_CURSOR_STRIDE, 1u);
+            k = (unsigned)rfl((int)k);
+            if (k >= ntake) break;  // drained: on to the next queue
+            const int64_t base = a.job_lo + ((int64_t)q + (int64_t)MVS_SWEEP_QUEUES * (k / per)) * MVS_XCD_CHUNK + (int64_t)(k % per) * MVS_SWEEP_TAKE;
+            const int64_t mine = base + wc.lane;
+            bool has = false;
+            if (wc.lane < MVS_SWEEP_TAKE && mine < a.job_hi) {
+                a.job_nstage[mine] = 0;
+                has = job_has_source(prm, a, mine);
+            }
+            unsigned long long t = ballot(has);
+            while (t) {  // the cells with work, in job order
+                const int l = __ffsll((long long)t) - 1;
+                t &= t - 1ull;
+                __syncthreads();  // the LDS scratch, frames, pivots and kept textures of the previous cell are dead
+                sweep_cell<false, SIMPLEX>(prm, a, wc, &acc, base + l, s_scratch, s_texs, nullptr, max_evals, xtol);
+            }
+        }
+    }
+    if (wc.lane == 0) sweep_acc_flush(a, acc, blockIdx.x & (MVS_COUNTER_SLOTS - 1));
 }
 __global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep(DParams prm, SweepArgs a) {
     __shared__ int s_scratch[192];
     extern __shared__ float s_texs[];
-    // XCD-aware job order: blocks are dealt round-robin over the 8 XCDs (block b runs on XCD b % 8).
-    // chunks of MVS_XCD_CHUNK consecutive jobs (a stretch of one grid row) go to one XCD, consecutive chunks to
-    // consecutive XCDs: the destination and its source cells share an L2, and every XCD gets the same mix of cheap and
-    // expensive regions.  (One contiguous band of cells per XCD left XCDs idle for a quarter of the launch: the bands
-    // -- one and a half views each -- differ in work; measured 770 -> 603 ms per iteration.)
-    const int64_t bi = blockIdx.x >> 3;
-    const int64_t job = a.job_lo + (bi / MVS_XCD_CHUNK) * (8 * MVS_XCD_CHUNK) + (int64_t)(blockIdx.x & 7u) * MVS_XCD_CHUNK + (bi % MVS_XCD_CHUNK);
-    if (job >= a.job_hi) return;
-    sweep_cell<false>(prm, a, job, s_scratch, s_texs, nullptr);
+    sweep_resident<false>(prm, a, s_scratch, s_texs, 0, 0.0f);
 }
 __global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep_simplex(DParams prm, SweepArgs a, int max_evals, float xtol) {
     __shared__ int s_scratch[192];
     extern __shared__ float s_texs[];
-    const int64_t job = sweep_job(a);
-    if (job >= a.job_hi) return;
-    sweep_cell<false, true>(prm, a, job, s_scratch, s_texs, nullptr, max_evals, xtol);
+    sweep_resident<true>(prm, a, s_scratch, s_texs, max_evals, xtol);
 }
 // the second tier: block b runs the cells retry_jobs[b], retry_jobs[b + gridDim.x], ... with big_tables slot b
+template <bool SIMPLEX>
+DEV void sweep_retry_cell(const DParams& prm, const SweepArgs& a, const int64_t job, int* s_scratch, float* s_texs, int* big_table, int max_evals, float xtol) {
+    WaveCtx wc = make_wave_ctx(prm);
+    SweepAcc acc = sweep_acc_zero();
+    sweep_cell<true, SIMPLEX>(prm, a, wc, &acc, job, s_scratch, s_texs, big_table, max_evals, xtol);
+    if (wc.lane == 0) sweep_acc_flush(a, acc, (unsigned)(job & (MVS_COUNTER_SLOTS - 1)));
+}
 __global__ __launch_bounds__(64, 1) void k_sweep_retry(DParams prm, SweepArgs a, int nretry) {
     __shared__ int s_scratch[192];
     extern __shared__ float s_texs[];
     int* big_table = a.big_tables + (size_t)blockIdx.x * MVS_FILTER2_HASH_CAP;
     for (int k = blockIdx.x; k < nretry; k += gridDim.x) {
         __syncthreads();
-        sweep_cell<true>(prm, a, (int64_t)a.retry_jobs[k], s_scratch, s_texs, big_table);
+        sweep_retry_cell<false>(prm, a, (int64_t)a.retry_jobs[k], s_scratch, s_texs, big_table, 0, 0.0f);
     }
 }
 __global__ __launch_bounds__(64, 1) void k_sweep_retry_simplex(DParams prm, SweepArgs a, int nretry, int max_evals, float xtol) {
@@ -667,7 +748,7 @@ __global__ __launch_bounds__(64, 1) void k_sweep_retry_simplex(DParams prm, Swee
     int* big_table = a.big_tables + (size_t)blockIdx.x * MVS_FILTER2_HASH_CAP;
     for (int k = blockIdx.x; k < nretry; k += gridDim.x) {
         __syncthreads();
-        sweep_cell<true, true>(prm, a, (int64_t)a.retry_jobs[k], s_scratch, s_texs, big_table, max_evals, xtol);
+        sweep_retry_cell<true>(prm, a, (int64_t)a.retry_jobs[k], s_scratch, s_texs, big_table, max_evals, xtol);
     }
 }
 
@@ -1299,9 +1380,21 @@ void mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hip
     if (nloc <= 0) return;
     // development knob: MVS_SWEEP_LDS_PAD=<bytes> raises the block's LDS allocation, i.e. lowers the waves per SIMD
     static const size_t pad = getenv("MVS_SWEEP_LDS_PAD") ? (size_t)atol(getenv("MVS_SWEEP_LDS_PAD")) : 0;
-    const int64_t nblocks = (nloc + 8 * MVS_XCD_CHUNK - 1) / (8 * MVS_XCD_CHUNK) * (8 * MVS_XCD_CHUNK);
-    if (rs.simplex) hipLaunchKernelGGL(k_sweep_simplex, dim3((unsigned)nblocks), dim3(64), mvsk_sweep_lds_bytes(prm) + pad, st, prm, a, rs.max_evals, rs.xtol);
-    else hipLaunchKernelGGL(k_sweep, dim3((unsigned)nblocks), dim3(64), mvsk_sweep_lds_bytes(prm) + pad, st, prm, a);
+    const size_t lds = mvsk_sweep_lds_bytes(prm) + pad;
+    // the resident grid: the waves the device holds at the launch bound (4 SIMDs per CU) and no more blocks than there are takes of
+    // work.  (Where the LDS allocation lets fewer waves in, the rest start late and find less work: nothing depends on residency.)
+    int dev = 0, cus = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
+    int64_t nblocks = (int64_t)cus * 4 * MVS_SWEEP_WAVES;
+    nblocks = std::min(nblocks, (nloc + MVS_SWEEP_TAKE - 1) / MVS_SWEEP_TAKE);
+    // development knob, read on every launch: MVS_SWEEP_GRID=<n> caps the number of resident blocks (the result does not depend on it)
+    if (const char* g = getenv("MVS_SWEEP_GRID")) {
+        const long cap = atol(g);
+        if (cap > 0) nblocks = std::min<int64_t>(nblocks, cap);
+    }
+    if (rs.simplex) hipLaunchKernelGGL(k_sweep_simplex, dim3((unsigned)nblocks), dim3(64), lds, st, prm, a, rs.max_evals, rs.xtol);
+    else hipLaunchKernelGGL(k_sweep, dim3((unsigned)nblocks), dim3(64), lds, st, prm, a);
 }
 void mvsk_job_work(const DParams& prm, const SweepArgs& a, int mode, int shift, int32_t* work, hipStream_t st) {
     if (a.njobs > 0) hipLaunchKernelGGL(k_job_work, dim3(nblk(a.njobs, 256)), dim3(256), 0, st, prm, a, mode, shift, work);

@@ -95,8 +95,10 @@ struct DParams {
 };
 
 #ifndef MVS_COUNTER_SLOTS
-#define MVS_COUNTER_SLOTS 256  // SweepArgs::counters: that many DCounters, job j adds into slot j % MVS_COUNTER_SLOTS
+#define MVS_COUNTER_SLOTS 256  // SweepArgs::counters: that many DCounters, block b of the sweep adds into slot b % MVS_COUNTER_SLOTS
 #endif
+#define MVS_SWEEP_QUEUES 8         // the sweep's job queues, one per XCD: chunk c of a launch's job range is in queue c % 8
+#define MVS_SWEEP_CURSOR_STRIDE 32 // SweepArgs::cursors: queue q's cursor is word q * 32 (a 128-byte line each)
 struct DCounters {
     unsigned long long candidates, prefiltered, patches, fail0, fail1, inserted, replaced, evals, view_evals, trimmed;
     // diagnostic build (-DMVS_STAGE_TIMING): wave cycles (s_memtime) per stage of the sweep, summed over waves:
@@ -126,4 +128,5 @@ struct SweepArgs {
     int32_t* big_tables;  // Optim::check's second tier (k_sweep_retry): 16384-slot id sets in global memory, one per block
     int32_t* retry_jobs;  // the destination cells (jobs) the first launch handed to the second tier, and
     int32_t* nretry;      //   how many
+    uint32_t* cursors;    // [MVS_SWEEP_QUEUES * MVS_SWEEP_CURSOR_STRIDE] the next chunk of every queue, zero before the launch
 };
