@@ -328,6 +328,8 @@ typedef struct mvs_timing {
     float commit_ms; /* commit */
     int32_t sweep_launches;
     float exchange_ms;      /* mvs_engine_exchange: count all-gather + record / kill-id broadcasts (HIP events) */
+    int32_t sweep_jobs_listed; /* destination cells the sweep's waves were handed: the jobs of this rank's range with a source entry that
+                                * starts a trial (in the four bytes that were padding: the struct's size and the other offsets stand) */
     int64_t exchange_bytes; /* bytes this rank received in them */
     int64_t check_retried_cells; /* destination cells whose Optim::check met more patches than the wave's LDS id set holds and that ran
                                   * again on the second tier (a 16384-slot set in global memory); normally 0 */

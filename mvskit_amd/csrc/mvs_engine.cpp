@@ -81,7 +81,12 @@ constexpr int trim_nparts = 256;   // (k_index_sort_trim: one per block index mo
 // the sweep's queue cursors (SweepArgs::cursors, uint32 each): eight 128-byte lines, the first on a line boundary of the buffer
 constexpr int sweep_cursors = (trim_parts + trim_nparts + 15) / 16 * 16;
 constexpr int sweep_cursor_words = MVS_SWEEP_QUEUES * MVS_SWEEP_CURSOR_STRIDE * (int)sizeof(uint32_t) / (int)sizeof(unsigned long long);
-constexpr int words = sweep_cursors + sweep_cursor_words;
+// behind them, cleared with them: the bounds of the sweep's job lists (SweepArgs::list_bounds, int32 each; the last = jobs listed)
+constexpr int sweep_list_bounds = sweep_cursors + sweep_cursor_words;
+constexpr int sweep_list_bound_words = (MVS_SWEEP_QUEUES + 1 + 1) / 2;
+constexpr int words = sweep_list_bounds + sweep_list_bound_words;
+// the scratch of mvsk_job_list holds a flag per job of the launch's range, rounded up to whole chunks in every queue
+constexpr int64_t job_list_pad = 1024 + 2;
 }  // namespace misc
 // The words of mvs_engine::fstat_buf (Filter::run's statistics).  k_filter_neighbor fixes the first two ranges itself.
 namespace fstat {
@@ -212,6 +217,8 @@ struct mvs_engine {
     DevBuf<DCounters> counters;
     DevBuf<int32_t> error_flag;
     DevBuf<int32_t> big_tables, retry_jobs;  // Optim::check's second tier (k_sweep_retry): 256 id sets of 16384 ints, the cells to run again
+    DevBuf<int32_t> job_list;                // the jobs of a launch that run a trial, per queue (SweepArgs::job_list); its flags and their scan
+                                             // lie in job_cnt and job_base_scan, which the commit fills only after the sweep
     int64_t retried_cells = 0;               // destination cells that went to the second tier since the engine was created
     int64_t pass_retried = 0;                // ... in the last pass
     SweepArgs sa{};
@@ -903,8 +910,8 @@ int mvs_engine_set_views(mvs_engine* e, int nviews, const mvs_view_desc* views) 
     int64_t njobs_max = 0;
     for (int v = 0; v < nviews; ++v) njobs_max += (int64_t)((e->hviews[v].gw + 1) / 2) * e->hviews[v].gh;
     const int maxstage = (e->prm.view_propagation ? 3 : 2) * e->prm.cap * e->prm.max_propag;
-    if (e->job_stage.ensure(njobs_max * maxstage) || e->job_nstage.ensure(njobs_max + 2) || e->job_cnt.ensure(njobs_max + 2) ||
-        e->job_base_scan.ensure(njobs_max + 2))
+    if (e->job_stage.ensure(njobs_max * maxstage) || e->job_nstage.ensure(njobs_max + 2) || e->job_cnt.ensure(njobs_max + misc::job_list_pad) ||
+        e->job_base_scan.ensure(njobs_max + misc::job_list_pad) || e->job_list.ensure(std::max<int64_t>(njobs_max, 16)))
         return MVS_ERR_HIP;
     const int64_t scan_n = std::max<int64_t>(std::max<int64_t>(nc, pool_cap), njobs_max);
     if (e->scan_tmp.ensure(scan_n / 256 + 4096)) return MVS_ERR_HIP;
@@ -1254,8 +1261,6 @@ static int pass_impl(mvs_engine* e, int iter, int pass, mvs_counters* out) {
         Range rg("mvs:index");
         if (int r = build_index(e, &trimmed)) return r;
     }
-    HIPCHK(hipEventRecord(e->ev[1], st));
-    Range rg_sweep(pass & 1 ? "mvs:sweep colour 1" : "mvs:sweep colour 0");
     // jobs: one per (swept view, row, half column) of the pass colour
     SweepArgs& a = e->sa;
     memset(&a, 0, sizeof a);
@@ -1302,7 +1307,6 @@ static int pass_impl(mvs_engine* e, int iter, int pass, mvs_counters* out) {
         }
         a.job_lo = cuts[R];
         a.job_hi = cuts[R + 1];
-        HIPCHK(hipMemsetAsync(e->job_nstage.p, 0, (size_t)nj * sizeof(int32_t), st));  // jobs of other shards stage nothing
     }
     a.staging = e->staging.p; a.staging_cap = e->staging.cap;
     a.stage_counter = e->misc.p + misc::stage_counter;
@@ -1319,11 +1323,20 @@ static int pass_impl(mvs_engine* e, int iter, int pass, mvs_counters* out) {
     HIPCHK(hipMemsetAsync(e->misc.p + misc::sweep_retry, 0, sizeof(unsigned long long), st));
     HIPCHK(hipMemsetAsync(e->misc.p + misc::stage_counter, 0, sizeof(unsigned long long), st));
     a.cursors = reinterpret_cast<uint32_t*>(e->misc.p + misc::sweep_cursors);
-    HIPCHK(hipMemsetAsync(e->misc.p + misc::sweep_cursors, 0, misc::sweep_cursor_words * sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(e->misc.p + misc::sweep_cursors, 0, (misc::sweep_cursor_words + misc::sweep_list_bound_words) * sizeof(unsigned long long), st));
     HIPCHK(hipMemsetAsync(e->counters.p, 0, MVS_COUNTER_SLOTS * sizeof(DCounters), st));
     HIPCHK(hipMemsetAsync(e->error_flag.p, 0, sizeof(int32_t), st));
     const DParams p = current_params(e);
     const RefineSel rs = refine_sel(e);
+    // The jobs of this launch that will run a trial, per queue, while the index is hot (part of index_ms); every job's job_nstage is
+    // cleared on the way.  The waves read the list bounds on the device: the host learns them with the counters, after the sweep.
+    if (int r = e->job_list.ensure(std::max<int64_t>(nj, 16))) return r;
+    if (e->job_cnt.ensure(nj + misc::job_list_pad) || e->job_base_scan.ensure(nj + misc::job_list_pad)) return MVS_ERR_HIP;
+    int32_t* list_bounds = reinterpret_cast<int32_t*>(e->misc.p + misc::sweep_list_bounds);
+    a.job_list = e->job_list.p; a.list_bounds = list_bounds;
+    mvsk_job_list(p, a, e->job_cnt.p, e->job_base_scan.p, reinterpret_cast<int32_t*>(e->scan_tmp.p), e->job_list.p, list_bounds, st);
+    HIPCHK(hipEventRecord(e->ev[1], st));
+    Range rg_sweep(pass & 1 ? "mvs:sweep colour 1" : "mvs:sweep colour 0");
     mvsk_sweep(p, a, rs, st);
     e->pass_retried = 0;
     if (want_vgrid(e)) {  // cells whose Optim::check outgrew the wave's LDS run again on the second tier (normally none)
@@ -1340,6 +1353,8 @@ static int pass_impl(mvs_engine* e, int iter, int pass, mvs_counters* out) {
     HIPCHK(hipMemcpyAsync(fill, e->misc.p + misc::fill_evals, sizeof fill, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(hcs.data(), e->counters.p, hcs.size() * sizeof(DCounters), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&herr, e->error_flag.p, sizeof herr, hipMemcpyDeviceToHost, st));
+    int32_t hbounds[MVS_SWEEP_QUEUES + 1];
+    HIPCHK(hipMemcpyAsync(hbounds, list_bounds, sizeof hbounds, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
     mvs_counters sum{};
@@ -1350,8 +1365,13 @@ static int pass_impl(mvs_engine* e, int iter, int pass, mvs_counters* out) {
     (void)hipEventElapsedTime(&ms, e->ev[1], e->ev[2]); e->timing.sweep_ms = ms;
     e->timing.commit_ms = 0.0f; e->timing.sweep_launches = 1; e->timing.exchange_ms = 0.0f; e->timing.exchange_bytes = 0;
     e->timing.check_retried_cells = e->pass_retried;
+    e->timing.sweep_jobs_listed = hbounds[MVS_SWEEP_QUEUES];
     e->staged = true; e->counted = false;
     if (out) *out = sum;
+#ifdef MVS_JOBLIST_COUNTS  // diagnostic build (k_job_list): what the former per-take test would have let through, beside what is listed
+    fprintf(stderr, "[job list] iter %d colour %d: jobs %lld, with any source entry %llu, listed %llu\n", iter, pass & 1, (long long)(a.job_hi - a.job_lo),
+            hcs[0].stage[0], hcs[0].stage[1]);
+#endif
 #ifdef MVS_STAGE_TIMING
     {
         unsigned long long stage[16] = {0};
@@ -1615,6 +1635,7 @@ int mvs_engine_propagate(mvs_engine* e, int iter, mvs_counters* out) {  // Propa
         add_counters(total, c);
         tt.index_ms += e->timing.index_ms; tt.sweep_ms += e->timing.sweep_ms; tt.commit_ms += e->timing.commit_ms; tt.sweep_launches += 1;
         tt.exchange_ms += e->timing.exchange_ms; tt.exchange_bytes += e->timing.exchange_bytes; tt.check_retried_cells += e->timing.check_retried_cells;
+        tt.sweep_jobs_listed += e->timing.sweep_jobs_listed;
     }
     e->timing = tt;
     if (out) *out = total;

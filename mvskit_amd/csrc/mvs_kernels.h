@@ -29,6 +29,11 @@ size_t mvsk_sweep_lds_bytes(const DParams& prm);
 void mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hipStream_t st);
 void mvsk_sweep_retry(const DParams& prm, const SweepArgs& a, int nretry, const RefineSel& rs, hipStream_t st);
 void mvsk_job_work(const DParams& prm, const SweepArgs& a, int mode, int shift, int32_t* work, hipStream_t st);
+// The sweep's job lists: clears job_nstage[0, njobs) and lists the jobs of [job_lo, job_hi) that run a trial, per queue.  flags and scan
+// are scratch of mvsk_job_list_seg(a) * MVS_SWEEP_QUEUES (< job_hi - job_lo + 1024) and one more ints; list holds up to job_hi - job_lo
+// jobs, bounds MVS_SWEEP_QUEUES + 1 ints (bounds[MVS_SWEEP_QUEUES] = the number listed; untouched when the range is empty)
+int mvsk_job_list_seg(const SweepArgs& a);
+void mvsk_job_list(const DParams& prm, const SweepArgs& a, int32_t* flags, int32_t* scan, int32_t* scan_tmp, int32_t* list, int32_t* bounds, hipStream_t st);
 void mvsk_job_cuts(const int32_t* scan, int64_t njobs, int n, int32_t* cuts, hipStream_t st);
 void mvsk_commit_count(const SweepArgs& a, int32_t* cnt, hipStream_t st);
 void mvsk_commit_copy(const SweepArgs& a, const int32_t* base, DPatch* dst, int64_t dst_cap, int32_t* per_view, int keep_key, hipStream_t st);

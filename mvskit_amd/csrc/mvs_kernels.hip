@@ -377,22 +377,29 @@ DEV void job_cell(const DParams& prm, const SweepArgs& a, int64_t job, int& v, i
     cy = local / halfw;
     cx = 2 * (local % halfw) + ((a.colour + cy) & 1);
 }
-// Has the job a destination cell (not the ghost job at cx == gw of an odd-width grid) with any source at all?  A lane per job.
-DEV bool job_has_source(const DParams& prm, const SweepArgs& a, int64_t job) {
+// The entries of a job's source lists that start trials in sweep_cell -- 0 for a job without a destination cell (the ghost job at
+// cx == gw of an odd-width grid, a job outside the grid) --: of the first min(csr_cnt, MVS_CAPMAX) entries of the cell above/below
+// and the cell beside, those whose reference view is the swept view; with view propagation, those of the cell's own list whose
+// reference view is another.  *dest = the destination cell's index entry (-1 without a cell).  A lane per job (k_job_list, k_job_work).
+DEV int job_trial_sources(const DParams& prm, const SweepArgs& a, int64_t job, int* dest) {
     int v, cx, cy;
     job_cell(prm, a, job, v, cx, cy);
     const DView* vw = prm.views + v;
     const int gw = vw->gw, gh = vw->gh;
-    if (cx >= gw || cy >= gh) return false;
-    const int sxs[2] = {cx, cx - a.inc}, sys[2] = {cy - a.inc, cy};
-    bool has = false;
-    for (int k = 0; k < 2; ++k) {
+    *dest = -1;
+    if (cx >= gw || cy >= gh) return 0;
+    *dest = vw->cell_base + cy * gw + cx;
+    const int sxs[3] = {cx, cx - a.inc, cx}, sys[3] = {cy - a.inc, cy, cy};
+    const int nsrc = prm.view_propagation ? 3 : 2;
+    int n = 0;
+    for (int k = 0; k < nsrc; ++k) {
         if (sxs[k] < 0 || gw <= sxs[k] || sys[k] < 0 || gh <= sys[k]) continue;
         const int g = vw->cell_base + sys[k] * gw + sxs[k];
-        has |= prm.csr_cnt[g] > 0;
+        const csr_off_t sb = prm.csr_start[g];
+        const int sn = min(prm.csr_cnt[g], MVS_CAPMAX);
+        for (int j = 0; j < sn; ++j) n += ((pgrid_ref(prm, sb + j) == v) != (k == 2)) ? 1 : 0;
     }
-    if (prm.view_propagation) has |= prm.csr_cnt[vw->cell_base + cy * gw + cx] > 0;
-    return has;
+    return n;
 }
 // Work proxy of a job, for cutting the job sequence into ranges of equal WORK (multi-GPU: every rank holds the same index,
 // computes the same proxy and finds the same cuts).  A job runs max_propag trials per source entry whose reference view is
@@ -403,26 +410,14 @@ DEV bool job_has_source(const DParams& prm, const SweepArgs& a, int64_t job) {
 __global__ void k_job_work(DParams prm, SweepArgs a, int mode, int shift, int32_t* __restrict__ work) {
     const int64_t job = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (job >= a.njobs) return;
-    int v, cx, cy;
-    job_cell(prm, a, job, v, cx, cy);
-    const DView* vw = prm.views + v;
-    const int gw = vw->gw, gh = vw->gh;
+    int dest;
+    const int n = job_trial_sources(prm, a, job, &dest);
     int w = 0;
-    if (cx < gw && cy < gh) {
-        const int sxs[3] = {cx, cx - a.inc, cx}, sys[3] = {cy - a.inc, cy, cy};
-        const int nsrc = prm.view_propagation ? 3 : 2;
-        int n = 0;
-        for (int k = 0; k < nsrc; ++k) {
-            if (sxs[k] < 0 || gw <= sxs[k] || sys[k] < 0 || gh <= sys[k]) continue;
-            const int g = vw->cell_base + sys[k] * gw + sxs[k];
-            const csr_off_t sb = prm.csr_start[g];
-            const int sn = prm.csr_cnt[g];
-            for (int j = 0; j < sn; ++j) n += ((pgrid_ref(prm, sb + j) == v) != (k == 2)) ? 1 : 0;
-        }
+    if (dest >= 0) {
         if (mode == 1) w = n;
         else {
             const int trials = n * prm.max_propag;
-            const int room = max(prm.cap - prm.csr_cnt[vw->cell_base + cy * gw + cx], 0);
+            const int room = max(prm.cap - prm.csr_cnt[dest], 0);
             const int full = min(trials, (room * 5 + 3) / 4);
             w = 32 * full + 2 * (trials - full);
         }
@@ -441,6 +436,58 @@ __global__ void k_job_cuts(const int32_t* __restrict__ scan, int64_t njobs, int 
     }
 }
 
+#ifndef MVS_XCD_CHUNK
+#define MVS_XCD_CHUNK 128
+#endif
+// The sweep's job lists (sweep_resident).  The launch's job range [job_lo, job_hi) is cut into chunks of MVS_XCD_CHUNK consecutive
+// jobs, chunk c belongs to queue c % 8; the flags of the jobs are laid out QUEUE-MAJOR -- queue q owns the slots [q seg, (q + 1) seg),
+// seg = its chunks rounded up over the queues, times MVS_XCD_CHUNK; a slot beyond job_hi has no job -- so that ONE exclusive scan of
+// the flags gives every listed job its place in a list that holds queue 0's jobs, then queue 1's, ..., each in ascending job order.
+DEV int64_t list_slot_job(const SweepArgs& a, int64_t slot, int seg) {
+    const int64_t q = slot / seg, r = slot % seg;
+    return a.job_lo + ((r / MVS_XCD_CHUNK) * MVS_SWEEP_QUEUES + q) * MVS_XCD_CHUNK + r % MVS_XCD_CHUNK;
+}
+// A thread per job of [0, njobs) clears its job_nstage (a job that is not listed stages nothing: other shards' jobs, jobs without a
+// trial); a thread per slot flags the slot's job if sweep_cell would run a trial for it (job_trial_sources).
+__global__ void k_job_list(DParams prm, SweepArgs a, int seg, int32_t* __restrict__ flags) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < a.njobs) a.job_nstage[t] = 0;
+    if (t >= (int64_t)MVS_SWEEP_QUEUES * seg) return;
+    const int64_t job = list_slot_job(a, t, seg);
+    int dest = -1;
+    const int n = job < a.job_hi ? job_trial_sources(prm, a, job, &dest) : 0;
+    flags[t] = n > 0 ? 1 : 0;
+#ifdef MVS_JOBLIST_COUNTS
+    // diagnostic build: how many jobs the test of the former take passed (a destination cell and ANY entry in a source list), and how
+    // many are listed, into the stage words of counter slot 0 (the host prints them per launch)
+    bool any = false;
+    if (dest >= 0) {
+        int v, cx, cy;
+        job_cell(prm, a, job, v, cx, cy);
+        const DView* vw = prm.views + v;
+        const int sxs[3] = {cx, cx - a.inc, cx}, sys[3] = {cy - a.inc, cy, cy};
+        for (int k = 0; k < (prm.view_propagation ? 3 : 2); ++k)
+            if (0 <= sxs[k] && sxs[k] < vw->gw && 0 <= sys[k] && sys[k] < vw->gh) any |= prm.csr_cnt[vw->cell_base + sys[k] * vw->gw + sxs[k]] > 0;
+    }
+    const unsigned long long m_any = __ballot(any), m_listed = __ballot(n > 0);
+    if ((threadIdx.x & 63) == 0) {
+        if (m_any) atomicAdd(&a.counters->stage[0], (unsigned long long)__popcll(m_any));
+        if (m_listed) atomicAdd(&a.counters->stage[1], (unsigned long long)__popcll(m_listed));
+    }
+#endif
+}
+// list[scan[slot]] = the job of every flagged slot (scan = the exclusive scan of the flags); bounds[q] = where queue q's jobs begin,
+// bounds[8] = the number of jobs listed
+__global__ void k_job_scatter(SweepArgs a, int seg, const int32_t* __restrict__ scan, int32_t* __restrict__ list, int32_t* __restrict__ bounds) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t nslots = (int64_t)MVS_SWEEP_QUEUES * seg;
+    if (t >= nslots) return;
+    const int32_t pos = scan[t];
+    if (t % seg == 0) bounds[t / seg] = pos;
+    if (t == nslots - 1) bounds[MVS_SWEEP_QUEUES] = scan[nslots];
+    if (scan[t + 1] != pos) list[pos] = (int32_t)list_slot_job(a, t, seg);
+}
+
 #ifndef MVS_SWEEP_WAVES
 #define MVS_SWEEP_WAVES 3  // waves per SIMD the register allocator is asked to fit: 168 VGPRs (4 waves = 128 VGPRs spills ~110 of them; measured 19.4 vs 18.9 M patches/s)
 #endif
@@ -455,9 +502,6 @@ __global__ void k_job_cuts(const int32_t* __restrict__ scan, int64_t njobs, int 
 #define ST_ADD(k, t0) { const unsigned long long t1_ = ST_NOW(); st_acc[k] += t1_ - (t0); (t0) = t1_; }
 #else
 #define ST_ADD(k, t0)
-#endif
-#ifndef MVS_XCD_CHUNK
-#define MVS_XCD_CHUNK 128
 #endif
 // The work counts of a wave, summed over its cells (wave-uniform: scalar registers) and added into one counter slot before it exits
 struct SweepAcc {
@@ -493,7 +537,7 @@ DEV void sweep_acc_flush(const SweepArgs& a, const SweepAcc& acc, unsigned slot)
     atomicAdd(&C->stage[14], acc.stage[14]); atomicAdd(&C->stage[15], acc.stage[15]);  // inside postProcess: setRefImage's pair sums and choice
 #endif
 }
-// One destination cell: `job` has a cell and a source (job_has_source), job_nstage[job] is 0.  The wave comes here cell after cell
+// One destination cell: `job` has a cell and a source entry that starts a trial (it is listed: k_job_list), job_nstage[job] is 0.  The wave comes here cell after cell
 // (the LDS of the previous cell is dead: the caller puts a barrier in between): everything a cell keeps is set up here, and what it
 // counted goes into `acc` when it is done -- nothing of a cell that gives up.
 // SIMPLEX = true: the refinement is refine_patch_simplex with max_evals / xtol (k_sweep_simplex, k_sweep_retry_simplex: the CONVERGED
@@ -666,51 +710,37 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WaveCtx& wc, SweepAc
 // b % 8), and a wave serves queue blockIdx.x & 7 first: a stretch of cells goes to one XCD and consecutive stretches to consecutive
 // XCDs, so a destination and its source cells share an L2 and every XCD gets the same mix of cheap and expensive regions.  (One
 // contiguous band of cells per XCD left XCDs idle for a quarter of the launch: the bands -- one and a half views each -- differ in
-// work; measured 770 -> 603 ms per iteration.)  A wave takes the next MVS_SWEEP_TAKE jobs of its queue with one atomicAdd WITH
+// work; measured 770 -> 603 ms per iteration.)
+// A queue is a LIST of the jobs of its chunks that will run a trial, in ascending job order (k_job_list / k_job_scatter, built while
+// the index is hot; list_bounds[q] .. list_bounds[q + 1] of job_list): a wave never meets a ghost job, a cell without a source, or a
+// cell whose source lists hold only patches of other reference views -- two jobs in three where the pool is dense -- and a launch
+// in which no cell has a source reads eight empty bounds and exits.  A wave takes the next job of its queue with one atomicAdd WITH
 // return on the queue's cursor (a cache line each, zero before the launch) -- in the middle of its work, like the staging-slot
 // counter, never as its last instruction -- and when its queue is drained it takes from the others, in the order q + 1, q + 2, ...;
 // when all eight are drained it adds its work counts into its counter slot and exits.  No grid barrier, no co-residency assumption:
 // a block that starts late finds less work, a grid of one wave drains everything.
-// Of a take every job gets a lane (job_has_source) that clears its job_nstage -- jobs beyond job_hi and the ghost jobs of an
-// odd-width grid end here --; the wave then runs the cells with work in job order.
-// MVS_SWEEP_TAKE is 1: the waves of an XCD must work on NEIGHBOURING cells at any one time, as the blocks of a one-block-per-cell
+// A take is ONE job: the waves of an XCD must work on NEIGHBOURING cells at any one time, as the blocks of a one-block-per-cell
 // launch do -- neighbours sample the same texels and read the same lists, and L1 / L2 serve them.  A wave that keeps a whole
 // chunk to itself spreads the 384 waves of an XCD over 384 chunks: sweep 333 ms per step against 281 for one block per cell;
-// takes of 64 / 16 / 4 / 1 jobs: 309 / 285 / 273.5 / 270.4 ms (profiles/r09_resident_ab.txt).  The cursor's atomic is one per
-// job then, 390 k per queue and launch: a round trip in ~430 us of work per cell.
-#ifndef MVS_SWEEP_TAKE
-#define MVS_SWEEP_TAKE 1
-#endif
-static_assert(MVS_SWEEP_TAKE <= 64 && MVS_XCD_CHUNK % MVS_SWEEP_TAKE == 0, "a take is a part of one chunk, a lane per job");
+// takes of 64 / 16 / 4 / 1 jobs (of unlisted jobs, a lane per job testing for a source): 309 / 285 / 273.5 / 270.4 ms
+// (profiles/r09_resident_ab.txt).  The cursor's atomic is one per listed job: a round trip in ~430 us of work per cell.
 template <bool SIMPLEX>
 DEV void sweep_resident(const DParams& prm, const SweepArgs& a, int* s_scratch, float* s_texs, int max_evals, float xtol) {
     WaveCtx wc = make_wave_ctx(prm);
     SweepAcc acc = sweep_acc_zero();
-    const int nchunks = (int)((a.job_hi - a.job_lo + MVS_XCD_CHUNK - 1) / MVS_XCD_CHUNK);
-    constexpr unsigned per = MVS_XCD_CHUNK / MVS_SWEEP_TAKE;  // takes per chunk
     for (unsigned step = 0; step < MVS_SWEEP_QUEUES; ++step) {
         const unsigned q = (blockIdx.x + step) & (MVS_SWEEP_QUEUES - 1u);
-        // queue q holds the chunks q, q + 8, ...: (nchunks - q + 7) / 8 of them, none if q >= nchunks
-        const unsigned ntake = (unsigned)((nchunks - (int)q + MVS_SWEEP_QUEUES - 1) / MVS_SWEEP_QUEUES) * per;
+        const int32_t qbegin = a.list_bounds[q];
+        const unsigned ntake = (unsigned)(a.list_bounds[q + 1] - qbegin);
+        if (ntake == 0u) continue;
         for (;;) {
             unsigned k = 0;
             if (wc.lane == 0) k = atomicAdd(a.cursors + q * MVS_SWEEP_CURSOR_STRIDE, 1u);
             k = (unsigned)rfl((int)k);
             if (k >= ntake) break;  // drained: on to the next queue
-            const int64_t base = a.job_lo + ((int64_t)q + (int64_t)MVS_SWEEP_QUEUES * (k / per)) * MVS_XCD_CHUNK + (int64_t)(k % per) * MVS_SWEEP_TAKE;
-            const int64_t mine = base + wc.lane;
-            bool has = false;
-            if (wc.lane < MVS_SWEEP_TAKE && mine < a.job_hi) {
-                a.job_nstage[mine] = 0;
-                has = job_has_source(prm, a, mine);
-            }
-            unsigned long long t = ballot(has);
-            while (t) {  // the cells with work, in job order
-                const int l = __ffsll((long long)t) - 1;
-                t &= t - 1ull;
-                __syncthreads();  // the LDS scratch, frames, pivots and kept textures of the previous cell are dead
-                sweep_cell<false, SIMPLEX>(prm, a, wc, &acc, base + l, s_scratch, s_texs, nullptr, max_evals, xtol);
-            }
+            const int64_t job = a.job_list[qbegin + (int32_t)k];
+            __syncthreads();  // the LDS scratch, frames, pivots and kept textures of the previous cell are dead
+            sweep_cell<false, SIMPLEX>(prm, a, wc, &acc, job, s_scratch, s_texs, nullptr, max_evals, xtol);
         }
     }
     if (wc.lane == 0) sweep_acc_flush(a, acc, blockIdx.x & (MVS_COUNTER_SLOTS - 1));
@@ -1381,13 +1411,12 @@ void mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hip
     // development knob: MVS_SWEEP_LDS_PAD=<bytes> raises the block's LDS allocation, i.e. lowers the waves per SIMD
     static const size_t pad = getenv("MVS_SWEEP_LDS_PAD") ? (size_t)atol(getenv("MVS_SWEEP_LDS_PAD")) : 0;
     const size_t lds = mvsk_sweep_lds_bytes(prm) + pad;
-    // the resident grid: the waves the device holds at the launch bound (4 SIMDs per CU) and no more blocks than there are takes of
-    // work.  (Where the LDS allocation lets fewer waves in, the rest start late and find less work: nothing depends on residency.)
+    // the resident grid: the waves the device holds at the launch bound (4 SIMDs per CU) and no more blocks than there are jobs.  (Where the LDS allocation lets fewer waves in, the rest start late and find less work: nothing depends on residency.)
     int dev = 0, cus = 0;
     (void)hipGetDevice(&dev);
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
     int64_t nblocks = (int64_t)cus * 4 * MVS_SWEEP_WAVES;
-    nblocks = std::min(nblocks, (nloc + MVS_SWEEP_TAKE - 1) / MVS_SWEEP_TAKE);
+    nblocks = std::min(nblocks, nloc);  // (how many of them are listed only the device knows)
     // development knob, read on every launch: MVS_SWEEP_GRID=<n> caps the number of resident blocks (the result does not depend on it)
     if (const char* g = getenv("MVS_SWEEP_GRID")) {
         const long cap = atol(g);
@@ -1398,6 +1427,19 @@ void mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hip
 }
 void mvsk_job_work(const DParams& prm, const SweepArgs& a, int mode, int shift, int32_t* work, hipStream_t st) {
     if (a.njobs > 0) hipLaunchKernelGGL(k_job_work, dim3(nblk(a.njobs, 256)), dim3(256), 0, st, prm, a, mode, shift, work);
+}
+int mvsk_job_list_seg(const SweepArgs& a) {
+    const int64_t nchunks = (std::max<int64_t>(a.job_hi - a.job_lo, 0) + MVS_XCD_CHUNK - 1) / MVS_XCD_CHUNK;
+    return (int)((nchunks + MVS_SWEEP_QUEUES - 1) / MVS_SWEEP_QUEUES) * MVS_XCD_CHUNK;
+}
+void mvsk_job_list(const DParams& prm, const SweepArgs& a, int32_t* flags, int32_t* scan, int32_t* scan_tmp, int32_t* list, int32_t* bounds, hipStream_t st) {
+    const int seg = mvsk_job_list_seg(a);
+    const int64_t nslots = (int64_t)MVS_SWEEP_QUEUES * seg, nthreads = std::max(nslots, a.njobs);
+    if (nthreads <= 0) return;
+    hipLaunchKernelGGL(k_job_list, dim3(nblk(nthreads, 256)), dim3(256), 0, st, prm, a, seg, flags);
+    if (nslots <= 0) return;
+    launch_exclusive_scan<int32_t, int32_t>(flags, scan, nslots, scan_tmp, st);
+    hipLaunchKernelGGL(k_job_scatter, dim3(nblk(nslots, 256)), dim3(256), 0, st, a, seg, scan, list, bounds);
 }
 void mvsk_job_cuts(const int32_t* scan, int64_t njobs, int n, int32_t* cuts, hipStream_t st) {
     if (njobs > 0) hipLaunchKernelGGL(k_job_cuts, dim3(nblk(njobs, 256)), dim3(256), 0, st, scan, njobs, n, cuts);

@@ -97,7 +97,7 @@ struct DParams {
 #ifndef MVS_COUNTER_SLOTS
 #define MVS_COUNTER_SLOTS 256  // SweepArgs::counters: that many DCounters, block b of the sweep adds into slot b % MVS_COUNTER_SLOTS
 #endif
-#define MVS_SWEEP_QUEUES 8         // the sweep's job queues, one per XCD: chunk c of a launch's job range is in queue c % 8
+#define MVS_SWEEP_QUEUES 8         // the sweep's job queues, one per XCD: the listed jobs of chunk c of a launch's job range are in queue c % 8
 #define MVS_SWEEP_CURSOR_STRIDE 32 // SweepArgs::cursors: queue q's cursor is word q * 32 (a 128-byte line each)
 struct DCounters {
     unsigned long long candidates, prefiltered, patches, fail0, fail1, inserted, replaced, evals, view_evals, trimmed;
@@ -120,7 +120,7 @@ struct SweepArgs {
     int64_t staging_cap;
     unsigned long long* stage_counter;
     int32_t* job_stage;   // [njobs][maxstage] staging slots in creation order
-    int32_t* job_nstage;  // [njobs]
+    int32_t* job_nstage;  // [njobs] cleared by k_job_list, written by the cells that ran
     int32_t maxstage;
     uint8_t* kill;        // [pool_cap]
     DCounters* counters;
@@ -128,5 +128,7 @@ struct SweepArgs {
     int32_t* big_tables;  // Optim::check's second tier (k_sweep_retry): 16384-slot id sets in global memory, one per block
     int32_t* retry_jobs;  // the destination cells (jobs) the first launch handed to the second tier, and
     int32_t* nretry;      //   how many
-    uint32_t* cursors;    // [MVS_SWEEP_QUEUES * MVS_SWEEP_CURSOR_STRIDE] the next chunk of every queue, zero before the launch
+    uint32_t* cursors;    // [MVS_SWEEP_QUEUES * MVS_SWEEP_CURSOR_STRIDE] the next list entry of every queue, zero before the launch
+    const int32_t* job_list;     // the jobs of [job_lo, job_hi) that run a trial, queue after queue, ascending within a queue (k_job_list)
+    const int32_t* list_bounds;  // [MVS_SWEEP_QUEUES + 1] queue q's jobs are job_list[list_bounds[q] .. list_bounds[q + 1])
 };

@@ -67,7 +67,7 @@ class Counters(C.Structure):
 
 class Timing(C.Structure):
     _fields_ = [("index_ms", C.c_float), ("sweep_ms", C.c_float), ("commit_ms", C.c_float), ("sweep_launches", C.c_int32),
-                ("exchange_ms", C.c_float), ("exchange_bytes", C.c_int64), ("check_retried_cells", C.c_int64)]
+                ("exchange_ms", C.c_float), ("sweep_jobs_listed", C.c_int32), ("exchange_bytes", C.c_int64), ("check_retried_cells", C.c_int64)]
 
 
 class FilterStats(C.Structure):
@@ -390,7 +390,8 @@ class Engine:
         t = Timing()
         self._check(self.L.mvs_engine_last_timing(self.h, C.byref(t)))
         return {"index_ms": t.index_ms, "sweep_ms": t.sweep_ms, "commit_ms": t.commit_ms, "sweep_launches": t.sweep_launches,
-                "exchange_ms": t.exchange_ms, "exchange_bytes": int(t.exchange_bytes), "check_retried_cells": int(t.check_retried_cells)}
+                "exchange_ms": t.exchange_ms, "exchange_bytes": int(t.exchange_bytes), "check_retried_cells": int(t.check_retried_cells),
+                "sweep_jobs_listed": int(t.sweep_jobs_listed)}
 
     def depth_normal_map(self, view, kind):
         gw, gh = self.grid_dims(view)
