@@ -206,6 +206,54 @@ typedef struct mvs_seed_view {
     const uint8_t* mask;
 } mvs_seed_view;
 int mvs_engine_seed_patches(mvs_engine* e, int64_t npoints, const float* xyz, const mvs_seed_view* views, int64_t* n_added);
+/* The cold start, for a caller who has images, masks and cameras but no depth point cloud: seed patches from random plane hypotheses
+ * scored on the device (PatchMatch stereo's usual start; no reference counterpart -- it stands where DepthNormInit::createPatches
+ * stands).  A job is a cell c = cy * gw + cx of a view v; the jobs run over all views and all cells, in (view, cell) order.
+ *   1. mask gate   the cell centre (propagate.cpp:147-148) at Option::m_level, pixel floorf(ic + 0.5f): outside the image, or on the
+ *                  background of a view that has a mask -> the job gives nothing.
+ *   2. hypotheses  `hypotheses` planes, hypothesis k from five draws u_j in [-0.5, 0.5) of the call's own counter-based stream (`seed`,
+ *                  the constant 0x5eed0001, v, c, k, j -- mvs_config.seed plays no part): the pixel (icx + csize u0, icy + csize u1);
+ *                  the depth uniform in inverse depth, 1/d = 1/dmax + (u2 + 0.5)(1/dmin - 1/dmax), along the view's optical axis;
+ *                  coord = Camera::unproject(d (px, py, 1)); the normal at the angle theta = max_tilt sqrt(u3 + 0.5) from the unit
+ *                  vector r towards the camera centre, in the direction phi = 2 pi (u4 + 0.5) of Filter::ortho's frame of r, normalised;
+ *                  normal.w = -coord . n.  The record: m_images = [v], no m_vimages, m_ncc = -1, scales and m_tmp 0, alive, id = k.
+ *   3. score       every hypothesis through Optim::preProcess and, when that passes, PatchManager::computeNcc on its result; the winner
+ *                  is the highest score, the lowest k among equals, and must score strictly above min_ncc -- else the job gives nothing.
+ *   4. patch       the winner through Optim::refinePatch with the engine's refiner (mvs_engine_set_refiner; HALVING draws under the key
+ *                  (0, 0, c, 0) as MVS_PROBE_REFINE does for record c; a CONVERGED run that spends its budget keeps its start), then
+ *                  Optim::postProcess.  Optim::check does not run, whatever the depth.  A job whose postProcess passes gives one patch.
+ *   5. append      the patches, in (view, cell) order, behind the pool: positions come from a scan, not from atomics, so two calls on
+ *                  the same state give the same pool bytes.  Records are alive, not settled, id = the pool index.
+ * Steps 3 and 4 are the functions behind mvs_engine_probe's ops 1, 0, 2 and 3, called as those call them: an appended record has the
+ * bytes that chain of probes gives.  postProcess reads the depth maps when the engine's depth > 0: they are built from the pool as it is
+ * at entry (nothing else of a pass's index build runs: no patch is scored or trimmed), so the patches of one call do not see each
+ * other and the result does not depend on launch order.  One consequence: MVS_PROBE_POSTPROCESS runs the whole index build, which
+ * kills the patches beyond MAX_NUM_OF_PATCHES of an over-full cell before the depth maps are made.  Over a pool with such a cell and
+ * depth > 0 the maps of the two can differ, and the equality with the chain of probes holds only for a pool that build would not trim
+ * (an empty pool, or one a pass has left).  Existing records are never modified; the cell indexes, the thresholds and the
+ * mvs_config.seed stream stay as they were; a second call appends again.  Not a collective: every rank of a multi-rank job makes the same
+ * call and ends with the same pool, as with mvs_engine_seed_patches.  Device memory for the call, released before it returns: one
+ * record and eight bytes per cell of the largest view.
+ * MVS_ERR_ARG: s null, hypotheses outside 1..64, a range pointer null, max_tilt not in (0, pi/3], no engine -- checked in that order,
+ * before the handle is read -- then, with the engine's view count, a range entry that is not finite or not 0 < min < max.
+ * MVS_ERR_STATE: views not set, or a pass waiting for its commit; MVS_ERR_HIP: an allocation or copy failed; MVS_ERR_CAPACITY: the patches
+ * do not fit the pool (known before the pool is written).  After any error the pool is what it was. */
+typedef struct mvs_seed_random {
+    int32_t hypotheses;      /* K, 1..64 per cell */
+    uint32_t seed;           /* own counter-based stream, independent of mvs_config.seed */
+    float max_tilt;          /* radians, 0 < max_tilt <= pi/3: largest angle between a hypothesis normal and the direction to the camera */
+    float min_ncc;           /* a winner must score above this; < 0 = the engine's nccThresholdBefore at the call */
+    const float* depth_min;  /* [nviews] depth range along each view's optical axis (oaxis . X), 0 < min < max, finite */
+    const float* depth_max;
+} mvs_seed_random;           /* 32 bytes */
+void mvs_default_seed_random(mvs_seed_random* s); /* K 8, seed 1, max_tilt pi/3, min_ncc -1, ranges NULL */
+int mvs_engine_seed_random(mvs_engine* e, const mvs_seed_random* s, int64_t* n_added /* may be NULL */);
+/* The diagnostic window of step 2: the hypotheses mvs_engine_seed_random builds -- by the same device function -- for the listed cells of
+ * `view` (any cell of the grid, whatever the mask gate makes of it), hypothesis k of cells[i] at out[i * K + k].  Only reads engine state.
+ * MVS_ERR_ARG as above, then: ncells negative, cells or out null (with ncells > 0), no engine; with the engine: view outside
+ * 0..nviews-1, a range entry as above, a cell outside the view's grid.  MVS_ERR_STATE: views not set. */
+int mvs_engine_seed_random_hypotheses(mvs_engine* e, const mvs_seed_random* s, int view, int64_t ncells, const int32_t* cells,
+                                      mvs_patch* out /* ncells * K */);
 /* Optional: sizes the two cell indexes (PatchManager::m_pgrids / m_vpgrids as lists, patch_manager.hpp) for `list_entries` memberships
  * each up front -- 0 = MAX_NUM_OF_PATCHES per cell of every view -- so that the calls below allocate nothing while the lists stay
  * below that.  Without it the buffers grow inside the first iterations of a run.  A buffer that the call allocates is written once

@@ -1095,6 +1095,117 @@ int mvs_engine_seed_patches(mvs_engine* e, int64_t npoints, const float* xyz, co
     return MVS_OK;
 }
 
+// The cold start (mvs_seed_random.hip): per view one launch of a wave per cell into a staging buffer of one record per cell of the largest
+// view, the keep flags scanned, the kept records gathered behind those of the views before -- into pool_alt, the commit's compaction
+// target, which holds nothing between calls: the pool itself is written once, after the last view, when the count is known to fit.
+namespace {
+// the checks of both entry points that need no handle, in the header's order
+int seed_random_args(const mvs_seed_random* s, const char* who) {
+    if (!s) { g_err = std::string(who) + ": parameters null"; return MVS_ERR_ARG; }
+    if (s->hypotheses < 1 || s->hypotheses > 64) { g_err = std::string(who) + ": hypotheses outside 1..64"; return MVS_ERR_ARG; }
+    if (!s->depth_min || !s->depth_max) { g_err = std::string(who) + ": depth range null"; return MVS_ERR_ARG; }
+    volatile double third = M_PI / 3.0;
+    if (!(s->max_tilt > 0.0f) || !(s->max_tilt <= (float)third)) { g_err = std::string(who) + ": max_tilt not in (0, pi/3]"; return MVS_ERR_ARG; }
+    return MVS_OK;
+}
+int seed_random_ranges(const mvs_engine* e, const mvs_seed_random* s, const char* who) {
+    for (int v = 0; v < e->cfg.nviews; ++v) {
+        const float lo = s->depth_min[v], hi = s->depth_max[v];
+        if (!std::isfinite(lo) || !std::isfinite(hi) || !(0.0f < lo) || !(lo < hi)) {
+            g_err = std::string(who) + ": depth range of view " + std::to_string(v) + " not finite or not 0 < min < max";
+            return MVS_ERR_ARG;
+        }
+    }
+    return MVS_OK;
+}
+SeedRandomArgs seed_random_launch(const mvs_engine* e, const mvs_seed_random* s, int view) {
+    const RefineSel rs = refine_sel(e);
+    SeedRandomArgs a;
+    a.seed = s->seed; a.K = s->hypotheses; a.max_tilt = s->max_tilt;
+    a.min_ncc = s->min_ncc < 0.0f ? e->prm.nccThresholdBefore : s->min_ncc;
+    a.view = view; a.dmin = s->depth_min[view]; a.dmax = s->depth_max[view];
+    a.simplex = rs.simplex; a.max_evals = rs.max_evals; a.xtol = rs.xtol;
+    return a;
+}
+}  // namespace
+
+void mvs_default_seed_random(mvs_seed_random* s) {
+    if (!s) return;
+    volatile double third = M_PI / 3.0;
+    s->hypotheses = 8; s->seed = 1; s->max_tilt = (float)third; s->min_ncc = -1.0f; s->depth_min = nullptr; s->depth_max = nullptr;
+}
+
+int mvs_engine_seed_random(mvs_engine* e, const mvs_seed_random* s, int64_t* n_added) {
+    if (int r = seed_random_args(s, "mvs_engine_seed_random")) return r;
+    if (!e) { g_err = "mvs_engine_seed_random: no engine"; return MVS_ERR_ARG; }
+    if (int r = seed_random_ranges(e, s, "mvs_engine_seed_random")) return r;
+    if (!e->have_views) { g_err = "mvs_engine_seed_random: views not set"; return MVS_ERR_STATE; }
+    if (e->staged) { g_err = "mvs_engine_seed_random: a pass is waiting for its commit"; return MVS_ERR_STATE; }
+    if (n_added) *n_added = 0;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:seed_random");
+    hipStream_t st = e->stream;
+    const int nviews = e->cfg.nviews;
+    int64_t max_cells = 0;
+    for (int v = 0; v < nviews; ++v) max_cells = std::max(max_cells, (int64_t)e->hviews[v].gw * e->hviews[v].gh);
+    DevBuf<DPatch> d_stage;
+    DevBuf<int32_t> d_keep, d_base, d_scan;
+    if (d_stage.ensure(max_cells) || d_keep.ensure(max_cells + 1) || d_base.ensure(max_cells + 1) || d_scan.ensure(max_cells / 256 + 4096)) return MVS_ERR_HIP;
+    // setVImagesVGrids reads m_dpgrids when depth > 0 (what MVS_PROBE_POSTPROCESS prepares): from the pool as it is now
+    if (e->prm.depth > 0) if (int r = build_depth(e)) return r;
+    const DParams p = current_params(e);
+    const int64_t room = e->pool.cap - e->pool_n;
+    int64_t total = 0;
+    for (int v = 0; v < nviews; ++v) {
+        const int n = e->hviews[v].gw * e->hviews[v].gh;
+        HIPCHK(hipMemsetAsync(d_keep.p, 0, sizeof(int32_t) * ((size_t)n + 1), st));
+        mvsk_seed_random(p, seed_random_launch(e, s, v), n, d_stage.p, d_keep.p, st);
+        mvsk_exclusive_scan(d_keep.p, d_base.p, n, d_scan.p, st);
+        int32_t kept = 0;
+        HIPCHK(hipMemcpyAsync(&kept, d_base.p + n, sizeof kept, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        if (total + (int64_t)kept > room) { g_err = "mvs_engine_seed_random: patch pool capacity exceeded (raise mvs_config.max_patches)"; return MVS_ERR_CAPACITY; }
+        mvsk_seed_random_gather(d_stage.p, d_keep.p, d_base.p, n, e->pool_alt.p + total, (int32_t)(e->pool_n + total), st);
+        total += kept;
+    }
+    if (total > 0) {
+        HIPCHK(hipMemcpyAsync(e->pool.p + e->pool_n, e->pool_alt.p, sizeof(DPatch) * (size_t)total, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        e->pool_n += total;
+    }
+    if (n_added) *n_added = total;
+    return MVS_OK;
+}
+
+int mvs_engine_seed_random_hypotheses(mvs_engine* e, const mvs_seed_random* s, int view, int64_t ncells, const int32_t* cells, mvs_patch* out) {
+    const char* who = "mvs_engine_seed_random_hypotheses";
+    if (int r = seed_random_args(s, who)) return r;
+    if (ncells < 0 || (ncells > 0 && (!cells || !out))) { g_err = std::string(who) + ": negative ncells, or cells / out null"; return MVS_ERR_ARG; }
+    if (ncells > (int64_t)INT32_MAX / 64) { g_err = std::string(who) + ": more than 2^25 cells in one call"; return MVS_ERR_ARG; }
+    if (!e) { g_err = std::string(who) + ": no engine"; return MVS_ERR_ARG; }
+    if (view < 0 || view >= e->cfg.nviews) { g_err = std::string(who) + ": no such view"; return MVS_ERR_ARG; }
+    if (int r = seed_random_ranges(e, s, who)) return r;
+    if (!e->have_views) { g_err = std::string(who) + ": views not set"; return MVS_ERR_STATE; }
+    const int grid = e->hviews[view].gw * e->hviews[view].gh;
+    for (int64_t i = 0; i < ncells; ++i)
+        if (cells[i] < 0 || cells[i] >= grid) { g_err = std::string(who) + ": a cell outside the view's grid"; return MVS_ERR_ARG; }
+    if (ncells == 0) return MVS_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    hipStream_t st = e->stream;
+    const int64_t nrec = ncells * s->hypotheses;
+    DevBuf<DPatch> d_out;
+    DevBuf<int32_t> d_cells;
+    if (d_out.ensure(nrec) || d_cells.ensure(ncells)) return MVS_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(d_cells.p, cells, sizeof(int32_t) * (size_t)ncells, hipMemcpyHostToDevice, st));
+    mvsk_seed_random_hypotheses(current_params(e), seed_random_launch(e, s, view), ncells, d_cells.p, d_out.p, st);
+    HIPCHK(hipMemcpyAsync(out, d_out.p, sizeof(mvs_patch) * (size_t)nrec, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return MVS_OK;
+}
+
 // Sizes the buffers of both cell indexes for `list_entries` memberships each (0: MAX_NUM_OF_PATCHES per cell of every view, what
 // m_pgrids holds after the trim), so that Propagate::run / Filter::run allocate nothing while the lists stay below that: the first
 // iterations of a run otherwise grow them inside the call (free + allocate, gigabytes at a time).  A reserve that fails may leave

@@ -76,3 +76,13 @@ void mvsk_seed_flags(const SeedCam* cams, int level, const float* xyz, const flo
                      hipStream_t st);
 void mvsk_seed_emit(const SeedCam* cams, int nviews, int level, float thr, float tmp_unit, const float* xyz, const float* sum, const unsigned long long* bits,
                     const int32_t* keep, const int32_t* base, int64_t n, DPatch* dst, hipStream_t st);
+// mvs_engine_seed_random (mvs_seed_random.hip): the cold start.  SeedRandomArgs: one view's launch by value -- the call's parameters, the
+// view and its depth range, the engine's refiner.
+struct SeedRandomArgs { uint32_t seed; int32_t K; float max_tilt, min_ncc; int32_t view; float dmin, dmax; int32_t simplex, max_evals; float xtol; };
+size_t mvsk_texs_lds_bytes(const DParams& prm);  // mvs_kernels.hip: the dynamic LDS of a wave that runs postProcess without Optim::check
+// the K hypotheses of cells[i] (cells of the view's grid) as records at out[i * K ..]
+void mvsk_seed_random_hypotheses(const DParams& prm, const SeedRandomArgs& a, int64_t ncells, const int32_t* cells, DPatch* out, hipStream_t st);
+// one wave per cell of the view: the patch of cell c, if it gives one, at stage[c] with keep[c] = 1 (keep zero before the launch); then,
+// with base = the exclusive scan of keep, the records to dst[base[c]] with id = id0 + base[c]
+void mvsk_seed_random(const DParams& prm, const SeedRandomArgs& a, int ncells, DPatch* stage, int32_t* keep, hipStream_t st);
+void mvsk_seed_random_gather(const DPatch* stage, const int32_t* keep, const int32_t* base, int ncells, DPatch* dst, int32_t id0, hipStream_t st);

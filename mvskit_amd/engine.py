@@ -4,6 +4,7 @@ There is no CPU path: if the HIP library is missing or no GPU is visible, creati
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -26,6 +27,7 @@ EXPORTS = [
     "mvs_engine_filter", "mvs_comm_unique_id", "mvs_engine_comm_init", "mvs_engine_comm_attach", "mvs_engine_comm_release",
     "mvs_engine_exchange", "mvs_list_cap", "mvs_engine_filter_stats", "mvs_patch_bytes", "mvs_engine_reserve", "mvs_engine_comm_info",
     "mvs_default_refiner", "mvs_engine_set_refiner", "mvs_engine_export_ply", "mvs_engine_seed_patches",
+    "mvs_default_seed_random", "mvs_engine_seed_random", "mvs_engine_seed_random_hypotheses",
 ]
 PLY_ASCII, PLY_BINARY_LE = 0, 1  # mvs_ply_format
 #: one vertex of the binary PLY file (mvs_engine_export_ply): 27 packed bytes
@@ -55,6 +57,12 @@ class ViewDesc(C.Structure):
 class SeedView(C.Structure):
     """mvs_seed_view: one view's world-space normal map and level-0 mask (mvs_engine_seed_patches)."""
     _fields_ = [("normals", C.c_void_p), ("mask", C.c_void_p)]
+
+
+class SeedRandom(C.Structure):
+    """mvs_seed_random: the parameters of a cold start (mvs_engine_seed_random); depth_min / depth_max point at one float per view."""
+    _fields_ = [("hypotheses", C.c_int32), ("seed", C.c_uint32), ("max_tilt", C.c_float), ("min_ncc", C.c_float),
+                ("depth_min", C.c_void_p), ("depth_max", C.c_void_p)]
 
 
 class Counters(C.Structure):
@@ -147,6 +155,11 @@ def load_library(cap32: bool = False, cap: int = 0):
         L.mvs_engine_export_ply.argtypes = [vp, C.c_int, C.c_int64, vp, C.POINTER(C.c_int64)]
     if hasattr(L, "mvs_engine_seed_patches"):
         L.mvs_engine_seed_patches.argtypes = [vp, C.c_int64, vp, C.POINTER(SeedView), C.POINTER(C.c_int64)]
+    if hasattr(L, "mvs_engine_seed_random"):
+        L.mvs_default_seed_random.argtypes = [C.POINTER(SeedRandom)]
+        L.mvs_default_seed_random.restype = None
+        L.mvs_engine_seed_random.argtypes = [vp, C.POINTER(SeedRandom), C.POINTER(C.c_int64)]
+        L.mvs_engine_seed_random_hypotheses.argtypes = [vp, C.POINTER(SeedRandom), C.c_int, C.c_int64, vp, vp]
     _libs[LIB_PATH] = L
     return L
 
@@ -209,7 +222,7 @@ class Engine:
                 descs[v].P[k] = float(P[k])
             descs[v].rgb = img.ctypes.data
             descs[v].mask = None
-            if masks is not None:
+            if masks is not None and masks[v] is not None:  # masks[v] None: that view has no mask
                 m = np.ascontiguousarray(np.asarray(masks[v], dtype=np.uint8)[:h, :w])
                 keep.append(m)
                 descs[v].mask = m.ctypes.data
@@ -285,6 +298,35 @@ class Engine:
         added = C.c_int64()
         self._check(self.L.mvs_engine_seed_patches(self.h, pts.shape[0], _ptr(pts), views, C.byref(added)))
         return added.value
+
+    def _seed_random_args(self, depth_min, depth_max, hypotheses, seed, max_tilt, min_ncc):
+        """mvs_seed_random from Python values; a scalar range serves every view.  Returns the struct and the arrays it points at."""
+        n = self.cfg.nviews
+        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(depth_min, dtype=np.float32), (n,)))
+        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(depth_max, dtype=np.float32), (n,)))
+        s = SeedRandom(int(hypotheses), int(seed), float(max_tilt), -1.0 if min_ncc is None else float(min_ncc), lo.ctypes.data, hi.ctypes.data)
+        return s, (lo, hi)
+
+    def seed_random(self, depth_min, depth_max, hypotheses=8, seed=1, max_tilt=math.pi / 3, min_ncc=None):
+        """The cold start (include/mvskit_engine.h, mvs_engine_seed_random): per cell of every view `hypotheses` random planes inside
+        [depth_min, depth_max] along the view's optical axis and within max_tilt of the direction to the camera, the best-scoring one
+        refined and post-processed on the device; the patches that pass are appended to the pool in (view, cell) order.  Ranges:
+        one value per view or a scalar for all.  min_ncc None: the engine's nccThresholdBefore.  Returns how many were appended."""
+        s, keep = self._seed_random_args(depth_min, depth_max, hypotheses, seed, max_tilt, min_ncc)
+        added = C.c_int64()
+        self._check(self.L.mvs_engine_seed_random(self.h, C.byref(s), C.byref(added)))
+        del keep
+        return added.value
+
+    def seed_random_hypotheses(self, view, cells, depth_min, depth_max, hypotheses=8, seed=1, max_tilt=math.pi / 3, min_ncc=None):
+        """The hypotheses seed_random scores, as records: `hypotheses` per listed cell (cy * gw + cx) of `view`, hypothesis k of cells[i]
+        at [i * hypotheses + k].  Reads engine state only."""
+        s, keep = self._seed_random_args(depth_min, depth_max, hypotheses, seed, max_tilt, min_ncc)
+        cells = np.ascontiguousarray(cells, dtype=np.int32).ravel()
+        out = np.zeros(cells.shape[0] * max(int(hypotheses), 0), dtype=self.dtype)
+        self._check(self.L.mvs_engine_seed_random_hypotheses(self.h, C.byref(s), int(view), cells.shape[0], _ptr(cells), _ptr(out)))
+        del keep
+        return out
 
     def reserve(self, list_entries=0):
         """Sizes the cell indexes up front (0: MAX_NUM_OF_PATCHES per cell of every view): no allocation inside the iterations."""
