@@ -254,6 +254,57 @@ int mvs_engine_seed_random(mvs_engine* e, const mvs_seed_random* s, int64_t* n_a
  * 0..nviews-1, a range entry as above, a cell outside the view's grid.  MVS_ERR_STATE: views not set. */
 int mvs_engine_seed_random_hypotheses(mvs_engine* e, const mvs_seed_random* s, int view, int64_t ncells, const int32_t* cells,
                                       mvs_patch* out /* ncells * K */);
+/* The warm start, for a caller who has images, cameras and the sparse 3-D points of structure-from-motion -- no normals, no per-view maps:
+ * a second front end to the cold start's chain (the PMVS-style start: the normal turned towards the reference camera, then optimised).
+ * A job is point i of xyz, coord = (x, y, z, 1); the jobs run over the points in their order.
+ *   1. gate        view v qualifies for the point when its depth d = oaxis . coord (the 4-vector product mvs_engine_depth_normal_map
+ *                  calls depth) is > 0, the pixel floorf(ic + 0.5f) of its projection at Option::m_level lies inside the image at that
+ *                  level and, where the view has a mask, on its foreground at that level (a view without a mask is foreground everywhere,
+ *                  the cold start's rule).  A non-finite coordinate qualifies nowhere.
+ *   2. hypotheses  the first min(`hypotheses`, qualifying views) views in ascending squared distance |center_v - X|^2, the lower view
+ *                  index first among equals.  Hypothesis k: reference view v_k, the point's coordinate untouched, the normal the unit
+ *                  vector r from the point to the centre of camera v_k, normal.w = -coord . r.  The record: m_images = [v_k], no
+ *                  m_vimages, m_ncc = -1, scales and m_tmp 0, alive, id = k.
+ *   3. score, 4. patch   as the cold start's steps 3 and 4, over the point's hypotheses; HALVING draws under the key (0, 0, i, 0) with
+ *                  the point's index i in the call, as MVS_PROBE_REFINE does for record i.  Optim::check does not run.
+ *   5. append      the patches, in point order, behind the pool: positions come from a scan, not from atomics, so two calls on the same
+ *                  state give the same pool bytes.  Records are alive, not settled, id = the pool index.  No thinning: several points of
+ *                  one cell give several patches, and the next pass's MAX_NUM_OF_PATCHES trim keeps the best.
+ * An appended record has the bytes the chain of probes gives (ops 1, 0, 2, 3 over the hypotheses of the diagnostic window below).  The
+ * depth maps postProcess reads when the engine's depth > 0 are built from the pool as it is at entry, with the cold start's caveat: over a
+ * pool with an over-full cell (one an index build would trim) and depth > 0 the maps of MVS_PROBE_POSTPROCESS can differ, and the
+ * equality with the chain holds only for a pool that build would not trim.  Existing records are never modified; the cell indexes, the
+ * thresholds and the mvs_config.seed stream stay as they were; a second call appends again.  Not a collective: every rank of a multi-rank
+ * job makes the same call and ends with the same pool.  The points stream through fixed buffers in chunks of 2^18 (the environment
+ * variable MVS_SEED_POINTS_CHUNK, a positive integer read at the call and cut to 2^22, overrides it; the pool bytes do not depend on
+ * it): device memory for the call, released before it returns, is one record and 20 bytes per point of a chunk.
+ * LIMITS: npoints <= 2^30 per call.
+ * MVS_ERR_ARG: s null, hypotheses outside 1..64, npoints negative, xyz null (with npoints > 0), no engine, npoints over the limit --
+ * checked in that order, before the handle is read.  MVS_ERR_STATE: views not set, or a pass waiting for its commit; MVS_ERR_HIP: an
+ * allocation or copy failed; MVS_ERR_CAPACITY: the patches do not fit the pool (the pool is written only after the last chunk).  After
+ * any error the pool is what it was, and a refused call writes nothing through n_added.  npoints == 0 appends nothing. */
+typedef struct mvs_seed_points {
+    int32_t hypotheses;      /* K, 1..64: at most K reference-view hypotheses per point, nearest qualifying views first */
+    float min_ncc;           /* a winner must score strictly above this; < 0 = the engine's nccThresholdBefore at the call */
+} mvs_seed_points;           /* 8 bytes */
+void mvs_default_seed_points(mvs_seed_points* s); /* K 4, min_ncc -1 */
+int mvs_engine_seed_points(mvs_engine* e, const mvs_seed_points* s, int64_t npoints, const float* xyz, int64_t* n_added /* may be NULL */);
+/* The diagnostic window of steps 1 and 2: the hypotheses the warm start builds -- by the same device function -- for every point:
+ * count[i] of them for point i, hypothesis k at out[i * K + k], all-zero bytes in the slots behind.  Only reads engine state.
+ * LIMITS: npoints * K <= 2^31 - 1.  MVS_ERR_ARG as above up to xyz, then: out or count null (with npoints > 0), no engine, the limit.
+ * MVS_ERR_STATE: views not set. */
+int mvs_engine_seed_points_hypotheses(mvs_engine* e, const mvs_seed_points* s, int64_t npoints, const float* xyz,
+                                      mvs_patch* out /* npoints * K */, int32_t* count /* npoints */);
+/* The depth range the same points give every view, as the cold start's depth_min / depth_max take it: count[v] = the number of points
+ * that pass view v's gate (step 1 above, d > 0 included), and the smallest and largest d among them -- the exact float extremes, whatever
+ * the order (an integer minimum / maximum over the bits of positive floats) -- widened on the host: depth_min = min / (1 + margin),
+ * depth_max = max * (1 + margin).  A view with no qualifying point gets count 0 and the range 0, 0, which the cold start refuses.  Only
+ * reads engine state.  LIMITS: npoints <= 2^30.
+ * MVS_ERR_ARG: npoints negative, xyz null (with npoints > 0), depth_min, depth_max or count null, margin not finite or < 0, no engine,
+ * npoints over the limit -- checked in that order, before the handle is read.  MVS_ERR_STATE: views not set.  A refused call writes
+ * nothing through its output pointers. */
+int mvs_engine_depth_ranges(mvs_engine* e, int64_t npoints, const float* xyz, float margin,
+                            float* depth_min, float* depth_max, int64_t* count /* each [nviews] */);
 /* Optional: sizes the two cell indexes (PatchManager::m_pgrids / m_vpgrids as lists, patch_manager.hpp) for `list_entries` memberships
  * each up front -- 0 = MAX_NUM_OF_PATCHES per cell of every view -- so that the calls below allocate nothing while the lists stay
  * below that.  Without it the buffers grow inside the first iterations of a run.  A buffer that the call allocates is written once

@@ -1206,6 +1206,163 @@ int mvs_engine_seed_random_hypotheses(mvs_engine* e, const mvs_seed_random* s, i
     return MVS_OK;
 }
 
+// The warm start (mvs_seed_points.hip): the points stream in chunks through fixed buffers -- per point of a chunk its coordinates, one
+// staged record, the keep flag and its scan -- one launch of a wave per point, the keep flags scanned, the kept records gathered behind
+// those of the chunks before into pool_alt, as the cold start gathers its views: the pool is written once, after the last chunk.
+namespace {
+constexpr int64_t SEED_POINTS_CHUNK = 1 << 18, SEED_POINTS_CHUNK_MAX = 1 << 22;
+int64_t seed_points_chunk() {  // MVS_SEED_POINTS_CHUNK, read at the call: a positive integer (anything else: the default)
+    const char* s = getenv("MVS_SEED_POINTS_CHUNK");
+    if (!s || !*s) return SEED_POINTS_CHUNK;
+    char* end = nullptr;
+    const long long v = strtoll(s, &end, 10);
+    if (*end || v <= 0) return SEED_POINTS_CHUNK;
+    return std::min<int64_t>(v, SEED_POINTS_CHUNK_MAX);
+}
+// the checks that need no handle, in the header's order
+int seed_points_args(const mvs_seed_points* s, int64_t npoints, const float* xyz, const char* who) {
+    if (!s) { g_err = std::string(who) + ": parameters null"; return MVS_ERR_ARG; }
+    if (s->hypotheses < 1 || s->hypotheses > 64) { g_err = std::string(who) + ": hypotheses outside 1..64"; return MVS_ERR_ARG; }
+    if (npoints < 0) { g_err = std::string(who) + ": negative npoints"; return MVS_ERR_ARG; }
+    if (npoints > 0 && !xyz) { g_err = std::string(who) + ": xyz null"; return MVS_ERR_ARG; }
+    return MVS_OK;
+}
+}  // namespace
+
+void mvs_default_seed_points(mvs_seed_points* s) {
+    if (!s) return;
+    s->hypotheses = 4; s->min_ncc = -1.0f;
+}
+
+int mvs_engine_seed_points(mvs_engine* e, const mvs_seed_points* s, int64_t npoints, const float* xyz, int64_t* n_added) {
+    const char* who = "mvs_engine_seed_points";
+    if (int r = seed_points_args(s, npoints, xyz, who)) return r;
+    if (!e) { g_err = std::string(who) + ": no engine"; return MVS_ERR_ARG; }
+    if (npoints > ((int64_t)1 << 30)) { g_err = std::string(who) + ": more than 2^30 points in one call"; return MVS_ERR_ARG; }
+    if (!e->have_views) { g_err = std::string(who) + ": views not set"; return MVS_ERR_STATE; }
+    if (e->staged) { g_err = std::string(who) + ": a pass is waiting for its commit"; return MVS_ERR_STATE; }
+    if (n_added) *n_added = 0;
+    if (npoints == 0) return MVS_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:seed_points");
+    hipStream_t st = e->stream;
+    const int64_t chunk = std::min(seed_points_chunk(), npoints);
+    DevBuf<float> d_xyz;
+    DevBuf<DPatch> d_stage;
+    DevBuf<int32_t> d_keep, d_base, d_scan;
+    if (d_xyz.ensure(3 * chunk) || d_stage.ensure(chunk) || d_keep.ensure(chunk + 1) || d_base.ensure(chunk + 1) || d_scan.ensure(chunk / 256 + 4096)) return MVS_ERR_HIP;
+    // setVImagesVGrids reads m_dpgrids when depth > 0 (what MVS_PROBE_POSTPROCESS prepares): from the pool as it is now
+    if (e->prm.depth > 0) if (int r = build_depth(e)) return r;
+    const DParams p = current_params(e);
+    const RefineSel rs = refine_sel(e);
+    SeedPointsArgs a;
+    a.K = s->hypotheses;
+    a.min_ncc = s->min_ncc < 0.0f ? e->prm.nccThresholdBefore : s->min_ncc;
+    a.simplex = rs.simplex; a.max_evals = rs.max_evals; a.xtol = rs.xtol;
+    const int64_t room = e->pool.cap - e->pool_n;
+    int64_t total = 0;
+    for (int64_t first = 0; first < npoints; first += chunk) {
+        const int64_t n = std::min(chunk, npoints - first);
+        a.first = first; a.n = (int32_t)n;
+        HIPCHK(hipMemcpyAsync(d_xyz.p, xyz + 3 * first, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(d_keep.p, 0, sizeof(int32_t) * ((size_t)n + 1), st));
+        mvsk_seed_points(p, a, d_xyz.p, d_stage.p, d_keep.p, st);
+        mvsk_exclusive_scan(d_keep.p, d_base.p, n, d_scan.p, st);
+        int32_t kept = 0;
+        HIPCHK(hipMemcpyAsync(&kept, d_base.p + n, sizeof kept, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        if (total + (int64_t)kept > room) { g_err = std::string(who) + ": patch pool capacity exceeded (raise mvs_config.max_patches)"; return MVS_ERR_CAPACITY; }
+        mvsk_seed_random_gather(d_stage.p, d_keep.p, d_base.p, (int)n, e->pool_alt.p + total, (int32_t)(e->pool_n + total), st);
+        total += kept;
+    }
+    if (total > 0) {
+        HIPCHK(hipMemcpyAsync(e->pool.p + e->pool_n, e->pool_alt.p, sizeof(DPatch) * (size_t)total, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        e->pool_n += total;
+    }
+    if (n_added) *n_added = total;
+    return MVS_OK;
+}
+
+int mvs_engine_seed_points_hypotheses(mvs_engine* e, const mvs_seed_points* s, int64_t npoints, const float* xyz, mvs_patch* out, int32_t* count) {
+    const char* who = "mvs_engine_seed_points_hypotheses";
+    if (int r = seed_points_args(s, npoints, xyz, who)) return r;
+    if (npoints > 0 && (!out || !count)) { g_err = std::string(who) + ": out or count null"; return MVS_ERR_ARG; }
+    if (!e) { g_err = std::string(who) + ": no engine"; return MVS_ERR_ARG; }
+    if (npoints * s->hypotheses > (int64_t)INT32_MAX) { g_err = std::string(who) + ": more than 2^31 - 1 hypotheses in one call"; return MVS_ERR_ARG; }
+    if (!e->have_views) { g_err = std::string(who) + ": views not set"; return MVS_ERR_STATE; }
+    if (npoints == 0) return MVS_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    hipStream_t st = e->stream;
+    const int K = s->hypotheses;
+    const int64_t chunk = std::min(std::max<int64_t>(seed_points_chunk() / K, 1), npoints);  // at most a chunk of records at a time
+    DevBuf<float> d_xyz;
+    DevBuf<DPatch> d_out;
+    DevBuf<int32_t> d_count;
+    if (d_xyz.ensure(3 * chunk) || d_out.ensure(chunk * K) || d_count.ensure(chunk)) return MVS_ERR_HIP;
+    const DParams p = current_params(e);
+    for (int64_t first = 0; first < npoints; first += chunk) {
+        const int64_t n = std::min(chunk, npoints - first);
+        HIPCHK(hipMemcpyAsync(d_xyz.p, xyz + 3 * first, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+        mvsk_seed_points_hypotheses(p, K, n, d_xyz.p, d_out.p, d_count.p, st);
+        HIPCHK(hipMemcpyAsync(out + first * K, d_out.p, sizeof(mvs_patch) * (size_t)(n * K), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(count + first, d_count.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));  // the buffers are reused by the next chunk
+        HIPCHK(hipGetLastError());
+    }
+    return MVS_OK;
+}
+
+int mvs_engine_depth_ranges(mvs_engine* e, int64_t npoints, const float* xyz, float margin, float* depth_min, float* depth_max, int64_t* count) {
+    const char* who = "mvs_engine_depth_ranges";
+    if (npoints < 0) { g_err = std::string(who) + ": negative npoints"; return MVS_ERR_ARG; }
+    if (npoints > 0 && !xyz) { g_err = std::string(who) + ": xyz null"; return MVS_ERR_ARG; }
+    if (!depth_min || !depth_max || !count) { g_err = std::string(who) + ": depth_min, depth_max or count null"; return MVS_ERR_ARG; }
+    if (!std::isfinite(margin) || !(margin >= 0.0f)) { g_err = std::string(who) + ": margin not finite or < 0"; return MVS_ERR_ARG; }
+    if (!e) { g_err = std::string(who) + ": no engine"; return MVS_ERR_ARG; }
+    if (npoints > ((int64_t)1 << 30)) { g_err = std::string(who) + ": more than 2^30 points in one call"; return MVS_ERR_ARG; }
+    if (!e->have_views) { g_err = std::string(who) + ": views not set"; return MVS_ERR_STATE; }
+    const int nviews = e->cfg.nviews;
+    std::vector<uint32_t> lo((size_t)nviews, 0xffffffffu), hi((size_t)nviews, 0u);
+    std::vector<unsigned long long> cnt((size_t)nviews, 0ull);
+    if (npoints > 0) {
+        HIPCHK(hipSetDevice(e->cfg.device));
+        hipStream_t st = e->stream;
+        const int64_t chunk = std::min(seed_points_chunk(), npoints);
+        DevBuf<float> d_xyz;
+        DevBuf<uint32_t> d_lohi;
+        DevBuf<unsigned long long> d_cnt;
+        if (d_xyz.ensure(3 * chunk) || d_lohi.ensure(2 * nviews) || d_cnt.ensure(nviews)) return MVS_ERR_HIP;
+        HIPCHK(hipMemsetAsync(d_lohi.p, 0xff, sizeof(uint32_t) * (size_t)nviews, st));
+        HIPCHK(hipMemsetAsync(d_lohi.p + nviews, 0, sizeof(uint32_t) * (size_t)nviews, st));
+        HIPCHK(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long) * (size_t)nviews, st));
+        const DParams p = current_params(e);
+        for (int64_t first = 0; first < npoints; first += chunk) {
+            const int64_t n = std::min(chunk, npoints - first);
+            HIPCHK(hipMemcpyAsync(d_xyz.p, xyz + 3 * first, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+            mvsk_depth_ranges(p, n, d_xyz.p, d_lohi.p, d_lohi.p + nviews, d_cnt.p, st);
+            HIPCHK(hipStreamSynchronize(st));  // the buffer is reused by the next chunk
+        }
+        HIPCHK(hipMemcpyAsync(lo.data(), d_lohi.p, sizeof(uint32_t) * (size_t)nviews, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hi.data(), d_lohi.p + nviews, sizeof(uint32_t) * (size_t)nviews, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, sizeof(unsigned long long) * (size_t)nviews, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+    }
+    const float widen = 1.0f + margin;
+    for (int v = 0; v < nviews; ++v) {
+        count[v] = (int64_t)cnt[(size_t)v];
+        depth_min[v] = depth_max[v] = 0.0f;
+        if (cnt[(size_t)v] == 0) continue;
+        float a, b;
+        memcpy(&a, &lo[(size_t)v], 4); memcpy(&b, &hi[(size_t)v], 4);
+        depth_min[v] = a / widen; depth_max[v] = b * widen;
+    }
+    return MVS_OK;
+}
+
 // Sizes the buffers of both cell indexes for `list_entries` memberships each (0: MAX_NUM_OF_PATCHES per cell of every view, what
 // m_pgrids holds after the trim), so that Propagate::run / Filter::run allocate nothing while the lists stay below that: the first
 // iterations of a run otherwise grow them inside the call (free + allocate, gigabytes at a time).  A reserve that fails may leave

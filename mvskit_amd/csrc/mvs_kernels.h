@@ -86,3 +86,12 @@ void mvsk_seed_random_hypotheses(const DParams& prm, const SeedRandomArgs& a, in
 // with base = the exclusive scan of keep, the records to dst[base[c]] with id = id0 + base[c]
 void mvsk_seed_random(const DParams& prm, const SeedRandomArgs& a, int ncells, DPatch* stage, int32_t* keep, hipStream_t st);
 void mvsk_seed_random_gather(const DPatch* stage, const int32_t* keep, const int32_t* base, int ncells, DPatch* dst, int32_t id0, hipStream_t st);
+// mvs_engine_seed_points (mvs_seed_points.hip): the warm start.  xyz: 3 floats per point of the launch.
+// the hypotheses of point i as records at out[i * K ..], count[i] of them, zero bytes in the slots behind
+void mvsk_seed_points_hypotheses(const DParams& prm, int K, int64_t n, const float* xyz, DPatch* out, int32_t* count, hipStream_t st);
+// one wave per point of the chunk: the patch of point j, if it gives one, at stage[j] with keep[j] = 1 (keep zero before the launch);
+// mvsk_seed_random_gather then moves the staged records behind the exclusive scan of keep
+void mvsk_seed_points(const DParams& prm, const SeedPointsArgs& a, const float* xyz, DPatch* stage, int32_t* keep, hipStream_t st);
+// per view: cnt[v] += the points that pass its gate, lo[v] / hi[v] = min / max with the bits of their depths (lo 0xffffffff, hi and cnt 0
+// before the first launch)
+void mvsk_depth_ranges(const DParams& prm, int64_t n, const float* xyz, uint32_t* lo, uint32_t* hi, unsigned long long* cnt, hipStream_t st);

@@ -28,6 +28,7 @@ EXPORTS = [
     "mvs_engine_exchange", "mvs_list_cap", "mvs_engine_filter_stats", "mvs_patch_bytes", "mvs_engine_reserve", "mvs_engine_comm_info",
     "mvs_default_refiner", "mvs_engine_set_refiner", "mvs_engine_export_ply", "mvs_engine_seed_patches",
     "mvs_default_seed_random", "mvs_engine_seed_random", "mvs_engine_seed_random_hypotheses",
+    "mvs_default_seed_points", "mvs_engine_seed_points", "mvs_engine_seed_points_hypotheses", "mvs_engine_depth_ranges",
 ]
 PLY_ASCII, PLY_BINARY_LE = 0, 1  # mvs_ply_format
 #: one vertex of the binary PLY file (mvs_engine_export_ply): 27 packed bytes
@@ -63,6 +64,11 @@ class SeedRandom(C.Structure):
     """mvs_seed_random: the parameters of a cold start (mvs_engine_seed_random); depth_min / depth_max point at one float per view."""
     _fields_ = [("hypotheses", C.c_int32), ("seed", C.c_uint32), ("max_tilt", C.c_float), ("min_ncc", C.c_float),
                 ("depth_min", C.c_void_p), ("depth_max", C.c_void_p)]
+
+
+class SeedPoints(C.Structure):
+    """mvs_seed_points: the parameters of a warm start (mvs_engine_seed_points)."""
+    _fields_ = [("hypotheses", C.c_int32), ("min_ncc", C.c_float)]
 
 
 class Counters(C.Structure):
@@ -160,6 +166,12 @@ def load_library(cap32: bool = False, cap: int = 0):
         L.mvs_default_seed_random.restype = None
         L.mvs_engine_seed_random.argtypes = [vp, C.POINTER(SeedRandom), C.POINTER(C.c_int64)]
         L.mvs_engine_seed_random_hypotheses.argtypes = [vp, C.POINTER(SeedRandom), C.c_int, C.c_int64, vp, vp]
+    if hasattr(L, "mvs_engine_seed_points"):
+        L.mvs_default_seed_points.argtypes = [C.POINTER(SeedPoints)]
+        L.mvs_default_seed_points.restype = None
+        L.mvs_engine_seed_points.argtypes = [vp, C.POINTER(SeedPoints), C.c_int64, vp, C.POINTER(C.c_int64)]
+        L.mvs_engine_seed_points_hypotheses.argtypes = [vp, C.POINTER(SeedPoints), C.c_int64, vp, vp, vp]
+        L.mvs_engine_depth_ranges.argtypes = [vp, C.c_int64, vp, C.c_float, vp, vp, vp]
     _libs[LIB_PATH] = L
     return L
 
@@ -327,6 +339,36 @@ class Engine:
         self._check(self.L.mvs_engine_seed_random_hypotheses(self.h, C.byref(s), int(view), cells.shape[0], _ptr(cells), _ptr(out)))
         del keep
         return out
+
+    def seed_points(self, points, hypotheses=4, min_ncc=None):
+        """The warm start (include/mvskit_engine.h, mvs_engine_seed_points): per point of `points` (N x 3 world coordinates, the sparse
+        points of structure-from-motion) at most `hypotheses` reference views, nearest first, each with the normal turned towards its
+        camera; the best-scoring one refined and post-processed on the device; the patches that pass are appended to the pool in point
+        order.  min_ncc None: the engine's nccThresholdBefore.  Returns how many were appended."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        s = SeedPoints(int(hypotheses), -1.0 if min_ncc is None else float(min_ncc))
+        added = C.c_int64()
+        self._check(self.L.mvs_engine_seed_points(self.h, C.byref(s), pts.shape[0], _ptr(pts), C.byref(added)))
+        return added.value
+
+    def seed_points_hypotheses(self, points, hypotheses=4, min_ncc=None):
+        """The hypotheses seed_points scores -> (records, count): count[i] hypotheses of point i at records[i * hypotheses ...], zero
+        records in the slots behind.  Reads engine state only."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        s = SeedPoints(int(hypotheses), -1.0 if min_ncc is None else float(min_ncc))
+        out = np.zeros(pts.shape[0] * max(int(hypotheses), 0), dtype=self.dtype)
+        count = np.zeros(pts.shape[0], np.int32)
+        self._check(self.L.mvs_engine_seed_points_hypotheses(self.h, C.byref(s), pts.shape[0], _ptr(pts), _ptr(out), _ptr(count)))
+        return out, count
+
+    def depth_ranges(self, points, margin=0.1):
+        """Per view the depth range of the points that pass its gate, widened by `margin` -> (depth_min, depth_max, count): float32
+        arrays that seed_random takes as they are, and the number of qualifying points per view (a view with none: 0, 0)."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = self.cfg.nviews
+        lo, hi, count = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int64)
+        self._check(self.L.mvs_engine_depth_ranges(self.h, pts.shape[0], _ptr(pts), float(margin), _ptr(lo), _ptr(hi), _ptr(count)))
+        return lo, hi, count
 
     def reserve(self, list_entries=0):
         """Sizes the cell indexes up front (0: MAX_NUM_OF_PATCHES per cell of every view): no allocation inside the iterations."""
