@@ -328,6 +328,69 @@ int mvs_engine_download_patches(mvs_engine* e, int64_t cap, mvs_patch* out, int6
 typedef enum mvs_ply_format { MVS_PLY_ASCII = 0, MVS_PLY_BINARY_LE = 1 } mvs_ply_format;
 int mvs_engine_export_ply(mvs_engine* e, int format, int64_t cap, uint8_t* out, int64_t* nbytes);
 
+/* Dense per-view maps and their cross-view fusion (no reference counterpart: the reference stops at the patches).  PatchMatch keeps a
+ * plane per cell; the dense map of a view is that plane evaluated at every pixel of the cell, at the working resolution: L =
+ * Option::m_level, view v has W_L x H_L pixels, the projection P_L, Minv (the inverse of its 3x3 block), the centre C and oaxis.
+ *   1. selection   per cell of every view.  source 0: among the alive patches whose reference view (images[0]) is v, the one with the
+ *                  highest m_ncc in the cell PatchManager::setGrids' rule gives it, the lowest id among equals (kind 1 of
+ *                  mvs_engine_depth_normal_map); all views in one pass over the pool.  source 1: the cell's m_dpgrids entry (kind 0).
+ *   2. render      pixel (x, y) of v, integers, lies in the cell (x / csize, y / csize); p = the cell's selection, n = p.normal.xyz, X0 =
+ *                  p.coord.xyz.  dir = Minv (x, y, 1); t = n.(X0 - C) / (n.dir); X = C + t dir; depth = oaxis . (X, 1).  The pixel is
+ *                  VALID when the cell has a selection, the view has no mask or its level-L mask is foreground at (x, y), n.dir is finite
+ *                  and not zero, t > 0, and depth > 0 and finite (a NaN fails every one of these).  Per pixel: depth; normal = the
+ *                  three floats of p.normal and conf = p.ncc, bit for bit; id = the pool index (what mvs_engine_download_patches calls
+ *                  id as long as no patch is dead); invalid pixels: quiet NaN and id -1.
+ *   3. agreement   a valid pixel of v with point X and normal n, against every view u != v: project X (Camera::project at level L), take
+ *                  the pixel (floorf(ic.x + 0.5f), floorf(ic.y + 0.5f)).  Bit u of the pixel's 64-bit agree word is set when the third
+ *                  homogeneous coordinate is > 0; that pixel lies inside u's image and is valid in u's render, with patch q;
+ *                  |s - 1| <= depth_tol for s = n_q.(X0_q - C_u) / (n_q.(X - C_u)) -- the relative depth difference, along u's ray through
+ *                  X, between X and q's plane (no depth map is read, the pixel size plays no part; a zero or non-finite denominator
+ *                  fails); and n . n_q >= normal_cos (skipped when normal_cos <= -1).  Bit v is never set; agree = 0 on invalid pixels.
+ *   4. fusion      a pixel is emitted when it is valid, popcount(agree) >= min_consistent and, with dedupe != 0, no bit u < v is set in
+ *                  agree: the lowest view of an agreeing set speaks for the surface point.  The records come in (view, y, x) order at
+ *                  positions from a scan, not from atomics: two calls on the same state give the same bytes.  rgb = the level-L pyramid
+ *                  texel of view v at (x, y).
+ * Both calls are stateless -- each renders what it needs and keeps nothing afterwards, so no map can go stale -- and only read engine
+ * state: pool, cell indexes, thresholds and the RNG stream stay as they were (source 1 rebuilds m_dpgrids from the pool, as
+ * mvs_engine_depth_normal_map does).  Neither is a collective: every rank holds the whole pool.  Output pointers may be host or device
+ * memory (hipMemcpyDefault).  Device memory for a call, released before it returns: 16 bytes (an id and a point) per pixel of ALL views
+ * -- and a flag byte more in mvs_engine_fused_points -- plus, per pixel of the LARGEST view, 8 bytes of agree words, 8 of scan and 20 of
+ * output maps (32 per emitted pixel of one view instead of the maps in mvs_engine_fused_points): the views stream through those.  48
+ * views of 4096 x 2160: 7.2 GB + 0.3 GB.
+ * mvs_engine_render_maps: out[v] takes view v's maps (depth H*W, normal H*W*3, conf, ids, agree; any pointer NULL: not wanted; out NULL:
+ *   none), n_valid[v] its number of valid pixels.
+ * mvs_engine_fused_points: out == NULL or cap < the count: *n = the exact count (MVS_ERR_CAPACITY when out != NULL; out is then not
+ *   written), mvs_engine_export_ply's convention.
+ * MVS_ERR_ARG, checked in this order before the handle is read: config NULL, source outside 0..1, min_consistent < 0, depth_tol not
+ * finite or <= 0, normal_cos not finite or > 1, (fused_points) cap < 0 or n NULL, no engine; then, with the engine's view count,
+ * min_consistent > nviews - 1.  MVS_ERR_STATE: views not set, or a pass waiting for its commit; MVS_ERR_HIP: an allocation or copy
+ * failed.  A refused call writes nothing through its output pointers. */
+typedef struct mvs_maps_config {
+    int32_t source;          /* 0: the best-NCC patch of the cell with reference view v; 1: the cell's m_dpgrids patch */
+    int32_t min_consistent;  /* fusion: at least that many agreeing other views */
+    float depth_tol;         /* agreement: |s - 1| <= depth_tol */
+    float normal_cos;        /* agreement: n . n_q >= normal_cos; <= -1: no normal test */
+    int32_t dedupe;          /* fusion: != 0 = only the lowest view of an agreeing set emits */
+    int32_t pad;
+} mvs_maps_config;           /* 24 bytes */
+void mvs_default_maps_config(mvs_maps_config* c); /* source 0, min_consistent 1, depth_tol 0.01, normal_cos 0.9, dedupe 1 */
+typedef struct mvs_view_maps {
+    float* depth;     /* H*W */
+    float* normal;    /* H*W*3 */
+    float* conf;      /* H*W */
+    int32_t* ids;     /* H*W */
+    uint64_t* agree;  /* H*W */
+} mvs_view_maps;      /* 40 bytes */
+int mvs_engine_render_maps(mvs_engine* e, const mvs_maps_config* c, mvs_view_maps* out /* [nviews] or NULL */, int64_t* n_valid /* [nviews] or NULL */);
+typedef struct mvs_fused_point {
+    float xyz[3];
+    float normal[3];
+    float conf;
+    uint8_t rgb[3];
+    uint8_t view;
+} mvs_fused_point;    /* 32 bytes */
+int mvs_engine_fused_points(mvs_engine* e, const mvs_maps_config* c, int64_t cap, mvs_fused_point* out /* host or device */, int64_t* n);
+
 /* Propagate::run(iter), propagate.cpp:28-64: two colour passes, each = index build + sweep + commit */
 int mvs_engine_propagate(mvs_engine* e, int iter, mvs_counters* out);
 

@@ -1502,6 +1502,171 @@ int mvs_engine_export_ply(mvs_engine* e, int format, int64_t cap, uint8_t* out, 
     return MVS_OK;
 }
 
+// Dense per-view maps and their fusion (mvs_maps.hip; the definitions are in mvskit_engine.h).  Both entry points are stateless: render_all
+// fills the id and the point of every pixel of every view, the views then stream one at a time through buffers sized for the largest.
+// The selection keys go where mvs_engine_depth_normal_map puts them: `best` (source 0; scratch that every user clears first, sized for
+// the cells of all views) or `dpgrid` (source 1; every pass and Filter::run rebuilds it).
+static_assert(sizeof(mvs_maps_config) == 24 && sizeof(mvs_view_maps) == 40 && sizeof(mvs_fused_point) == 32, "the maps structs are 24, 40 and 32 bytes");
+namespace {
+struct MapsBufs {
+    MapsArgs args{};
+    int64_t total_pix = 0, max_pix = 0;
+    DevBuf<int32_t> ids;             // [total_pix] the pool index behind every pixel of every view, -1 = invalid
+    DevBuf<float> pts;               // [3 total_pix] its point
+    DevBuf<unsigned long long> agree;  // the views stream through these: [max_pix] each
+    DevBuf<int32_t> flag, base, scan;
+    DevBuf<float> maps;              // [5 max_pix] depth, normal, conf of the view under way
+    DevBuf<uint8_t> flag8;           // [total_pix] fused_points: the emitted pixels, between its counting and its gathering pass
+    DevBuf<mvs_fused_point> recs;    // fused_points: the records of one view
+};
+
+int maps_args(const mvs_maps_config* c, const char* who) {
+    if (!c) { g_err = std::string(who) + ": config null"; return MVS_ERR_ARG; }
+    if (c->source < 0 || c->source > 1) { g_err = std::string(who) + ": source must be 0 or 1"; return MVS_ERR_ARG; }
+    if (c->min_consistent < 0) { g_err = std::string(who) + ": min_consistent negative"; return MVS_ERR_ARG; }
+    if (!std::isfinite(c->depth_tol) || !(c->depth_tol > 0.0f)) { g_err = std::string(who) + ": depth_tol not finite or <= 0"; return MVS_ERR_ARG; }
+    if (!std::isfinite(c->normal_cos) || !(c->normal_cos <= 1.0f)) { g_err = std::string(who) + ": normal_cos not finite or > 1"; return MVS_ERR_ARG; }
+    return MVS_OK;
+}
+int maps_state(const mvs_engine* e, const mvs_maps_config* c, const char* who) {
+    if (c->min_consistent > e->cfg.nviews - 1) { g_err = std::string(who) + ": min_consistent exceeds the number of other views"; return MVS_ERR_ARG; }
+    if (!e->have_views) { g_err = std::string(who) + ": views not set"; return MVS_ERR_STATE; }
+    if (e->staged) { g_err = std::string(who) + ": a pass is waiting for its commit"; return MVS_ERR_STATE; }
+    return MVS_OK;
+}
+int64_t maps_npix(const mvs_engine* e, int v) { return (int64_t)e->hviews[v].W[e->cfg.level] * e->hviews[v].H[e->cfg.level]; }
+
+// steps 1 and 2 for every view: b.ids and b.pts
+int render_all(mvs_engine* e, const mvs_maps_config* c, MapsBufs& b) {
+    hipStream_t st = e->stream;
+    const int nviews = e->cfg.nviews;
+    b.total_pix = b.max_pix = 0;
+    for (int v = 0; v < nviews; ++v) {
+        b.args.pix_base[v] = b.total_pix;
+        b.total_pix += maps_npix(e, v);
+        b.max_pix = std::max(b.max_pix, maps_npix(e, v));
+    }
+    for (int v = nviews; v <= MVS_MAXVIEWS; ++v) b.args.pix_base[v] = b.total_pix;
+    b.args.depth_tol = c->depth_tol; b.args.normal_cos = c->normal_cos;
+    if (b.max_pix > (int64_t)INT32_MAX - 4096) { g_err = "maps: a view of more than 2^31 - 4097 pixels"; return MVS_ERR_ARG; }
+    if (b.ids.ensure(b.total_pix) || b.pts.ensure(3 * b.total_pix) || b.flag.ensure(b.max_pix + 1) || b.base.ensure(b.max_pix + 1) ||
+        b.scan.ensure(b.max_pix / 256 + 4096))
+        return MVS_ERR_HIP;
+    const unsigned long long* sel = nullptr;
+    if (c->source == 1) {
+        if (int r = build_depth(e)) return r;
+        sel = e->dpgrid.p;
+    } else {
+        HIPCHK(hipMemsetAsync(e->best.p, 0, (size_t)e->total_cells * sizeof(unsigned long long), st));
+        mvsk_maps_select(current_params(e), e->best.p, st);
+        sel = e->best.p;
+    }
+    const DParams p = current_params(e);
+    for (int v = 0; v < nviews; ++v)
+        mvsk_maps_render(p, v, e->hviews[v].W[e->cfg.level], e->hviews[v].H[e->cfg.level], c->source, sel, b.ids.p + b.args.pix_base[v],
+                         b.pts.p + 3 * b.args.pix_base[v], st);
+    HIPCHK(hipGetLastError());
+    return MVS_OK;
+}
+// the number of set flags of one view: b.flag -> b.base (the exclusive scan), *count = its last element
+int maps_scan(mvs_engine* e, MapsBufs& b, int64_t npix, int64_t* count) {
+    mvsk_exclusive_scan(b.flag.p, b.base.p, npix, b.scan.p, e->stream);
+    int32_t n = 0;
+    HIPCHK(hipMemcpyAsync(&n, b.base.p + npix, sizeof n, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipGetLastError());
+    *count = n;
+    return MVS_OK;
+}
+}  // namespace
+
+void mvs_default_maps_config(mvs_maps_config* c) {
+    if (!c) return;
+    c->source = 0; c->min_consistent = 1; c->depth_tol = 0.01f; c->normal_cos = 0.9f; c->dedupe = 1; c->pad = 0;
+}
+
+int mvs_engine_render_maps(mvs_engine* e, const mvs_maps_config* c, mvs_view_maps* out, int64_t* n_valid) {
+    const char* who = "mvs_engine_render_maps";
+    if (int r = maps_args(c, who)) return r;
+    if (!e) { g_err = std::string(who) + ": no engine"; return MVS_ERR_ARG; }
+    if (int r = maps_state(e, c, who)) return r;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:render_maps");
+    hipStream_t st = e->stream;
+    MapsBufs b;
+    if (int r = render_all(e, c, b)) return r;
+    const DParams p = current_params(e);
+    for (int v = 0; v < e->cfg.nviews; ++v) {
+        const int64_t npix = maps_npix(e, v), pix0 = b.args.pix_base[v];
+        const mvs_view_maps o = out ? out[v] : mvs_view_maps{nullptr, nullptr, nullptr, nullptr, nullptr};
+        if (o.depth || o.normal || o.conf || o.agree) {
+            if ((o.agree && b.agree.ensure(b.max_pix)) || b.maps.ensure(5 * b.max_pix)) return MVS_ERR_HIP;
+            float* d_depth = b.maps.p, *d_normal = b.maps.p + b.max_pix, *d_conf = b.maps.p + 4 * b.max_pix;
+            mvsk_maps_agree(p, b.args, v, npix, b.ids.p, b.pts.p, o.agree ? b.agree.p : nullptr, o.depth ? d_depth : nullptr,
+                            o.normal ? d_normal : nullptr, o.conf ? d_conf : nullptr, st);
+            if (o.depth) HIPCHK(hipMemcpyAsync(o.depth, d_depth, (size_t)npix * sizeof(float), hipMemcpyDefault, st));
+            if (o.normal) HIPCHK(hipMemcpyAsync(o.normal, d_normal, (size_t)npix * 3 * sizeof(float), hipMemcpyDefault, st));
+            if (o.conf) HIPCHK(hipMemcpyAsync(o.conf, d_conf, (size_t)npix * sizeof(float), hipMemcpyDefault, st));
+            if (o.agree) HIPCHK(hipMemcpyAsync(o.agree, b.agree.p, (size_t)npix * sizeof(uint64_t), hipMemcpyDefault, st));
+        }
+        if (o.ids) HIPCHK(hipMemcpyAsync(o.ids, b.ids.p + pix0, (size_t)npix * sizeof(int32_t), hipMemcpyDefault, st));
+        if (n_valid) {
+            mvsk_maps_flag(npix, v, b.ids.p + pix0, nullptr, 0, 0, b.flag.p, nullptr, st);
+            if (int r = maps_scan(e, b, npix, &n_valid[v])) return r;
+        }
+        HIPCHK(hipStreamSynchronize(st));  // the buffers are reused by the next view
+        HIPCHK(hipGetLastError());
+    }
+    return MVS_OK;
+}
+
+int mvs_engine_fused_points(mvs_engine* e, const mvs_maps_config* c, int64_t cap, mvs_fused_point* out, int64_t* n) {
+    const char* who = "mvs_engine_fused_points";
+    if (int r = maps_args(c, who)) return r;
+    if (cap < 0 || !n) { g_err = std::string(who) + ": cap negative or n null"; return MVS_ERR_ARG; }
+    if (!e) { g_err = std::string(who) + ": no engine"; return MVS_ERR_ARG; }
+    if (int r = maps_state(e, c, who)) return r;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:fused_points");
+    hipStream_t st = e->stream;
+    const int nviews = e->cfg.nviews;
+    MapsBufs b;
+    if (int r = render_all(e, c, b)) return r;
+    if (b.agree.ensure(b.max_pix) || (out && b.flag8.ensure(b.total_pix))) return MVS_ERR_HIP;
+    const DParams p = current_params(e);
+    // the counting pass: per view the agree words, the flags (kept as bytes for the gathering pass) and their number
+    std::vector<int64_t> count((size_t)nviews, 0);
+    int64_t total = 0, most = 0;
+    for (int v = 0; v < nviews; ++v) {
+        const int64_t npix = maps_npix(e, v), pix0 = b.args.pix_base[v];
+        mvsk_maps_agree(p, b.args, v, npix, b.ids.p, b.pts.p, b.agree.p, nullptr, nullptr, nullptr, st);
+        mvsk_maps_flag(npix, v, b.ids.p + pix0, b.agree.p, c->min_consistent, c->dedupe, b.flag.p, out ? b.flag8.p + pix0 : nullptr, st);
+        if (int r = maps_scan(e, b, npix, &count[(size_t)v])) return r;
+        total += count[(size_t)v];
+        most = std::max(most, count[(size_t)v]);
+    }
+    if (!out) { *n = total; return MVS_OK; }
+    if (cap < total) { *n = total; g_err = std::string(who) + ": cap is smaller than the number of points (*n)"; return MVS_ERR_CAPACITY; }
+    // the gathering pass: the records of a view behind the scan of its flags, copied behind those of the views before it
+    if (most > 0 && b.recs.ensure(most)) return MVS_ERR_HIP;
+    int64_t pos = 0;
+    for (int v = 0; v < nviews; ++v) {
+        const int64_t npix = maps_npix(e, v), pix0 = b.args.pix_base[v], nv = count[(size_t)v];
+        if (nv == 0) continue;
+        mvsk_maps_expand(npix, b.flag8.p + pix0, b.flag.p, st);
+        int64_t again = 0;
+        if (int r = maps_scan(e, b, npix, &again)) return r;
+        if (again != nv) { g_err = std::string(who) + ": the two passes disagree"; return MVS_ERR_HIP; }
+        mvsk_maps_gather(p, v, npix, b.ids.p + pix0, b.pts.p + 3 * pix0, b.flag.p, b.base.p, b.recs.p, nv, st);
+        HIPCHK(hipMemcpyAsync(out + pos, b.recs.p, (size_t)nv * sizeof(mvs_fused_point), hipMemcpyDefault, st));
+        HIPCHK(hipStreamSynchronize(st));  // the buffers are reused by the next view
+        HIPCHK(hipGetLastError());
+        pos += nv;
+    }
+    *n = total;
+    return MVS_OK;
+}
+
 // A pass that failed (staging or Optim::check capacity in this rank's shard, a HIP error) leaves its status in the engine:
 // with a communicator attached the next mvs_engine_exchange hands it to every rank, so that all of them give the pass up
 // together instead of waiting in a collective for a rank that has already returned.

@@ -95,3 +95,22 @@ void mvsk_seed_points(const DParams& prm, const SeedPointsArgs& a, const float* 
 // per view: cnt[v] += the points that pass its gate, lo[v] / hi[v] = min / max with the bits of their depths (lo 0xffffffff, hi and cnt 0
 // before the first launch)
 void mvsk_depth_ranges(const DParams& prm, int64_t n, const float* xyz, uint32_t* lo, uint32_t* hi, unsigned long long* cnt, hipStream_t st);
+// mvs_engine_render_maps / mvs_engine_fused_points (mvs_maps.hip): dense per-view maps and their fusion.  MapsArgs: what the agreement
+// launch of one view needs by value -- where every view's pixels start in the all-view id and point buffers, and the two tolerances.
+struct MapsArgs { int64_t pix_base[MVS_MAXVIEWS + 1]; float depth_tol, normal_cos; };
+// source 0's selection of every view in one pass over the pool (k_best_ncc_map's keys; sel[0, total_cells) zero before the launch)
+void mvsk_maps_select(const DParams& prm, unsigned long long* sel, hipStream_t st);
+// one view (W x H at m_level): the selected plane of every pixel's cell cut by the pixel's ray -> ids[y W + x] (-1: invalid) and the point
+// pts[3 (y W + x) ..] (NaN); source 0: sel = the keys above, source 1: m_dpgrids (k_depth_maps' keys)
+void mvsk_maps_render(const DParams& prm, int view, int W, int H, int source, const unsigned long long* sel, int32_t* ids, float* pts, hipStream_t st);
+// one view's agree words and depth / normal / conf maps (npix values each, any of them null) from the ids and points of ALL views
+void mvsk_maps_agree(const DParams& prm, const MapsArgs& a, int view, int64_t npix, const int32_t* ids, const float* pts, unsigned long long* agree,
+                     float* depth, float* normal, float* conf, hipStream_t st);
+// flag[i] (and the byte flag8[i], if given) = pixel i of the view counts: valid and, with agree, consistent and not spoken for by a lower
+// view; ids: the view's slice
+void mvsk_maps_flag(int64_t npix, int view, const int32_t* ids, const unsigned long long* agree, int min_consistent, int dedupe, int32_t* flag,
+                    uint8_t* flag8, hipStream_t st);
+void mvsk_maps_expand(int64_t npix, const uint8_t* flag8, int32_t* flag, hipStream_t st);
+// the 32-byte records (mvs_fused_point) of the view's flagged pixels at out[base[i]], base = the exclusive scan of flag; ids, pts: the view's slices
+void mvsk_maps_gather(const DParams& prm, int view, int64_t npix, const int32_t* ids, const float* pts, const int32_t* flag, const int32_t* base,
+                      void* out, int64_t cap, hipStream_t st);

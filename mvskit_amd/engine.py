@@ -29,10 +29,13 @@ EXPORTS = [
     "mvs_default_refiner", "mvs_engine_set_refiner", "mvs_engine_export_ply", "mvs_engine_seed_patches",
     "mvs_default_seed_random", "mvs_engine_seed_random", "mvs_engine_seed_random_hypotheses",
     "mvs_default_seed_points", "mvs_engine_seed_points", "mvs_engine_seed_points_hypotheses", "mvs_engine_depth_ranges",
+    "mvs_default_maps_config", "mvs_engine_render_maps", "mvs_engine_fused_points",
 ]
 PLY_ASCII, PLY_BINARY_LE = 0, 1  # mvs_ply_format
 #: one vertex of the binary PLY file (mvs_engine_export_ply): 27 packed bytes
 PLY_VERTEX_DTYPE = np.dtype([("xyz", "<f4", (3,)), ("normal", "<f4", (3,)), ("rgb", "u1", (3,))])
+#: mvs_fused_point: one record of mvs_engine_fused_points, 32 bytes
+FUSED_POINT_DTYPE = np.dtype([("xyz", "<f4", (3,)), ("normal", "<f4", (3,)), ("conf", "<f4"), ("rgb", "u1", (3,)), ("view", "u1")])
 
 
 class Config(C.Structure):
@@ -69,6 +72,17 @@ class SeedRandom(C.Structure):
 class SeedPoints(C.Structure):
     """mvs_seed_points: the parameters of a warm start (mvs_engine_seed_points)."""
     _fields_ = [("hypotheses", C.c_int32), ("min_ncc", C.c_float)]
+
+
+class MapsConfig(C.Structure):
+    """mvs_maps_config: the parameters of mvs_engine_render_maps / mvs_engine_fused_points."""
+    _fields_ = [("source", C.c_int32), ("min_consistent", C.c_int32), ("depth_tol", C.c_float), ("normal_cos", C.c_float),
+                ("dedupe", C.c_int32), ("pad", C.c_int32)]
+
+
+class ViewMaps(C.Structure):
+    """mvs_view_maps: where one view's maps go (host or device pointers, any of them null)."""
+    _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("conf", C.c_void_p), ("ids", C.c_void_p), ("agree", C.c_void_p)]
 
 
 class Counters(C.Structure):
@@ -172,6 +186,11 @@ def load_library(cap32: bool = False, cap: int = 0):
         L.mvs_engine_seed_points.argtypes = [vp, C.POINTER(SeedPoints), C.c_int64, vp, C.POINTER(C.c_int64)]
         L.mvs_engine_seed_points_hypotheses.argtypes = [vp, C.POINTER(SeedPoints), C.c_int64, vp, vp, vp]
         L.mvs_engine_depth_ranges.argtypes = [vp, C.c_int64, vp, C.c_float, vp, vp, vp]
+    if hasattr(L, "mvs_engine_render_maps"):
+        L.mvs_default_maps_config.argtypes = [C.POINTER(MapsConfig)]
+        L.mvs_default_maps_config.restype = None
+        L.mvs_engine_render_maps.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(ViewMaps), vp]
+        L.mvs_engine_fused_points.argtypes = [vp, C.POINTER(MapsConfig), C.c_int64, vp, C.POINTER(C.c_int64)]
     _libs[LIB_PATH] = L
     return L
 
@@ -407,6 +426,59 @@ class Engine:
         end = data.index(b"end_header\n") + len(b"end_header\n")
         n = int(data[:end].split(b"element vertex ")[1].split(b"\n")[0])
         return np.frombuffer(data, dtype=PLY_VERTEX_DTYPE, count=n, offset=end).copy()
+
+    # ---- dense maps and fusion
+    def _maps_config(self, source, min_consistent, depth_tol, normal_cos, dedupe):
+        c = MapsConfig()
+        self.L.mvs_default_maps_config(C.byref(c))
+        c.source, c.min_consistent, c.depth_tol, c.normal_cos, c.dedupe = int(source), int(min_consistent), float(depth_tol), float(normal_cos), int(dedupe)
+        return c
+
+    def level_shape(self, v):
+        """(H, W) of view v at the engine's level: the shape of its dense maps"""
+        w, h = C.c_int(), C.c_int()
+        self._check(self.L.mvs_engine_get_pyramid(self.h, v, self.cfg.level, None, C.byref(w), C.byref(h)))
+        return h.value, w.value
+
+    def render_maps(self, source=0, depth_tol=0.01, normal_cos=0.9, views=None):
+        """The dense maps of every view at the engine's level (include/mvskit_engine.h, mvs_engine_render_maps): a list with one dict per
+        view -- depth [H, W] float32, normal [H, W, 3], conf [H, W], ids [H, W] int32 (-1: invalid; NaN in the float maps there) and
+        agree [H, W] uint64 (bit u: view u agrees) -- or None for a view that `views` (default: all) does not list.  source 0: the
+        best-NCC patch of each cell among those with that reference view; 1: the cell's depth-map patch.  Reads engine state only."""
+        n = self.cfg.nviews
+        want = range(n) if views is None else [int(v) for v in views]
+        if any(v < 0 or v >= n for v in want):
+            raise ValueError(f"render_maps: views must lie in 0..{n - 1}")
+        c = self._maps_config(source, 0, depth_tol, normal_cos, 1)
+        slots = (ViewMaps * n)()
+        res = [None] * n
+        for v in want:
+            h, w = self.level_shape(v)
+            res[v] = {"depth": np.zeros((h, w), np.float32), "normal": np.zeros((h, w, 3), np.float32), "conf": np.zeros((h, w), np.float32),
+                      "ids": np.zeros((h, w), np.int32), "agree": np.zeros((h, w), np.uint64)}
+            for k, a in res[v].items():
+                setattr(slots[v], k, a.ctypes.data)
+        self._check(self.L.mvs_engine_render_maps(self.h, C.byref(c), slots, None))
+        return res
+
+    def valid_pixels(self, source=0):
+        """the number of valid pixels of every view's dense map (int64 per view), without downloading a map"""
+        c = self._maps_config(source, 0, 0.01, 0.9, 1)
+        out = np.zeros(self.cfg.nviews, np.int64)
+        self._check(self.L.mvs_engine_render_maps(self.h, C.byref(c), None, _ptr(out)))
+        return out
+
+    def fused_points(self, source=0, min_consistent=1, depth_tol=0.01, normal_cos=0.9, dedupe=True):
+        """The dense point cloud of the pixels that at least `min_consistent` other views agree with (include/mvskit_engine.h,
+        mvs_engine_fused_points), as a FUSED_POINT_DTYPE array in (view, y, x) order; with dedupe only the lowest view of an agreeing set
+        emits.  Makes the size call first.  Reads engine state only."""
+        c = self._maps_config(source, min_consistent, depth_tol, normal_cos, 1 if dedupe else 0)
+        n = C.c_int64()
+        self._check(self.L.mvs_engine_fused_points(self.h, C.byref(c), 0, None, C.byref(n)))
+        out = np.zeros(n.value, dtype=FUSED_POINT_DTYPE)
+        if n.value:
+            self._check(self.L.mvs_engine_fused_points(self.h, C.byref(c), n.value, _ptr(out), C.byref(n)))
+        return out[:n.value]
 
     # ---- the hot path
     def propagate(self, it):
