@@ -117,6 +117,16 @@ DEV float wave_min(float x) {
     x = fminf(x, dpp_f<0x140>(x));
     return fminf(fminf(rlf(x, 0), rlf(x, 16)), fminf(rlf(x, 32), rlf(x, 48)));
 }
+// Picks the smallest remaining: the lane of `active` (not empty) whose x is smallest, the lowest lane among equals, taken out of `active`;
+// where every remaining x is a NaN, the first remaining lane.  (sort_images spells the step out: with the helper the sweep's machine code changes.)
+DEV int wave_pick_min(float x, int lane, unsigned long long& active) {
+    const bool act = (active >> lane) & 1ull;
+    const float m = wave_min(act ? x : __int_as_float(0x7f800000));
+    const unsigned long long eq = ballot(act && x == m);
+    const int sel = eq ? __ffsll((long long)eq) - 1 : __ffsll((long long)active) - 1;
+    active &= ~(1ull << sel);
+    return sel;
+}
 
 // ------------------------------------------------------------------ deterministic libm subset
 // (same kernels, constants and evaluation order as the oracle's pm_* functions)

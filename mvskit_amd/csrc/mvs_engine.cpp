@@ -746,6 +746,89 @@ template <typename C> void add_counters(mvs_counters& a, const C& b) {
     a.inserted += b.inserted; a.replaced += b.replaced; a.evals += b.evals; a.view_evals += b.view_evals; a.trimmed += b.trimmed;
 }
 
+// The state an entry point asks of its handle, each level with those before it, checked in this order: a handle, views, no pass waiting
+// for its commit.  An entry point that has checks of its own between two of them asks twice.
+enum Need { NEED_ENGINE, NEED_VIEWS, NEED_IDLE };
+int need_state(const mvs_engine* e, Need need, const char* who) {
+    if (!e) { g_err = std::string(who) + ": no engine"; return MVS_ERR_ARG; }
+    if (need >= NEED_VIEWS && !e->have_views) { g_err = std::string(who) + ": views not set"; return MVS_ERR_STATE; }
+    if (need >= NEED_IDLE && e->staged) { g_err = std::string(who) + ": a pass is waiting for its commit"; return MVS_ERR_STATE; }
+    return MVS_OK;
+}
+
+// flags[0, n) -> base[0, n], their exclusive scan, and *count = base[n], the number of set flags, read back: the stream is idle on return
+// (scan: n / 256 + 4096 ints of scratch)
+int scan_total(mvs_engine* e, const int32_t* flags, int32_t* base, int32_t* scan, int64_t n, int64_t* count) {
+    mvsk_exclusive_scan(flags, base, n, scan, e->stream);
+    int32_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, base + n, sizeof total, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipGetLastError());
+    *count = total;
+    return MVS_OK;
+}
+
+// xyz streams through a device buffer of `chunk` points: per chunk fn(first, n, d_xyz) with points [first, first + n) of the call in d_xyz.
+// The next chunk overwrites the buffer in stream order.
+template <typename Fn> int for_point_chunks(mvs_engine* e, const float* xyz, int64_t npoints, int64_t chunk, Fn&& fn) {
+    DevBuf<float> d_xyz;
+    if (d_xyz.ensure(3 * chunk)) return MVS_ERR_HIP;
+    for (int64_t first = 0; first < npoints; first += chunk) {
+        const int64_t n = std::min(chunk, npoints - first);
+        HIPCHK(hipMemcpyAsync(d_xyz.p, xyz + 3 * first, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, e->stream));
+        if (int r = fn(first, n, (const float*)d_xyz.p)) return r;
+    }
+    return MVS_OK;
+}
+
+// what the launches of both seeding front ends share: min_ncc < 0 asks for nccThresholdBefore; the engine's refiner
+SeedChainArgs seed_chain_args(const mvs_engine* e, int hypotheses, float min_ncc) {
+    const RefineSel rs = refine_sel(e);
+    return SeedChainArgs{hypotheses, min_ncc < 0.0f ? e->prm.nccThresholdBefore : min_ncc, rs.simplex, rs.max_evals, rs.xtol};
+}
+
+// The staged append of the seeding front ends (mvs_engine_seed_random: a batch is a view's cells; mvs_engine_seed_points: a chunk's
+// points).  A launch stages the patch of job j, if it gives one, at stage[j] with keep[j] = 1; the keep flags are scanned and the kept
+// records gathered behind those of the batches before -- into pool_alt, the commit's compaction target, which holds nothing between
+// calls: the pool itself is written once, after the last batch, when the count is known to fit.
+struct StagedAppend {
+    mvs_engine* e;
+    const char* who;
+    DevBuf<DPatch> stage;
+    DevBuf<int32_t> keep, base, scan;
+    int64_t total = 0, room;
+    StagedAppend(mvs_engine* e, const char* who) : e(e), who(who), room(e->pool.cap - e->pool_n) {}
+    // the buffers for batches of up to max_jobs jobs, and what postProcess reads
+    int begin(int64_t max_jobs) {
+        if (stage.ensure(max_jobs) || keep.ensure(max_jobs + 1) || base.ensure(max_jobs + 1) || scan.ensure(max_jobs / 256 + 4096)) return MVS_ERR_HIP;
+        // setVImagesVGrids reads m_dpgrids when depth > 0 (what MVS_PROBE_POSTPROCESS prepares): from the pool as it is now
+        if (e->prm.depth > 0) if (int r = build_depth(e)) return r;
+        return MVS_OK;
+    }
+    // one batch of n jobs: launch(stage, keep) starts its waves
+    template <typename Launch> int batch(int64_t n, Launch&& launch) {
+        HIPCHK(hipMemsetAsync(keep.p, 0, sizeof(int32_t) * ((size_t)n + 1), e->stream));
+        launch(stage.p, keep.p);
+        int64_t kept = 0;
+        if (int r = scan_total(e, keep.p, base.p, scan.p, n, &kept)) return r;
+        if (total + kept > room) { g_err = std::string(who) + ": patch pool capacity exceeded (raise mvs_config.max_patches)"; return MVS_ERR_CAPACITY; }
+        mvsk_seed_gather(stage.p, keep.p, base.p, (int)n, e->pool_alt.p + total, (int32_t)(e->pool_n + total), e->stream);
+        total += kept;
+        return MVS_OK;
+    }
+    // the gathered records into the pool
+    int commit(int64_t* n_added) {
+        if (total > 0) {
+            HIPCHK(hipMemcpyAsync(e->pool.p + e->pool_n, e->pool_alt.p, sizeof(DPatch) * (size_t)total, hipMemcpyDeviceToDevice, e->stream));
+            HIPCHK(hipStreamSynchronize(e->stream));
+            HIPCHK(hipGetLastError());
+            e->pool_n += total;
+        }
+        if (n_added) *n_added = total;
+        return MVS_OK;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -1033,9 +1116,7 @@ int mvs_engine_seed_patches(mvs_engine* e, int64_t npoints, const float* xyz, co
     // the arguments first, the handle after them
     if (npoints < 0 || (npoints > 0 && !xyz) || !views) { g_err = "mvs_engine_seed_patches: negative npoints, or xyz / views null"; return MVS_ERR_ARG; }
     if (npoints > (int64_t)INT32_MAX - 4096) { g_err = "mvs_engine_seed_patches: more than 2^31 - 4097 points in one call"; return MVS_ERR_ARG; }
-    if (!e) { g_err = "mvs_engine_seed_patches: no engine"; return MVS_ERR_ARG; }
-    if (!e->have_views) { g_err = "mvs_engine_seed_patches: views not set"; return MVS_ERR_STATE; }
-    if (e->staged) { g_err = "mvs_engine_seed_patches: a pass is waiting for its commit"; return MVS_ERR_STATE; }
+    if (int r = need_state(e, NEED_IDLE, "mvs_engine_seed_patches")) return r;
     if (n_added) *n_added = 0;
     if (npoints == 0) return MVS_OK;
     HIPCHK(hipSetDevice(e->cfg.device));
@@ -1074,12 +1155,9 @@ int mvs_engine_seed_patches(mvs_engine* e, int64_t npoints, const float* xyz, co
         HIPCHK(hipStreamSynchronize(st));  // the two buffers are reused by the next view
     }
     mvsk_seed_flags(d_cams.p, e->cfg.level, d_xyz.p, d_sum.p, d_bits.p, n, d_keep.p, st);
-    mvsk_exclusive_scan(d_keep.p, d_base.p, n, d_scan.p, st);
-    int32_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, d_base.p + n, sizeof total, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    if (e->pool_n + (int64_t)total > e->pool.cap) { g_err = "mvs_engine_seed_patches: patch pool capacity exceeded (raise mvs_config.max_patches)"; return MVS_ERR_CAPACITY; }
+    int64_t total = 0;
+    if (int r = scan_total(e, d_keep.p, d_base.p, d_scan.p, n, &total)) return r;
+    if (e->pool_n + total > e->pool.cap) { g_err = "mvs_engine_seed_patches: patch pool capacity exceeded (raise mvs_config.max_patches)"; return MVS_ERR_CAPACITY; }
     if (total > 0) {
         // Optim::sortImages' threshold as the mirror writes it (optim.cpp:222), in float; Patch::m_ncc = -1 in mvs_engine_upload_patches' score2
         volatile float deg10 = 10.0f * (float)M_PI / 180.0f;
@@ -1088,16 +1166,15 @@ int mvs_engine_seed_patches(mvs_engine* e, int64_t npoints, const float* xyz, co
         mvsk_seed_emit(d_cams.p, nviews, e->cfg.level, thr, tmp_unit, d_xyz.p, d_sum.p, d_bits.p, d_keep.p, d_base.p, n, e->pool.p + e->pool_n, st);
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipGetLastError());
-        e->pool_n += (int64_t)total;
+        e->pool_n += total;
         e->ncc_dirty = true;
     }
-    if (n_added) *n_added = (int64_t)total;
+    if (n_added) *n_added = total;
     return MVS_OK;
 }
 
-// The cold start (mvs_seed_random.hip): per view one launch of a wave per cell into a staging buffer of one record per cell of the largest
-// view, the keep flags scanned, the kept records gathered behind those of the views before -- into pool_alt, the commit's compaction
-// target, which holds nothing between calls: the pool itself is written once, after the last view, when the count is known to fit.
+// The cold start (mvs_seed_random.hip): per view one launch of a wave per cell, a batch of the staged append (StagedAppend) with a staging
+// buffer of one record per cell of the largest view.
 namespace {
 // the checks of both entry points that need no handle, in the header's order
 int seed_random_args(const mvs_seed_random* s, const char* who) {
@@ -1119,13 +1196,7 @@ int seed_random_ranges(const mvs_engine* e, const mvs_seed_random* s, const char
     return MVS_OK;
 }
 SeedRandomArgs seed_random_launch(const mvs_engine* e, const mvs_seed_random* s, int view) {
-    const RefineSel rs = refine_sel(e);
-    SeedRandomArgs a;
-    a.seed = s->seed; a.K = s->hypotheses; a.max_tilt = s->max_tilt;
-    a.min_ncc = s->min_ncc < 0.0f ? e->prm.nccThresholdBefore : s->min_ncc;
-    a.view = view; a.dmin = s->depth_min[view]; a.dmax = s->depth_max[view];
-    a.simplex = rs.simplex; a.max_evals = rs.max_evals; a.xtol = rs.xtol;
-    return a;
+    return SeedRandomArgs{seed_chain_args(e, s->hypotheses, s->min_ncc), s->seed, s->max_tilt, view, s->depth_min[view], s->depth_max[view]};
 }
 }  // namespace
 
@@ -1136,47 +1207,25 @@ void mvs_default_seed_random(mvs_seed_random* s) {
 }
 
 int mvs_engine_seed_random(mvs_engine* e, const mvs_seed_random* s, int64_t* n_added) {
-    if (int r = seed_random_args(s, "mvs_engine_seed_random")) return r;
-    if (!e) { g_err = "mvs_engine_seed_random: no engine"; return MVS_ERR_ARG; }
-    if (int r = seed_random_ranges(e, s, "mvs_engine_seed_random")) return r;
-    if (!e->have_views) { g_err = "mvs_engine_seed_random: views not set"; return MVS_ERR_STATE; }
-    if (e->staged) { g_err = "mvs_engine_seed_random: a pass is waiting for its commit"; return MVS_ERR_STATE; }
+    const char* who = "mvs_engine_seed_random";
+    if (int r = seed_random_args(s, who)) return r;
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
+    if (int r = seed_random_ranges(e, s, who)) return r;
+    if (int r = need_state(e, NEED_IDLE, who)) return r;
     if (n_added) *n_added = 0;
     HIPCHK(hipSetDevice(e->cfg.device));
     Range rg("mvs:seed_random");
-    hipStream_t st = e->stream;
     const int nviews = e->cfg.nviews;
     int64_t max_cells = 0;
     for (int v = 0; v < nviews; ++v) max_cells = std::max(max_cells, (int64_t)e->hviews[v].gw * e->hviews[v].gh);
-    DevBuf<DPatch> d_stage;
-    DevBuf<int32_t> d_keep, d_base, d_scan;
-    if (d_stage.ensure(max_cells) || d_keep.ensure(max_cells + 1) || d_base.ensure(max_cells + 1) || d_scan.ensure(max_cells / 256 + 4096)) return MVS_ERR_HIP;
-    // setVImagesVGrids reads m_dpgrids when depth > 0 (what MVS_PROBE_POSTPROCESS prepares): from the pool as it is now
-    if (e->prm.depth > 0) if (int r = build_depth(e)) return r;
+    StagedAppend sa(e, who);
+    if (int r = sa.begin(max_cells)) return r;
     const DParams p = current_params(e);
-    const int64_t room = e->pool.cap - e->pool_n;
-    int64_t total = 0;
     for (int v = 0; v < nviews; ++v) {
         const int n = e->hviews[v].gw * e->hviews[v].gh;
-        HIPCHK(hipMemsetAsync(d_keep.p, 0, sizeof(int32_t) * ((size_t)n + 1), st));
-        mvsk_seed_random(p, seed_random_launch(e, s, v), n, d_stage.p, d_keep.p, st);
-        mvsk_exclusive_scan(d_keep.p, d_base.p, n, d_scan.p, st);
-        int32_t kept = 0;
-        HIPCHK(hipMemcpyAsync(&kept, d_base.p + n, sizeof kept, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
-        if (total + (int64_t)kept > room) { g_err = "mvs_engine_seed_random: patch pool capacity exceeded (raise mvs_config.max_patches)"; return MVS_ERR_CAPACITY; }
-        mvsk_seed_random_gather(d_stage.p, d_keep.p, d_base.p, n, e->pool_alt.p + total, (int32_t)(e->pool_n + total), st);
-        total += kept;
+        if (int r = sa.batch(n, [&](DPatch* stage, int32_t* keep) { mvsk_seed_random(p, seed_random_launch(e, s, v), n, stage, keep, e->stream); })) return r;
     }
-    if (total > 0) {
-        HIPCHK(hipMemcpyAsync(e->pool.p + e->pool_n, e->pool_alt.p, sizeof(DPatch) * (size_t)total, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
-        e->pool_n += total;
-    }
-    if (n_added) *n_added = total;
-    return MVS_OK;
+    return sa.commit(n_added);
 }
 
 int mvs_engine_seed_random_hypotheses(mvs_engine* e, const mvs_seed_random* s, int view, int64_t ncells, const int32_t* cells, mvs_patch* out) {
@@ -1184,10 +1233,10 @@ int mvs_engine_seed_random_hypotheses(mvs_engine* e, const mvs_seed_random* s, i
     if (int r = seed_random_args(s, who)) return r;
     if (ncells < 0 || (ncells > 0 && (!cells || !out))) { g_err = std::string(who) + ": negative ncells, or cells / out null"; return MVS_ERR_ARG; }
     if (ncells > (int64_t)INT32_MAX / 64) { g_err = std::string(who) + ": more than 2^25 cells in one call"; return MVS_ERR_ARG; }
-    if (!e) { g_err = std::string(who) + ": no engine"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
     if (view < 0 || view >= e->cfg.nviews) { g_err = std::string(who) + ": no such view"; return MVS_ERR_ARG; }
     if (int r = seed_random_ranges(e, s, who)) return r;
-    if (!e->have_views) { g_err = std::string(who) + ": views not set"; return MVS_ERR_STATE; }
+    if (int r = need_state(e, NEED_VIEWS, who)) return r;
     const int grid = e->hviews[view].gw * e->hviews[view].gh;
     for (int64_t i = 0; i < ncells; ++i)
         if (cells[i] < 0 || cells[i] >= grid) { g_err = std::string(who) + ": a cell outside the view's grid"; return MVS_ERR_ARG; }
@@ -1206,9 +1255,8 @@ int mvs_engine_seed_random_hypotheses(mvs_engine* e, const mvs_seed_random* s, i
     return MVS_OK;
 }
 
-// The warm start (mvs_seed_points.hip): the points stream in chunks through fixed buffers -- per point of a chunk its coordinates, one
-// staged record, the keep flag and its scan -- one launch of a wave per point, the keep flags scanned, the kept records gathered behind
-// those of the chunks before into pool_alt, as the cold start gathers its views: the pool is written once, after the last chunk.
+// The warm start (mvs_seed_points.hip): the points stream in chunks through fixed buffers (for_point_chunks) -- per point of a chunk its
+// coordinates, one staged record, the keep flag and its scan -- one launch of a wave per point, a batch of the staged append.
 namespace {
 constexpr int64_t SEED_POINTS_CHUNK = 1 << 18, SEED_POINTS_CHUNK_MAX = 1 << 22;
 int64_t seed_points_chunk() {  // MVS_SEED_POINTS_CHUNK, read at the call: a positive integer (anything else: the default)
@@ -1237,82 +1285,50 @@ void mvs_default_seed_points(mvs_seed_points* s) {
 int mvs_engine_seed_points(mvs_engine* e, const mvs_seed_points* s, int64_t npoints, const float* xyz, int64_t* n_added) {
     const char* who = "mvs_engine_seed_points";
     if (int r = seed_points_args(s, npoints, xyz, who)) return r;
-    if (!e) { g_err = std::string(who) + ": no engine"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
     if (npoints > ((int64_t)1 << 30)) { g_err = std::string(who) + ": more than 2^30 points in one call"; return MVS_ERR_ARG; }
-    if (!e->have_views) { g_err = std::string(who) + ": views not set"; return MVS_ERR_STATE; }
-    if (e->staged) { g_err = std::string(who) + ": a pass is waiting for its commit"; return MVS_ERR_STATE; }
+    if (int r = need_state(e, NEED_IDLE, who)) return r;
     if (n_added) *n_added = 0;
     if (npoints == 0) return MVS_OK;
     HIPCHK(hipSetDevice(e->cfg.device));
     Range rg("mvs:seed_points");
-    hipStream_t st = e->stream;
     const int64_t chunk = std::min(seed_points_chunk(), npoints);
-    DevBuf<float> d_xyz;
-    DevBuf<DPatch> d_stage;
-    DevBuf<int32_t> d_keep, d_base, d_scan;
-    if (d_xyz.ensure(3 * chunk) || d_stage.ensure(chunk) || d_keep.ensure(chunk + 1) || d_base.ensure(chunk + 1) || d_scan.ensure(chunk / 256 + 4096)) return MVS_ERR_HIP;
-    // setVImagesVGrids reads m_dpgrids when depth > 0 (what MVS_PROBE_POSTPROCESS prepares): from the pool as it is now
-    if (e->prm.depth > 0) if (int r = build_depth(e)) return r;
+    StagedAppend sa(e, who);
+    if (int r = sa.begin(chunk)) return r;
     const DParams p = current_params(e);
-    const RefineSel rs = refine_sel(e);
-    SeedPointsArgs a;
-    a.K = s->hypotheses;
-    a.min_ncc = s->min_ncc < 0.0f ? e->prm.nccThresholdBefore : s->min_ncc;
-    a.simplex = rs.simplex; a.max_evals = rs.max_evals; a.xtol = rs.xtol;
-    const int64_t room = e->pool.cap - e->pool_n;
-    int64_t total = 0;
-    for (int64_t first = 0; first < npoints; first += chunk) {
-        const int64_t n = std::min(chunk, npoints - first);
-        a.first = first; a.n = (int32_t)n;
-        HIPCHK(hipMemcpyAsync(d_xyz.p, xyz + 3 * first, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemsetAsync(d_keep.p, 0, sizeof(int32_t) * ((size_t)n + 1), st));
-        mvsk_seed_points(p, a, d_xyz.p, d_stage.p, d_keep.p, st);
-        mvsk_exclusive_scan(d_keep.p, d_base.p, n, d_scan.p, st);
-        int32_t kept = 0;
-        HIPCHK(hipMemcpyAsync(&kept, d_base.p + n, sizeof kept, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
-        if (total + (int64_t)kept > room) { g_err = std::string(who) + ": patch pool capacity exceeded (raise mvs_config.max_patches)"; return MVS_ERR_CAPACITY; }
-        mvsk_seed_random_gather(d_stage.p, d_keep.p, d_base.p, (int)n, e->pool_alt.p + total, (int32_t)(e->pool_n + total), st);
-        total += kept;
-    }
-    if (total > 0) {
-        HIPCHK(hipMemcpyAsync(e->pool.p + e->pool_n, e->pool_alt.p, sizeof(DPatch) * (size_t)total, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipGetLastError());
-        e->pool_n += total;
-    }
-    if (n_added) *n_added = total;
-    return MVS_OK;
+    SeedPointsArgs a{seed_chain_args(e, s->hypotheses, s->min_ncc), 0, 0};
+    if (int r = for_point_chunks(e, xyz, npoints, chunk, [&](int64_t first, int64_t n, const float* d_xyz) {
+            a.first = first; a.n = (int32_t)n;
+            return sa.batch(n, [&](DPatch* stage, int32_t* keep) { mvsk_seed_points(p, a, d_xyz, stage, keep, e->stream); });
+        }))
+        return r;
+    return sa.commit(n_added);
 }
 
 int mvs_engine_seed_points_hypotheses(mvs_engine* e, const mvs_seed_points* s, int64_t npoints, const float* xyz, mvs_patch* out, int32_t* count) {
     const char* who = "mvs_engine_seed_points_hypotheses";
     if (int r = seed_points_args(s, npoints, xyz, who)) return r;
     if (npoints > 0 && (!out || !count)) { g_err = std::string(who) + ": out or count null"; return MVS_ERR_ARG; }
-    if (!e) { g_err = std::string(who) + ": no engine"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
     if (npoints * s->hypotheses > (int64_t)INT32_MAX) { g_err = std::string(who) + ": more than 2^31 - 1 hypotheses in one call"; return MVS_ERR_ARG; }
-    if (!e->have_views) { g_err = std::string(who) + ": views not set"; return MVS_ERR_STATE; }
+    if (int r = need_state(e, NEED_VIEWS, who)) return r;
     if (npoints == 0) return MVS_OK;
     HIPCHK(hipSetDevice(e->cfg.device));
     hipStream_t st = e->stream;
     const int K = s->hypotheses;
     const int64_t chunk = std::min(std::max<int64_t>(seed_points_chunk() / K, 1), npoints);  // at most a chunk of records at a time
-    DevBuf<float> d_xyz;
     DevBuf<DPatch> d_out;
     DevBuf<int32_t> d_count;
-    if (d_xyz.ensure(3 * chunk) || d_out.ensure(chunk * K) || d_count.ensure(chunk)) return MVS_ERR_HIP;
+    if (d_out.ensure(chunk * K) || d_count.ensure(chunk)) return MVS_ERR_HIP;
     const DParams p = current_params(e);
-    for (int64_t first = 0; first < npoints; first += chunk) {
-        const int64_t n = std::min(chunk, npoints - first);
-        HIPCHK(hipMemcpyAsync(d_xyz.p, xyz + 3 * first, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
-        mvsk_seed_points_hypotheses(p, K, n, d_xyz.p, d_out.p, d_count.p, st);
+    return for_point_chunks(e, xyz, npoints, chunk, [&](int64_t first, int64_t n, const float* d_xyz) -> int {
+        mvsk_seed_points_hypotheses(p, K, n, d_xyz, d_out.p, d_count.p, st);
         HIPCHK(hipMemcpyAsync(out + first * K, d_out.p, sizeof(mvs_patch) * (size_t)(n * K), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(count + first, d_count.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));  // the buffers are reused by the next chunk
         HIPCHK(hipGetLastError());
-    }
-    return MVS_OK;
+        return MVS_OK;
+    });
 }
 
 int mvs_engine_depth_ranges(mvs_engine* e, int64_t npoints, const float* xyz, float margin, float* depth_min, float* depth_max, int64_t* count) {
@@ -1321,30 +1337,28 @@ int mvs_engine_depth_ranges(mvs_engine* e, int64_t npoints, const float* xyz, fl
     if (npoints > 0 && !xyz) { g_err = std::string(who) + ": xyz null"; return MVS_ERR_ARG; }
     if (!depth_min || !depth_max || !count) { g_err = std::string(who) + ": depth_min, depth_max or count null"; return MVS_ERR_ARG; }
     if (!std::isfinite(margin) || !(margin >= 0.0f)) { g_err = std::string(who) + ": margin not finite or < 0"; return MVS_ERR_ARG; }
-    if (!e) { g_err = std::string(who) + ": no engine"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
     if (npoints > ((int64_t)1 << 30)) { g_err = std::string(who) + ": more than 2^30 points in one call"; return MVS_ERR_ARG; }
-    if (!e->have_views) { g_err = std::string(who) + ": views not set"; return MVS_ERR_STATE; }
+    if (int r = need_state(e, NEED_VIEWS, who)) return r;
     const int nviews = e->cfg.nviews;
     std::vector<uint32_t> lo((size_t)nviews, 0xffffffffu), hi((size_t)nviews, 0u);
     std::vector<unsigned long long> cnt((size_t)nviews, 0ull);
     if (npoints > 0) {
         HIPCHK(hipSetDevice(e->cfg.device));
         hipStream_t st = e->stream;
-        const int64_t chunk = std::min(seed_points_chunk(), npoints);
-        DevBuf<float> d_xyz;
         DevBuf<uint32_t> d_lohi;
         DevBuf<unsigned long long> d_cnt;
-        if (d_xyz.ensure(3 * chunk) || d_lohi.ensure(2 * nviews) || d_cnt.ensure(nviews)) return MVS_ERR_HIP;
+        if (d_lohi.ensure(2 * nviews) || d_cnt.ensure(nviews)) return MVS_ERR_HIP;
         HIPCHK(hipMemsetAsync(d_lohi.p, 0xff, sizeof(uint32_t) * (size_t)nviews, st));
         HIPCHK(hipMemsetAsync(d_lohi.p + nviews, 0, sizeof(uint32_t) * (size_t)nviews, st));
         HIPCHK(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long) * (size_t)nviews, st));
         const DParams p = current_params(e);
-        for (int64_t first = 0; first < npoints; first += chunk) {
-            const int64_t n = std::min(chunk, npoints - first);
-            HIPCHK(hipMemcpyAsync(d_xyz.p, xyz + 3 * first, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
-            mvsk_depth_ranges(p, n, d_xyz.p, d_lohi.p, d_lohi.p + nviews, d_cnt.p, st);
-            HIPCHK(hipStreamSynchronize(st));  // the buffer is reused by the next chunk
-        }
+        if (int r = for_point_chunks(e, xyz, npoints, std::min(seed_points_chunk(), npoints), [&](int64_t, int64_t n, const float* d_xyz) -> int {
+                mvsk_depth_ranges(p, n, d_xyz, d_lohi.p, d_lohi.p + nviews, d_cnt.p, st);
+                HIPCHK(hipStreamSynchronize(st));  // the buffer is reused by the next chunk
+                return MVS_OK;
+            }))
+            return r;
         HIPCHK(hipMemcpyAsync(lo.data(), d_lohi.p, sizeof(uint32_t) * (size_t)nviews, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(hi.data(), d_lohi.p + nviews, sizeof(uint32_t) * (size_t)nviews, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, sizeof(unsigned long long) * (size_t)nviews, hipMemcpyDeviceToHost, st));
@@ -1438,9 +1452,7 @@ int mvs_engine_export_ply(mvs_engine* e, int format, int64_t cap, uint8_t* out, 
     // the arguments first, the handle after them
     if (format != MVS_PLY_ASCII && format != MVS_PLY_BINARY_LE) { g_err = "mvs_engine_export_ply: format must be MVS_PLY_ASCII or MVS_PLY_BINARY_LE"; return MVS_ERR_ARG; }
     if (!nbytes || cap < 0) { g_err = "mvs_engine_export_ply: nbytes is null or cap negative"; return MVS_ERR_ARG; }
-    if (!e) { g_err = "mvs_engine_export_ply: no engine"; return MVS_ERR_ARG; }
-    if (!e->have_views) { g_err = "mvs_engine_export_ply: views not set"; return MVS_ERR_STATE; }
-    if (e->staged) { g_err = "mvs_engine_export_ply: a pass is waiting for its commit"; return MVS_ERR_STATE; }
+    if (int r = need_state(e, NEED_IDLE, "mvs_engine_export_ply")) return r;
     HIPCHK(hipSetDevice(e->cfg.device));
     Range rg("mvs:export_ply");
     hipStream_t st = e->stream;
@@ -1530,9 +1542,7 @@ int maps_args(const mvs_maps_config* c, const char* who) {
 }
 int maps_state(const mvs_engine* e, const mvs_maps_config* c, const char* who) {
     if (c->min_consistent > e->cfg.nviews - 1) { g_err = std::string(who) + ": min_consistent exceeds the number of other views"; return MVS_ERR_ARG; }
-    if (!e->have_views) { g_err = std::string(who) + ": views not set"; return MVS_ERR_STATE; }
-    if (e->staged) { g_err = std::string(who) + ": a pass is waiting for its commit"; return MVS_ERR_STATE; }
-    return MVS_OK;
+    return need_state(e, NEED_IDLE, who);
 }
 int64_t maps_npix(const mvs_engine* e, int v) { return (int64_t)e->hviews[v].W[e->cfg.level] * e->hviews[v].H[e->cfg.level]; }
 
@@ -1568,16 +1578,6 @@ int render_all(mvs_engine* e, const mvs_maps_config* c, MapsBufs& b) {
     HIPCHK(hipGetLastError());
     return MVS_OK;
 }
-// the number of set flags of one view: b.flag -> b.base (the exclusive scan), *count = its last element
-int maps_scan(mvs_engine* e, MapsBufs& b, int64_t npix, int64_t* count) {
-    mvsk_exclusive_scan(b.flag.p, b.base.p, npix, b.scan.p, e->stream);
-    int32_t n = 0;
-    HIPCHK(hipMemcpyAsync(&n, b.base.p + npix, sizeof n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipGetLastError());
-    *count = n;
-    return MVS_OK;
-}
 }  // namespace
 
 void mvs_default_maps_config(mvs_maps_config* c) {
@@ -1588,7 +1588,7 @@ void mvs_default_maps_config(mvs_maps_config* c) {
 int mvs_engine_render_maps(mvs_engine* e, const mvs_maps_config* c, mvs_view_maps* out, int64_t* n_valid) {
     const char* who = "mvs_engine_render_maps";
     if (int r = maps_args(c, who)) return r;
-    if (!e) { g_err = std::string(who) + ": no engine"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
     if (int r = maps_state(e, c, who)) return r;
     HIPCHK(hipSetDevice(e->cfg.device));
     Range rg("mvs:render_maps");
@@ -1612,7 +1612,7 @@ int mvs_engine_render_maps(mvs_engine* e, const mvs_maps_config* c, mvs_view_map
         if (o.ids) HIPCHK(hipMemcpyAsync(o.ids, b.ids.p + pix0, (size_t)npix * sizeof(int32_t), hipMemcpyDefault, st));
         if (n_valid) {
             mvsk_maps_flag(npix, v, b.ids.p + pix0, nullptr, 0, 0, b.flag.p, nullptr, st);
-            if (int r = maps_scan(e, b, npix, &n_valid[v])) return r;
+            if (int r = scan_total(e, b.flag.p, b.base.p, b.scan.p, npix, &n_valid[v])) return r;
         }
         HIPCHK(hipStreamSynchronize(st));  // the buffers are reused by the next view
         HIPCHK(hipGetLastError());
@@ -1624,7 +1624,7 @@ int mvs_engine_fused_points(mvs_engine* e, const mvs_maps_config* c, int64_t cap
     const char* who = "mvs_engine_fused_points";
     if (int r = maps_args(c, who)) return r;
     if (cap < 0 || !n) { g_err = std::string(who) + ": cap negative or n null"; return MVS_ERR_ARG; }
-    if (!e) { g_err = std::string(who) + ": no engine"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
     if (int r = maps_state(e, c, who)) return r;
     HIPCHK(hipSetDevice(e->cfg.device));
     Range rg("mvs:fused_points");
@@ -1641,7 +1641,7 @@ int mvs_engine_fused_points(mvs_engine* e, const mvs_maps_config* c, int64_t cap
         const int64_t npix = maps_npix(e, v), pix0 = b.args.pix_base[v];
         mvsk_maps_agree(p, b.args, v, npix, b.ids.p, b.pts.p, b.agree.p, nullptr, nullptr, nullptr, st);
         mvsk_maps_flag(npix, v, b.ids.p + pix0, b.agree.p, c->min_consistent, c->dedupe, b.flag.p, out ? b.flag8.p + pix0 : nullptr, st);
-        if (int r = maps_scan(e, b, npix, &count[(size_t)v])) return r;
+        if (int r = scan_total(e, b.flag.p, b.base.p, b.scan.p, npix, &count[(size_t)v])) return r;
         total += count[(size_t)v];
         most = std::max(most, count[(size_t)v]);
     }
@@ -1655,7 +1655,7 @@ int mvs_engine_fused_points(mvs_engine* e, const mvs_maps_config* c, int64_t cap
         if (nv == 0) continue;
         mvsk_maps_expand(npix, b.flag8.p + pix0, b.flag.p, st);
         int64_t again = 0;
-        if (int r = maps_scan(e, b, npix, &again)) return r;
+        if (int r = scan_total(e, b.flag.p, b.base.p, b.scan.p, npix, &again)) return r;
         if (again != nv) { g_err = std::string(who) + ": the two passes disagree"; return MVS_ERR_HIP; }
         mvsk_maps_gather(p, v, npix, b.ids.p + pix0, b.pts.p + 3 * pix0, b.flag.p, b.base.p, b.recs.p, nv, st);
         HIPCHK(hipMemcpyAsync(out + pos, b.recs.p, (size_t)nv * sizeof(mvs_fused_point), hipMemcpyDefault, st));

@@ -76,21 +76,22 @@ void mvsk_seed_flags(const SeedCam* cams, int level, const float* xyz, const flo
                      hipStream_t st);
 void mvsk_seed_emit(const SeedCam* cams, int nviews, int level, float thr, float tmp_unit, const float* xyz, const float* sum, const unsigned long long* bits,
                     const int32_t* keep, const int32_t* base, int64_t n, DPatch* dst, hipStream_t st);
-// mvs_engine_seed_random (mvs_seed_random.hip): the cold start.  SeedRandomArgs: one view's launch by value -- the call's parameters, the
-// view and its depth range, the engine's refiner.
-struct SeedRandomArgs { uint32_t seed; int32_t K; float max_tilt, min_ncc; int32_t view; float dmin, dmax; int32_t simplex, max_evals; float xtol; };
+// mvs_engine_seed_random (mvs_seed_random.hip): the cold start, the first of two front ends to one chain (mvs_seed_chain.cuh; SeedChainArgs
+// in mvs_types.h is what their launches share).  SeedRandomArgs: one view's launch by value -- the call's parameters, the
+// view and its depth range.
+struct SeedRandomArgs { SeedChainArgs chain; uint32_t seed; float max_tilt; int32_t view; float dmin, dmax; };
 size_t mvsk_texs_lds_bytes(const DParams& prm);  // mvs_kernels.hip: the dynamic LDS of a wave that runs postProcess without Optim::check
 // the K hypotheses of cells[i] (cells of the view's grid) as records at out[i * K ..]
 void mvsk_seed_random_hypotheses(const DParams& prm, const SeedRandomArgs& a, int64_t ncells, const int32_t* cells, DPatch* out, hipStream_t st);
-// one wave per cell of the view: the patch of cell c, if it gives one, at stage[c] with keep[c] = 1 (keep zero before the launch); then,
-// with base = the exclusive scan of keep, the records to dst[base[c]] with id = id0 + base[c]
+// one wave per cell of the view: the patch of cell c, if it gives one, at stage[c] with keep[c] = 1 (keep zero before the launch)
 void mvsk_seed_random(const DParams& prm, const SeedRandomArgs& a, int ncells, DPatch* stage, int32_t* keep, hipStream_t st);
-void mvsk_seed_random_gather(const DPatch* stage, const int32_t* keep, const int32_t* base, int ncells, DPatch* dst, int32_t id0, hipStream_t st);
+// both front ends' staged append: with base = the exclusive scan of keep, the staged records of the n jobs to dst[base[j]] with
+// id = id0 + base[j] (mvs_seed_random.hip)
+void mvsk_seed_gather(const DPatch* stage, const int32_t* keep, const int32_t* base, int n, DPatch* dst, int32_t id0, hipStream_t st);
 // mvs_engine_seed_points (mvs_seed_points.hip): the warm start.  xyz: 3 floats per point of the launch.
 // the hypotheses of point i as records at out[i * K ..], count[i] of them, zero bytes in the slots behind
 void mvsk_seed_points_hypotheses(const DParams& prm, int K, int64_t n, const float* xyz, DPatch* out, int32_t* count, hipStream_t st);
-// one wave per point of the chunk: the patch of point j, if it gives one, at stage[j] with keep[j] = 1 (keep zero before the launch);
-// mvsk_seed_random_gather then moves the staged records behind the exclusive scan of keep
+// one wave per point of the chunk: the patch of point j, if it gives one, at stage[j] with keep[j] = 1 (keep zero before the launch)
 void mvsk_seed_points(const DParams& prm, const SeedPointsArgs& a, const float* xyz, DPatch* stage, int32_t* keep, hipStream_t st);
 // per view: cnt[v] += the points that pass its gate, lo[v] / hi[v] = min / max with the bits of their depths (lo 0xffffffff, hi and cnt 0
 // before the first launch)

@@ -102,7 +102,7 @@ __global__ __launch_bounds__(SEED_BLOCK) void k_seed_flags(const SeedCam* __rest
 }
 
 // Optim::sortImages(patch, 0), optim.cpp:221-258, in the wave-wide form of mvsdev::sort_images: lane v is view v, the minimum of the
-// remaining units by wave_min + ballot, the lowest lane among equals (std::min_element on the shrinking arrays, which stay in view order)
+// remaining units by wave_pick_min, the lowest lane among equals (std::min_element on the shrinking arrays, which stay in view order)
 __global__ __launch_bounds__(SEED_BLOCK) void k_seed_emit(const SeedCam* __restrict__ cams, int nviews, int level, float thr, float tmp_unit,
                                                          const float* __restrict__ xyz, const float* __restrict__ sum,
                                                          const unsigned long long* __restrict__ bits, const int32_t* __restrict__ keep,
@@ -122,14 +122,10 @@ __global__ __launch_bounds__(SEED_BLOCK) void k_seed_emit(const SeedCam* __restr
         unsigned long long active = ballot(valid);
         int out = 0, k = 0;
         while (active) {
-            const bool act = (active >> lane) & 1ull;
-            const float m = wave_min(act ? unit : __int_as_float(0x7f800000));
-            const unsigned long long eq = ballot(act && unit == m);
-            const int sel = eq ? __ffsll((long long)eq) - 1 : __ffsll((long long)active) - 1;  // NaN guard: first remaining
+            const int sel = wave_pick_min(unit, lane, active);
             if (lane == k) out = sel;
             const F4 rsel{rlf(ray.x, sel), rlf(ray.y, sel), rlf(ray.z, sel), rlf(ray.w, sel)};
-            active &= ~(1ull << sel);
-            if (act && lane != sel) {
+            if ((active >> lane) & 1ull) {  // the lanes that remain
                 float d = 0.0f;
                 d += rsel.x * ray.x; d += rsel.y * ray.y; d += rsel.z * ray.z; d += rsel.w * ray.w;
                 const float ftmp = fminf(thr, fmaxf(thr / 2.0f, 1.0f - d));

@@ -133,13 +133,19 @@ struct SweepArgs {
     const int32_t* list_bounds;  // [MVS_SWEEP_QUEUES + 1] queue q's jobs are job_list[list_bounds[q] .. list_bounds[q + 1])
 };
 
-// Arguments of one chunk's launch of the warm start (mvs_seed_points.hip): the call's parameters, the chunk's place in the call's point
-// list (point j of the chunk is point first + j of the call: the key of its HALVING draws), the engine's refiner.
-struct SeedPointsArgs {
+// What the launches of both seeding front ends share (seed_chain in mvs_seed_chain.cuh): the number of hypotheses asked for, the score the
+// winner must exceed, the engine's refiner.
+struct SeedChainArgs {
     int32_t K;
     float min_ncc;
-    int64_t first;
-    int32_t n;
     int32_t simplex, max_evals;
     float xtol;
+};
+
+// Arguments of one chunk's launch of the warm start (mvs_seed_points.hip): the chunk's place in the call's point list (point j of the
+// chunk is point first + j of the call: the key of its HALVING draws).
+struct SeedPointsArgs {
+    SeedChainArgs chain;
+    int64_t first;
+    int32_t n;
 };
