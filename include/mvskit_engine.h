@@ -391,6 +391,64 @@ typedef struct mvs_fused_point {
 } mvs_fused_point;    /* 32 bytes */
 int mvs_engine_fused_points(mvs_engine* e, const mvs_maps_config* c, int64_t cap, mvs_fused_point* out /* host or device */, int64_t* n);
 
+/* Triangle mesh: a truncated signed distance volume over the dense maps, then marching tetrahedra (no reference counterpart).  The
+ * volume is a lattice of nx x ny x nz points; point (i, j, k) has the linear index p = (k ny + j) nx + i and the position origin[c] +
+ * (float)idx[c] * voxel (one multiplication, one addition).  fp32 throughout, IEEE division, no atomics: every position in an output
+ * comes from a scan, so two calls give the same bytes.
+ * mvs_engine_tsdf: renders and computes agreement exactly as mvs_engine_fused_points does (stateless, reads the engine only).  A pixel
+ *   is USABLE when it is valid and popcount(agree) >= c->min_consistent; dedupe plays no part.  For lattice point X the views v = 0 ..
+ *   nviews-1 are walked in ascending order:
+ *     1. ic = Camera::project(v, (X, 1)) at level L; ic.z > 0; the pixel (floorf(ic.x + 0.5f), floorf(ic.y + 0.5f)) lies inside the
+ *        image at level L and is usable, with patch q;
+ *     2. den = n_q.(X - C_v), num = n_q.(X0_q - C_v) (the agreement step's expressions); den finite and not zero; s = num / den;
+ *        dz = oaxis_v.(X, 1) > 0;
+ *     3. sd = (s - 1.0f) * dz: the signed distance, in depth units, from X to q's plane along v's ray; positive in front of the
+ *        surface, exact for a planar scene;
+ *     4. when sd >= -trunc: sum = sum + fminf(sd / trunc, 1.0f), n = n + 1; otherwise the view says nothing about X.
+ *   count[p] = n; tsdf[p] = sum / (float)n, a quiet NaN when n == 0.  A NaN fails every comparison above.  Device memory for the call:
+ *   17 bytes per pixel of all views and 16 per pixel of the largest (the maps), 8 per lattice point.
+ * mvs_engine_extract_mesh: marching tetrahedra over a caller's volume (tsdf and count: host or device, count may be NULL); needs a
+ *   device but no views.
+ *     OBSERVED   tsdf[p] is not NaN and count[p] >= min_count (count == NULL: every non-NaN point); INSIDE: observed and tsdf < 0 (an
+ *                exact zero is outside).
+ *     EDGES      cube corners are numbered c = dx + 2 dy + 4 dz; every cube is split into the six tetrahedra along its main diagonal,
+ *                as corner tuples (0,1,3,7) (0,1,5,7) (0,2,3,7) (0,2,6,7) (0,4,5,7) (0,4,6,7).  Every tetrahedron edge is a lattice
+ *                point p (the endpoint with the lower coordinates) plus a direction d = dx + 2 dy + 4 dz in 1..7; its slot is d - 1.
+ *     VERTICES   one per edge (p, d) whose endpoints a = p and b = p + d lie in the lattice, are both observed, and of which exactly one
+ *                is inside: t = Fa / (Fa - Fb), pos = pa + t * (pb - pa) per component, in that order of operations.  Vertices are
+ *                numbered by ascending (p, slot).  A vertex on the rim of the observed region that no triangle uses may occur.
+ *     TRIANGLES  only cubes whose eight corners are all observed give triangles: in ascending cube order (the linear index of corner
+ *                0), tetrahedra in the order above, at most two each.  With the tetrahedron's corners in ascending position: one
+ *                corner a differs from the other three b < c < d: (e(a,b), e(a,c), e(a,d)); two inside a < b and two outside c < d:
+ *                (q0,q1,q2) and (q0,q2,q3) with q = e(a,c), e(a,d), e(b,d), e(b,c).  The normal (v1 - v0) x (v2 - v0) points from the
+ *                inside corners to the outside ones (towards the cameras): a triangle that would not is emitted with its second and
+ *                third vertex swapped.  Vertex ids are int32, three per triangle.
+ *   Sizes follow mvs_engine_export_ply's convention: with verts == NULL, tris == NULL or a cap (in vertices / triangles) too small, *n_v
+ *   and *n_t are the exact counts and nothing else is written; MVS_ERR_CAPACITY when a non-NULL output is too small.  Device memory for
+ *   the call: 18 bytes per lattice point (two bytes of flags, a count, the vertex scan and the 64-bit triangle scan), 8 more for a
+ *   volume that comes from the host, and the mesh itself (12 bytes a vertex, 12 a triangle).
+ * mvs_engine_mesh: mvs_engine_tsdf, then mvs_engine_extract_mesh on its volume, which stays on the device; the same bytes.
+ * LIMITS: each dimension 2..1024, nx ny nz <= 2^28.
+ * MVS_ERR_ARG, checked in this order before the handle is read: (tsdf, mesh) the config checks of mvs_engine_fused_points; the volume
+ * NULL; voxel, then trunc, not finite or <= 0; a dimension outside 2..1024; the product over 2^28; min_count < 1; (tsdf) tsdf or count
+ * NULL; (extract_mesh) tsdf NULL; (extract_mesh, mesh) n_v or n_t NULL, a negative cap; no engine; then (tsdf, mesh) min_consistent >
+ * nviews - 1.  MVS_ERR_STATE (tsdf, mesh): views not set, or a pass waiting for its commit; extract_mesh asks
+ * for a device only, which every engine has (mvs_engine_create fails without one).  MVS_ERR_HIP: an allocation or copy
+ * failed.  A refused call writes nothing. */
+typedef struct mvs_volume {
+    float origin[3];    /* world position of lattice point (0,0,0) */
+    float voxel;        /* lattice spacing, > 0, finite */
+    int32_t dims[3];    /* nx, ny, nz lattice points */
+    float trunc;        /* truncation distance in depth units, > 0, finite */
+    int32_t min_count;  /* a lattice point is OBSERVED when at least this many views contributed; >= 1 */
+    int32_t pad;
+} mvs_volume;           /* 40 bytes */
+int mvs_engine_tsdf(mvs_engine* e, const mvs_maps_config* c, const mvs_volume* vol, float* tsdf /* [nz ny nx] */, int32_t* count /* alike */);
+int mvs_engine_extract_mesh(mvs_engine* e, const mvs_volume* vol, const float* tsdf, const int32_t* count /* or NULL */, int64_t cap_v,
+                            float* verts /* [cap_v][3] */, int64_t cap_t, int32_t* tris /* [cap_t][3] */, int64_t* n_v, int64_t* n_t);
+int mvs_engine_mesh(mvs_engine* e, const mvs_maps_config* c, const mvs_volume* vol, int64_t cap_v, float* verts, int64_t cap_t, int32_t* tris,
+                    int64_t* n_v, int64_t* n_t);
+
 /* Propagate::run(iter), propagate.cpp:28-64: two colour passes, each = index build + sweep + commit */
 int mvs_engine_propagate(mvs_engine* e, int iter, mvs_counters* out);
 

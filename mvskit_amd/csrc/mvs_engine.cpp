@@ -1667,6 +1667,148 @@ int mvs_engine_fused_points(mvs_engine* e, const mvs_maps_config* c, int64_t cap
     return MVS_OK;
 }
 
+// Triangle mesh (mvs_mesh.hip; the definitions are in mvskit_engine.h).  Stateless like the maps calls: the volume and every working
+// array live in buffers of the call.  mesh_tsdf leaves the volume on the device, mesh_extract takes one from there; the three entry
+// points differ in where the volume comes from and goes to.
+static_assert(sizeof(mvs_volume) == 40, "mvs_volume is 40 bytes");
+namespace {
+int volume_args(const mvs_volume* vol, const char* who) {
+    if (!vol) { g_err = std::string(who) + ": volume null"; return MVS_ERR_ARG; }
+    if (!std::isfinite(vol->voxel) || !(vol->voxel > 0.0f)) { g_err = std::string(who) + ": voxel not finite or <= 0"; return MVS_ERR_ARG; }
+    if (!std::isfinite(vol->trunc) || !(vol->trunc > 0.0f)) { g_err = std::string(who) + ": trunc not finite or <= 0"; return MVS_ERR_ARG; }
+    for (int c = 0; c < 3; ++c)
+        if (vol->dims[c] < 2 || vol->dims[c] > 1024) { g_err = std::string(who) + ": a dimension outside 2..1024"; return MVS_ERR_ARG; }
+    if ((int64_t)vol->dims[0] * vol->dims[1] * vol->dims[2] > ((int64_t)1 << 28)) { g_err = std::string(who) + ": more than 2^28 lattice points"; return MVS_ERR_ARG; }
+    if (vol->min_count < 1) { g_err = std::string(who) + ": min_count < 1"; return MVS_ERR_ARG; }
+    return MVS_OK;
+}
+int mesh_out_args(int64_t cap_v, int64_t cap_t, const int64_t* n_v, const int64_t* n_t, const char* who) {
+    if (!n_v || !n_t) { g_err = std::string(who) + ": n_v or n_t null"; return MVS_ERR_ARG; }
+    if (cap_v < 0 || cap_t < 0) { g_err = std::string(who) + ": a negative cap"; return MVS_ERR_ARG; }
+    return MVS_OK;
+}
+MeshVol mesh_vol(const mvs_volume* vol) {
+    return MeshVol{{vol->origin[0], vol->origin[1], vol->origin[2]}, vol->voxel, vol->dims[0], vol->dims[1], vol->dims[2], vol->trunc, vol->min_count};
+}
+struct MeshVolume {
+    DevBuf<float> tsdf;
+    DevBuf<int32_t> count;
+};
+
+// the volume of the engine's maps into d (the stream is idle on return)
+int mesh_tsdf(mvs_engine* e, const mvs_maps_config* c, const MeshVol& mv, MeshVolume& d) {
+    hipStream_t st = e->stream;
+    const int64_t N = mesh_npoints(mv);
+    MapsBufs b;
+    if (int r = render_all(e, c, b)) return r;
+    if (b.agree.ensure(b.max_pix) || b.flag8.ensure(b.total_pix) || d.tsdf.ensure(N) || d.count.ensure(N)) return MVS_ERR_HIP;
+    const DParams p = current_params(e);
+    // usability: fused_points' counting pass without dedupe, kept as a byte per pixel of all views (the views follow each other in stream order)
+    for (int v = 0; v < e->cfg.nviews; ++v) {
+        const int64_t npix = maps_npix(e, v), pix0 = b.args.pix_base[v];
+        mvsk_maps_agree(p, b.args, v, npix, b.ids.p, b.pts.p, b.agree.p, nullptr, nullptr, nullptr, st);
+        mvsk_maps_flag(npix, v, b.ids.p + pix0, b.agree.p, c->min_consistent, 0, b.flag.p, b.flag8.p + pix0, st);
+    }
+    mvsk_mesh_tsdf(p, b.args, mv, b.ids.p, b.flag8.p, d.tsdf.p, d.count.p, st);
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return MVS_OK;
+}
+
+// marching tetrahedra over a device volume (count may be null)
+int mesh_extract(mvs_engine* e, const MeshVol& mv, const float* d_tsdf, const int32_t* d_count, int64_t cap_v, float* verts, int64_t cap_t, int32_t* tris,
+                 int64_t* n_v, int64_t* n_t, const char* who) {
+    hipStream_t st = e->stream;
+    const int64_t N = mesh_npoints(mv);
+    DevBuf<uint8_t> state, mask;
+    DevBuf<int32_t> cnt, vbase, d_tris;
+    DevBuf<int64_t> tbase, scan;
+    DevBuf<float> d_verts;
+    if (state.ensure(N) || mask.ensure(N) || cnt.ensure(N + 1) || vbase.ensure(N + 1) || tbase.ensure(N + 1) || scan.ensure(N / 256 + 4096)) return MVS_ERR_HIP;
+    mvsk_mesh_state(mv, d_tsdf, d_count, state.p, st);
+    mvsk_mesh_edges(mv, state.p, mask.p, cnt.p, st);
+    mvsk_exclusive_scan(cnt.p, vbase.p, N, reinterpret_cast<int32_t*>(scan.p), st);
+    mvsk_mesh_tcount(mv, state.p, cnt.p, st);
+    mvsk_exclusive_scan_off(cnt.p, tbase.p, N, scan.p, st);
+    int32_t nv32 = 0;
+    int64_t nt = 0;
+    HIPCHK(hipMemcpyAsync(&nv32, vbase.p + N, sizeof nv32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&nt, tbase.p + N, sizeof nt, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    const int64_t nv = nv32;
+    *n_v = nv; *n_t = nt;
+    if ((verts && cap_v < nv) || (tris && cap_t < nt)) { g_err = std::string(who) + ": a cap is smaller than the mesh (*n_v, *n_t)"; return MVS_ERR_CAPACITY; }
+    if (!verts || !tris) return MVS_OK;
+    if (nv > 0) {
+        if (d_verts.ensure(3 * nv)) return MVS_ERR_HIP;
+        mvsk_mesh_verts(mv, d_tsdf, mask.p, vbase.p, d_verts.p, nv, st);
+        HIPCHK(hipMemcpyAsync(verts, d_verts.p, (size_t)nv * 3 * sizeof(float), hipMemcpyDefault, st));
+    }
+    if (nt > 0) {
+        if (d_tris.ensure(3 * nt)) return MVS_ERR_HIP;
+        mvsk_mesh_tris(mv, state.p, mask.p, vbase.p, tbase.p, d_tris.p, nt, st);
+        HIPCHK(hipMemcpyAsync(tris, d_tris.p, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDefault, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return MVS_OK;
+}
+}  // namespace
+
+int mvs_engine_tsdf(mvs_engine* e, const mvs_maps_config* c, const mvs_volume* vol, float* tsdf, int32_t* count) {
+    const char* who = "mvs_engine_tsdf";
+    if (int r = maps_args(c, who)) return r;
+    if (int r = volume_args(vol, who)) return r;
+    if (!tsdf || !count) { g_err = std::string(who) + ": tsdf or count null"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
+    if (int r = maps_state(e, c, who)) return r;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:tsdf");
+    const MeshVol mv = mesh_vol(vol);
+    const int64_t N = mesh_npoints(mv);
+    MeshVolume d;
+    if (int r = mesh_tsdf(e, c, mv, d)) return r;
+    HIPCHK(hipMemcpyAsync(tsdf, d.tsdf.p, (size_t)N * sizeof(float), hipMemcpyDefault, e->stream));
+    HIPCHK(hipMemcpyAsync(count, d.count.p, (size_t)N * sizeof(int32_t), hipMemcpyDefault, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MVS_OK;
+}
+
+int mvs_engine_extract_mesh(mvs_engine* e, const mvs_volume* vol, const float* tsdf, const int32_t* count, int64_t cap_v, float* verts, int64_t cap_t,
+                            int32_t* tris, int64_t* n_v, int64_t* n_t) {
+    const char* who = "mvs_engine_extract_mesh";
+    if (int r = volume_args(vol, who)) return r;
+    if (!tsdf) { g_err = std::string(who) + ": tsdf null"; return MVS_ERR_ARG; }
+    if (int r = mesh_out_args(cap_v, cap_t, n_v, n_t, who)) return r;
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:extract_mesh");
+    const MeshVol mv = mesh_vol(vol);
+    const int64_t N = mesh_npoints(mv);
+    MeshVolume d;  // the caller's volume, from wherever it lies
+    if (d.tsdf.ensure(N) || (count && d.count.ensure(N))) return MVS_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(d.tsdf.p, tsdf, (size_t)N * sizeof(float), hipMemcpyDefault, e->stream));
+    if (count) HIPCHK(hipMemcpyAsync(d.count.p, count, (size_t)N * sizeof(int32_t), hipMemcpyDefault, e->stream));
+    return mesh_extract(e, mv, d.tsdf.p, count ? d.count.p : nullptr, cap_v, verts, cap_t, tris, n_v, n_t, who);
+}
+
+int mvs_engine_mesh(mvs_engine* e, const mvs_maps_config* c, const mvs_volume* vol, int64_t cap_v, float* verts, int64_t cap_t, int32_t* tris,
+                    int64_t* n_v, int64_t* n_t) {
+    const char* who = "mvs_engine_mesh";
+    if (int r = maps_args(c, who)) return r;
+    if (int r = volume_args(vol, who)) return r;
+    if (int r = mesh_out_args(cap_v, cap_t, n_v, n_t, who)) return r;
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
+    if (int r = maps_state(e, c, who)) return r;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:mesh");
+    const MeshVol mv = mesh_vol(vol);
+    MeshVolume d;
+    if (int r = mesh_tsdf(e, c, mv, d)) return r;
+    return mesh_extract(e, mv, d.tsdf.p, d.count.p, cap_v, verts, cap_t, tris, n_v, n_t, who);
+}
+
 // A pass that failed (staging or Optim::check capacity in this rank's shard, a HIP error) leaves its status in the engine:
 // with a communicator attached the next mvs_engine_exchange hands it to every rank, so that all of them give the pass up
 // together instead of waiting in a collective for a rank that has already returned.

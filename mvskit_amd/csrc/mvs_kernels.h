@@ -115,3 +115,20 @@ void mvsk_maps_expand(int64_t npix, const uint8_t* flag8, int32_t* flag, hipStre
 // the 32-byte records (mvs_fused_point) of the view's flagged pixels at out[base[i]], base = the exclusive scan of flag; ids, pts: the view's slices
 void mvsk_maps_gather(const DParams& prm, int view, int64_t npix, const int32_t* ids, const float* pts, const int32_t* flag, const int32_t* base,
                       void* out, int64_t cap, hipStream_t st);
+// mvs_engine_tsdf / mvs_engine_extract_mesh / mvs_engine_mesh (mvs_mesh.hip): a truncated signed distance volume over the dense maps and
+// marching tetrahedra over a volume.  MeshVol: mvs_volume by value.  Every array has one element per lattice point, p = (k ny + j) nx + i.
+struct MeshVol { float origin[3]; float voxel; int32_t nx, ny, nz; float trunc; int32_t min_count; };
+inline int64_t mesh_npoints(const MeshVol& vol) { return (int64_t)vol.nx * vol.ny * vol.nz; }
+// ids / usable: every view's pixels (view v's at a.pix_base[v]): the id map of mvsk_maps_render and the flag bytes of mvsk_maps_flag without dedupe
+void mvsk_mesh_tsdf(const DParams& prm, const MapsArgs& a, const MeshVol& vol, const int32_t* ids, const uint8_t* usable, float* tsdf, int32_t* count,
+                    hipStream_t st);
+// state[p]: bit 0 OBSERVED (tsdf not NaN and, with count, count >= min_count), bit 1 INSIDE (observed and tsdf < 0)
+void mvsk_mesh_state(const MeshVol& vol, const float* tsdf, const int32_t* count, uint8_t* state, hipStream_t st);
+// mask[p]: bit d - 1 = the edge (p, d) carries a vertex; cnt[p] = their number
+void mvsk_mesh_edges(const MeshVol& vol, const uint8_t* state, uint8_t* mask, int32_t* cnt, hipStream_t st);
+// the vertices of p at verts[3 (vbase[p] + rank) ..], vbase = the exclusive scan of cnt; nothing at or beyond cap_v
+void mvsk_mesh_verts(const MeshVol& vol, const float* tsdf, const uint8_t* mask, const int32_t* vbase, float* verts, int64_t cap_v, hipStream_t st);
+// cnt[p] = the triangles of the cube whose corner 0 is p; then, with tbase = their exclusive scan, the triangles at tris[3 tbase[p] ..]
+void mvsk_mesh_tcount(const MeshVol& vol, const uint8_t* state, int32_t* cnt, hipStream_t st);
+void mvsk_mesh_tris(const MeshVol& vol, const uint8_t* state, const uint8_t* mask, const int32_t* vbase, const int64_t* tbase, int32_t* tris,
+                    int64_t cap_t, hipStream_t st);

@@ -30,6 +30,7 @@ EXPORTS = [
     "mvs_default_seed_random", "mvs_engine_seed_random", "mvs_engine_seed_random_hypotheses",
     "mvs_default_seed_points", "mvs_engine_seed_points", "mvs_engine_seed_points_hypotheses", "mvs_engine_depth_ranges",
     "mvs_default_maps_config", "mvs_engine_render_maps", "mvs_engine_fused_points",
+    "mvs_engine_tsdf", "mvs_engine_extract_mesh", "mvs_engine_mesh",
 ]
 PLY_ASCII, PLY_BINARY_LE = 0, 1  # mvs_ply_format
 #: one vertex of the binary PLY file (mvs_engine_export_ply): 27 packed bytes
@@ -83,6 +84,17 @@ class MapsConfig(C.Structure):
 class ViewMaps(C.Structure):
     """mvs_view_maps: where one view's maps go (host or device pointers, any of them null)."""
     _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("conf", C.c_void_p), ("ids", C.c_void_p), ("agree", C.c_void_p)]
+
+
+class Volume(C.Structure):
+    """mvs_volume: the lattice of mvs_engine_tsdf / mvs_engine_extract_mesh / mvs_engine_mesh, 40 bytes."""
+    _fields_ = [("origin", C.c_float * 3), ("voxel", C.c_float), ("dims", C.c_int32 * 3), ("trunc", C.c_float), ("min_count", C.c_int32),
+                ("pad", C.c_int32)]
+
+    @property
+    def shape(self):
+        """(nz, ny, nx): the shape of the volume's arrays"""
+        return self.dims[2], self.dims[1], self.dims[0]
 
 
 class Counters(C.Structure):
@@ -191,6 +203,10 @@ def load_library(cap32: bool = False, cap: int = 0):
         L.mvs_default_maps_config.restype = None
         L.mvs_engine_render_maps.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(ViewMaps), vp]
         L.mvs_engine_fused_points.argtypes = [vp, C.POINTER(MapsConfig), C.c_int64, vp, C.POINTER(C.c_int64)]
+    if hasattr(L, "mvs_engine_tsdf"):
+        L.mvs_engine_tsdf.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(Volume), vp, vp]
+        L.mvs_engine_extract_mesh.argtypes = [vp, C.POINTER(Volume), vp, vp, C.c_int64, vp, C.c_int64, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.mvs_engine_mesh.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(Volume), C.c_int64, vp, C.c_int64, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     _libs[LIB_PATH] = L
     return L
 
@@ -480,6 +496,51 @@ class Engine:
             self._check(self.L.mvs_engine_fused_points(self.h, C.byref(c), n.value, _ptr(out), C.byref(n)))
         return out[:n.value]
 
+    # ---- triangle mesh
+    def tsdf(self, volume, source=0, min_consistent=1, depth_tol=0.01, normal_cos=0.9):
+        """The truncated signed distance of every lattice point of `volume` to the dense maps' planes, averaged over the views that see
+        it (include/mvskit_engine.h, mvs_engine_tsdf): (tsdf [nz, ny, nx] float32, NaN where no view contributed; count, int32).  Reads
+        engine state only."""
+        c = self._maps_config(source, min_consistent, depth_tol, normal_cos, 0)
+        tsdf, count = np.zeros(volume.shape, np.float32), np.zeros(volume.shape, np.int32)
+        self._check(self.L.mvs_engine_tsdf(self.h, C.byref(c), C.byref(volume), _ptr(tsdf), _ptr(count)))
+        return tsdf, count
+
+    def _mesh(self, call, cap_v=0, cap_t=0):
+        """-> (verts [n, 3] float32, tris [m, 3] int32).  With estimated caps the full call comes first, and only a mesh that does not fit
+        them (MVS_ERR_CAPACITY leaves the exact counts) is run again; without, the size call comes first."""
+        nv, nt = C.c_int64(), C.c_int64()
+        if cap_v > 0 and cap_t > 0:
+            verts, tris = np.zeros((cap_v, 3), np.float32), np.zeros((cap_t, 3), np.int32)
+            status = call(cap_v, _ptr(verts), cap_t, _ptr(tris), C.byref(nv), C.byref(nt))
+            if status == 0:
+                return verts[:nv.value].copy(), tris[:nt.value].copy()
+            if status != -4:  # MVS_ERR_CAPACITY
+                self._check(status)
+        else:
+            self._check(call(0, None, 0, None, C.byref(nv), C.byref(nt)))
+        verts, tris = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
+        if nv.value or nt.value:
+            self._check(call(nv.value, _ptr(verts), nt.value, _ptr(tris), C.byref(nv), C.byref(nt)))
+        return verts, tris
+
+    def extract_mesh(self, volume, tsdf, count=None):
+        """Marching tetrahedra over a volume (include/mvskit_engine.h, mvs_engine_extract_mesh): (verts [n, 3] float32, tris [m, 3] int32),
+        the triangles facing from negative to positive values.  A lattice point counts when its value is not NaN and, with `count`, count
+        >= volume.min_count.  Needs no views."""
+        tsdf = np.ascontiguousarray(tsdf, dtype=np.float32)
+        count = None if count is None else np.ascontiguousarray(count, dtype=np.int32)
+        if tsdf.size != np.prod(volume.shape) or (count is not None and count.size != tsdf.size):
+            raise ValueError("extract_mesh: tsdf and count must have one value per lattice point")
+        return self._mesh(lambda *a: self.L.mvs_engine_extract_mesh(self.h, C.byref(volume), _ptr(tsdf), _ptr(count), *a))
+
+    def mesh(self, volume, source=0, min_consistent=1, depth_tol=0.01, normal_cos=0.9, cap_v=0, cap_t=0):
+        """extract_mesh(volume, *tsdf(volume, ...)) with the volume staying on the device (mvs_engine_mesh): the same arrays.  Every
+        call of mvs_engine_mesh fuses the volume, the size call too: with estimates cap_v and cap_t (vertices, triangles) that hold the
+        mesh the volume is fused once; estimates that prove too small cost one more call."""
+        c = self._maps_config(source, min_consistent, depth_tol, normal_cos, 0)
+        return self._mesh(lambda *a: self.L.mvs_engine_mesh(self.h, C.byref(c), C.byref(volume), *a), int(cap_v), int(cap_t))
+
     # ---- the hot path
     def propagate(self, it):
         c = Counters()
@@ -571,3 +632,43 @@ class Engine:
         out_i = np.zeros(n, np.int32)
         self._check(self.L.mvs_engine_probe(self.h, op, n, _ptr(recs), None, _ptr(out_rec), _ptr(out_f), _ptr(out_i)))
         return out_rec, out_f, out_i
+
+
+def make_volume(origin, voxel, dims, trunc, min_count=1):
+    """an mvs_volume: lattice point (i, j, k) at origin + (i, j, k) * voxel, dims = (nx, ny, nz)"""
+    v = Volume()
+    for k in range(3):
+        v.origin[k], v.dims[k] = float(origin[k]), int(dims[k])
+    v.voxel, v.trunc, v.min_count, v.pad = float(voxel), float(trunc), int(min_count), 0
+    return v
+
+
+def volume_around(xyz, voxel, trunc_voxels=4, pad_voxels=2, min_count=1):
+    """The mvs_volume of spacing `voxel` around points xyz [n, 3] (those of fused_points(), say): their bounding box with pad_voxels
+    lattice points more on every side, trunc = trunc_voxels * voxel."""
+    xyz = np.asarray(xyz, dtype=np.float64).reshape(-1, 3)
+    if xyz.shape[0] == 0 or not np.isfinite(xyz).all() or not voxel > 0:
+        raise ValueError("volume_around: needs finite points and a positive voxel")
+    lo = xyz.min(axis=0) - pad_voxels * voxel
+    dims = np.ceil((xyz.max(axis=0) + pad_voxels * voxel - lo) / voxel).astype(np.int64) + 1
+    if (dims < 2).any() or (dims > 1024).any() or int(np.prod(dims)) > 1 << 28:
+        raise ValueError(f"volume_around: {dims.tolist()} lattice points: each dimension must lie in 2..1024, their product must not exceed 2^28")
+    return make_volume(lo, voxel, dims, trunc_voxels * voxel, min_count)
+
+
+def write_mesh_ply(path, verts, tris, binary=True):
+    """verts [n, 3] and tris [m, 3] as a PLY file: element vertex (float x, y, z) and element face (list uchar int vertex_indices)"""
+    verts = np.ascontiguousarray(verts, dtype="<f4").reshape(-1, 3)
+    tris = np.ascontiguousarray(tris, dtype="<i4").reshape(-1, 3)
+    head = (f"ply\nformat {'binary_little_endian' if binary else 'ascii'} 1.0\nelement vertex {verts.shape[0]}\nproperty float x\n"
+            f"property float y\nproperty float z\nelement face {tris.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
+    with open(path, "wb") as f:
+        f.write(head.encode("ascii"))
+        if binary:
+            faces = np.zeros(tris.shape[0], dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+            faces["n"], faces["v"] = 3, tris
+            f.write(verts.tobytes())
+            f.write(faces.tobytes())
+        else:
+            f.write("".join(f"{x:.9g} {y:.9g} {z:.9g}\n" for x, y, z in verts.tolist()).encode("ascii"))
+            f.write("".join(f"3 {a} {b} {c}\n" for a, b, c in tris.tolist()).encode("ascii"))
