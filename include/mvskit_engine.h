@@ -556,6 +556,17 @@ typedef struct mvs_timing {
 } mvs_timing;
 int mvs_engine_last_timing(mvs_engine* e, mvs_timing* t);
 
+/* How the sweep refined its trials, summed over every pass since the engine was created.  A trial is a candidate that reached
+ * Optim::refinePatch.  Two consecutive trials of a destination cell are refined together (one pass of the per-view arithmetic for both)
+ * when the second is certain to find room in the cell and both lists have at most 8 views under tau; results do not depend on it.
+ *   out[0] trials refined as one of a pair
+ *   out[1] alone: no trial was left in the cell to join it       out[2] alone: the cell had no guaranteed room for a second one
+ *   out[3] alone: the trial that would have joined it failed generatePatch / preProcess
+ *   out[4] alone: one of the two lists was longer than 8 views
+ *   out[5] trials that can pair, whether or not they did (MVS_SWEEP_PAIR=0 in the environment, or the CONVERGED refiner, refines every
+ *          trial alone: out[0] is then 0 and out[5] says what would pair); out[1] + ... + out[5] = all trials */
+int mvs_engine_sweep_pairs(mvs_engine* e, int64_t out[6]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -218,6 +218,19 @@ DEV float rng_uniform(uint32_t seed, uint32_t a, uint32_t b, uint32_t c, uint32_
     return (float)(h >> 8) * (1.0f / 16777216.0f) - 0.5f;
 }
 
+// rng_uniform in two parts, rng_tail(seed-to-d prefix, e): where two keys d share a wave, the prefix of each is taken once
+DEV uint32_t rng_prefix(uint32_t seed, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+    uint32_t h = mix32(seed ^ 0x9e3779b9u);
+    h = mix32(h ^ a) + 0x85ebca6bu;
+    h = mix32(h ^ b) + 0xc2b2ae35u;
+    h = mix32(h ^ c) + 0x27d4eb2fu;
+    return mix32(h ^ d) + 0x165667b1u;
+}
+DEV float rng_tail(uint32_t h, uint32_t e) {
+    h = mix32(h ^ e);
+    return (float)(h >> 8) * (1.0f / 16777216.0f) - 0.5f;
+}
+
 // ------------------------------------------------------------------ camera (image/camera.cpp)
 // Camera::project, camera.cpp:310-326
 DEV F3 project(const DView* vw, F4 X, int level) {
@@ -282,6 +295,17 @@ DEV void cell_of(const DParams& prm, const DView* vw, F4 coord, int& ix, int& iy
 template <int LANE> DEV float row_bcast_f(float x) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x150 + LANE, 0xf, 0xf, false));  // row_newbcast:LANE
 }
+// PAIR (the two-candidate refinement steps, refine_patch_pair): a row holds TWO patches, one per half of 8 lanes (vw may then differ between
+// the halves); lanes 8 s + 0..2 take the three projections of half s and each half reads its own back -- the same row broadcasts, written
+// into one half of the row at a time (DPP bank mask: banks 0-1 are lanes 0..7 of a row, banks 2-3 lanes 8..15).
+template <int LANE, int BANKS> DEV float row_bcast_banks_f(float old, float x) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(x), 0x150 + LANE, 0xf, BANKS, false));
+}
+template <int LANE, bool PAIR> DEV float half_bcast_f(float x) {
+    if constexpr (PAIR) return row_bcast_banks_f<8 + LANE, 0xC>(row_bcast_banks_f<LANE, 0x3>(x, x), x);
+    else return row_bcast_f<LANE>(x);
+}
+template <bool PAIR = false>
 DEV void get_paxes(const DParams& prm, const DView* vw, F4 coord, F4 normal, F4& px, F4& py) {
     const F4 ctr = ld4(vw->center);
     const float ips = vw->ipscale;
@@ -296,14 +320,14 @@ DEV void get_paxes(const DParams& prm, const DView* vw, F4 coord, F4 normal, F4&
     F3 x3 = cross3(y3, n3);
     px = {x3.x * pscale, x3.y * pscale, x3.z * pscale, 0.0f};
     py = {y3.x * pscale, y3.y * pscale, y3.z * pscale, 0.0f};
-    const int j = lane_id() & 15;
+    const int j = lane_id() & (PAIR ? 7 : 15);
     const float a = j == 1 ? 1.0f : 0.0f, b = j == 2 ? 1.0f : 0.0f;
     const F4 X{fma_(b, py.x, fma_(a, px.x, coord.x)), fma_(b, py.y, fma_(a, px.y, coord.y)), fma_(b, py.z, fma_(a, px.z, coord.z)), coord.w};
     const F3 ic = project_regs(P, X);
-    const F3 c0{row_bcast_f<0>(ic.x), row_bcast_f<0>(ic.y), row_bcast_f<0>(ic.z)};
+    const F3 c0{half_bcast_f<0, PAIR>(ic.x), half_bcast_f<0, PAIR>(ic.y), half_bcast_f<0, PAIR>(ic.z)};
     const float inv = rcp_rn(norm3(sub3(ic, c0)));  // lane 1: 1 / xdis, lane 2: 1 / ydis (lane 0 and the rest: 1 / 0, never read)
-    px = scl4(px, row_bcast_f<1>(inv));
-    py = scl4(py, row_bcast_f<2>(inv));
+    px = scl4(px, half_bcast_f<1, PAIR>(inv));
+    py = scl4(py, half_bcast_f<2, PAIR>(inv));
 }
 DEV float robustincc(float incc) { return div_rn(incc, 1 + 3 * incc); }
 DEV float unrobustincc(float r) { return div_rn(r, 1 - 3 * r); }
@@ -592,6 +616,94 @@ DEV void eval_steps4(const DParams& prm, WaveCtx& wc, const ClsConst& cc, const 
     const float m0r = bperm_f(a0, m_r), m0g = bperm_f(a0, m_g), m0b = bperm_f(a0, m_b), inv0 = bperm_f(a0, inv_l);
     const float dot = P01 - fma_(P1b, m0b, fma_(P1g, m0g, P1r * m0r));
     incc_l = 1.0f - (dot * (inv0 * inv_l)) * prm.inv_3sz;
+}
+
+// eval_steps4 for TWO candidates (refine_patch_pair): frame lane 16 g + 8 s + k holds the frame of (candidate s, proposal g, view k), k < n_s <= 8.
+// One publication; the sampling -- the peeled reference view and the view loop, the very code above -- once per candidate, from the frames
+// fb + 8 s + k and the pivots 8 s + k into the lanes lc == 8 s + k; then ONE pass of the extras, the per-view scalars (reference lane 16 g + 8 s)
+// and, in the caller, the robust INCCs.  okm[s][g]: the views of (candidate s, proposal g) that sample; returns the same bits by frame lane.
+DEV unsigned long long eval_steps4_pair(const DParams& prm, WaveCtx& wc, const ClsConst& cc, const Frame& f, int n0, int n1, unsigned (&okm)[2][4], float& incc_l) {
+    frames_publish(wc, f, 64);
+    const unsigned long long okb = ballot(f.ok != 0);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) { okm[0][g] = (unsigned)((okb >> (16 * g)) & 0xffull); okm[1][g] = (unsigned)((okb >> (16 * g + 8)) & 0xffull); }
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+        wc.view_evals += ((okm[0][g] & 1u) ? (unsigned)__popc(okm[0][g]) : 0u) + ((okm[1][g] & 1u) ? (unsigned)__popc(okm[1][g]) : 0u);
+    const int lc = wc.lane & 15;
+    float P1r = 0.0f, P1g = 0.0f, P1b = 0.0f, P2 = 0.0f, P01 = 0.0f;
+#pragma nounroll
+    for (int s = 0; s < 2; ++s) {
+        const int n = s ? n1 : n0;
+        const int fb = cc.fb + 8 * s, pb = MVS_PIVOT_LDS4 + 8 * s, lb = 8 * s;
+        float c0[3][3];
+        ClsPend pend[3];
+        const int vlast = max(n - 1, 0);
+        {
+            const ClsFrame fr = cls_frame(fb);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) pend[j] = cls_issue(fr, cls_opaque(cc.cs[j]));
+        }
+        {   // the reference view
+            const float4 pv = mvs_dyn_lds4[pb];
+            const ClsFrame fn = cls_frame(fb + min(1, vlast));
+            float s1r = 0.0f, s1g = 0.0f, s1b = 0.0f, s2 = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const unsigned cs = cls_opaque(cc.cs[j]);
+                float r, g, b;
+                cls_colour(pend[j], cs, pv.x, pv.y, pv.z, r, g, b);
+                pend[j] = cls_issue(fn, cs);
+                c0[j][0] = r; c0[j][1] = g; c0[j][2] = b;
+                s1r += r; s1g += g; s1b += b;
+                s2 = fma_(r, r, s2); s2 = fma_(g, g, s2); s2 = fma_(b, b, s2);
+            }
+            MVS_ROW_STEP4(0xB1) MVS_ROW_STEP4(0x4E) MVS_ROW_STEP4(0x141) MVS_ROW_STEP4(0x140)
+            if (lc >= lb) { P1r = s1r; P1g = s1g; P1b = s1b; P2 = s2; }  // this candidate's half; lanes lc != 8 s are overwritten below or unused
+        }
+        for (int k = 1; k < n; ++k) {
+            const float4 pv = mvs_dyn_lds4[pb + k];
+            const ClsFrame fn = cls_frame(fb + min(k + 1, vlast));
+            float s1r = 0.0f, s1g = 0.0f, s1b = 0.0f, s2 = 0.0f, s01 = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const unsigned cs = cls_opaque(cc.cs[j]);
+                float r, g, b;
+                cls_colour(pend[j], cs, pv.x, pv.y, pv.z, r, g, b);
+                pend[j] = cls_issue(fn, cs);
+                s1r += r; s1g += g; s1b += b;
+                s2 = fma_(r, r, s2); s2 = fma_(g, g, s2); s2 = fma_(b, b, s2);
+                s01 = fma_(r, c0[j][0], s01); s01 = fma_(g, c0[j][1], s01); s01 = fma_(b, c0[j][2], s01);
+            }
+            MVS_ROW_STEP5(0xB1) MVS_ROW_STEP5(0x4E) MVS_ROW_STEP5(0x141) MVS_ROW_STEP5(0x140)
+            if (lc == lb + k) { P1r = s1r; P1g = s1g; P1b = s1b; P2 = s2; P01 = s01; }
+        }
+    }
+    const int a0 = (wc.lane & 56) << 2;  // ds_bpermute address of lane 16 g + 8 s: the reference view of this lane's candidate and proposal
+    if (cc.nx > 0) {
+        const float4 pv = mvs_dyn_lds4[MVS_PIVOT_LDS4 + lc];
+        ClsFrame fr;
+        fr.tlx = f.tlx; fr.tly = f.tly; fr.dxx = f.dxx; fr.dxy = f.dxy; fr.dyx = f.dyx; fr.dyy = f.dyy; fr.w = f.w;
+        fr.base = ((unsigned long long)f.img_hi << 32) | (unsigned long long)f.img_lo;
+        {
+            const int q = cc.xbase;
+            const unsigned cs = (unsigned)(q % prm.wsize) | ((unsigned)(q / prm.wsize) << 8) | (1u << 16);
+            const ClsPend pe = cls_issue(fr, cs);
+            float r, g, b;
+            cls_colour(pe, cs, pv.x, pv.y, pv.z, r, g, b);
+            const float r0 = bperm_f(a0, r), g0 = bperm_f(a0, g), b0 = bperm_f(a0, b);
+            P1r += r; P1g += g; P1b += b;
+            P2 = fma_(r, r, P2); P2 = fma_(g, g, P2); P2 = fma_(b, b, P2);
+            P01 = fma_(r, r0, P01); P01 = fma_(g, g0, P01); P01 = fma_(b, b0, P01);
+        }
+    }
+    const float m_r = P1r * prm.inv_sz, m_g = P1g * prm.inv_sz, m_b = P1b * prm.inv_sz;
+    const float ssd = fmaxf(P2 - fma_(P1b, m_b, fma_(P1g, m_g, P1r * m_r)), 0.0f);
+    const float inv_l = inv_msd(prm, ssd);
+    const float m0r = bperm_f(a0, m_r), m0g = bperm_f(a0, m_g), m0b = bperm_f(a0, m_b), inv0 = bperm_f(a0, inv_l);
+    const float dot = P01 - fma_(P1b, m0b, fma_(P1g, m0g, P1r * m0r));
+    incc_l = 1.0f - (dot * (inv0 * inv_l)) * prm.inv_3sz;
+    return okb;
 }
 
 // ------------------------------------------------------------------ class-lane evaluation of ONE patch against n views
@@ -1321,6 +1433,199 @@ DEV void refine_patch(const DParams& prm, WaveCtx& wc, Cand& c, uint32_t k0, uin
     c.normal.w = 0.0f;
     if (w_out) *w_out = w;
     else c.ncc = 1.0f - unrobustincc(compute_incc(prm, wc, c.coord, c.normal, c.img, c.nimg, w, 1));
+}
+
+// ------------------------------------------------------------------ two candidates in one refinement
+// A candidate that waits for a partner (sweep_cell) lies in a static LDS block of MVS_PEND_INTS ints: the scalars of its Cand, the three
+// view-lane arrays a candidate has before postProcess (m_images and their cells; the m_vimages side is empty until then), and the weights
+// of its refinement once it ran.  Behind them, the working block of a pair's refinement: per candidate s the 16 values a frame lane takes
+// each step (RefineCtx, the step's starting point, the prefix of the draws' key, min(tau, nimg)) and m_images at 8 s + k.
+#define MVS_PEND_IMG 16
+#define MVS_PEND_GX 80
+#define MVS_PEND_GY 144
+#define MVS_PEND_W 208
+#define MVS_PEND_CTX 272   // 2 x 16 floats, 16-byte aligned
+#define MVS_PEND_XIMG 304  // 16 ints
+#define MVS_PEND_INTS 320
+DEV float rff(float x) { return __int_as_float(rfl(__float_as_int(x))); }
+DEV void pend_store(int* st, const WaveCtx& wc, const Cand& c, float w) {
+    __syncthreads();
+    if (wc.lane == 0) {
+        float* f = reinterpret_cast<float*>(st);
+        f[0] = c.coord.x; f[1] = c.coord.y; f[2] = c.coord.z; f[3] = c.coord.w;
+        f[4] = c.normal.x; f[5] = c.normal.y; f[6] = c.normal.z; f[7] = c.normal.w;
+        f[8] = c.ncc; f[9] = c.dscale; f[10] = c.ascale; f[11] = c.tmp;
+        st[12] = c.nimg; st[13] = c.nvimg;
+    }
+    st[MVS_PEND_IMG + wc.lane] = c.img; st[MVS_PEND_GX + wc.lane] = c.gx; st[MVS_PEND_GY + wc.lane] = c.gy;
+    st[MVS_PEND_W + wc.lane] = __float_as_int(w);
+    __syncthreads();
+}
+DEV void pend_load(const int* st, const WaveCtx& wc, Cand& c, float& w) {
+    const float* f = reinterpret_cast<const float*>(st);
+    c.coord = {rff(f[0]), rff(f[1]), rff(f[2]), rff(f[3])};
+    c.normal = {rff(f[4]), rff(f[5]), rff(f[6]), rff(f[7])};
+    c.ncc = rff(f[8]); c.dscale = rff(f[9]); c.ascale = rff(f[10]); c.tmp = rff(f[11]);
+    c.nimg = rfl(st[12]); c.nvimg = rfl(st[13]);
+    c.img = st[MVS_PEND_IMG + wc.lane]; c.gx = st[MVS_PEND_GX + wc.lane]; c.gy = st[MVS_PEND_GY + wc.lane];
+    c.vimg = 0; c.vgx = 0; c.vgy = 0;
+    w = __int_as_float(st[MVS_PEND_W + wc.lane]);
+}
+// cost_func4 for the four proposals of TWO candidates: lane 16 g + 8 s + k decodes proposal g of candidate s (rc, imgx, szl and x0..x2 are
+// that lane's), builds its patch axes and the frame of view k < szl = min(tau, nimg) of candidate s (<= 8).  fv[s][g]: the cost of proposal g
+// of candidate s -- the eight means in lanes j < 8 (candidate j >> 2, proposal j & 3), added in cost_func's order, one fp64 division.
+DEV void cost_func4_pair(const DParams& prm, WaveCtx& wc, const RefineCtx& rc, int imgx, int sz0, int sz1, int szl, float x0, float x1, float x2,
+                         double (&fv)[2][4], const ClsConst& cc) {
+    F4 coord, normal, px, py;
+    decode(prm, rc, x0, x1, x2, coord, normal);
+    get_paxes<true>(prm, prm.views + rc.ref, coord, normal, px, py);
+    const Frame f = make_frame(prm, coord, px, py, normal, imgx, (wc.lane & 7) < szl);
+    wc.evals += 8u;
+    unsigned okm[2][4];
+    float incc_l;
+    const unsigned long long okb = eval_steps4_pair(prm, wc, cc, f, sz0, sz1, okm, incc_l);
+    const float val_l = robustincc(incc_l);
+    // lane j < 8 takes the mean of candidate j >> 2, proposal j & 3, whose frame lanes start at src.  (Taken from an opaque copy of the
+    // lane number: as a loop invariant of the whole kernel the address only turns into a spilled register.)
+    const int src = (int)(((cls_opaque((unsigned)wc.lane) & 3u) << 4) | ((cls_opaque((unsigned)wc.lane) & 4u) << 1));
+    const unsigned okl = (unsigned)(okb >> src) & 0xffu;
+    double num = 0.0;
+    int den = 0;
+    const int szm = max(sz0, sz1);  // a view beyond a candidate's own list never samples: its bit is clear
+    for (int i = 1; i < szm; ++i) {
+        const float v = bperm_f(4 * (src + i), val_l);
+        const bool ok = (okl >> i) & 1u;
+        num = ok ? num + (double)v : num;
+        den += ok ? 1 : 0;
+    }
+    const double q = num / (double)den;
+    const int min0 = min(prm.minImageNum, sz0), min1 = min(prm.minImageNum, sz1);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        fv[0][j] = ((okm[0][j] & 1u) && rli(den, j) >= min0 - 1) ? rld(q, j) : 2.0;
+        fv[1][j] = ((okm[1][j] & 1u) && rli(den, 4 + j) >= min1 - 1) ? rld(q, 4 + j) : 2.0;
+    }
+}
+// refine_patch for two candidates of one cell at once (sweep_cell): candidate 0 is the one stashed at st (pend_store), candidate 1 is c1; both
+// have min(tau, nimg) <= 8.  Per candidate every value and every operation is refine_patch's, with that candidate's draws (k3a / k3b); what
+// changes is where the work of the frame lanes runs -- decode, getPAxes, the frames, the extra sample, the per-view scalars, the robust
+// INCCs and the cost means are issued once for both, candidate s in lanes 16 g + 8 s + k (refine_patch leaves the lanes 16 g + 8 .. 15 idle).
+// Leaves the refined coord / normal of candidate 0 and its weights in the stash, those of candidate 1 in c1 and w1.
+DEV void refine_patch_pair(const DParams& prm, WaveCtx& wc, int* st, Cand& c1, uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3a, uint32_t k3b, float& w1) {
+    float* const ctx = reinterpret_cast<float*>(st + MVS_PEND_CTX);
+    int* const ximg = st + MVS_PEND_XIMG;
+    const float amin = -23.99999f, amax = 23.99999f;
+    double fbest0 = 2.0, fbest1 = 2.0;
+    int sz0 = 0, sz1 = 0;
+    w1 = 0.0f;
+#pragma nounroll
+    for (int s = 0; s < 2; ++s) {  // the first evaluation, which also gives the pivots, candidate after candidate
+        F4 coord = c1.coord, normal = c1.normal;
+        float dscale = c1.dscale;
+        int img = c1.img, nimg = c1.nimg;
+        if (s == 0) {
+            const float* f = reinterpret_cast<const float*>(st);
+            coord = {rff(f[0]), rff(f[1]), rff(f[2]), rff(f[3])};
+            normal = {rff(f[4]), rff(f[5]), rff(f[6]), rff(f[7])};
+            dscale = rff(f[9]); nimg = rfl(st[12]);
+            img = st[MVS_PEND_IMG + wc.lane];
+        }
+        RefineCtx rc;
+        rc.center = coord;
+        rc.ref = rli(img, 0);
+        rc.ray = nrm4(sub4(coord, ld4((prm.views + rc.ref)->center)));
+        rc.dscale = dscale;
+        rc.ascale = prm.ascaleConst;
+        const float w = compute_weights(prm, wc, coord, normal, img, nimg);
+        if (s == 0) st[MVS_PEND_W + wc.lane] = __float_as_int(w);
+        else w1 = w;
+        float x[3];
+        encode(prm, rc, coord, normal, x);
+        x[1] = fmaxf(fminf(x[1], amax), amin);
+        x[2] = fmaxf(fminf(x[2], amax), amin);
+        double fv[4];
+        float piv[3] = {128.0f, 128.0f, 128.0f};
+        cost_func4(prm, wc, rc, __shfl(img, wc.lane & 15), nimg, false, x[0], x[1], x[2], fv, piv);
+        __syncthreads();
+        if (wc.lane < 8) {
+            mvs_dyn_lds4[MVS_PIVOT_LDS4 + 8 * s + wc.lane] = make_float4(piv[0], piv[1], piv[2], 0.0f);
+            ximg[8 * s + wc.lane] = img;
+        }
+        const int sz = min(prm.tau, nimg);
+        if (wc.lane == 0) {
+            float* d = ctx + 16 * s;
+            d[0] = rc.center.x; d[1] = rc.center.y; d[2] = rc.center.z; d[3] = rc.center.w;
+            d[4] = rc.ray.x; d[5] = rc.ray.y; d[6] = rc.ray.z; d[7] = rc.ray.w;
+            d[8] = rc.dscale; d[9] = __int_as_float(rc.ref); d[10] = x[0]; d[11] = x[1]; d[12] = x[2];
+            d[13] = __int_as_float((int)rng_prefix(prm.seed, k0, k1, k2, s ? k3b : k3a)); d[14] = __int_as_float(sz); d[15] = 0.0f;
+        }
+        if (s == 0) { fbest0 = fv[0]; sz0 = sz; } else { fbest1 = fv[0]; sz1 = sz; }
+    }
+    __syncthreads();
+    const ClsConst cc = wc.cc;
+    float rd = prm.rd0, ra = prm.ra0;
+    const int g = wc.lane >> 4;
+    const uint32_t gj = (uint32_t)min(g, 2);
+    const float4* const my = reinterpret_cast<const float4*>(ctx + 16 * ((wc.lane >> 3) & 1));
+    for (int k = 0; k < prm.refine_steps; ++k) {
+        const float4 A = my[0], B = my[1], Cq = my[2], D = my[3];  // this lane's candidate, from LDS every step: nothing of it stays in registers
+        RefineCtx rc;
+        rc.center = {A.x, A.y, A.z, A.w};
+        rc.ray = {B.x, B.y, B.z, B.w};
+        rc.dscale = Cq.x; rc.ref = __float_as_int(Cq.y); rc.ascale = prm.ascaleConst;
+        const float bx0 = Cq.z, bx1 = Cq.w, bx2 = D.x;
+        const uint32_t hp = (uint32_t)__float_as_int(D.y);
+        const int szl = __float_as_int(D.z);
+        const int imgx = ximg[wc.lane & 15];
+        const uint32_t draw = 16u + ((uint32_t)(k * 3) + gj) * 3u;
+        const float u0 = 2.0f * rng_tail(hp, draw + 0);
+        const float u1 = 2.0f * rng_tail(hp, draw + 1);
+        const float u2 = 2.0f * rng_tail(hp, draw + 2);
+        float cx0 = (gj == 1u) ? bx0 : fma_(u0, rd, bx0);
+        float cx1 = (gj == 0u) ? bx1 : fmaxf(fminf(fma_(u1, ra, bx1), amax), amin);
+        float cx2 = (gj == 0u) ? bx2 : fmaxf(fminf(fma_(u2, ra, bx2), amax), amin);
+        if (g == 3) {
+            cx0 = bx0 - (cx0 - bx0);
+            cx1 = fmaxf(fminf(bx1 - (cx1 - bx1), amax), amin);
+            cx2 = fmaxf(fminf(bx2 - (cx2 - bx2), amax), amin);
+        }
+        double fv[2][4];
+        cost_func4_pair(prm, wc, rc, imgx, sz0, sz1, szl, cx0, cx1, cx2, fv, cc);
+        __syncthreads();  // every lane has read its candidate's block
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            int jb = 0;
+            double fstep = fv[s][0];
+#pragma unroll
+            for (int j = 1; j < 4; ++j) if (fv[s][j] < fstep) { fstep = fv[s][j]; jb = j; }
+            const double fb = s ? fbest1 : fbest0;
+            if (fstep < fb) {
+                if (s) fbest1 = fstep; else fbest0 = fstep;
+                const float n0 = rlf(cx0, 16 * jb + 8 * s), n1 = rlf(cx1, 16 * jb + 8 * s), n2 = rlf(cx2, 16 * jb + 8 * s);
+                if (wc.lane == 0) { ctx[16 * s + 10] = n0; ctx[16 * s + 11] = n1; ctx[16 * s + 12] = n2; }
+            }
+        }
+        __syncthreads();
+        rd *= 0.5f; ra *= 0.5f;
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const float* d = ctx + 16 * s;
+        RefineCtx rc;
+        rc.center = {rff(d[0]), rff(d[1]), rff(d[2]), rff(d[3])};
+        rc.ray = {rff(d[4]), rff(d[5]), rff(d[6]), rff(d[7])};
+        rc.dscale = rff(d[8]); rc.ref = rfl(__float_as_int(d[9])); rc.ascale = prm.ascaleConst;
+        F4 coord, normal;
+        decode(prm, rc, rff(d[10]), rff(d[11]), rff(d[12]), coord, normal);
+        normal.w = 0.0f;
+        if (s) { c1.coord = coord; c1.normal = normal; }
+        else if (wc.lane == 0) {
+            float* f = reinterpret_cast<float*>(st);
+            f[0] = coord.x; f[1] = coord.y; f[2] = coord.z; f[3] = coord.w;
+            f[4] = normal.x; f[5] = normal.y; f[6] = normal.z; f[7] = normal.w;
+        }
+    }
+    __syncthreads();
 }
 
 // Optim::refinePatch run to convergence (mvs_refiner CONVERGED): a bounded Nelder-Mead over the same three

@@ -219,6 +219,7 @@ struct mvs_engine {
     DevBuf<int32_t> big_tables, retry_jobs;  // Optim::check's second tier (k_sweep_retry): 256 id sets of 16384 ints, the cells to run again
     DevBuf<int32_t> job_list;                // the jobs of a launch that run a trial, per queue (SweepArgs::job_list); its flags and their scan
                                              // lie in job_cnt and job_base_scan, which the commit fills only after the sweep
+    int64_t sweep_pairs[6] = {0, 0, 0, 0, 0, 0};  // DCounters::pair, summed over the passes since the engine was created (mvs_engine_sweep_pairs)
     int64_t retried_cells = 0;               // destination cells that went to the second tier since the engine was created
     int64_t pass_retried = 0;                // ... in the last pass
     SweepArgs sa{};
@@ -1933,7 +1934,10 @@ static int pass_impl(mvs_engine* e, int iter, int pass, mvs_counters* out) {
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
     mvs_counters sum{};
-    for (const DCounters& c : hcs) add_counters(sum, c);
+    for (const DCounters& c : hcs) {
+        add_counters(sum, c);
+        for (int k = 0; k < 6; ++k) e->sweep_pairs[k] += (int64_t)c.pair[k];
+    }
     sum.evals += fill[0]; sum.view_evals += fill[1]; sum.trimmed = (int64_t)trimmed;
     float ms = 0.0f;
     (void)hipEventElapsedTime(&ms, e->ev[0], e->ev[1]); e->timing.index_ms = ms;
@@ -2379,6 +2383,12 @@ int mvs_engine_filter(mvs_engine* e, int64_t* removed4) {  // Filter::run, filte
 int mvs_engine_filter_stats(mvs_engine* e, mvs_filter_stats* out) {
     if (!e || !out) return MVS_ERR_ARG;
     *out = e->fstats;
+    return MVS_OK;
+}
+
+int mvs_engine_sweep_pairs(mvs_engine* e, int64_t out[6]) {
+    if (!e || !out) return MVS_ERR_ARG;
+    for (int k = 0; k < 6; ++k) out[k] = e->sweep_pairs[k];
     return MVS_OK;
 }
 

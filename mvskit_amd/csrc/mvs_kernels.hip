@@ -507,6 +507,7 @@ __global__ void k_job_scatter(SweepArgs a, int seg, const int32_t* __restrict__ 
 struct SweepAcc {
     unsigned cand, pref, patch, f0, f1, ins, rep;
     unsigned long long evals, view_evals;
+    unsigned pair[6];  // DCounters::pair
 #ifdef MVS_STAGE_TIMING
     unsigned long long stage[16];
 #endif
@@ -515,6 +516,7 @@ DEV SweepAcc sweep_acc_zero() {
     SweepAcc acc;
     acc.cand = acc.pref = acc.patch = acc.f0 = acc.f1 = acc.ins = acc.rep = 0u;
     acc.evals = acc.view_evals = 0ull;
+    for (int k = 0; k < 6; ++k) acc.pair[k] = 0u;
 #ifdef MVS_STAGE_TIMING
     for (int k = 0; k < 16; ++k) acc.stage[k] = 0ull;
 #endif
@@ -531,6 +533,7 @@ DEV void sweep_acc_flush(const SweepArgs& a, const SweepAcc& acc, unsigned slot)
     if (acc.rep) atomicAdd(&C->replaced, (unsigned long long)acc.rep);
     if (acc.evals) atomicAdd(&C->evals, acc.evals);
     if (acc.view_evals) atomicAdd(&C->view_evals, acc.view_evals);
+    for (int k = 0; k < 6; ++k) if (acc.pair[k]) atomicAdd(&C->pair[k], (unsigned long long)acc.pair[k]);
 #ifdef MVS_STAGE_TIMING
     for (int k = 0; k < 12; ++k) if (acc.stage[k]) atomicAdd(&C->stage[k], acc.stage[k]);
     atomicMax(&C->stage[12], acc.stage[12]); atomicMax(&C->stage[13], acc.stage[13]);
@@ -543,7 +546,7 @@ DEV void sweep_acc_flush(const SweepArgs& a, const SweepAcc& acc, unsigned slot)
 // SIMPLEX = true: the refinement is refine_patch_simplex with max_evals / xtol (k_sweep_simplex, k_sweep_retry_simplex: the CONVERGED
 // refiner of mvs_engine_set_refiner); the default kernels keep the halving search and never see the two arguments.
 template <bool BIG, bool SIMPLEX = false>
-DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WaveCtx& wc, SweepAcc* acc, const int64_t job, int* s_scratch, float* s_texs,
+DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WaveCtx& wc, SweepAcc* acc, const int64_t job, int* s_scratch, int* s_pend, float* s_texs,
                     int* big_table, int max_evals = 0, float xtol = 0.0f) {
 #ifdef MVS_STAGE_TIMING
     unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -580,108 +583,164 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WaveCtx& wc, SweepAc
     // reference keeps commented out (propagate.cpp:110-120) -- this cell's own list: a patch of another reference view
     // that is listed here proposes itself with view v as the reference
     const int nsrc = prm.view_propagation ? 3 : 2;
-    for (int sidx = 0; sidx < nsrc; ++sidx) {
+    // Two consecutive trials of the cell are refined TOGETHER where the second is certain to find room (refine_patch_pair): a candidate that
+    // has passed preProcess waits in s_pend for the next one that does.  Everything after the refinement -- postProcess, Optim::check, the
+    // staging slot, the live list -- then runs candidate by candidate in trial order, as if each had been refined in its turn.  When the
+    // sources are through (the pass sidx == nsrc below) a candidate still waiting is finished alone.
+    bool pend = false, pend_failed = false;  // a candidate waits; a trial that would have joined it failed generate / preProcess
+    uint32_t pend_k3 = 0u;
+    int pend_sz = 0;
+    unsigned n_pair = 0, n_elig = 0, n_last = 0, n_noroom = 0, n_lost = 0, n_long = 0;  // DCounters::pair
+    for (int sidx = 0; sidx <= nsrc; ++sidx) {
+        const bool flush = sidx == nsrc;
         const int scx = sidx < 2 ? sxs[sidx] : cx, scy = sidx < 2 ? sys[sidx] : cy;
-        if (scx < 0 || gw <= scx || scy < 0 || gh <= scy) continue;
-        const int g = vw->cell_base + scy * gw + scx;
-        const csr_off_t sb = prm.csr_start[g];
-        const int sn = min(prm.csr_cnt[g], MVS_CAPMAX);  // a trimmed list: at most MAX_NUM_OF_PATCHES <= 32 entries
+        if (!flush && (scx < 0 || gw <= scx || scy < 0 || gh <= scy)) continue;
         const int as_view = sidx == 2 ? v : -1;
         // the entries of the source list, a lane each, in ONE round trip (the walk used to read entry after entry: a dependent load
         // per entry, six in seven of them only to find another reference view); then the sources in list order
         int E_id = 0;
         bool E_take = false;
-        if (wc.lane < sn) { E_id = pgrid_id(prm, sb + wc.lane); E_take = (pgrid_ref(prm, sb + wc.lane) == v) != (sidx == 2); }
-        unsigned todo = (unsigned)ballot(E_take);
+        if (!flush) {
+            const int g = vw->cell_base + scy * gw + scx;
+            const csr_off_t sb = prm.csr_start[g];
+            const int sn = min(prm.csr_cnt[g], MVS_CAPMAX);  // a trimmed list: at most MAX_NUM_OF_PATCHES <= 32 entries
+            if (wc.lane < sn) { E_id = pgrid_id(prm, sb + wc.lane); E_take = (pgrid_ref(prm, sb + wc.lane) == v) != (sidx == 2); }
+        }
+        unsigned todo = flush ? (pend ? 1u : 0u) : (unsigned)ballot(E_take);
         while (todo) {
             const int n = __ffs((int)todo) - 1;
             todo &= todo - 1u;
             const DPatch* sp = prm.pool + rli(E_id, n);
             const int srcslot = sidx * prm.cap + n;
             // ---- Propagate::propagatePatch, propagate.cpp:153-213
-            for (int it = 0; it < prm.max_propag; ++it) {
+            const int ntrial = flush ? 1 : prm.max_propag;
+            for (int it = 0; it < ntrial; ++it) {
                 ST_ADD(7, st_t)
                 const int np = L_n;
-                const uint32_t k0 = (uint32_t)a.iter, k1 = (uint32_t)v, k2 = (uint32_t)cell, k3 = (uint32_t)(srcslot * 16 + it);
+                const uint32_t k0 = (uint32_t)a.iter, k1 = (uint32_t)v, k2 = (uint32_t)cell;
+                uint32_t k3 = (uint32_t)(srcslot * 16 + it);
                 Cand c;
+                float keep_w = 0.0f;  // computeWeights of refinePatch, for the m_ncc postProcess takes from its first evaluation
                 int worst = -1;
-                float worst_ncc = 0.0f;
-                F3 ic;
-                if (np < prm.cap) {
-                    const float ra = rng_uniform(prm.seed, k0, k1, k2, k3, 0) * (float)prm.csize;
-                    const float rb = rng_uniform(prm.seed, k0, k1, k2, k3, 1) * (float)prm.csize;
-                    ic = {icx + ra, icy + rb, 1.0f};
-                } else {
-                    worst = rli(L_id, prm.cap - 1);
-                    worst_ncc = rlf(L_ncc, prm.cap - 1);
-                    const DPatch* wp = worst >= MVS_NEWBASE ? a.staging + (worst - MVS_NEWBASE) : prm.pool + worst;
-                    ic = project(vw, ld4(wp->coord), prm.level);
-                }
-                {
-                    Cand src;  // loaded per trial: its registers are free again during the refinement
-                    load_cand(sp, wc, src);
-                    const bool gen_ok = generate_patch(prm, wc, s_scratch, src, ic, c, as_view, np >= prm.cap);
-                    ST_ADD(1, st_t)
-                    if (!gen_ok) continue;
-                }
-                ++n_cand;
-                if (np >= prm.cap && c.ncc < worst_ncc) { ++n_pref; continue; }
-                ++n_patch;
-                const int pre_r = pre_process(prm, wc, s_scratch, c);
-                ST_ADD(2, st_t)
-                if (pre_r == -1) { ++n_f0; continue; }
-                float keep_w;  // computeWeights of refinePatch, for the m_ncc postProcess takes from its first evaluation
-                if constexpr (SIMPLEX) (void)refine_patch_simplex(prm, wc, c, max_evals, xtol, &keep_w);
-                else refine_patch(prm, wc, c, k0, k1, k2, k3, &keep_w);
-                ST_ADD(3, st_t)
-                const int post_r = post_process(prm, wc, s_scratch, s_texs, tstride, c, keep_w, true);
-                ST_ADD(4, st_t)
-                if (post_r == -1) { ++n_f1; continue; }
-                if (prm.depth >= 2 && prm.enable_check) {  // Optim::check, optim.cpp:292
-                    __syncthreads();
-                    if (wc.lane < MVS_CAPMAX) s_scratch[wc.lane] = L_id;  // publish the live list of this cell
-                    __syncthreads();
-                    #ifdef MVS_STAGE_TIMING
-                    const CheckCtx cx{a.staging, v, cell, L_n, s_scratch, st_acc};
-#else
-                    const CheckCtx cx{a.staging, v, cell, L_n, s_scratch, nullptr};
-#endif
-                    const int chk_r = check_patch<BIG>(prm, wc, cx, c, s_texs, a.error_flag, big_table);
-                    ST_ADD(5, st_t)
-                    if (!BIG && chk_r < 0) { gave_up = true; break; }  // the neighbourhood does not fit LDS: this cell goes to k_sweep_retry
-                    if (chk_r) { ++n_f1; continue; }
-                }
-                // staging slot for the accepted patch
-                unsigned long long slot64 = 0;
-                if (wc.lane == 0) slot64 = atomicAdd(a.stage_counter, 1ull);
-                const int64_t slot = ((int64_t)rfl((int)(slot64 >> 32)) << 32) | (uint32_t)rfl((int)(slot64 & 0xffffffffull));
-                if (slot >= a.staging_cap || ns >= a.maxstage) {
-                    if (wc.lane == 0) atomicOr(a.error_flag, 1);
-                    continue;
-                }
-                if (np == prm.cap) {  // removePatch(worst), propagate.cpp:198-201
-                    if (wc.lane == 0) {
-                        if (worst >= MVS_NEWBASE) a.staging[worst - MVS_NEWBASE].flags &= ~1;
-                        else a.kill[worst] = 1;
+                int nfin = 1;         // candidates to finish now: this one, or the waiting one and this one
+                if (!flush) {
+                    float worst_ncc = 0.0f;
+                    F3 ic;
+                    if (np < prm.cap) {
+                        const float ra = rng_uniform(prm.seed, k0, k1, k2, k3, 0) * (float)prm.csize;
+                        const float rb = rng_uniform(prm.seed, k0, k1, k2, k3, 1) * (float)prm.csize;
+                        ic = {icx + ra, icy + rb, 1.0f};
+                    } else {
+                        worst = rli(L_id, prm.cap - 1);
+                        worst_ncc = rlf(L_ncc, prm.cap - 1);
+                        const DPatch* wp = worst >= MVS_NEWBASE ? a.staging + (worst - MVS_NEWBASE) : prm.pool + worst;
+                        ic = project(vw, ld4(wp->coord), prm.level);
                     }
-                    --L_n;
-                    ++n_rep;
-                } else ++n_ins;
-                store_cand(a.staging + slot, wc, c, 1 | (v << 8), cell);
-                if (wc.lane == 0) a.job_stage[job * a.maxstage + ns] = (int32_t)slot;
-                ++ns;
-                // PatchManager::addPatch into this cell's own list if the patch lands here
-                const bool lands = ballot(wc.lane < c.nimg && c.img == v && c.gy * gw + c.gx == cell) != 0ull;
-                if (lands) {
-                    const int nid = MVS_NEWBASE + (int)slot;
-                    const int pos = __popcll(ballot(wc.lane < L_n && rank_before(L_ncc, L_id, c.ncc, nid)));
-                    const int up_id = __shfl_up(L_id, 1);
-                    const float up_ncc = __shfl_up(L_ncc, 1);
-                    if (wc.lane > pos) { L_id = up_id; L_ncc = up_ncc; }
-                    if (wc.lane == pos) { L_id = nid; L_ncc = c.ncc; }
-                    ++L_n;
+                    {
+                        Cand src;  // loaded per trial: its registers are free again during the refinement
+                        load_cand(sp, wc, src);
+                        const bool gen_ok = generate_patch(prm, wc, s_scratch, src, ic, c, as_view, np >= prm.cap);
+                        ST_ADD(1, st_t)
+                        if (!gen_ok) { pend_failed |= pend; continue; }
+                    }
+                    ++n_cand;
+                    if (np >= prm.cap && c.ncc < worst_ncc) { ++n_pref; continue; }
+                    ++n_patch;
+                    const int pre_r = pre_process(prm, wc, s_scratch, c);
+                    ST_ADD(2, st_t)
+                    if (pre_r == -1) { ++n_f0; pend_failed |= pend; continue; }
+                    if (!pend && np + 1 < prm.cap) {
+                        // Room for this trial AND the next: the next one, whatever becomes of this one, still takes the np < cap branch above and
+                        // reads nothing of the live list before Optim::check -- it may be generated first and refined together with this one.
+                        pend_store(s_pend, wc, c, 0.0f);
+                        pend = true; pend_failed = false; pend_k3 = k3; pend_sz = min(prm.tau, c.nimg);
+                        continue;
+                    }
+                    if (pend) nfin = 2;
+                    else ++n_noroom;  // no guaranteed room for a partner
+                } else {
+                    pend_load(s_pend, wc, c, keep_w);  // nothing came to join the waiting candidate
+                    k3 = pend_k3;
+                    if (pend_failed) ++n_lost; else ++n_last;
                 }
-                ST_ADD(6, st_t)
+                bool paired = false;
+                if (nfin == 2) {
+                    // the waiting candidate is the earlier trial: it is finished first, this one takes its place in the stash meanwhile
+                    const bool fits = pend_sz <= 8 && min(prm.tau, c.nimg) <= 8;
+                    if (!fits) n_long += 2;
+                    else n_elig += 2;
+                    if constexpr (!SIMPLEX) {
+                        if (fits && a.pair) {
+                            refine_patch_pair(prm, wc, s_pend, c, k0, k1, k2, pend_k3, k3, keep_w);
+                            paired = true;
+                            n_pair += 2;
+                        }
+                    }
+                    Cand first;
+                    float first_w;
+                    pend_load(s_pend, wc, first, first_w);
+                    pend_store(s_pend, wc, c, keep_w);
+                    c = first; keep_w = first_w;
+                    const uint32_t t = k3; k3 = pend_k3; pend_k3 = t;
+                }
+                pend = false;
+                for (int fi = 0; fi < nfin; ++fi) {
+                    if (fi == 1) { pend_load(s_pend, wc, c, keep_w); k3 = pend_k3; }
+                    if (!paired) {
+                        if constexpr (SIMPLEX) (void)refine_patch_simplex(prm, wc, c, max_evals, xtol, &keep_w);
+                        else refine_patch(prm, wc, c, k0, k1, k2, k3, &keep_w);
+                    }
+                    ST_ADD(3, st_t)
+                    const int post_r = post_process(prm, wc, s_scratch, s_texs, tstride, c, keep_w, true);
+                    ST_ADD(4, st_t)
+                    if (post_r == -1) { ++n_f1; continue; }
+                    if (prm.depth >= 2 && prm.enable_check) {  // Optim::check, optim.cpp:292
+                        __syncthreads();
+                        if (wc.lane < MVS_CAPMAX) s_scratch[wc.lane] = L_id;  // publish the live list of this cell
+                        __syncthreads();
+                        #ifdef MVS_STAGE_TIMING
+                        const CheckCtx cx{a.staging, v, cell, L_n, s_scratch, st_acc};
+#else
+                        const CheckCtx cx{a.staging, v, cell, L_n, s_scratch, nullptr};
+#endif
+                        const int chk_r = check_patch<BIG>(prm, wc, cx, c, s_texs, a.error_flag, big_table);
+                        ST_ADD(5, st_t)
+                        if (!BIG && chk_r < 0) { gave_up = true; break; }  // the neighbourhood does not fit LDS: this cell goes to k_sweep_retry
+                        if (chk_r) { ++n_f1; continue; }
+                    }
+                    // staging slot for the accepted patch
+                    unsigned long long slot64 = 0;
+                    if (wc.lane == 0) slot64 = atomicAdd(a.stage_counter, 1ull);
+                    const int64_t slot = ((int64_t)rfl((int)(slot64 >> 32)) << 32) | (uint32_t)rfl((int)(slot64 & 0xffffffffull));
+                    if (slot >= a.staging_cap || ns >= a.maxstage) {
+                        if (wc.lane == 0) atomicOr(a.error_flag, 1);
+                        continue;
+                    }
+                    if (L_n == prm.cap) {  // removePatch(worst), propagate.cpp:198-201 (the list is as long as when the trial began: np)
+                        if (wc.lane == 0) {
+                            if (worst >= MVS_NEWBASE) a.staging[worst - MVS_NEWBASE].flags &= ~1;
+                            else a.kill[worst] = 1;
+                        }
+                        --L_n;
+                        ++n_rep;
+                    } else ++n_ins;
+                    store_cand(a.staging + slot, wc, c, 1 | (v << 8), cell);
+                    if (wc.lane == 0) a.job_stage[job * a.maxstage + ns] = (int32_t)slot;
+                    ++ns;
+                    // PatchManager::addPatch into this cell's own list if the patch lands here
+                    const bool lands = ballot(wc.lane < c.nimg && c.img == v && c.gy * gw + c.gx == cell) != 0ull;
+                    if (lands) {
+                        const int nid = MVS_NEWBASE + (int)slot;
+                        const int pos = __popcll(ballot(wc.lane < L_n && rank_before(L_ncc, L_id, c.ncc, nid)));
+                        const int up_id = __shfl_up(L_id, 1);
+                        const float up_ncc = __shfl_up(L_ncc, 1);
+                        if (wc.lane > pos) { L_id = up_id; L_ncc = up_ncc; }
+                        if (wc.lane == pos) { L_id = nid; L_ncc = c.ncc; }
+                        ++L_n;
+                    }
+                    ST_ADD(6, st_t)
+                }
+                if (gave_up) break;
             }
             if (gave_up) break;
         }
@@ -695,6 +754,8 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WaveCtx& wc, SweepAc
     {  // wave-uniform sums: scalar registers, the caller's SweepAcc being a local
         acc->cand += n_cand; acc->pref += n_pref; acc->patch += n_patch; acc->f0 += n_f0; acc->f1 += n_f1; acc->ins += n_ins; acc->rep += n_rep;
         acc->evals += wc.evals; acc->view_evals += wc.view_evals;
+        acc->pair[0] += n_pair; acc->pair[5] += n_elig;
+        acc->pair[1] += n_last; acc->pair[2] += n_noroom; acc->pair[3] += n_lost; acc->pair[4] += n_long;
 #ifdef MVS_STAGE_TIMING
         st_acc[0] = ST_NOW() - st_begin;
         for (int k = 0; k < 12; ++k) acc->stage[k] += st_acc[k];
@@ -725,7 +786,7 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WaveCtx& wc, SweepAc
 // takes of 64 / 16 / 4 / 1 jobs (of unlisted jobs, a lane per job testing for a source): 309 / 285 / 273.5 / 270.4 ms
 // (profiles/r09_resident_ab.txt).  The cursor's atomic is one per listed job: a round trip in ~430 us of work per cell.
 template <bool SIMPLEX>
-DEV void sweep_resident(const DParams& prm, const SweepArgs& a, int* s_scratch, float* s_texs, int max_evals, float xtol) {
+DEV void sweep_resident(const DParams& prm, const SweepArgs& a, int* s_scratch, int* s_pend, float* s_texs, int max_evals, float xtol) {
     WaveCtx wc = make_wave_ctx(prm);
     SweepAcc acc = sweep_acc_zero();
     for (unsigned step = 0; step < MVS_SWEEP_QUEUES; ++step) {
@@ -740,45 +801,49 @@ DEV void sweep_resident(const DParams& prm, const SweepArgs& a, int* s_scratch, 
             if (k >= ntake) break;  // drained: on to the next queue
             const int64_t job = a.job_list[qbegin + (int32_t)k];
             __syncthreads();  // the LDS scratch, frames, pivots and kept textures of the previous cell are dead
-            sweep_cell<false, SIMPLEX>(prm, a, wc, &acc, job, s_scratch, s_texs, nullptr, max_evals, xtol);
+            sweep_cell<false, SIMPLEX>(prm, a, wc, &acc, job, s_scratch, s_pend, s_texs, nullptr, max_evals, xtol);
         }
     }
     if (wc.lane == 0) sweep_acc_flush(a, acc, blockIdx.x & (MVS_COUNTER_SLOTS - 1));
 }
 __global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep(DParams prm, SweepArgs a) {
     __shared__ int s_scratch[192];
+    __shared__ __attribute__((aligned(16))) int s_pend[MVS_PEND_INTS];  // a waiting candidate, the working block of a pair (mvs_device.cuh)
     extern __shared__ float s_texs[];
-    sweep_resident<false>(prm, a, s_scratch, s_texs, 0, 0.0f);
+    sweep_resident<false>(prm, a, s_scratch, s_pend, s_texs, 0, 0.0f);
 }
 __global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep_simplex(DParams prm, SweepArgs a, int max_evals, float xtol) {
     __shared__ int s_scratch[192];
+    __shared__ __attribute__((aligned(16))) int s_pend[MVS_PEND_INTS];  // a waiting candidate, the working block of a pair (mvs_device.cuh)
     extern __shared__ float s_texs[];
-    sweep_resident<true>(prm, a, s_scratch, s_texs, max_evals, xtol);
+    sweep_resident<true>(prm, a, s_scratch, s_pend, s_texs, max_evals, xtol);
 }
 // the second tier: block b runs the cells retry_jobs[b], retry_jobs[b + gridDim.x], ... with big_tables slot b
 template <bool SIMPLEX>
-DEV void sweep_retry_cell(const DParams& prm, const SweepArgs& a, const int64_t job, int* s_scratch, float* s_texs, int* big_table, int max_evals, float xtol) {
+DEV void sweep_retry_cell(const DParams& prm, const SweepArgs& a, const int64_t job, int* s_scratch, int* s_pend, float* s_texs, int* big_table, int max_evals, float xtol) {
     WaveCtx wc = make_wave_ctx(prm);
     SweepAcc acc = sweep_acc_zero();
-    sweep_cell<true, SIMPLEX>(prm, a, wc, &acc, job, s_scratch, s_texs, big_table, max_evals, xtol);
+    sweep_cell<true, SIMPLEX>(prm, a, wc, &acc, job, s_scratch, s_pend, s_texs, big_table, max_evals, xtol);
     if (wc.lane == 0) sweep_acc_flush(a, acc, (unsigned)(job & (MVS_COUNTER_SLOTS - 1)));
 }
 __global__ __launch_bounds__(64, 1) void k_sweep_retry(DParams prm, SweepArgs a, int nretry) {
     __shared__ int s_scratch[192];
+    __shared__ __attribute__((aligned(16))) int s_pend[MVS_PEND_INTS];  // a waiting candidate, the working block of a pair (mvs_device.cuh)
     extern __shared__ float s_texs[];
     int* big_table = a.big_tables + (size_t)blockIdx.x * MVS_FILTER2_HASH_CAP;
     for (int k = blockIdx.x; k < nretry; k += gridDim.x) {
         __syncthreads();
-        sweep_retry_cell<false>(prm, a, (int64_t)a.retry_jobs[k], s_scratch, s_texs, big_table, 0, 0.0f);
+        sweep_retry_cell<false>(prm, a, (int64_t)a.retry_jobs[k], s_scratch, s_pend, s_texs, big_table, 0, 0.0f);
     }
 }
 __global__ __launch_bounds__(64, 1) void k_sweep_retry_simplex(DParams prm, SweepArgs a, int nretry, int max_evals, float xtol) {
     __shared__ int s_scratch[192];
+    __shared__ __attribute__((aligned(16))) int s_pend[MVS_PEND_INTS];  // a waiting candidate, the working block of a pair (mvs_device.cuh)
     extern __shared__ float s_texs[];
     int* big_table = a.big_tables + (size_t)blockIdx.x * MVS_FILTER2_HASH_CAP;
     for (int k = blockIdx.x; k < nretry; k += gridDim.x) {
         __syncthreads();
-        sweep_retry_cell<true>(prm, a, (int64_t)a.retry_jobs[k], s_scratch, s_texs, big_table, max_evals, xtol);
+        sweep_retry_cell<true>(prm, a, (int64_t)a.retry_jobs[k], s_scratch, s_pend, s_texs, big_table, max_evals, xtol);
     }
 }
 
@@ -1405,6 +1470,13 @@ size_t mvsk_sweep_lds_bytes(const DParams& prm) {
     const size_t need = texs > chk ? texs : chk;
     return need > (size_t)MVS_FRAME_LDS_BYTES ? need : (size_t)MVS_FRAME_LDS_BYTES;  // the frames + pivots of a refinement step
 }
+// A/B and test switch, read on every launch: MVS_SWEEP_PAIR=0 makes every trial refine alone (the result does not depend on it)
+static SweepArgs sweep_args_with_switches(const SweepArgs& a) {
+    SweepArgs b = a;
+    const char* p = getenv("MVS_SWEEP_PAIR");
+    b.pair = (p && atoi(p) == 0) ? 0 : 1;
+    return b;
+}
 void mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hipStream_t st) {
     const int64_t nloc = a.job_hi - a.job_lo;
     if (nloc <= 0) return;
@@ -1422,8 +1494,9 @@ void mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hip
         const long cap = atol(g);
         if (cap > 0) nblocks = std::min<int64_t>(nblocks, cap);
     }
-    if (rs.simplex) hipLaunchKernelGGL(k_sweep_simplex, dim3((unsigned)nblocks), dim3(64), lds, st, prm, a, rs.max_evals, rs.xtol);
-    else hipLaunchKernelGGL(k_sweep, dim3((unsigned)nblocks), dim3(64), lds, st, prm, a);
+    const SweepArgs b = sweep_args_with_switches(a);
+    if (rs.simplex) hipLaunchKernelGGL(k_sweep_simplex, dim3((unsigned)nblocks), dim3(64), lds, st, prm, b, rs.max_evals, rs.xtol);
+    else hipLaunchKernelGGL(k_sweep, dim3((unsigned)nblocks), dim3(64), lds, st, prm, b);
 }
 void mvsk_job_work(const DParams& prm, const SweepArgs& a, int mode, int shift, int32_t* work, hipStream_t st) {
     if (a.njobs > 0) hipLaunchKernelGGL(k_job_work, dim3(nblk(a.njobs, 256)), dim3(256), 0, st, prm, a, mode, shift, work);
@@ -1447,8 +1520,9 @@ void mvsk_job_cuts(const int32_t* scan, int64_t njobs, int n, int32_t* cuts, hip
 void mvsk_sweep_retry(const DParams& prm, const SweepArgs& a, int nretry, const RefineSel& rs, hipStream_t st) {
     if (nretry <= 0) return;
     const dim3 grid((unsigned)std::min(nretry, MVS_BIG_SLOTS));
-    if (rs.simplex) hipLaunchKernelGGL(k_sweep_retry_simplex, grid, dim3(64), mvsk_sweep_lds_bytes(prm), st, prm, a, nretry, rs.max_evals, rs.xtol);
-    else hipLaunchKernelGGL(k_sweep_retry, grid, dim3(64), mvsk_sweep_lds_bytes(prm), st, prm, a, nretry);
+    const SweepArgs b = sweep_args_with_switches(a);
+    if (rs.simplex) hipLaunchKernelGGL(k_sweep_retry_simplex, grid, dim3(64), mvsk_sweep_lds_bytes(prm), st, prm, b, nretry, rs.max_evals, rs.xtol);
+    else hipLaunchKernelGGL(k_sweep_retry, grid, dim3(64), mvsk_sweep_lds_bytes(prm), st, prm, b, nretry);
 }
 void mvsk_commit_count(const SweepArgs& a, int32_t* cnt, hipStream_t st) { hipLaunchKernelGGL(k_commit_count, dim3(nblk(a.njobs, 256)), dim3(256), 0, st, a, cnt); }
 void mvsk_commit_copy(const SweepArgs& a, const int32_t* base, DPatch* dst, int64_t dst_cap, int32_t* per_view, int keep_key, hipStream_t st) {

@@ -105,6 +105,11 @@ struct DCounters {
     // 0 whole wave, 1 generatePatch, 2 preProcess, 3 refinePatch, 4 postProcess, 5 check, 6 staging/insert, 7 prologue
     // 8 computeGain, 9 findNeighbors search, 10 compaction + sort, 11 filterQuad
     unsigned long long stage[16];
+    // the sweep's trials by how they were refined (mvs_engine_sweep_pairs): 0 as one of a pair (refine_patch_pair); alone because 1 no
+    // trial was left in the cell to join it, 2 the cell had no guaranteed room for a second one, 3 the trial that would have joined it
+    // failed generate / preProcess, 4 one of the two lists was longer than 8 views; 5 trials that can pair, whether or not they did
+    // (MVS_SWEEP_PAIR=0, the CONVERGED refiner) -- 1 + 2 + 3 + 4 + 5 = the trials refined
+    unsigned long long pair[6];
 };
 
 // Arguments of one sweep launch (one colour pass over the owned views).
@@ -131,6 +136,7 @@ struct SweepArgs {
     uint32_t* cursors;    // [MVS_SWEEP_QUEUES * MVS_SWEEP_CURSOR_STRIDE] the next list entry of every queue, zero before the launch
     const int32_t* job_list;     // the jobs of [job_lo, job_hi) that run a trial, queue after queue, ascending within a queue (k_job_list)
     const int32_t* list_bounds;  // [MVS_SWEEP_QUEUES + 1] queue q's jobs are job_list[list_bounds[q] .. list_bounds[q + 1])
+    int32_t pair;                // 1: consecutive trials of a cell are refined two at a time where they can be (set by the launcher: MVS_SWEEP_PAIR)
 };
 
 // What the launches of both seeding front ends share (seed_chain in mvs_seed_chain.cuh): the number of hypotheses asked for, the score the

@@ -30,7 +30,7 @@ EXPORTS = [
     "mvs_default_seed_random", "mvs_engine_seed_random", "mvs_engine_seed_random_hypotheses",
     "mvs_default_seed_points", "mvs_engine_seed_points", "mvs_engine_seed_points_hypotheses", "mvs_engine_depth_ranges",
     "mvs_default_maps_config", "mvs_engine_render_maps", "mvs_engine_fused_points",
-    "mvs_engine_tsdf", "mvs_engine_extract_mesh", "mvs_engine_mesh",
+    "mvs_engine_tsdf", "mvs_engine_extract_mesh", "mvs_engine_mesh", "mvs_engine_sweep_pairs",
 ]
 PLY_ASCII, PLY_BINARY_LE = 0, 1  # mvs_ply_format
 #: one vertex of the binary PLY file (mvs_engine_export_ply): 27 packed bytes
@@ -203,6 +203,8 @@ def load_library(cap32: bool = False, cap: int = 0):
         L.mvs_default_maps_config.restype = None
         L.mvs_engine_render_maps.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(ViewMaps), vp]
         L.mvs_engine_fused_points.argtypes = [vp, C.POINTER(MapsConfig), C.c_int64, vp, C.POINTER(C.c_int64)]
+    if hasattr(L, "mvs_engine_sweep_pairs"):
+        L.mvs_engine_sweep_pairs.argtypes = [vp, C.POINTER(C.c_int64)]
     if hasattr(L, "mvs_engine_tsdf"):
         L.mvs_engine_tsdf.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(Volume), vp, vp]
         L.mvs_engine_extract_mesh.argtypes = [vp, C.POINTER(Volume), vp, vp, C.c_int64, vp, C.c_int64, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -609,6 +611,14 @@ class Engine:
         return {"index_ms": t.index_ms, "sweep_ms": t.sweep_ms, "commit_ms": t.commit_ms, "sweep_launches": t.sweep_launches,
                 "exchange_ms": t.exchange_ms, "exchange_bytes": int(t.exchange_bytes), "check_retried_cells": int(t.check_retried_cells),
                 "sweep_jobs_listed": int(t.sweep_jobs_listed)}
+
+    #: mvs_engine_sweep_pairs: the sweep's trials by how they were refined, since the engine was created
+    SWEEP_PAIR_KEYS = ("paired", "alone_no_partner", "alone_no_room", "alone_partner_failed", "alone_long_list", "can_pair")
+
+    def sweep_pairs(self):
+        out = (C.c_int64 * 6)()
+        self._check(self.L.mvs_engine_sweep_pairs(self.h, out))
+        return dict(zip(self.SWEEP_PAIR_KEYS, (int(x) for x in out)))
 
     def depth_normal_map(self, view, kind):
         gw, gh = self.grid_dims(view)
