@@ -449,6 +449,58 @@ int mvs_engine_extract_mesh(mvs_engine* e, const mvs_volume* vol, const float* t
 int mvs_engine_mesh(mvs_engine* e, const mvs_maps_config* c, const mvs_volume* vol, int64_t cap_v, float* verts, int64_t cap_t, int32_t* tris,
                     int64_t* n_v, int64_t* n_t);
 
+/* Vertex normals and colours of a triangle mesh (no reference counterpart): what a viewer needs to show the mesh shaded and coloured.
+ * verts: n_v x 3 floats, tris: n_t x 3 int32 vertex ids -- those of mvs_engine_mesh, or any caller's.  Both calls are stateless and only
+ * read the engine; all pointers may be host or device memory (hipMemcpyDefault).
+ * mvs_engine_mesh_normals: area-weighted vertex normals as an ORDER-FREE INTEGER SUM: the result does not depend on the order in which the
+ *   hardware meets the triangles or in which they are listed, two calls give the same bytes, and a vertex of any valence costs what any
+ *   other costs per triangle (a fan of tens of thousands of triangles round one vertex included): no sorted float sum.  Needs a device
+ *   but no views, like mvs_engine_extract_mesh.
+ *     FACE VECTOR  e1 = v1 - v0, e2 = v2 - v0, f = e1 x e2 in fp32 without contraction, each component a*b - c*d as two products and one
+ *                  subtraction.  A triangle with a non-finite component in f contributes nothing.
+ *     SCALE        M = the largest |f_c| over all contributing triangles and components.  M == 0: every normal is (0, 0, 0).  Otherwise
+ *                  E = floor(log2 M) (the frexp exponent minus one) and S = 2^(30 - E), so that every |f_c S| < 2^31.
+ *     SUM          q = llrint((double)f_c * S), round-half-even (the product is exact); A_i = the sum of q over every corner occurrence of
+ *                  vertex i, three int64 per vertex, by 64-bit integer atomic adds: integer addition is associative.  A face whose
+ *                  components are all below 2^-31 M (an area 2^31 times smaller than the largest) rounds to zero and VANISHES from the sum.
+ *     NORMALISE    in fp64: a = (double)A_i, len = sqrt(ax*ax + ay*ay + az*az) evaluated left to right without contraction, n =
+ *                  (float)(a / len); len == 0 (a vertex no triangle uses, faces that cancel) gives (0, 0, 0).
+ *   LIMITS: n_v, n_t in 0 .. 2^30.  Device memory for the call: 48 bytes a vertex (position, three int64, normal) and 12 a triangle.
+ *   MVS_ERR_ARG, checked in this order before the handle is read: a negative count or a count over the limit; verts NULL with n_v > 0; tris
+ *   NULL with n_t > 0; normals NULL with n_v > 0; no engine.  Then, after one validating pass on the device: an index outside 0 .. n_v - 1
+ *   (nothing is written in that case).  MVS_ERR_HIP: an allocation or copy failed.  A refused call writes nothing.
+ * mvs_engine_mesh_colours: renders and computes agreement exactly as mvs_engine_tsdf does; a pixel is USABLE when it is valid and
+ *   popcount(agree) >= c->min_consistent.  For vertex X with normal n (normals == NULL or a zero normal: no facing test, weight 1) the views
+ *   v = 0 .. nviews-1 are walked in ascending order:
+ *     1. PROJECT  ic = Camera::project(v, (X, 1)) at level L; ic.z > 0; ic lies in mvs_engine_export_ply's sampling window, ic.x >= 0, ic.y
+ *                 >= 0, ic.x < W-1, ic.y < H-1; the view has no mask, or its level-L mask is foreground at the nearest pixel
+ *                 (floorf(ic.x + 0.5f), floorf(ic.y + 0.5f)) -- the render step's mask rule;
+ *     2. FACING   d = C_v - X, w = n.d / sqrtf(d.d) (IEEE division and square root); w >= min_cos;
+ *     3. SURFACE  at the nearest pixel.  Usable, with patch q: s = n_q.(X0_q - C_v) / (n_q.(X - C_v)), the tsdf step's expressions (a zero
+ *                 or non-finite denominator fails); the view is CONFIRMED when |s - 1| <= occl_tol and skipped otherwise: X is occluded
+ *                 behind that view's surface or floats in front of it.  Not usable: the view is UNCONFIRMED;
+ *     4. SAMPLE   the bilinear sample of the level-L pyramid at (ic.x, ic.y), mvs_engine_export_ply's expressions in its order;
+ *     5. per tier and channel: sw += w, sc += w * sample, and a count.
+ *   A NaN fails every comparison above.  The confirmed tier is chosen if its count is > 0, otherwise the unconfirmed tier if its count is
+ *   > 0: rgb_c = min(255, (int)floorf(sc / sw + 0.5f)) (0 where that is negative or a NaN, which takes a min_cos <= 0); used = count | 0x80
+ *   for the confirmed tier, count for the unconfirmed one (a count is at most 64).  With no view at all rgb = (128, 128, 128), the grey of
+ *   PatchManager::writePly for an empty list, and used = 0.  A pool without an alive patch has no surface to hold a vertex against: no
+ *   view counts then, every vertex is grey with used = 0 (nothing is rendered).  Device memory for the call: the maps' 17 bytes per pixel of all views and 16
+ *   per pixel of the largest, plus 28 bytes a vertex (position, normal, colour, used).
+ *   LIMITS: n_v in 0 .. 2^30.
+ *   MVS_ERR_ARG, checked in this order before the handle is read: the config checks of mvs_engine_fused_points; m NULL; occl_tol not finite
+ *   or <= 0; min_cos not finite or outside [-1, 1]; n_v negative or over the limit; verts or rgb NULL with n_v > 0; no engine; then
+ *   min_consistent > nviews - 1.  MVS_ERR_STATE: views not set, or a pass waiting for its commit.  MVS_ERR_HIP: an allocation or copy
+ *   failed.  A refused call writes nothing. */
+typedef struct mvs_mesh_colouring {
+    float occl_tol;  /* surface test: |s - 1| <= occl_tol confirms the view; > 0, finite */
+    float min_cos;   /* facing: n . ray >= min_cos; in [-1, 1] */
+} mvs_mesh_colouring; /* 8 bytes */
+void mvs_default_mesh_colouring(mvs_mesh_colouring* m); /* occl_tol 0.01, min_cos 0.1 */
+int mvs_engine_mesh_normals(mvs_engine* e, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, float* normals /* [n_v][3] */);
+int mvs_engine_mesh_colours(mvs_engine* e, const mvs_maps_config* c, const mvs_mesh_colouring* m, int64_t n_v, const float* verts,
+                            const float* normals /* or NULL */, uint8_t* rgb /* [n_v][3] */, uint8_t* used /* [n_v] or NULL */);
+
 /* Propagate::run(iter), propagate.cpp:28-64: two colour passes, each = index build + sweep + commit */
 int mvs_engine_propagate(mvs_engine* e, int iter, mvs_counters* out);
 

@@ -1696,13 +1696,11 @@ struct MeshVolume {
     DevBuf<int32_t> count;
 };
 
-// the volume of the engine's maps into d (the stream is idle on return)
-int mesh_tsdf(mvs_engine* e, const mvs_maps_config* c, const MeshVol& mv, MeshVolume& d) {
+// the maps and their usability into b: b.ids and, a byte per pixel of all views, b.flag8 (launched, not waited for)
+int render_usable(mvs_engine* e, const mvs_maps_config* c, MapsBufs& b) {
     hipStream_t st = e->stream;
-    const int64_t N = mesh_npoints(mv);
-    MapsBufs b;
     if (int r = render_all(e, c, b)) return r;
-    if (b.agree.ensure(b.max_pix) || b.flag8.ensure(b.total_pix) || d.tsdf.ensure(N) || d.count.ensure(N)) return MVS_ERR_HIP;
+    if (b.agree.ensure(b.max_pix) || b.flag8.ensure(b.total_pix)) return MVS_ERR_HIP;
     const DParams p = current_params(e);
     // usability: fused_points' counting pass without dedupe, kept as a byte per pixel of all views (the views follow each other in stream order)
     for (int v = 0; v < e->cfg.nviews; ++v) {
@@ -1710,6 +1708,17 @@ int mesh_tsdf(mvs_engine* e, const mvs_maps_config* c, const MeshVol& mv, MeshVo
         mvsk_maps_agree(p, b.args, v, npix, b.ids.p, b.pts.p, b.agree.p, nullptr, nullptr, nullptr, st);
         mvsk_maps_flag(npix, v, b.ids.p + pix0, b.agree.p, c->min_consistent, 0, b.flag.p, b.flag8.p + pix0, st);
     }
+    return MVS_OK;
+}
+
+// the volume of the engine's maps into d (the stream is idle on return)
+int mesh_tsdf(mvs_engine* e, const mvs_maps_config* c, const MeshVol& mv, MeshVolume& d) {
+    hipStream_t st = e->stream;
+    const int64_t N = mesh_npoints(mv);
+    MapsBufs b;
+    if (int r = render_usable(e, c, b)) return r;
+    if (d.tsdf.ensure(N) || d.count.ensure(N)) return MVS_ERR_HIP;
+    const DParams p = current_params(e);
     mvsk_mesh_tsdf(p, b.args, mv, b.ids.p, b.flag8.p, d.tsdf.p, d.count.p, st);
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
@@ -1808,6 +1817,91 @@ int mvs_engine_mesh(mvs_engine* e, const mvs_maps_config* c, const mvs_volume* v
     MeshVolume d;
     if (int r = mesh_tsdf(e, c, mv, d)) return r;
     return mesh_extract(e, mv, d.tsdf.p, d.count.p, cap_v, verts, cap_t, tris, n_v, n_t, who);
+}
+
+// Vertex normals and colours of a mesh (mvs_mesh_attr.hip; the definitions are in mvskit_engine.h).  Stateless like the mesh calls: the
+// caller's arrays come into buffers of the call from wherever they lie, the results leave from there.
+static_assert(sizeof(mvs_mesh_colouring) == 8, "mvs_mesh_colouring is 8 bytes");
+#define MESH_ATTR_MAX ((int64_t)1 << 30)
+
+int mvs_engine_mesh_normals(mvs_engine* e, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, float* normals) {
+    const char* who = "mvs_engine_mesh_normals";
+    if (n_v < 0 || n_t < 0 || n_v > MESH_ATTR_MAX || n_t > MESH_ATTR_MAX) { g_err = std::string(who) + ": a count negative or over 2^30"; return MVS_ERR_ARG; }
+    if (!verts && n_v > 0) { g_err = std::string(who) + ": verts null"; return MVS_ERR_ARG; }
+    if (!tris && n_t > 0) { g_err = std::string(who) + ": tris null"; return MVS_ERR_ARG; }
+    if (!normals && n_v > 0) { g_err = std::string(who) + ": normals null"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
+    if (n_v == 0 && n_t == 0) return MVS_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:mesh_normals");
+    hipStream_t st = e->stream;
+    DevBuf<float> d_verts, d_normals;
+    DevBuf<int32_t> d_tris;
+    DevBuf<long long> acc;
+    DevBuf<uint32_t> words;  // [0] the bits of the largest component, [1] an index out of range
+    if (d_verts.ensure(3 * n_v) || d_tris.ensure(3 * n_t) || words.ensure(2)) return MVS_ERR_HIP;
+    if (n_v > 0) HIPCHK(hipMemcpyAsync(d_verts.p, verts, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
+    if (n_t > 0) HIPCHK(hipMemcpyAsync(d_tris.p, tris, (size_t)n_t * 3 * sizeof(int32_t), hipMemcpyDefault, st));
+    HIPCHK(hipMemsetAsync(words.p, 0, 2 * sizeof(uint32_t), st));
+    mvsk_mesh_normals_scan(n_v, d_verts.p, n_t, d_tris.p, words.p, words.p + 1, st);
+    uint32_t bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, words.p + 1, sizeof bad, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    if (bad) { g_err = std::string(who) + ": a vertex index outside 0 .. n_v - 1"; return MVS_ERR_ARG; }
+    if (n_v == 0) return MVS_OK;
+    if (acc.ensure(3 * n_v) || d_normals.ensure(3 * n_v)) return MVS_ERR_HIP;
+    HIPCHK(hipMemsetAsync(acc.p, 0, (size_t)n_v * 3 * sizeof(long long), st));
+    mvsk_mesh_normals_accum(d_verts.p, n_t, d_tris.p, words.p, acc.p, st);
+    mvsk_mesh_normals_finish(n_v, acc.p, d_normals.p, st);
+    HIPCHK(hipMemcpyAsync(normals, d_normals.p, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return MVS_OK;
+}
+
+void mvs_default_mesh_colouring(mvs_mesh_colouring* m) {
+    if (!m) return;
+    m->occl_tol = 0.01f; m->min_cos = 0.1f;
+}
+
+int mvs_engine_mesh_colours(mvs_engine* e, const mvs_maps_config* c, const mvs_mesh_colouring* m, int64_t n_v, const float* verts, const float* normals,
+                            uint8_t* rgb, uint8_t* used) {
+    const char* who = "mvs_engine_mesh_colours";
+    if (int r = maps_args(c, who)) return r;
+    if (!m) { g_err = std::string(who) + ": colouring null"; return MVS_ERR_ARG; }
+    if (!std::isfinite(m->occl_tol) || !(m->occl_tol > 0.0f)) { g_err = std::string(who) + ": occl_tol not finite or <= 0"; return MVS_ERR_ARG; }
+    if (!std::isfinite(m->min_cos) || !(m->min_cos >= -1.0f && m->min_cos <= 1.0f)) { g_err = std::string(who) + ": min_cos not finite or outside [-1, 1]"; return MVS_ERR_ARG; }
+    if (n_v < 0 || n_v > MESH_ATTR_MAX) { g_err = std::string(who) + ": n_v negative or over 2^30"; return MVS_ERR_ARG; }
+    if ((!verts || !rgb) && n_v > 0) { g_err = std::string(who) + ": verts or rgb null"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
+    if (int r = maps_state(e, c, who)) return r;
+    if (n_v == 0) return MVS_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:mesh_colours");
+    hipStream_t st = e->stream;
+    DevBuf<float> d_verts, d_normals;
+    DevBuf<uint8_t> d_rgb, d_used;
+    if (d_rgb.ensure(3 * n_v) || d_used.ensure(n_v)) return MVS_ERR_HIP;
+    int64_t alive = 0;
+    if (int r = mvs_engine_num_patches(e, &alive)) return r;
+    MapsBufs b;
+    if (alive == 0) {  // no surface to hold a vertex against: no view counts
+        HIPCHK(hipMemsetAsync(d_rgb.p, 128, (size_t)n_v * 3, st));
+        HIPCHK(hipMemsetAsync(d_used.p, 0, (size_t)n_v, st));
+    } else {
+        if (int r = render_usable(e, c, b)) return r;
+        if (d_verts.ensure(3 * n_v) || (normals && d_normals.ensure(3 * n_v))) return MVS_ERR_HIP;
+        HIPCHK(hipMemcpyAsync(d_verts.p, verts, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
+        if (normals) HIPCHK(hipMemcpyAsync(d_normals.p, normals, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
+        mvsk_mesh_colours(current_params(e), b.args, MeshColourArgs{m->occl_tol, m->min_cos}, n_v, d_verts.p, normals ? d_normals.p : nullptr, b.ids.p,
+                          b.flag8.p, d_rgb.p, d_used.p, st);
+    }
+    HIPCHK(hipMemcpyAsync(rgb, d_rgb.p, (size_t)n_v * 3, hipMemcpyDefault, st));
+    if (used) HIPCHK(hipMemcpyAsync(used, d_used.p, (size_t)n_v, hipMemcpyDefault, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return MVS_OK;
 }
 
 // A pass that failed (staging or Optim::check capacity in this rank's shard, a HIP error) leaves its status in the engine:

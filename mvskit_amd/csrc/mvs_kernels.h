@@ -132,3 +132,16 @@ void mvsk_mesh_verts(const MeshVol& vol, const float* tsdf, const uint8_t* mask,
 void mvsk_mesh_tcount(const MeshVol& vol, const uint8_t* state, int32_t* cnt, hipStream_t st);
 void mvsk_mesh_tris(const MeshVol& vol, const uint8_t* state, const uint8_t* mask, const int32_t* vbase, const int64_t* tbase, int32_t* tris,
                     int64_t cap_t, hipStream_t st);
+// mvs_engine_mesh_normals / mvs_engine_mesh_colours (mvs_mesh_attr.hip): vertex normals as an order-free integer sum, vertex colours
+// blended from the views that see the vertex.  verts: 3 floats a vertex, tris: 3 ids a triangle.
+// every triangle's ids checked against n_v (*bad != 0 when one lies outside; such a triangle reads no vertex) and *mbits = the bits of
+// the largest |component| of the finite face vectors; both words zero before the launch
+void mvsk_mesh_normals_scan(int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, uint32_t* mbits, uint32_t* bad, hipStream_t st);
+// acc[3 i ..] += the face vectors around vertex i, scaled by the power of two that *mbits gives and rounded to integers (acc zero before
+// the launch, every id valid); then normals[3 i ..] = acc[3 i ..] normalised in fp64
+void mvsk_mesh_normals_accum(const float* verts, int64_t n_t, const int32_t* tris, const uint32_t* mbits, long long* acc, hipStream_t st);
+void mvsk_mesh_normals_finish(int64_t n_v, const long long* acc, float* normals, hipStream_t st);
+// MeshColourArgs: mvs_mesh_colouring by value.  ids / usable as for mvsk_mesh_tsdf; normals and used may be null; rgb: 3 bytes a vertex
+struct MeshColourArgs { float occl_tol, min_cos; };
+void mvsk_mesh_colours(const DParams& prm, const MapsArgs& a, const MeshColourArgs& m, int64_t n_v, const float* verts, const float* normals,
+                       const int32_t* ids, const uint8_t* usable, uint8_t* rgb, uint8_t* used, hipStream_t st);

@@ -31,6 +31,7 @@ EXPORTS = [
     "mvs_default_seed_points", "mvs_engine_seed_points", "mvs_engine_seed_points_hypotheses", "mvs_engine_depth_ranges",
     "mvs_default_maps_config", "mvs_engine_render_maps", "mvs_engine_fused_points",
     "mvs_engine_tsdf", "mvs_engine_extract_mesh", "mvs_engine_mesh", "mvs_engine_sweep_pairs",
+    "mvs_default_mesh_colouring", "mvs_engine_mesh_normals", "mvs_engine_mesh_colours",
 ]
 PLY_ASCII, PLY_BINARY_LE = 0, 1  # mvs_ply_format
 #: one vertex of the binary PLY file (mvs_engine_export_ply): 27 packed bytes
@@ -95,6 +96,11 @@ class Volume(C.Structure):
     def shape(self):
         """(nz, ny, nx): the shape of the volume's arrays"""
         return self.dims[2], self.dims[1], self.dims[0]
+
+
+class MeshColouring(C.Structure):
+    """mvs_mesh_colouring: the two thresholds of mvs_engine_mesh_colours, 8 bytes."""
+    _fields_ = [("occl_tol", C.c_float), ("min_cos", C.c_float)]
 
 
 class Counters(C.Structure):
@@ -209,6 +215,11 @@ def load_library(cap32: bool = False, cap: int = 0):
         L.mvs_engine_tsdf.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(Volume), vp, vp]
         L.mvs_engine_extract_mesh.argtypes = [vp, C.POINTER(Volume), vp, vp, C.c_int64, vp, C.c_int64, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.mvs_engine_mesh.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(Volume), C.c_int64, vp, C.c_int64, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    if hasattr(L, "mvs_engine_mesh_normals"):
+        L.mvs_default_mesh_colouring.argtypes = [C.POINTER(MeshColouring)]
+        L.mvs_default_mesh_colouring.restype = None
+        L.mvs_engine_mesh_normals.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp]
+        L.mvs_engine_mesh_colours.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(MeshColouring), C.c_int64, vp, vp, vp, vp]
     _libs[LIB_PATH] = L
     return L
 
@@ -543,6 +554,44 @@ class Engine:
         c = self._maps_config(source, min_consistent, depth_tol, normal_cos, 0)
         return self._mesh(lambda *a: self.L.mvs_engine_mesh(self.h, C.byref(c), C.byref(volume), *a), int(cap_v), int(cap_t))
 
+    # ---- vertex normals and colours of a mesh
+    def mesh_normals(self, verts, tris):
+        """Area-weighted vertex normals of the mesh verts [n, 3], tris [m, 3] (include/mvskit_engine.h, mvs_engine_mesh_normals): float32
+        [n, 3], unit length, zero for a vertex that no triangle with an area uses.  An order-free integer sum: the same bytes whatever
+        order the triangles are listed in.  Needs no views."""
+        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        out = np.zeros((verts.shape[0], 3), np.float32)
+        self._check(self.L.mvs_engine_mesh_normals(self.h, verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), _ptr(out)))
+        return out
+
+    def mesh_colours(self, verts, normals=None, source=0, min_consistent=1, depth_tol=0.01, normal_cos=0.9, occl_tol=0.01, min_cos=0.1):
+        """A colour per vertex from the views that see it (include/mvskit_engine.h, mvs_engine_mesh_colours): (rgb [n, 3] uint8, used [n]
+        uint8).  A view counts when the vertex projects into its sampling window (and foreground), faces it (normal . ray >= min_cos; no
+        test without normals or for a zero normal) and is not contradicted by the view's dense map (a usable pixel whose plane lies more
+        than occl_tol, relative, before or behind the vertex).  Views whose map confirms the vertex are blended if there are any (used =
+        their number | 0x80), otherwise the views whose map says nothing there (used = their number); grey and 0 with no view at all.
+        Reads engine state only."""
+        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        if normals is not None:
+            normals = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+            if normals.shape != verts.shape:
+                raise ValueError("mesh_colours: one normal per vertex")
+        c = self._maps_config(source, min_consistent, depth_tol, normal_cos, 0)
+        m = MeshColouring(float(occl_tol), float(min_cos))
+        rgb, used = np.zeros((verts.shape[0], 3), np.uint8), np.zeros(verts.shape[0], np.uint8)
+        self._check(self.L.mvs_engine_mesh_colours(self.h, C.byref(c), C.byref(m), verts.shape[0], _ptr(verts), _ptr(normals), _ptr(rgb), _ptr(used)))
+        return rgb, used
+
+    def coloured_mesh(self, volume, source=0, min_consistent=1, depth_tol=0.01, normal_cos=0.9, occl_tol=0.01, min_cos=0.1, cap_v=0, cap_t=0):
+        """mesh, mesh_normals and mesh_colours chained: (verts, tris, normals, rgb, used), what write_mesh_ply takes.  Every step renders
+        the maps it needs itself."""
+        kw = dict(source=source, min_consistent=min_consistent, depth_tol=depth_tol, normal_cos=normal_cos)
+        verts, tris = self.mesh(volume, cap_v=cap_v, cap_t=cap_t, **kw)
+        normals = self.mesh_normals(verts, tris)
+        rgb, used = self.mesh_colours(verts, normals, occl_tol=occl_tol, min_cos=min_cos, **kw)
+        return verts, tris, normals, rgb, used
+
     # ---- the hot path
     def propagate(self, it):
         c = Counters()
@@ -666,19 +715,38 @@ def volume_around(xyz, voxel, trunc_voxels=4, pad_voxels=2, min_count=1):
     return make_volume(lo, voxel, dims, trunc_voxels * voxel, min_count)
 
 
-def write_mesh_ply(path, verts, tris, binary=True):
-    """verts [n, 3] and tris [m, 3] as a PLY file: element vertex (float x, y, z) and element face (list uchar int vertex_indices)"""
+def write_mesh_ply(path, verts, tris, binary=True, normals=None, colours=None):
+    """verts [n, 3] and tris [m, 3] as a PLY file: element vertex (float x, y, z; with normals [n, 3] float nx, ny, nz behind them; with
+    colours [n, 3] uchar red, green, blue last) and element face (list uchar int vertex_indices)"""
     verts = np.ascontiguousarray(verts, dtype="<f4").reshape(-1, 3)
     tris = np.ascontiguousarray(tris, dtype="<i4").reshape(-1, 3)
-    head = (f"ply\nformat {'binary_little_endian' if binary else 'ascii'} 1.0\nelement vertex {verts.shape[0]}\nproperty float x\n"
-            f"property float y\nproperty float z\nelement face {tris.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
+    fields, props = [("xyz", "<f4", (3,))], "property float x\nproperty float y\nproperty float z\n"
+    cols = [verts]
+    if normals is not None:
+        normals = np.ascontiguousarray(normals, dtype="<f4").reshape(-1, 3)
+        fields.append(("normal", "<f4", (3,)))
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
+        cols.append(normals)
+    if colours is not None:
+        colours = np.ascontiguousarray(colours, dtype="u1").reshape(-1, 3)
+        fields.append(("rgb", "u1", (3,)))
+        props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+        cols.append(colours)
+    if any(c.shape != verts.shape for c in cols):
+        raise ValueError("write_mesh_ply: normals and colours need one row per vertex")
+    head = (f"ply\nformat {'binary_little_endian' if binary else 'ascii'} 1.0\nelement vertex {verts.shape[0]}\n{props}"
+            f"element face {tris.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
     with open(path, "wb") as f:
         f.write(head.encode("ascii"))
         if binary:
             faces = np.zeros(tris.shape[0], dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
             faces["n"], faces["v"] = 3, tris
-            f.write(verts.tobytes())
+            rows = np.zeros(verts.shape[0], dtype=np.dtype(fields))  # packed: 12, 24, 15 or 27 bytes a vertex
+            for (name, _, _), c in zip(fields, cols):
+                rows[name] = c
+            f.write(rows.tobytes())
             f.write(faces.tobytes())
         else:
-            f.write("".join(f"{x:.9g} {y:.9g} {z:.9g}\n" for x, y, z in verts.tolist()).encode("ascii"))
+            lists = [c.tolist() for c in cols]
+            f.write("".join(" ".join(f"{x:.9g}" if isinstance(x, float) else str(x) for c in row for x in c) + "\n" for row in zip(*lists)).encode("ascii"))
             f.write("".join(f"3 {a} {b} {c}\n" for a, b, c in tris.tolist()).encode("ascii"))

@@ -1,0 +1,236 @@
+"""mvs_engine_mesh_colours on the GPU against the float64 reading of tests/mesh_attr_reading.py (colours64, on _render64 / _agree64 of
+tests/test_gpu_maps.py with their `unsure` masks), on the four plane scenes, pools and the lattice of tests/test_gpu_mesh_tsdf.py, with
+occl_tol = DEPTH_TOL.
+
+Every case colours two vertex sets.  (a) the mesh of Engine.mesh with the normals of Engine.mesh_normals.  (b) a caller's set built to
+reach every branch: a jittered 24 x 16 grid on the plane z = 0 that covers the views' images and a margin around them, with the normal
+(0, 0, 1); its copies at z = +0.2 and -0.2 (5 % of the depth of 4), which no view may confirm; a copy with the normal (0, 0, -1), which
+must come out grey with used == 0; a copy with zero normals; a row of vertices that project outside every image; in the masked case
+the surface points behind pixels of view 1's band, for which view 1 takes no part; and the whole set once more with normals = None.
+
+A (vertex, view) pair is unsure when its projection lies within 1e-3 pixel of a nearest-pixel rounding boundary across which the mask,
+the usability or the patch differs, or of the window's edge; when |s - 1| lies within 1e-5 of occl_tol or w within 1e-5 of min_cos; or
+when the pixel's usability rests on an unsure agree pair.  A vertex with such a pair is left out, and every case asserts that these are
+fewer than 5 % of the vertices that any view reaches (the figures are in DESIGN.md, f-8).  On the others `used` is exact and
+|rgb - mean64| <= 0.51 per channel: half a unit of rounding plus 0.01 -- the fp32 chain of about 20 operations on values up to 255 errs
+by under 1e-3."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import mesh_attr_reading as ar
+from mvskit_amd import engine, synth
+from test_gpu_maps import DEPTH_TOL, NORMAL_COS, _agree64, _cams, _engine, _render64
+from test_gpu_mesh_tsdf import PLAIN, lattice, many_view_seeds
+from test_gpu_seed_random import _mask_at, _scene
+
+pytestmark = pytest.mark.gpu
+MVS_ERR_STATE = -2
+MIN_COS = 0.1
+KW = dict(min_consistent=1, depth_tol=DEPTH_TOL, normal_cos=NORMAL_COS)
+CKW = dict(occl_tol=DEPTH_TOL, min_cos=MIN_COS, **KW)
+GREY = np.array([128, 128, 128], np.uint8)
+
+
+def caller_set(sc, level, band_view=None, band=None):
+    """-> (verts [n, 3] float32, normals [n, 3] float32, {name: slice})"""
+    foot = 4.0 / (765.702941895 * sc.W / 640.0 / 2 ** level)
+    W, H = sc.W >> level, sc.H >> level
+    rng = np.random.default_rng(17)
+    gx, gy = np.meshgrid(np.linspace(-0.56, 0.56, 24) * W * foot, np.linspace(-0.56, 0.56, 16) * H * foot)
+    step = 1.12 * W * foot / 23
+    xy = np.stack([gx.ravel(), gy.ravel()], 1) + rng.uniform(-0.3, 0.3, (gx.size, 2)) * step
+    n = xy.shape[0]
+    up, zero = np.tile([0.0, 0.0, 1.0], (n, 1)), np.zeros((n, 3))
+
+    def at(z):
+        return np.concatenate([xy, np.full((n, 1), z)], 1)
+
+    parts = [("plane", at(0.0), up), ("above", at(0.2), up), ("below", at(-0.2), up), ("facing_away", at(0.0), -up), ("zero_normal", at(0.0), zero),
+             ("outside", at(0.0)[:24] + [60.0, 0.0, 0.0], up[:24])]
+    if band is not None:
+        pts = sc.points[band_view][4:sc.H - 4:3, band][:, ::2].reshape(-1, 3).astype(np.float64)
+        pts = pts[np.isfinite(pts).all(1)]
+        parts.append(("band", pts, np.tile([0.0, 0.0, 1.0], (pts.shape[0], 1))))
+    groups, pos = {}, 0
+    for name, v, _ in parts:
+        groups[name] = slice(pos, pos + v.shape[0])
+        pos += v.shape[0]
+    return (np.concatenate([p[1] for p in parts]).astype(np.float32), np.concatenate([p[2] for p in parts]).astype(np.float32), groups)
+
+
+def maps_reading(pat, ids, cams):
+    X = [_render64(pat, ids[v], cams[v])[1] for v in range(len(cams))]
+    bits, unsure = zip(*[_agree64(pat, ids, X, cams, v, DEPTH_TOL, NORMAL_COS) for v in range(len(cams))])
+    return bits, unsure
+
+
+def check_colours(name, r, rgb, used, cap=0.05):
+    """the engine's colours against the reading r -> the largest colour error"""
+    sure, reached = r["sure"], r["reached"]
+    left_out = int((~sure & reached).sum())
+    print(f"colours[{name}]: {int(reached.sum())} of {reached.size} vertices reached, {left_out} left out "
+          f"({100.0 * left_out / max(int(reached.sum()), 1):.2f} %)")
+    assert reached.sum() > 0 and left_out < cap * reached.sum(), "the float64 reading leaves out too many vertices"
+    assert rgb.dtype == np.uint8 and used.dtype == np.uint8 and rgb.shape == (sure.size, 3) and used.shape == (sure.size,)
+    wrong = sure & (used != r["used"])
+    assert not wrong.any(), f"used differs from the reading at {int(wrong.sum())} vertices outside the margins, first {np.nonzero(wrong)[0][:5]}"
+    assert (used[~reached & sure] == 0).all()
+    none = sure & (r["used"] == 0)
+    assert (rgb[none] == GREY).all()
+    have = sure & (r["used"] > 0)
+    worst = float(np.abs(rgb[have].astype(np.float64) - r["mean"][have]).max()) if have.any() else 0.0
+    print(f"colours[{name}]: {int(have.sum())} coloured, {int((used[sure] >= 0x80).sum())} confirmed, {int(((used[sure] > 0) & (used[sure] < 0x80)).sum())} "
+          f"unconfirmed, {int(none.sum())} with used == 0; colour error at most {worst:.5f}")
+    assert worst <= 0.51
+    return worst
+
+
+def _case(sc, ekw, masks=None, list_cap=None, seeds=None, band=None):
+    level, csize = ekw["level"], ekw["csize"]
+    sizes = [(sc.W, sc.H)] * sc.nviews
+    seeds = synth.make_seeds(sc, level, csize, stride=1) if seeds is None else seeds
+    e = _engine(sc, ekw, masks, sizes, list_cap, seeds)
+    alive = e.patches()
+    pat = np.zeros(int(alive["id"].max()) + 1, alive.dtype)
+    pat[alive["id"]] = alive
+    thr = e.thresholds()
+    cams = _cams(sc, level, sizes)
+    ids = [m["ids"] for m in e.render_maps(depth_tol=DEPTH_TOL, normal_cos=NORMAL_COS)]
+    bits, unsure = maps_reading(pat, ids, cams)
+    images = [e.pyramid(v, level) for v in range(sc.nviews)]
+    lmasks = None if masks is None else [None if m is None else _mask_at(m, sizes[v], level) for v, m in enumerate(masks)]
+    vol = lattice(sc, level)
+
+    def reading(verts, normals):
+        return ar.colours64(pat, ids, bits, unsure, cams, images, lmasks, verts, normals, 1, DEPTH_TOL, MIN_COS)
+
+    # (a) the engine's own mesh
+    verts, tris = e.mesh(vol, **KW)
+    normals = e.mesh_normals(verts, tris)
+    assert normals.tobytes() == ar.normals_exact(verts, tris).tobytes()
+    rgb, used = e.mesh_colours(verts, normals, **CKW)
+    again = e.mesh_colours(verts, normals, **CKW)
+    assert again[0].tobytes() == rgb.tobytes() and again[1].tobytes() == used.tobytes(), "two calls give different bytes"
+    assert verts.shape[0] > 256
+    check_colours("mesh", reading(verts, normals), rgb, used)
+    assert (used >= 0x80).sum() > 0.5 * used.size, "most vertices of the mesh lie on the surface the views agree on"
+    chained = e.coloured_mesh(vol, **CKW)
+    assert [a.tobytes() for a in chained] == [a.tobytes() for a in (verts, tris, normals, rgb, used)], "coloured_mesh differs from the three calls chained"
+
+    # (b) the caller's set
+    bverts, bnormals, groups = caller_set(sc, level, 1 if band else None, band)
+    brgb, bused = e.mesh_colours(bverts, bnormals, **CKW)
+    r = reading(bverts, bnormals)
+    check_colours("caller", r, brgb, bused)
+    sure, n = r["sure"], bused.size
+    for g in ("above", "below"):
+        assert (bused[groups[g]] < 0x80).all(), f"a vertex 5 % of the depth {g} the plane was confirmed"
+    assert (bused[groups["facing_away"]] == 0).all() and (brgb[groups["facing_away"]] == GREY).all()
+    assert (bused[groups["outside"]] == 0).all() and (brgb[groups["outside"]] == GREY).all()
+    assert (bused[groups["zero_normal"]] >= 0x80).any()
+    confirmed = sure & (bused >= 0x80)
+    assert confirmed.sum() >= 0.10 * n and (sure & (bused > 0) & (bused < 0x80)).sum() >= 1 and (sure & (bused == 0)).sum() >= 0.10 * n
+    assert np.unique(brgb[confirmed], axis=0).shape[0] > 1, "every confirmed vertex has the same colour"
+    if band:
+        b = groups["band"]
+        assert (r["used"][b][sure[b]] & 0x7f).max() <= sc.nviews - 1 and (bused[b][sure[b]] & 0x7f).max() <= sc.nviews - 1
+        assert (bused[b] >= 0x80).any()
+    # without normals: no facing test, weight 1 -- the copy that faces away is coloured like the plane's
+    nrgb, nused = e.mesh_colours(bverts, None, **CKW)
+    check_colours("caller, normals = None", reading(bverts, None), nrgb, nused)
+    assert nused[groups["facing_away"]].tobytes() == nused[groups["plane"]].tobytes() and (nused[groups["plane"]] >= 0x80).any()
+    assert nrgb[groups["zero_normal"]].tobytes() == brgb[groups["zero_normal"]].tobytes()
+
+    # nothing of the engine's state moved
+    assert e.patches().tobytes() == alive.tobytes() and e.thresholds() == thr
+    t = _engine(sc, ekw, masks, sizes, list_cap, seeds)
+    assert t.patches().tobytes() == alive.tobytes()
+    assert e.propagate(1) == t.propagate(1)
+    assert e.patches().tobytes() == t.patches().tobytes()
+    t.close()
+    e.close()
+
+
+def test_plain():
+    """3 views of 96 x 64 on the textured plane, csize 2"""
+    _case(_scene(3, 96, 64, 30.0), PLAIN)
+
+
+def test_ragged_grid_with_a_mask_band():
+    """4 views of 97 x 63, csize 3, view 1 with a background band: it takes no part for the vertices behind the band"""
+    sc = _scene(4, 97, 63, 30.0)
+    band = np.full((sc.H, sc.W), 255, np.uint8)
+    band[:, 40:52] = 0
+    _case(sc, dict(level=0, csize=3, minImageNum=2, depth=0, max_patches=4 * 33 * 21 * 2 * 9), masks=[None, band, None, None], band=slice(41, 51))
+
+
+def test_level_one():
+    """3 views of 192 x 128 at level 1: P_L, the level's image size and pyramid"""
+    _case(_scene(3, 192, 128, 30.0), dict(level=1, csize=2, minImageNum=2, depth=0))
+
+
+def test_many_views():
+    """40 views of 48 x 32 with the 64-view library (192-byte records), on an arc of 0.25 degrees"""
+    sc = _scene(40, 48, 32, 0.25)
+    _case(sc, dict(level=0, csize=2, minImageNum=3, depth=0), list_cap=64, seeds=many_view_seeds(sc))
+
+
+def test_empty_pool_and_states():
+    """an empty pool gives grey and used == 0 everywhere; mesh_colours asks for views and an idle engine, mesh_normals for neither"""
+    sc = _scene(3, 96, 64, 30.0)
+    e = _engine(sc, PLAIN, None, None, None, None)
+    vol = lattice(sc, 0)
+    bverts, bnormals, _ = caller_set(sc, 0)
+    for nrm in (bnormals, None):
+        rgb, used = e.mesh_colours(bverts, nrm, **CKW)
+        assert (rgb == GREY).all() and (used == 0).all()
+    out = e.coloured_mesh(vol, **CKW)
+    assert [a.shape for a in out] == [(0, 3), (0, 3), (0, 3), (0, 3), (0,)]
+    with pytest.raises(engine.EngineError) as err:
+        e.mesh_colours(bverts, bnormals, min_consistent=3)  # more than the two other views
+    assert err.value.status == -1
+    tri_v, tri_t = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], np.float32), np.array([[0, 1, 2]], np.int32)
+    e.upload_patches(synth.make_seeds(sc, 0, 2, stride=4))
+    e.engine_pass(0, 0)
+    with pytest.raises(engine.EngineError) as err:
+        e.mesh_colours(bverts, bnormals)
+    assert err.value.status == MVS_ERR_STATE
+    assert (e.mesh_normals(tri_v, tri_t) == np.array([0, 0, 1], np.float32)).all()  # needs no idle engine
+    e.commit_local()
+    rgb, used = e.mesh_colours(bverts, bnormals)
+    assert (used > 0).any()
+    # rgb alone (used may be null), into a buffer at an odd address
+    c, m = e._maps_config(0, 1, 0.01, 0.9, 0), engine.MeshColouring(0.01, 0.1)
+    buf = np.full(3 * bverts.shape[0] + 2, 77, np.uint8)
+    e._check(e.L.mvs_engine_mesh_colours(e.h, C.byref(c), C.byref(m), bverts.shape[0], bverts.ctypes.data_as(C.c_void_p), bnormals.ctypes.data_as(C.c_void_p),
+                                         C.c_void_p(buf.ctypes.data + 1), None))
+    assert buf[0] == 77 and buf[-1] == 77 and buf[1:-1].tobytes() == rgb.tobytes()
+    e.close()
+    bare = engine.Engine(3)  # views never set
+    with pytest.raises(engine.EngineError) as err:
+        bare.mesh_colours(bverts, bnormals)
+    assert err.value.status == MVS_ERR_STATE
+    assert (bare.mesh_normals(tri_v, tri_t) == np.array([0, 0, 1], np.float32)).all()
+    bare.close()
+
+
+def test_device_tensors():
+    """vertices, normals and the outputs as torch device tensors: the same bytes as through host pointers"""
+    import torch
+
+    sc = _scene(3, 96, 64, 30.0)
+    e = _engine(sc, PLAIN, None, None, None, synth.make_seeds(sc, 0, 2, stride=1))
+    bverts, bnormals, _ = caller_set(sc, 0)
+    rgb, used = e.mesh_colours(bverts, bnormals, **CKW)
+    dev = torch.device("cuda", e.cfg.device)
+    dV, dN = torch.from_numpy(bverts).to(dev), torch.from_numpy(bnormals).to(dev)
+    dC = torch.zeros((bverts.shape[0], 3), dtype=torch.uint8, device=dev)
+    dU = torch.zeros(bverts.shape[0], dtype=torch.uint8, device=dev)
+    c, m = e._maps_config(0, 1, DEPTH_TOL, NORMAL_COS, 0), engine.MeshColouring(DEPTH_TOL, MIN_COS)
+    torch.cuda.synchronize(dev)
+    e._check(e.L.mvs_engine_mesh_colours(e.h, C.byref(c), C.byref(m), bverts.shape[0], C.c_void_p(dV.data_ptr()), C.c_void_p(dN.data_ptr()),
+                                         C.c_void_p(dC.data_ptr()), C.c_void_p(dU.data_ptr())))
+    assert dC.cpu().numpy().tobytes() == rgb.tobytes() and dU.cpu().numpy().tobytes() == used.tobytes() and (used >= 0x80).any()
+    e.close()
