@@ -15,6 +15,7 @@ from .synth import MAX_IMAGES, PATCH_DTYPE  # noqa: F401  (PATCH_DTYPE mirrors m
 
 PROBE_NCC, PROBE_PREPROCESS, PROBE_REFINE, PROBE_POSTPROCESS, PROBE_COST, PROBE_MATH, PROBE_REFINE_X = range(7)
 REFINE_HALVING, REFINE_CONVERGED = 0, 1  # mvs_refine_mode
+MVS_OK, MVS_ERR_ARG, MVS_ERR_STATE, MVS_ERR_HIP, MVS_ERR_CAPACITY, MVS_ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5  # mvs_status
 
 #: every symbol include/mvskit_engine.h declares
 EXPORTS = [
@@ -528,7 +529,7 @@ class Engine:
             status = call(cap_v, _ptr(verts), cap_t, _ptr(tris), C.byref(nv), C.byref(nt))
             if status == 0:
                 return verts[:nv.value].copy(), tris[:nt.value].copy()
-            if status != -4:  # MVS_ERR_CAPACITY
+            if status != MVS_ERR_CAPACITY:
                 self._check(status)
         else:
             self._check(call(0, None, 0, None, C.byref(nv), C.byref(nt)))

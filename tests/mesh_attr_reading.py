@@ -2,11 +2,11 @@
 
 normals_exact() restates mvs_engine_mesh_normals operation by operation: float32 face vectors, the power-of-two scale from the largest
 component, int64 sums, float64 normalisation, the cast.  Equality of bytes is the yardstick.
-colours64() restates mvs_engine_mesh_colours in float64 on _render64 / _agree64 of tests/test_gpu_maps.py (their bits and `unsure`
+colours64() restates mvs_engine_mesh_colours in float64 on render64 / agree64 of tests/maps_reading.py (their bits and `unsure`
 masks), as mesh_reading.tsdf64 does for the volume, and says which vertices have a (vertex, view) pair inside a margin."""
 import numpy as np
 
-from mesh_reading import _popcount
+from maps_reading import popcount
 
 
 def normals_exact(verts, tris):
@@ -52,7 +52,7 @@ def _bilinear64(img, x, y):
 
 def colours64(pat, ids, bits, unsure, cams, images, masks, verts, normals, min_consistent=1, occl_tol=0.01, min_cos=0.1):
     """mvs_engine_mesh_colours in float64.  pat: the records by pool index; ids[v], bits[v], unsure[v]: view v's id map and the agree
-    words of _agree64 with their margins; cams: _cams of tests/test_gpu_maps.py; images[v]: the level-L pyramid [H, W, 3] uint8; masks[v]:
+    words of agree64 with their margins; cams: cameras64 of tests/maps_reading.py; images[v]: the level-L pyramid [H, W, 3] uint8; masks[v]:
     the level-L mask as booleans, or None; normals: [n, 3] or None.
     -> dict of per-vertex arrays: mean [n, 3] (the unrounded weighted mean; NaN with no view), used (uint8), sure (no pair of the vertex
     lies inside a margin), reached (some view has the vertex in its sampling window), confirmed (the confirmed tier was chosen)"""
@@ -77,9 +77,9 @@ def colours64(pat, ids, bits, unsure, cams, images, masks, verts, normals, min_c
         xs, ys = np.where(win, x, 0.0), np.where(win, y, 0.0)
         fx, fy = np.floor(xs + 0.5).astype(int), np.floor(ys + 0.5).astype(int)
         valid = ids[v] >= 0
-        use = valid & (_popcount(bits[v]) >= min_consistent)
-        use_lo = valid & (_popcount(bits[v] & ~unsure[v]) >= min_consistent)
-        use_hi = valid & (_popcount(bits[v] | unsure[v]) >= min_consistent)
+        use = valid & (popcount(bits[v]) >= min_consistent)
+        use_lo = valid & (popcount(bits[v] & ~unsure[v]) >= min_consistent)
+        use_hi = valid & (popcount(bits[v] | unsure[v]) >= min_consistent)
         fg = np.ones((H, W), bool) if masks is None or masks[v] is None else np.asarray(masks[v], bool)
         # what the surface test meets at a pixel: background -2, not usable -1, else the patch
         state = np.where(fg, np.where(use, ids[v], -1), -2)

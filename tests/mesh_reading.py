@@ -1,11 +1,13 @@
 """The yardstick of the mesh calls (include/mvskit_engine.h, "Triangle mesh"): marching tetrahedra in numpy float32, written from the rule
-text in the stated operation order, and a float64 reading of the TSDF on top of _render64 / _agree64 of tests/test_gpu_maps.py.
+text in the stated operation order, and a float64 reading of the TSDF on top of render64 / agree64 of tests/maps_reading.py.
 
 extract() restates mvs_engine_extract_mesh: equality is the yardstick (vertex count, order and bits; the triangle list).  The orientation
 of a triangle is not read from a table here: it is decided on the tetrahedron's ideal geometry -- the crossings at the edge midpoints,
 the normal against the direction from the centroid of the inside corners to that of the outside ones -- which is the rule's own words.
 tsdf64() restates mvs_engine_tsdf in float64 and says which (point, view) pairs lie inside a margin."""
 import numpy as np
+
+from maps_reading import popcount
 
 #: the Kuhn split of a cube along its main diagonal, as corner tuples (corner c = dx + 2 dy + 4 dz)
 TETS = ((0, 1, 3, 7), (0, 1, 5, 7), (0, 2, 3, 7), (0, 2, 6, 7), (0, 4, 5, 7), (0, 4, 6, 7))
@@ -136,13 +138,9 @@ def sphere_volume(dims, centers, radius, origin=(0.0, 0.0, 0.0), voxel=1.0):
     return d.astype(np.float32)
 
 
-def _popcount(a):
-    return np.unpackbits(np.ascontiguousarray(a).view(np.uint8).reshape(a.shape + (8,)), axis=-1).sum(-1)
-
-
 def tsdf64(pat, ids, bits, unsure, cams, min_consistent, origin, voxel, dims, trunc):
     """mvs_engine_tsdf in float64.  pat: the records by pool index; ids[v], bits[v], unsure[v]: view v's id map and the agree words of
-    _agree64 with their margins; cams: _cams of tests/test_gpu_maps.py.
+    agree64 with their margins; cams: cameras64 of tests/maps_reading.py.
     -> dict of [nz, ny, nx] arrays: tsdf, count, sure (no pair of the point lies inside a margin), reached (some view takes the point to
     a usable pixel), bound (max over the contributing views of dz / (|cos(n_q, ray)| trunc))"""
     nx, ny, nz = dims
@@ -159,9 +157,9 @@ def tsdf64(pat, ids, bits, unsure, cams, min_consistent, origin, voxel, dims, tr
         inside = (fx >= 0) & (fx < cam["W"]) & (fy >= 0) & (fy < cam["H"])
         cy, cx = np.clip(fy, 0, cam["H"] - 1), np.clip(fx, 0, cam["W"] - 1)
         valid = ids[v] >= 0
-        use_lo = valid & (_popcount(bits[v] & ~unsure[v]) >= min_consistent)  # usable whatever the unsure pairs give
-        use_hi = valid & (_popcount(bits[v] | unsure[v]) >= min_consistent)   # usable if they all agree
-        use = valid & (_popcount(bits[v]) >= min_consistent)
+        use_lo = valid & (popcount(bits[v] & ~unsure[v]) >= min_consistent)  # usable whatever the unsure pairs give
+        use_hi = valid & (popcount(bits[v] | unsure[v]) >= min_consistent)   # usable if they all agree
+        use = valid & (popcount(bits[v]) >= min_consistent)
         met = inside & use[cy, cx]
         # a pixel whose usability rests on an unsure agree pair
         sure &= ~(inside & (use_lo != use_hi)[cy, cx])

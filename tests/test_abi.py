@@ -25,6 +25,8 @@ def test_header_symbols_are_exported(lib):
     assert declared == set(engine.EXPORTS), declared ^ set(engine.EXPORTS)
     for name in declared:
         assert hasattr(lib, name), name
+    status = {k: int(v) for k, v in re.findall(r"\b(MVS_OK|MVS_ERR_[A-Z_]+) = (-?\d+)", re.search(r"typedef enum mvs_status \{(.*?)\}", hdr, re.S).group(1))}
+    assert len(status) == 6 and status == {k: getattr(engine, k) for k in status}, status
 
 
 def test_record_layouts_match_header():

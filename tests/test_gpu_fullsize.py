@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from mvskit_amd import engine, synth
+from parity_support import cells_in_ref_view
 
 pytestmark = pytest.mark.gpu
 CFG = dict(level=0, csize=2, wsize=7, minImageNum=3, enable_check=1, seed=1)
@@ -114,16 +115,6 @@ def test_full_size_properties(full_scene):
     e.close()
 
 
-def _cells_in_ref_view(sc, seeds, csize=2):
-    """Cell (cx, cy) of every seed in its reference view: PatchManager::setGrids, patch_manager.cpp:241-250."""
-    ref = seeds["images"][:, 0].astype(np.int64)
-    P = sc.P.astype(np.float64)[ref]
-    X = seeds["coord"].astype(np.float64)
-    x = np.einsum("nij,nj->ni", P, X)
-    px, py = x[:, 0] / x[:, 2], x[:, 1] / x[:, 2]
-    return np.floor(px + 0.5).astype(np.int64) // csize, np.floor(py + 0.5).astype(np.int64) // csize
-
-
 def test_full_size_windowed_parity_vs_oracle(full_scene):
     """BASELINE configs[1] geometry (12 x 1920x1080: 960x540 cells per view, 6.2 M cells, cell_base up to 5.7 M, rows of
     1920 texels) against the CPU oracle -- affordable because the seeds are confined to one 64x64-cell window per view,
@@ -133,10 +124,10 @@ def test_full_size_windowed_parity_vs_oracle(full_scene):
     job-index error that the 384x216 parity scenes cannot see."""
     import oracle_binding as ob
 
-    from test_gpu_parity import REL_TOL, _maps_close
+    from parity_support import REL_TOL, maps_close
 
     sc, seeds = full_scene
-    cx, cy = _cells_in_ref_view(sc, seeds)
+    cx, cy = cells_in_ref_view(sc, seeds)
     ref = seeds["images"][:, 0].astype(np.int64)
     gw, gh = 960, 540
     keep = np.zeros(seeds.shape[0], bool)
@@ -172,7 +163,7 @@ def test_full_size_windowed_parity_vs_oracle(full_scene):
     np.testing.assert_allclose(pe["normal"], po["normal"], rtol=0, atol=REL_TOL)
     np.testing.assert_allclose(pe["ncc"], po["ncc"], rtol=REL_TOL, atol=1e-5)
     assert (pe["coord"] == po["coord"]).all(axis=1).mean() > 0.99
-    tot, bad = _maps_close(o, e, sc.nviews)
+    tot, bad = maps_close(o, e, sc.nviews)
     assert tot > 5000 and bad == 0, (tot, bad)
     o.close()
     e.close()
@@ -241,7 +232,7 @@ def test_config4_48_views_4k_five_iterations(scene_48x4k):
     sc = scene_48x4k
     n = sc.nviews
     seeds = synth.make_seeds(sc, level=0, csize=2, stride=4, seed=777)
-    cx, cy = _cells_in_ref_view(sc, seeds)
+    cx, cy = cells_in_ref_view(sc, seeds)
     assert seeds.shape[0] > 5_000_000 and len(set(seeds["images"][:, 0].tolist())) == n
     assert cx.min() < 64 and cx.max() > 1855 and cy.min() < 64 and cy.max() > 1015  # no mask: the seeds reach the borders of the grids
     MAX_PATCHES = 128_000_000
@@ -314,12 +305,12 @@ def test_config4_windowed_parity_vs_oracle(scene_48x4k):
     counter equal, lists equal, coordinates and both depth / normal maps within the north-star tolerance."""
     import oracle_binding as ob
 
-    from test_gpu_parity import REL_TOL
+    from parity_support import REL_TOL
 
     sc = scene_48x4k
     views = [47, 46, 44, 40, 33, 20]
     seeds = synth.make_seeds(sc, level=0, csize=2, stride=3, seed=31, views=views)
-    cx, cy = _cells_in_ref_view(sc, seeds)
+    cx, cy = cells_in_ref_view(sc, seeds)
     ref = seeds["images"][:, 0].astype(np.int64)
     gw, gh = 1920, 1080
     corners = {47: (gw - 70 - 64, gh - 70 - 64), 46: (70, gh - 70 - 64), 44: (gw - 70 - 64, 70), 40: (70, 70), 33: (gw - 150 - 64, gh // 2), 20: (gw // 2, gh - 150 - 64)}

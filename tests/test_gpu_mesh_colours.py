@@ -1,5 +1,5 @@
-"""mvs_engine_mesh_colours on the GPU against the float64 reading of tests/mesh_attr_reading.py (colours64, on _render64 / _agree64 of
-tests/test_gpu_maps.py with their `unsure` masks), on the four plane scenes, pools and the lattice of tests/test_gpu_mesh_tsdf.py, with
+"""mvs_engine_mesh_colours on the GPU against the float64 reading of tests/mesh_attr_reading.py (colours64, on render64 / agree64 of
+tests/maps_reading.py with their `unsure` masks), on the four plane scenes, pools and the lattice of tests/test_gpu_mesh_tsdf.py, with
 occl_tol = DEPTH_TOL.
 
 Every case colours two vertex sets.  (a) the mesh of Engine.mesh with the normals of Engine.mesh_normals.  (b) a caller's set built to
@@ -20,13 +20,12 @@ import numpy as np
 import pytest
 
 import mesh_attr_reading as ar
+from maps_reading import DEPTH_TOL, NORMAL_COS, cameras64, render_agree64
 from mvskit_amd import engine, synth
-from test_gpu_maps import DEPTH_TOL, NORMAL_COS, _agree64, _cams, _engine, _render64
-from test_gpu_mesh_tsdf import PLAIN, lattice, many_view_seeds
-from test_gpu_seed_random import _mask_at, _scene
+from mvskit_amd.engine import MVS_ERR_STATE
+from scene_support import PLAIN, cached_scene, engine_with_pool, lattice, many_view_seeds, mask_at
 
 pytestmark = pytest.mark.gpu
-MVS_ERR_STATE = -2
 MIN_COS = 0.1
 KW = dict(min_consistent=1, depth_tol=DEPTH_TOL, normal_cos=NORMAL_COS)
 CKW = dict(occl_tol=DEPTH_TOL, min_cos=MIN_COS, **KW)
@@ -60,12 +59,6 @@ def caller_set(sc, level, band_view=None, band=None):
     return (np.concatenate([p[1] for p in parts]).astype(np.float32), np.concatenate([p[2] for p in parts]).astype(np.float32), groups)
 
 
-def maps_reading(pat, ids, cams):
-    X = [_render64(pat, ids[v], cams[v])[1] for v in range(len(cams))]
-    bits, unsure = zip(*[_agree64(pat, ids, X, cams, v, DEPTH_TOL, NORMAL_COS) for v in range(len(cams))])
-    return bits, unsure
-
-
 def check_colours(name, r, rgb, used, cap=0.05):
     """the engine's colours against the reading r -> the largest colour error"""
     sure, reached = r["sure"], r["reached"]
@@ -91,16 +84,16 @@ def _case(sc, ekw, masks=None, list_cap=None, seeds=None, band=None):
     level, csize = ekw["level"], ekw["csize"]
     sizes = [(sc.W, sc.H)] * sc.nviews
     seeds = synth.make_seeds(sc, level, csize, stride=1) if seeds is None else seeds
-    e = _engine(sc, ekw, masks, sizes, list_cap, seeds)
+    e = engine_with_pool(sc, ekw, masks, sizes, list_cap, seeds)
     alive = e.patches()
     pat = np.zeros(int(alive["id"].max()) + 1, alive.dtype)
     pat[alive["id"]] = alive
     thr = e.thresholds()
-    cams = _cams(sc, level, sizes)
+    cams = cameras64(sc, level, sizes)
     ids = [m["ids"] for m in e.render_maps(depth_tol=DEPTH_TOL, normal_cos=NORMAL_COS)]
-    bits, unsure = maps_reading(pat, ids, cams)
+    bits, unsure = render_agree64(pat, ids, cams)
     images = [e.pyramid(v, level) for v in range(sc.nviews)]
-    lmasks = None if masks is None else [None if m is None else _mask_at(m, sizes[v], level) for v, m in enumerate(masks)]
+    lmasks = None if masks is None else [None if m is None else mask_at(m, sizes[v], level) for v, m in enumerate(masks)]
     vol = lattice(sc, level)
 
     def reading(verts, normals):
@@ -145,7 +138,7 @@ def _case(sc, ekw, masks=None, list_cap=None, seeds=None, band=None):
 
     # nothing of the engine's state moved
     assert e.patches().tobytes() == alive.tobytes() and e.thresholds() == thr
-    t = _engine(sc, ekw, masks, sizes, list_cap, seeds)
+    t = engine_with_pool(sc, ekw, masks, sizes, list_cap, seeds)
     assert t.patches().tobytes() == alive.tobytes()
     assert e.propagate(1) == t.propagate(1)
     assert e.patches().tobytes() == t.patches().tobytes()
@@ -155,12 +148,12 @@ def _case(sc, ekw, masks=None, list_cap=None, seeds=None, band=None):
 
 def test_plain():
     """3 views of 96 x 64 on the textured plane, csize 2"""
-    _case(_scene(3, 96, 64, 30.0), PLAIN)
+    _case(cached_scene(3, 96, 64, 30.0), PLAIN)
 
 
 def test_ragged_grid_with_a_mask_band():
     """4 views of 97 x 63, csize 3, view 1 with a background band: it takes no part for the vertices behind the band"""
-    sc = _scene(4, 97, 63, 30.0)
+    sc = cached_scene(4, 97, 63, 30.0)
     band = np.full((sc.H, sc.W), 255, np.uint8)
     band[:, 40:52] = 0
     _case(sc, dict(level=0, csize=3, minImageNum=2, depth=0, max_patches=4 * 33 * 21 * 2 * 9), masks=[None, band, None, None], band=slice(41, 51))
@@ -168,19 +161,19 @@ def test_ragged_grid_with_a_mask_band():
 
 def test_level_one():
     """3 views of 192 x 128 at level 1: P_L, the level's image size and pyramid"""
-    _case(_scene(3, 192, 128, 30.0), dict(level=1, csize=2, minImageNum=2, depth=0))
+    _case(cached_scene(3, 192, 128, 30.0), dict(level=1, csize=2, minImageNum=2, depth=0))
 
 
 def test_many_views():
     """40 views of 48 x 32 with the 64-view library (192-byte records), on an arc of 0.25 degrees"""
-    sc = _scene(40, 48, 32, 0.25)
+    sc = cached_scene(40, 48, 32, 0.25)
     _case(sc, dict(level=0, csize=2, minImageNum=3, depth=0), list_cap=64, seeds=many_view_seeds(sc))
 
 
 def test_empty_pool_and_states():
     """an empty pool gives grey and used == 0 everywhere; mesh_colours asks for views and an idle engine, mesh_normals for neither"""
-    sc = _scene(3, 96, 64, 30.0)
-    e = _engine(sc, PLAIN, None, None, None, None)
+    sc = cached_scene(3, 96, 64, 30.0)
+    e = engine_with_pool(sc, PLAIN, None, None, None, None)
     vol = lattice(sc, 0)
     bverts, bnormals, _ = caller_set(sc, 0)
     for nrm in (bnormals, None):
@@ -220,8 +213,8 @@ def test_device_tensors():
     """vertices, normals and the outputs as torch device tensors: the same bytes as through host pointers"""
     import torch
 
-    sc = _scene(3, 96, 64, 30.0)
-    e = _engine(sc, PLAIN, None, None, None, synth.make_seeds(sc, 0, 2, stride=1))
+    sc = cached_scene(3, 96, 64, 30.0)
+    e = engine_with_pool(sc, PLAIN, None, None, None, synth.make_seeds(sc, 0, 2, stride=1))
     bverts, bnormals, _ = caller_set(sc, 0)
     rgb, used = e.mesh_colours(bverts, bnormals, **CKW)
     dev = torch.device("cuda", e.cfg.device)

@@ -8,9 +8,9 @@ import pytest
 
 import mesh_reading as mr
 from mvskit_amd import engine
+from mvskit_amd.engine import MVS_ERR_CAPACITY
 
 pytestmark = pytest.mark.gpu
-MVS_ERR_CAPACITY = -4
 
 
 @pytest.fixture(scope="module")

@@ -9,10 +9,10 @@ import pytest
 import mesh_attr_reading as ar
 import mesh_reading as mr
 from mvskit_amd import engine
-from test_mesh_attr_reading import grid_mesh
+from mvskit_amd.engine import MVS_ERR_ARG
+from scene_support import grid_mesh
 
 pytestmark = pytest.mark.gpu
-MVS_ERR_ARG = -1
 
 
 @pytest.fixture(scope="module")

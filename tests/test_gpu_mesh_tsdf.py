@@ -1,5 +1,5 @@
-"""mvs_engine_tsdf and mvs_engine_mesh on the GPU against the float64 reading of tests/mesh_reading.py (tsdf64, on _render64 / _agree64 of
-tests/test_gpu_maps.py with their `unsure` masks).
+"""mvs_engine_tsdf and mvs_engine_mesh on the GPU against the float64 reading of tests/mesh_reading.py (tsdf64, on render64 / agree64 of
+tests/maps_reading.py with their `unsure` masks).
 
 The pool of every case is that of the maps tests: synth.make_seeds uploaded, then propagate(0) once.  The scene is the textured plane z = 0
 seen from a radius of 4; the lattice is 24 x 20 x 12 points around the origin at 1.5 pixel footprints, trunc = 4 voxels, its origin shifted
@@ -22,35 +22,17 @@ import numpy as np
 import pytest
 
 import mesh_reading as mr
+from maps_reading import DEPTH_TOL, NORMAL_COS, cameras64, render_agree64
 from mvskit_amd import engine, synth
-from test_gpu_maps import DEPTH_TOL, NORMAL_COS, _agree64, _cams, _engine, _render64
-from test_gpu_seed_random import _scene
+from mvskit_amd.engine import MVS_ERR_STATE
+from scene_support import DIMS, PLAIN, cached_scene, engine_with_pool, lattice, many_view_seeds
 
 pytestmark = pytest.mark.gpu
-MVS_ERR_STATE = -2
-DIMS, SHIFT, TRUNC_VOXELS = (24, 20, 12), (0.31, 0.17, 0.43), 4
-PLAIN = dict(level=0, csize=2, minImageNum=2, depth=0)
-
-
-def lattice(sc, level, min_count=1):
-    """the case's mvs_volume: 1.5 pixel footprints at the scene's radius of 4, around the origin"""
-    foot = 4.0 / (765.702941895 * sc.W / 640.0 / 2 ** level)
-    voxel = 1.5 * foot
-    origin = [(-DIMS[c] / 2 + SHIFT[c]) * voxel for c in range(3)]
-    return engine.make_volume(origin, voxel, DIMS, TRUNC_VOXELS * voxel, min_count)
-
-
-def many_view_seeds(sc):
-    """one seed per cell, exact to 2 % of a pixel footprint and half a degree (the left half of test_gpu_maps.test_many_views' seeds): the
-    rough half of that test leaves pixels with no or one agreeing view, whose usability then rests on one pair, and every lattice point
-    behind such a pixel would be left out (11 % of the reached points on the CPU oracle's pool)"""
-    return synth.make_seeds(sc, 0, 2, stride=1, depth_noise=0.02, normal_noise_deg=0.5)
 
 
 def reading(pat, ids, cams, vol, min_consistent=1):
     """tsdf64 of the volume over the pool `pat` (records by pool index) and the id maps"""
-    X = [_render64(pat, ids[v], cams[v])[1] for v in range(len(cams))]
-    bits, unsure = zip(*[_agree64(pat, ids, X, cams, v, DEPTH_TOL, NORMAL_COS) for v in range(len(cams))])
+    bits, unsure = render_agree64(pat, ids, cams)
     return mr.tsdf64(pat, ids, bits, unsure, cams, min_consistent, vol.origin[:], vol.voxel, vol.dims[:], vol.trunc)
 
 
@@ -82,12 +64,12 @@ def _case(sc, ekw, masks=None, list_cap=None, seeds=None):
     level, csize = ekw["level"], ekw["csize"]
     sizes = [(sc.W, sc.H)] * sc.nviews
     seeds = synth.make_seeds(sc, level, csize, stride=1) if seeds is None else seeds
-    e = _engine(sc, ekw, masks, sizes, list_cap, seeds)
+    e = engine_with_pool(sc, ekw, masks, sizes, list_cap, seeds)
     alive = e.patches()
     pat = np.zeros(int(alive["id"].max()) + 1, alive.dtype)
     pat[alive["id"]] = alive
     thr = e.thresholds()
-    cams = _cams(sc, level, sizes)
+    cams = cameras64(sc, level, sizes)
     ids = [m["ids"] for m in e.render_maps(depth_tol=DEPTH_TOL, normal_cos=NORMAL_COS)]
     vol = lattice(sc, level)
     kw = dict(min_consistent=1, depth_tol=DEPTH_TOL, normal_cos=NORMAL_COS)
@@ -121,7 +103,7 @@ def _case(sc, ekw, masks=None, list_cap=None, seeds=None):
     assert np.median(dist) < vol.voxel
     # nothing of the engine's state moved
     assert e.patches().tobytes() == alive.tobytes() and e.thresholds() == thr
-    t = _engine(sc, ekw, masks, sizes, list_cap, seeds)
+    t = engine_with_pool(sc, ekw, masks, sizes, list_cap, seeds)
     assert t.patches().tobytes() == alive.tobytes()
     assert e.propagate(1) == t.propagate(1)
     assert e.patches().tobytes() == t.patches().tobytes()
@@ -131,12 +113,12 @@ def _case(sc, ekw, masks=None, list_cap=None, seeds=None):
 
 def test_plain():
     """3 views of 96 x 64 on the textured plane, csize 2"""
-    _case(_scene(3, 96, 64, 30.0), PLAIN)
+    _case(cached_scene(3, 96, 64, 30.0), PLAIN)
 
 
 def test_ragged_grid_with_a_mask_band():
     """4 views of 97 x 63, csize 3, view 1 with a background band: its pixels there are not usable"""
-    sc = _scene(4, 97, 63, 30.0)
+    sc = cached_scene(4, 97, 63, 30.0)
     band = np.full((sc.H, sc.W), 255, np.uint8)
     band[:, 40:52] = 0
     _case(sc, dict(level=0, csize=3, minImageNum=2, depth=0, max_patches=4 * 33 * 21 * 2 * 9), masks=[None, band, None, None])
@@ -144,12 +126,12 @@ def test_ragged_grid_with_a_mask_band():
 
 def test_level_one():
     """3 views of 192 x 128 at level 1: P_L and the level's image size"""
-    _case(_scene(3, 192, 128, 30.0), dict(level=1, csize=2, minImageNum=2, depth=0))
+    _case(cached_scene(3, 192, 128, 30.0), dict(level=1, csize=2, minImageNum=2, depth=0))
 
 
 def test_many_views():
     """40 views of 48 x 32 with the 64-view library (192-byte records), on an arc of 0.25 degrees (the module's docstring)"""
-    sc = _scene(40, 48, 32, 0.25)
+    sc = cached_scene(40, 48, 32, 0.25)
     _case(sc, dict(level=0, csize=2, minImageNum=3, depth=0), list_cap=64, seeds=many_view_seeds(sc))
 
 
@@ -158,23 +140,23 @@ def test_many_views_on_a_wide_arc():
     pixel base for a high view shows in count and tsdf.  The 5 % cap does not hold on this arc (the module's docstring): count and tsdf
     are compared on the points outside the margins, which must be at least three quarters of the reached ones -- each of the 40 pairs
     of a point lies within 1e-3 pixel of a boundary with probability 4e-3 at most, 15 % in all if the views were independent."""
-    sc = _scene(40, 48, 32, 1.0)
-    e = _engine(sc, dict(level=0, csize=2, minImageNum=3, depth=0), None, [(sc.W, sc.H)] * 40, 64, many_view_seeds(sc))
+    sc = cached_scene(40, 48, 32, 1.0)
+    e = engine_with_pool(sc, dict(level=0, csize=2, minImageNum=3, depth=0), None, [(sc.W, sc.H)] * 40, 64, many_view_seeds(sc))
     alive = e.patches()
     pat = np.zeros(int(alive["id"].max()) + 1, alive.dtype)
     pat[alive["id"]] = alive
     ids = [m["ids"] for m in e.render_maps(depth_tol=DEPTH_TOL, normal_cos=NORMAL_COS)]
     vol = lattice(sc, 0)
     tsdf, count = e.tsdf(vol, min_consistent=1, depth_tol=DEPTH_TOL, normal_cos=NORMAL_COS)
-    check_volume(reading(pat, ids, _cams(sc, 0, [(sc.W, sc.H)] * 40), vol), tsdf, count, cap=0.25)
+    check_volume(reading(pat, ids, cameras64(sc, 0, [(sc.W, sc.H)] * 40), vol), tsdf, count, cap=0.25)
     assert count.max() == 40
     e.close()
 
 
 def test_empty_pool_and_staged_pass():
     """an empty pool gives an all-NaN volume, zero counts and an empty mesh; a pass staged and not committed is refused"""
-    sc = _scene(3, 96, 64, 30.0)
-    e = _engine(sc, PLAIN, None, None, None, None)
+    sc = cached_scene(3, 96, 64, 30.0)
+    e = engine_with_pool(sc, PLAIN, None, None, None, None)
     vol = lattice(sc, 0)
     tsdf, count = e.tsdf(vol)
     assert np.isnan(tsdf).all() and (count == 0).all()

@@ -7,31 +7,13 @@ import pytest
 
 import oracle_binding as ob
 from mvskit_amd import engine, synth
+from parity_support import REL_TOL, cmp_records, dense_pool, maps_close, pair
 
 pytestmark = pytest.mark.gpu
 
-REL_TOL = 1e-3  # BASELINE.json north_star: depth/normal maps within 1e-3 relative
-
-
-def _pair(scene, **kw):
-    n = scene.nviews
-    okw = dict(level=0, csize=2, wsize=7, minImageNum=kw.pop("minImageNum", 3), schedule=ob.SCHEDULE_ENGINE,
-               sum_mode=ob.SUM_TREE64, enable_check=0, nthreads=8)
-    ekw = dict(level=0, csize=2, wsize=7, minImageNum=okw["minImageNum"], enable_check=0)
-    for k, v in kw.items():
-        okw[k] = v
-        ekw[k] = v
-    if okw.get("list_cap", 0) > 32:
-        okw["wide"] = True  # 64 views per list: the oracle's wide build (192-byte records, as libmvskit_engine_cap64.so)
-    o = ob.Oracle(n, **okw)
-    e = engine.Engine(n, **ekw)
-    o.set_scene(scene)
-    e.set_scene(scene)
-    return o, e
-
 
 def test_math_probe_bit_exact(small_plane_scene):
-    o, e = _pair(small_plane_scene, minImageNum=2)
+    o, e = pair(small_plane_scene, minImageNum=2)
     x = np.concatenate([np.linspace(-1.5707, 1.5707, 4001), np.linspace(-1, 1, 2001), np.linspace(-30, 30, 1001)]).astype(np.float32)
     got = e.probe(engine.PROBE_MATH, values=x)
     L = ob.lib()
@@ -47,7 +29,7 @@ def test_math_probe_bit_exact(small_plane_scene):
 
 
 def test_pyramid_bit_exact(small_multi_scene):
-    o, e = _pair(small_multi_scene)
+    o, e = pair(small_multi_scene)
     for v in (0, 3):
         for level in range(3):
             np.testing.assert_array_equal(e.pyramid(v, level), o.pyramid(v, level))
@@ -55,7 +37,7 @@ def test_pyramid_bit_exact(small_multi_scene):
 
 
 def test_ncc_batch(small_multi_scene):
-    o, e = _pair(small_multi_scene)
+    o, e = pair(small_multi_scene)
     seeds = synth.make_seeds(small_multi_scene, stride=6)
     assert seeds.shape[0] > 300
     _, got, _ = e.probe(engine.PROBE_NCC, seeds)
@@ -65,18 +47,8 @@ def test_ncc_batch(small_multi_scene):
     assert (got == exp).mean() > 0.999, f"bit-exact fraction {(got == exp).mean()}"
 
 
-def _cmp_records(a, b, what):
-    assert a["nimages"] == b["nimages"], what
-    n = int(a["nimages"])
-    np.testing.assert_array_equal(a["images"][:n], b["images"][:n], err_msg=what)
-    np.testing.assert_allclose(a["coord"], b["coord"], rtol=REL_TOL, atol=1e-6, err_msg=what)
-    np.testing.assert_allclose(a["normal"], b["normal"], rtol=0, atol=REL_TOL, err_msg=what)
-    for f in ("ncc", "dscale", "ascale"):
-        np.testing.assert_allclose(a[f], b[f], rtol=REL_TOL, atol=1e-6, err_msg=what + f)
-
-
 def test_pre_refine_post_chain(small_multi_scene):
-    o, e = _pair(small_multi_scene)
+    o, e = pair(small_multi_scene)
     seeds = synth.make_seeds(small_multi_scene, stride=8, seed=31)[:200]
     pre_rec, _, pre_flag = e.probe(engine.PROBE_PREPROCESS, seeds)
     keep = []
@@ -85,7 +57,7 @@ def test_pre_refine_post_chain(small_multi_scene):
         f, r = o.preprocess(s)
         assert f == pre_flag[i], i
         if f == 0:
-            _cmp_records(pre_rec[i], r, f"pre {i}")
+            cmp_records(pre_rec[i], r, f"pre {i}")
             keep.append(i)
     assert len(keep) > 50
     sub = pre_rec[keep]
@@ -96,7 +68,7 @@ def test_pre_refine_post_chain(small_multi_scene):
         x = o.encode(sub[j])
         assert abs(cost[j] - o.cost(sub[j], x)) <= 1e-6
         _, r = o.refine(sub[j], (0, 0, j, 0))
-        _cmp_records(ref_rec[j], r, f"refine {j}")
+        cmp_records(ref_rec[j], r, f"refine {j}")
         exact += int(ref_rec[j]["coord"].tobytes() == r["coord"].tobytes() and ref_rec[j]["normal"].tobytes() == r["normal"].tobytes())
         post_in.append(r)
     assert exact >= 0.98 * len(keep), f"refine bit-exact {exact}/{len(keep)}"
@@ -109,30 +81,15 @@ def test_pre_refine_post_chain(small_multi_scene):
         f, r = o.postprocess(post_in[j])
         assert f == post_flag[j], j
         if f == 0:
-            _cmp_records(post_rec[j], r, f"post {j}")
+            cmp_records(post_rec[j], r, f"post {j}")
             assert post_rec[j]["nvimages"] == r["nvimages"]
             npass += 1
     assert npass > 20
 
 
-def _maps_close(o, e, nviews):
-    tot = bad = 0
-    for v in range(nviews):
-        for kind in (0, 1):
-            do, no, io = o.depth_normal_map(v, kind)
-            de, ne, ie = e.depth_normal_map(v, kind)
-            assert (np.isnan(do) == np.isnan(de)).all(), f"empty mask differs view {v} kind {kind}"
-            m = ~np.isnan(do)
-            tot += int(m.sum())
-            rel = np.abs(do[m] - de[m]) / np.abs(do[m])
-            ang = np.arccos(np.clip((no[m] * ne[m]).sum(-1), -1, 1))
-            bad += int(((rel > REL_TOL) | (ang > REL_TOL)).sum())
-    return tot, bad
-
-
 def test_propagate_two_iterations_matches_oracle(small_multi_scene):
     sc = small_multi_scene
-    o, e = _pair(sc, seed=7)
+    o, e = pair(sc, seed=7)
     seeds = synth.make_seeds(sc, stride=4, seed=5)
     o.add_patches(seeds)
     e.upload_patches(seeds)
@@ -150,14 +107,14 @@ def test_propagate_two_iterations_matches_oracle(small_multi_scene):
         np.testing.assert_allclose(pe["normal"], po["normal"], rtol=0, atol=REL_TOL)
         np.testing.assert_allclose(pe["ncc"], po["ncc"], rtol=REL_TOL, atol=1e-6)
         assert (po["coord"].view(np.uint32) == pe["coord"].view(np.uint32)).all(axis=1).mean() > 0.999
-    tot, bad = _maps_close(o, e, sc.nviews)
+    tot, bad = maps_close(o, e, sc.nviews)
     assert tot > 2000 and bad == 0
 
 
 def test_check_stage_probe(small_multi_scene):
     """Optim::check (optim.cpp:300-323: computeGain, findNeighbors, filterQuad) through postProcess at m_depth = 2."""
     sc = small_multi_scene
-    o, e = _pair(sc, seed=11, enable_check=1)
+    o, e = pair(sc, seed=11, enable_check=1)
     seeds = synth.make_seeds(sc, stride=2, seed=3)
     o.add_patches(seeds)
     e.upload_patches(seeds)
@@ -173,7 +130,7 @@ def test_check_stage_probe(small_multi_scene):
         f, r = o.postprocess(cand[j])
         assert f == post_flag[j], j
         if f == 0:
-            _cmp_records(post_rec[j], r, f"post+check {j}")
+            cmp_records(post_rec[j], r, f"post+check {j}")
             np.testing.assert_allclose(post_rec[j]["tmp"], r["tmp"], rtol=REL_TOL, atol=1e-5)  # m_tmp = gain
             passed += 1
         else:
@@ -184,7 +141,7 @@ def test_check_stage_probe(small_multi_scene):
 def test_three_iterations_with_check(small_multi_scene):
     """PmMvps::run's loop (pmmvps.cpp:90-110) without Filter::run: m_depth 1, 2, 3 -- Optim::check active from iteration 1."""
     sc = small_multi_scene
-    o, e = _pair(sc, seed=13, enable_check=1)
+    o, e = pair(sc, seed=13, enable_check=1)
     seeds = synth.make_seeds(sc, stride=4, seed=17)
     o.add_patches(seeds)
     e.upload_patches(seeds)
@@ -201,7 +158,7 @@ def test_three_iterations_with_check(small_multi_scene):
     np.testing.assert_allclose(pe["coord"], po["coord"], rtol=REL_TOL, atol=1e-6)
     np.testing.assert_allclose(pe["normal"], po["normal"], rtol=0, atol=REL_TOL)
     np.testing.assert_allclose(pe["tmp"], po["tmp"], rtol=REL_TOL, atol=1e-5)
-    tot, bad = _maps_close(o, e, sc.nviews)
+    tot, bad = maps_close(o, e, sc.nviews)
     assert tot > 2000 and bad == 0
 
 
@@ -246,7 +203,7 @@ def test_engine_rccl_exchange_world1_equals_local_commit(small_multi_scene):
 
 
 def _one_iteration_matches(sc, seeds, masks=None, **kw):
-    o, e = _pair(sc, **kw)
+    o, e = pair(sc, **kw)
     if masks is not None:
         o.set_scene(sc, masks=masks)
         e.set_scene(sc, masks=masks)
@@ -343,7 +300,7 @@ def test_many_view_libraries_two_iterations_with_check_and_filter(list_cap, nvie
     Filter::run removal counts equal to the oracle's with the same cap."""
     sc = synth.make_scene(nviews=nviews, W=160, H=120, arc_deg=120.0, radius=4.0, kind="multi")
     seeds = synth.make_seeds(sc, stride=4 if nviews <= 20 else 6, seed=3)
-    o, e = _pair(sc, seed=9, enable_check=1, list_cap=list_cap)
+    o, e = pair(sc, seed=9, enable_check=1, list_cap=list_cap)
     assert e.list_cap == list_cap and e.dtype.itemsize == (192 if list_cap == 64 else 128)
     o.add_patches(seeds)
     e.upload_patches(seeds)
@@ -363,7 +320,7 @@ def test_many_view_libraries_two_iterations_with_check_and_filter(list_cap, nvie
     np.testing.assert_array_equal(po["images"], pe["images"])
     np.testing.assert_array_equal(po["vimages"], pe["vimages"])
     np.testing.assert_allclose(pe["coord"], po["coord"], rtol=REL_TOL, atol=1e-6)
-    tot, bad = _maps_close(o, e, sc.nviews)
+    tot, bad = maps_close(o, e, sc.nviews)
     # 20 overlapping views put several patches of nearly the same depth into a cell: where two of them lie within the
     # coordinate tolerance of each other the nearest one may differ (5 of 107 490 cells when this was written)
     assert tot > 2000 and bad <= tot * 1e-4, (tot, bad)
@@ -374,8 +331,8 @@ def test_view_propagation_matches_oracle(small_multi_scene):
     trash/propagate_view_propagation_simiar_to_original.cpp:95-147), as an option of the engine schedule."""
     sc = small_multi_scene
     seeds = synth.make_seeds(sc, stride=4, seed=23, views=[0, sc.nviews // 2])
-    o, e = _pair(sc, seed=5, view_propagation=1)
-    o0, _ = _pair(sc, seed=5)
+    o, e = pair(sc, seed=5, view_propagation=1)
+    o0, _ = pair(sc, seed=5)
     for x in (o, e, o0):
         (x.add_patches if hasattr(x, "add_patches") else x.upload_patches)(seeds)
     for it in range(2):
@@ -391,7 +348,7 @@ def test_view_propagation_matches_oracle(small_multi_scene):
 
 
 def test_empty_pool_and_reupload(small_plane_scene):
-    o, e = _pair(small_plane_scene, minImageNum=2)
+    o, e = pair(small_plane_scene, minImageNum=2)
     assert e.propagate(0)["patches"] == 0 and e.num_patches() == 0
     seeds = synth.make_seeds(small_plane_scene, stride=8, seed=1)
     ragged = seeds.copy()
@@ -405,7 +362,7 @@ def test_empty_pool_and_reupload(small_plane_scene):
 def test_filter_run_matches_oracle(small_multi_scene):
     """Filter::run (filter.cpp:25-49) after each Propagate::run, as PmMvps::run does (pmmvps.cpp:95-105)."""
     sc = small_multi_scene
-    o, e = _pair(sc, seed=21, enable_check=1)
+    o, e = pair(sc, seed=21, enable_check=1)
     seeds = synth.make_seeds(sc, stride=3, seed=19)
     o.add_patches(seeds)
     e.upload_patches(seeds)
@@ -449,7 +406,7 @@ def test_filter_packed_geometry_gives_what_the_records_give(small_multi_scene, m
     odd["coord"][::7, 3] = 1.0009765625  # homogeneous coordinates the reference would take as they are
     for variant, sd in (("packed", seeds), ("records", seeds), ("odd w", odd)):
         monkeypatch.setenv("MVS_FAULT_NOPACK", "1" if variant == "records" else "0")
-        o, e = _pair(sc, seed=21, enable_check=1)
+        o, e = pair(sc, seed=21, enable_check=1)
         o.add_patches(sd)
         e.upload_patches(sd)
         for it in range(2):
@@ -474,7 +431,7 @@ def test_reserve_sizes_the_indexes_up_front(small_multi_scene):
     request later changes nothing, a larger one between two calls replaces the buffers without harm, a negative one is refused."""
     sc = small_multi_scene
     seeds = synth.make_seeds(sc, stride=3, seed=19)
-    o, e = _pair(sc, seed=21, enable_check=1)
+    o, e = pair(sc, seed=21, enable_check=1)
     e.reserve()
     o.add_patches(seeds)
     e.upload_patches(seeds)
@@ -500,7 +457,7 @@ def test_min_image_num_above_eight():
     Filter::run on a narrow arc, where every view sees the surface: counters, lists and survivors equal the oracle's."""
     sc = synth.make_scene(nviews=12, W=160, H=120, arc_deg=22.0, radius=4.0, kind="multi")
     seeds = synth.make_seeds(sc, stride=4, seed=11)
-    o, e = _pair(sc, seed=13, enable_check=1, minImageNum=9)
+    o, e = pair(sc, seed=13, enable_check=1, minImageNum=9)
     o.add_patches(seeds)
     e.upload_patches(seeds)
     for it in range(2):
@@ -530,7 +487,7 @@ def test_filter_run_tiny_and_ragged_pools(small_plane_scene, npatch):
     filterSmallGroups meets nothing): the four removal counts and the survivors equal the oracle's."""
     sc = small_plane_scene
     seeds = synth.make_seeds(sc, stride=3, seed=41)[:npatch]
-    o, e = _pair(sc, seed=2, enable_check=1, minImageNum=2)
+    o, e = pair(sc, seed=2, enable_check=1, minImageNum=2)
     if npatch:
         o.add_patches(seeds)
         e.upload_patches(seeds)
@@ -558,8 +515,8 @@ def test_filter_small_groups_literal_labelling():
     calls, and differ from the default mode's at least once."""
     sc = synth.make_scene(nviews=5, W=256, H=160, arc_deg=60.0, radius=4.0, kind="multi")
     seeds = synth.make_seeds(sc, stride=3, seed=19)
-    o, e = _pair(sc, seed=21, enable_check=1, literal_groups=1)
-    o1, _ = _pair(sc, seed=21, enable_check=1)
+    o, e = pair(sc, seed=21, enable_check=1, literal_groups=1)
+    o1, _ = pair(sc, seed=21, enable_check=1)
     for x in (o, e, o1):
         (x.add_patches if x is not e else x.upload_patches)(seeds)
     differs = 0
@@ -581,33 +538,15 @@ def test_filter_small_groups_literal_labelling():
         x.close()
 
 
-def _dense_pool(sc, per_cell, window=12, ref=0):
-    """`per_cell` patches in every cell of a `window` x `window` block of view `ref`'s grid (make_seeds' noisy plane seeds, one
-    draw per RNG seed), scored and scaled by hand: what Filter::run meets after a few iterations without the trim."""
-    recs = []
-    for k in range(per_cell):
-        sd = synth.make_seeds(sc, stride=1, seed=100 + k, views=[ref])
-        P = sc.P.astype(np.float64)[ref]
-        x = sd["coord"].astype(np.float64) @ P.T
-        cx = np.floor(x[:, 0] / x[:, 2] + 0.5).astype(int) // 2
-        cy = np.floor(x[:, 1] / x[:, 2] + 0.5).astype(int) // 2
-        keep = (cx >= 60) & (cx < 60 + window) & (cy >= 50) & (cy < 50 + window)
-        recs.append(sd[keep])
-    pool = np.ascontiguousarray(np.concatenate(recs))
-    pool["ncc"] = 0.9
-    pool["dscale"] = 0.004
-    return pool
-
-
 def test_filter_neighbor_dense_cells_take_the_retry_launch(small_plane_scene):
     """Filter::filterNeighbor on cells that hold 30 patches each: a patch meets ~750 others in its 5x5 cells, more neighbours than the
     first launch's row buffer holds (576), so it goes to the second launch (16384-slot id set, 64 KB of LDS) -- the path the
     reference's unbounded findNeighbors (patch_manager.cpp:671-728) needs and no other test reaches.  Removal counts, lists and the
     surviving patches equal the oracle's, whose table-size rule is the same."""
     sc = small_plane_scene
-    pool = _dense_pool(sc, per_cell=30)
+    pool = dense_pool(sc, per_cell=30)
     assert pool.shape[0] > 4000
-    o, e = _pair(sc, seed=3, enable_check=1, minImageNum=2)
+    o, e = pair(sc, seed=3, enable_check=1, minImageNum=2)
     o.add_patches(pool)
     e.upload_patches(pool)
     o.update_threshold()
@@ -632,8 +571,8 @@ def test_check_second_tier_dense_cells(small_plane_scene):
     set in global memory; the reference's findNeighbors is unbounded (patch_manager.cpp:671-728) and the oracle's table-size rule
     is the same.  Counters, lists and coordinates equal the oracle's."""
     sc = small_plane_scene
-    pool = _dense_pool(sc, per_cell=30, window=5)
-    o, e = _pair(sc, seed=4, enable_check=1, minImageNum=2, max_propag=8)
+    pool = dense_pool(sc, per_cell=30, window=5)
+    o, e = pair(sc, seed=4, enable_check=1, minImageNum=2, max_propag=8)
     o.add_patches(pool)
     e.upload_patches(pool)
     o.update_threshold()
@@ -678,7 +617,7 @@ def test_mixed_configurations(case):
         masks = np.full((nv, H, W), 255, np.uint8)
         masks[:, : H // 6, :] = 0
         masks[case % nv, :, : W // 5] = 60
-    o, e = _pair(sc, level=level, csize=csize, wsize=wsize, minImageNum=mi, seed=40 + case, enable_check=1, view_propagation=vprop, max_propag=maxp)
+    o, e = pair(sc, level=level, csize=csize, wsize=wsize, minImageNum=mi, seed=40 + case, enable_check=1, view_propagation=vprop, max_propag=maxp)
     if masks is not None:
         o.set_scene(sc, masks=masks)
         e.set_scene(sc, masks=masks)

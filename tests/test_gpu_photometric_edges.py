@@ -15,14 +15,11 @@ import numpy as np
 import pytest
 
 import edge_scenes as es
+from edge_scenes import GROUPS, group_name, level_counts, level_table, second_reading, within_bound
 from mvskit_amd import engine, synth
-from test_edge_scenes import GROUPS, group_name, level_counts, level_table, second_reading, within_bound
-from test_gpu_parity import REL_TOL, _cmp_records, _maps_close, _pair
-from test_gpu_ply_export import level_inputs, restate_ply
-from test_gpu_ragged_shapes import COUNTERS, REMOVALS, _loop_two_iterations, _pair_sized
-from test_gpu_sweep_resident import _sweep_grid
-from test_gpu_seed_points import _yardstick as points_yardstick
-from test_gpu_seed_random import _ranges, _strip, _yardstick as random_yardstick
+from parity_support import COUNTERS, REL_TOL, REMOVALS, cmp_records, loop_two_iterations, maps_close, pair, pair_sized, sweep_grid
+from ply_support import level_inputs, restate_ply
+from scene_support import points_yardstick, random_yardstick, ranges, strip
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -58,7 +55,7 @@ def _probe_chain(o, e, seeds, what, pool=None):
         f, r = o.preprocess(s)
         assert f == pre_flag[i], (what, "preProcess flag", i, f, pre_flag[i], s["coord"])
         if f == 0:
-            _cmp_records(pre_rec[i], r, f"{what} pre {i}")
+            cmp_records(pre_rec[i], r, f"{what} pre {i}")
             keep.append(i)
     fig = dict(seeds=len(seeds), ncc_exact=share_ncc, kept=len(keep), cost_exact=None, refine_exact=None, post_passed=0)
     # cost_func and refinePatch on the seeds themselves, with a depth step of the scenes' size (setScales gives 0.003 .. 0.03 here):
@@ -69,7 +66,7 @@ def _probe_chain(o, e, seeds, what, pool=None):
     fig["raw_cost_exact"] = _values_agree(cost, [o.cost(r, o.encode(r)) for r in raw], what + " cost of the seeds")
     ref_rec, _, _ = e.probe(engine.PROBE_REFINE, raw)
     for j, r in enumerate(raw):
-        _cmp_records(ref_rec[j], o.refine(r, (0, 0, j, 0))[1], f"{what} refine of seed {j}")
+        cmp_records(ref_rec[j], o.refine(r, (0, 0, j, 0))[1], f"{what} refine of seed {j}")
     if not keep:
         return fig
     sub = pre_rec[keep]
@@ -79,7 +76,7 @@ def _probe_chain(o, e, seeds, what, pool=None):
     post_in, exact = [], 0
     for j in range(len(keep)):
         _, r = o.refine(sub[j], (0, 0, j, 0))
-        _cmp_records(ref_rec[j], r, f"{what} refine {j}")
+        cmp_records(ref_rec[j], r, f"{what} refine {j}")
         exact += int(ref_rec[j]["coord"].tobytes() == r["coord"].tobytes() and ref_rec[j]["normal"].tobytes() == r["normal"].tobytes())
         post_in.append(r)
     fig["refine_exact"] = exact / len(keep)
@@ -91,7 +88,7 @@ def _probe_chain(o, e, seeds, what, pool=None):
         f, r = o.postprocess(post_in[j])
         assert f == post_flag[j], (what, "postProcess flag", j, f, post_flag[j])
         if f == 0:
-            _cmp_records(post_rec[j], r, f"{what} post {j}")
+            cmp_records(post_rec[j], r, f"{what} post {j}")
             assert post_rec[j]["nvimages"] == r["nvimages"]
             fig["post_passed"] += 1
     return fig
@@ -102,7 +99,7 @@ def _probe_chain(o, e, seeds, what, pool=None):
 @pytest.mark.parametrize("cls", range(8), ids=lambda c: es.CLASS_NAMES[c])
 def test_probes_per_class(cls, wsize):
     sc = es.patchwork()[0]
-    o, e = _pair(sc, minImageNum=2, wsize=wsize)
+    o, e = pair(sc, minImageNum=2, wsize=wsize)
     what = f"class {es.CLASS_NAMES[cls]}, wsize {wsize}"
     fig = _probe_chain(o, e, es.class_seeds(cls, 240), what)
     print(what, fig)
@@ -156,7 +153,7 @@ def test_converged_refiner_on_flat_classes(cls):
     For those candidates only the two-pass checks above apply; they are counted and printed.  For the others the record's two-pass
     cost is not above the start's by more than the same bound."""
     sc = es.patchwork()[0]
-    o, e = _pair(sc, minImageNum=2)
+    o, e = pair(sc, minImageNum=2)
     cands = [r for f, r in (o.preprocess(s) for s in es.class_seeds(cls, 1000)) if f == 0][:60]
     cands = np.array(cands, dtype=o.dtype)
     print("class", es.CLASS_NAMES[cls], "candidates", cands.shape[0])
@@ -211,9 +208,9 @@ def test_device_within_the_second_reading_bound(group):
     r = second_reading(group)
     if isinstance(group, tuple):
         sc, sizes, _, _ = es.mixed(group[1])
-        o, e = _pair_sized(sc, sizes=sizes, level=group[1], minImageNum=2)
+        o, e = pair_sized(sc, sizes=sizes, level=group[1], minImageNum=2)
     else:
-        o, e = _pair(es.patchwork()[0], minImageNum=2)
+        o, e = pair(es.patchwork()[0], minImageNum=2)
     _, ncc, _ = e.probe(engine.PROBE_NCC, r["seeds"])
     x = 1.0 - ncc.astype(np.float64)
     ok1, w1 = within_bound(x / (1.0 + 3.0 * x), r["incc"][:, 1])
@@ -237,14 +234,14 @@ def test_mixed_scale_probes(level):
     test refuses (test_level_coverage counts those per wanted value), and per wanted value the device keeps at least 30 pairs."""
     sc, sizes, grid, border = es.mixed(level)
     seeds, tab, oflags = level_table(level)
-    o, e = _pair_sized(sc, sizes=sizes, level=level, minImageNum=2)
+    o, e = pair_sized(sc, sizes=sizes, level=level, minImageNum=2)
     for v, (w, h) in enumerate(sizes):
         assert e.pyramid(v, level + 2).shape == (h >> (level + 2), w >> (level + 2), 3)
     pre_rec, _, flag = e.probe(engine.PROBE_PREPROCESS, seeds)
     bad = np.nonzero(flag != oflags)[0]
     assert bad.size == 0, (level, "preProcess flags differ", bad[:10], flag[bad[:10]], oflags[bad[:10]], seeds["coord"][bad[:10]])
     for i in np.nonzero(flag == 0)[0]:
-        _cmp_records(pre_rec[i], o.preprocess(seeds[i])[1], f"level {level} pre {i}")
+        cmp_records(pre_rec[i], o.preprocess(seeds[i])[1], f"level {level} pre {i}")
     kept = np.array([flag[t["seed"]] == 0 and int(t["view"]) in _kept_views(pre_rec[t["seed"]]) for t in tab])
     assert not (kept & ~tab["ok"]).any(), "the device keeps a view whose window the oracle refuses"
     dev = level_counts(np.rec.fromarrays([tab["wanted"], kept, np.zeros(kept.shape, bool)], names="wanted,ok,ref_ok"), level)
@@ -283,8 +280,8 @@ def test_mixed_scale_loop(level):
     counters, removals, lists, maps as test_gpu_ragged_shapes.py asserts them, ncc, bit-equal coordinates > 0.999, and every scale
     the reference view of at least 200 survivors."""
     sc, sizes, grid, _ = es.mixed(level)
-    o, e = _pair_sized(sc, sizes=sizes, level=level, csize=2, wsize=7, minImageNum=2, seed=7, enable_check=1)
-    _loop_two_iterations(o, e, sc, grid, None, f"mixed scale, level {level}")
+    o, e = pair_sized(sc, sizes=sizes, level=level, csize=2, wsize=7, minImageNum=2, seed=7, enable_check=1)
+    loop_two_iterations(o, e, sc, grid, None, f"mixed scale, level {level}")
     po = _survivors_agree(o, e, f"mixed scale, level {level}")
     refs = np.bincount(np.asarray(es.MIXED_SCALES)[po["images"][:, 0]], minlength=4)
     print("survivors by the scale (1, 1/2, 1/4, 1/8) of their reference view", refs)
@@ -298,9 +295,9 @@ def test_mixed_scale_loop_64_view_library():
     views to seconds): the two iterations and every comparison of test_mixed_scale_loop."""
     scales = tuple(k % 3 for k in range(20))
     sc, sizes, seeds, _ = es.mixed_scale_scene(scales=scales, W=256, H=192, arc_deg=100.0, stride=6)
-    o, e = _pair_sized(sc, sizes=sizes, level=0, csize=2, wsize=7, minImageNum=3, seed=9, enable_check=1, list_cap=64)
+    o, e = pair_sized(sc, sizes=sizes, level=0, csize=2, wsize=7, minImageNum=3, seed=9, enable_check=1, list_cap=64)
     assert e.list_cap == 64
-    _loop_two_iterations(o, e, sc, seeds, None, "20 views of mixed scale")
+    loop_two_iterations(o, e, sc, seeds, None, "20 views of mixed scale")
     po = _survivors_agree(o, e, "20 views of mixed scale")
     refs = np.bincount(np.asarray(scales)[po["images"][:, 0]], minlength=3)
     print("20 views: survivors by the scale (1, 1/2, 1/4) of the reference view", refs, "longest list", int(po["nimages"].max()))
@@ -330,7 +327,7 @@ def _loop(o, engines, seeds, iterations, what):
         print(what, "it", it, "oracle", co, ro)
         o.update_threshold()
         for e, grid in engines:
-            with _sweep_grid(grid):
+            with sweep_grid(grid):
                 ce, re_ = e.propagate(it), e.filter()
             assert co == ce, (what, grid, it, co, ce)
             assert [ro[k] for k in REMOVALS] == [re_[k] for k in REMOVALS], (what, grid, it, ro, re_)
@@ -348,14 +345,14 @@ def test_patchwork_loop():
     sc, classes, _, _ = es.patchwork()
     seeds = synth.make_seeds(sc, level=1, stride=2, seed=5)
     kw = dict(masks=_tile_masks(classes), level=1, csize=2, wsize=7, minImageNum=2, seed=7, enable_check=1)
-    o, e = _pair_sized(sc, **kw)
+    o, e = pair_sized(sc, **kw)
     e1 = engine.Engine(sc.nviews, **{k: v for k, v in kw.items() if k != "masks"})
     e1.set_scene(sc, masks=kw["masks"])
     total = _loop(o, [(e, None), (e1, 1)], seeds, 3, "patchwork loop")
     assert total["fail0"] > 100 and total["fail1"] > 100 and total["replaced"] > 100, total
     for x, grid in ((e, "default grid"), (e1, "grid of 1")):
         _survivors_agree(o, x, "patchwork loop, " + grid)
-        tot, bad = _maps_close(o, x, sc.nviews)
+        tot, bad = maps_close(o, x, sc.nviews)
         assert bad == 0 and tot > 2000, (grid, tot, bad)
         pairs = x.sweep_pairs()
         print("patchwork loop,", grid, "trials by how they were refined", pairs)
@@ -369,11 +366,11 @@ def test_flat_sphere_loop():
     sc, classes = es.patchwork_scene(arc_deg=45.0, kind="multi", flat_sphere=True)
     assert (classes == es.CONST).sum(axis=(1, 2)).min() > 4000
     seeds = synth.make_seeds(sc, level=1, stride=2, seed=5)
-    o, e = _pair(sc, level=1, minImageNum=2, seed=7, enable_check=1)
+    o, e = pair(sc, level=1, minImageNum=2, seed=7, enable_check=1)
     total = _loop(o, [(e, None)], seeds, 2, "flat sphere")
     assert total["fail0"] > 100 and total["inserted"] > 1000, total
     _survivors_agree(o, e, "flat sphere")
-    tot, bad = _maps_close(o, e, sc.nviews)
+    tot, bad = maps_close(o, e, sc.nviews)
     assert bad == 0 and tot > 2000, (tot, bad)
     o.close()
     e.close()
@@ -390,7 +387,7 @@ def _tie_engine(sc):
 
 
 def _chain_last_among_equals(e, sc, lo, hi, K, seed, tilt):
-    """test_gpu_seed_random._yardstick with the WRONG rule -- the highest k among equals (>= where the kernel has >) -- for scenes
+    """scene_support.random_yardstick with the WRONG rule -- the highest k among equals (>= where the kernel has >) -- for scenes
     without masks at level 0, csize 2: what a kernel that let a later hypothesis replace an equal earlier one would append"""
     thr = np.float32(e.thresholds()[1])
     kept = []
@@ -425,7 +422,7 @@ def _chain_of(e, pre, n, K, who, k):
     batch[who] = pre[who * K + k]
     ref, _, _ = e.probe(engine.PROBE_REFINE, batch)
     post, _, pflag = e.probe(engine.PROBE_POSTPROCESS, ref)
-    return {r.tobytes() for r in _strip(post[who[pflag[who] == 0]])}
+    return {r.tobytes() for r in strip(post[who[pflag[who] == 0]])}
 
 
 def _exact_ties(flag, ncc, K):
@@ -441,7 +438,7 @@ def test_ties_seed_random():
     class (a) itself does not tie -- its scores are rounding noise that differs from hypothesis to hypothesis -- and is counted apart."""
     sc, classes, _, _ = es.patchwork()
     K, seed, tilt = 8, 3, np.radians(10.0)
-    lo, hi = _ranges(sc)
+    lo, hi = ranges(sc)
     e = _tie_engine(sc)
     added = e.seed_random(lo, hi, hypotheses=K, seed=seed, max_tilt=tilt)  # min_ncc: the engine's nccThresholdBefore, -1 here
     got = e.patches()
@@ -450,10 +447,10 @@ def test_ties_seed_random():
     want, gated = random_yardstick(e, sc, lo, hi, K, seed, tilt, None, None, 0, 2)
     print(f"seed_random on the patchwork: {added} appended, chain keeps {want.shape[0]} of {gated} cells")
     assert got.shape[0] == want.shape[0] and got.shape[0] > 0
-    assert _strip(got).tobytes() == _strip(want).tobytes()
+    assert strip(got).tobytes() == strip(want).tobytes()
     wrong = _chain_last_among_equals(e, sc, lo, hi, K, seed, tilt)
-    assert _strip(wrong).tobytes() != _strip(got).tobytes(), "the rule among equal scores does not show in what is appended"
-    appended = {r.tobytes() for r in _strip(got)}
+    assert strip(wrong).tobytes() != strip(got).tobytes(), "the rule among equal scores does not show in what is appended"
+    appended = {r.tobytes() for r in strip(got)}
     ties = {es.CONST: 0, es.BLACK: 0}
     first = last = 0
     for v in range(sc.nviews):
@@ -499,7 +496,7 @@ def test_ties_seed_points():
     want, denom = points_yardstick(e, pts, K, 2)
     print(f"seed_points on the patchwork: {n} points, {added} appended, chain keeps {want.shape[0]} of {denom}")
     assert got.shape[0] == want.shape[0] and got.shape[0] > 0
-    assert _strip(got).tobytes() == _strip(want).tobytes()
+    assert strip(got).tobytes() == strip(want).tobytes()
     hyp, count = e.seed_points_hypotheses(pts, hypotheses=K)
     full = np.nonzero(np.repeat(count == K, K))[0]
     pre, flag, ncc = np.zeros(n * K, e.dtype), np.ones(n * K, np.int32), np.full(n * K, np.nan, F)
@@ -509,7 +506,7 @@ def test_ties_seed_points():
     who = np.nonzero(tie)[0]
     print("points whose 4 hypotheses tie exactly: class a", int((tie & (cls == es.CONST)).sum()), "class a0", int((tie & (cls == es.BLACK)).sum()))
     assert (tie & (cls == es.BLACK)).sum() >= 50
-    appended = {r.tobytes() for r in _strip(got)}
+    appended = {r.tobytes() for r in strip(got)}
     win, lose = _chain_of(e, pre, n, K, who, 0), _chain_of(e, pre, n, K, who, K - 1)
     print("hypothesis 0 reaches the pool for", len(win), "of them; records hypothesis 3 would have given instead:", len(lose - win))
     assert win <= appended and not ((lose - win) & appended)
@@ -548,7 +545,7 @@ def test_hostile_records_through_the_gates():
     normals 1e-4 off the camera's x axis: flags equal the oracle's, values are compared where the oracle's are finite and must be
     NaN where the oracle's are."""
     sc = es.patchwork()[0]
-    o, e = _pair(sc, minImageNum=2)
+    o, e = pair(sc, minImageNum=2)
     recs = es.hostile_records(sc)
     assert np.isfinite(recs["coord"]).all() and np.isfinite(recs["normal"]).all()
     _, got, _ = e.probe(engine.PROBE_NCC, recs)
@@ -562,7 +559,7 @@ def test_hostile_records_through_the_gates():
         f, want = o.preprocess(r)
         assert f == flag[i], (i, f, flag[i])
         if f == 0:
-            _cmp_records(pre_rec[i], want, f"hostile pre {i}")
+            cmp_records(pre_rec[i], want, f"hostile pre {i}")
     _, cost, _ = e.probe(engine.PROBE_COST, recs)
     expc = np.array([o.cost(r, o.encode(r)) for r in recs], F)
     print("hostile cost: oracle", expc, "device", cost)

@@ -7,39 +7,13 @@ Every case asserts its own raggedness from grid_dims / the pyramid shapes and it
 import numpy as np
 import pytest
 
-import oracle_binding as ob
 from mvskit_amd import engine, synth
-from test_gpu_parity import REL_TOL, _cmp_records, _maps_close, _pair
-from test_gpu_ply_export import level_inputs, restate_ply
-from test_oracle_second_reading import RefCam, ref_get_paxes, ref_project
+from parity_support import REL_TOL, cmp_records, grid_of, loop_two_iterations, pair, pair_sized, seeds_for_sizes
+from ply_support import level_inputs, restate_ply
+from second_reading import RefCam, ref_get_paxes, ref_project
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-COUNTERS = ("candidates", "prefiltered", "patches", "fail0", "fail1", "inserted", "replaced", "evals", "view_evals", "trimmed")
-REMOVALS = ("outside", "exact", "neighbor", "groups")
-
-
-def _grid(w, h, level, csize):
-    """gw, gh = ceil(W[level] / csize), ceil(H[level] / csize), W[level] = W >> level (patch_manager.cpp:36-37, image.cpp:135-138)"""
-    return -(-(w >> level) // csize), -(-(h >> level) // csize)
-
-
-def _pair_sized(sc, masks=None, sizes=None, full_cells=False, **kw):
-    """_pair with masks / per-view sizes.  full_cells: the engine's pool holds MAX_NUM_OF_PATCHES = max_propag * csize^2 patches in
-    every cell (mvs_config.max_patches).  The default is four per cell, half of that staged per pass, which the csize 3 scenes here,
-    with up to 18 per cell, exceed: the engine then refuses the pass with MVS_ERR_CAPACITY and names max_patches."""
-    if full_cells:
-        wh = sizes or [(sc.W, sc.H)] * sc.nviews
-        cells = sum(gw * gh for gw, gh in (_grid(w, h, kw["level"], kw["csize"]) for w, h in wh))
-        o = ob.Oracle(sc.nviews, schedule=ob.SCHEDULE_ENGINE, sum_mode=ob.SUM_TREE64, nthreads=8, **kw)
-        e = engine.Engine(sc.nviews, max_patches=cells * kw.get("max_propag", 2) * kw["csize"] ** 2, **kw)
-    else:
-        o, e = _pair(sc, **kw)
-        if masks is None and sizes is None:
-            return o, e
-    o.set_scene(sc, masks=masks, sizes=sizes)
-    e.set_scene(sc, masks=masks, sizes=sizes)
-    return o, e
 
 
 # ------------------------------------------------------------------ 1. pyramids and grids
@@ -57,8 +31,8 @@ def test_pyramids_and_grids_odd_sizes(W, H):
     sc = synth.make_scene(nviews=2, W=W, H=H, arc_deg=20.0, radius=4.0, kind="plane", keep_geometry=False)
     level = 1
     for csize in (2, 1, 3):
-        o, e = _pair(sc, level=level, csize=csize, minImageNum=2)
-        want = _grid(W, H, level, csize)
+        o, e = pair(sc, level=level, csize=csize, minImageNum=2)
+        want = grid_of(W, H, level, csize)
         for v in range(2):
             assert e.grid_dims(v) == o.grid_dims(v) == want, (csize, v)
         if csize == 2:
@@ -88,7 +62,7 @@ def test_views_below_eight_pixels_are_refused(W, H):
 
 # ------------------------------------------------------------------ 2. masks below an odd level 0
 def _one_iteration(sc, seeds, masks, **kw):
-    o, e = _pair_sized(sc, masks=masks, **kw)
+    o, e = pair_sized(sc, masks=masks, **kw)
     o.add_patches(seeds)
     e.upload_patches(seeds)
     co, ce = o.propagate(0), e.propagate(0)
@@ -119,7 +93,7 @@ def test_masks_on_odd_sizes_at_level_one():
     sc = synth.make_scene(nviews=4, W=203, H=151, arc_deg=45.0, radius=4.0, kind="multi")
     kw = dict(level=1, csize=1, wsize=5, minImageNum=2, seed=7)
     seeds = synth.make_seeds(sc, level=1, csize=1, stride=2, seed=5)
-    o, e = _pair(sc, **kw)
+    o, e = pair(sc, **kw)
     assert e.grid_dims(0) == o.grid_dims(0) == (101, 75) and e.pyramid(0, 1).shape == (75, 101, 3)
     o.close()
     e.close()
@@ -187,38 +161,6 @@ def _edge_counts(o, nviews):
     return out
 
 
-def _loop_two_iterations(o, e, sc, seeds, floors, what):
-    o.add_patches(seeds)
-    e.upload_patches(seeds)
-    for it in range(2):
-        co, ce = o.propagate(it), e.propagate(it)
-        print(what, "it", it, "oracle", co, "engine", ce)
-        assert co == ce, (what, it, co, ce)
-        assert set(COUNTERS) <= set(co)
-        if floors is not None:
-            assert 2 * co["patches"] >= floors[it][0] and 2 * co["inserted"] >= floors[it][1], (what, it, co, floors)
-        ro, re_ = o.filter(), e.filter()
-        print(what, "it", it, "removed: oracle", ro, "engine", re_)
-        assert [ro[k] for k in REMOVALS] == [re_[k] for k in REMOVALS], (what, it, ro, re_)
-        if it == 0:
-            assert sum(ro[k] > 0 for k in REMOVALS) >= 3, (what, ro)
-        o.update_threshold()
-        e.update_threshold()
-    po, pe = o.patches(), e.patches()
-    assert po.shape == pe.shape and po.shape[0] > 0
-    np.testing.assert_array_equal(po["nimages"], pe["nimages"])
-    np.testing.assert_array_equal(po["images"], pe["images"])
-    np.testing.assert_array_equal(po["vimages"], pe["vimages"])
-    np.testing.assert_allclose(pe["coord"], po["coord"], rtol=REL_TOL, atol=1e-6)
-    np.testing.assert_allclose(pe["normal"], po["normal"], rtol=0, atol=REL_TOL)
-    tot, bad = _maps_close(o, e, sc.nviews)
-    same = float((pe["coord"] == po["coord"]).all(axis=1).mean())
-    print(what, "pool", po.shape[0], "map cells", tot, "bad", bad, "bit-equal coordinates", same)
-    assert bad == 0 and tot > 2000, (what, tot, bad)
-    assert same > 0.99, (what, same)
-    return po
-
-
 @pytest.mark.parametrize("case", range(len(LOOP_CASES)))
 def test_whole_loop_on_ragged_grids(case):
     """Two iterations of PmMvps::run's loop (Propagate::run, Filter::run, updateThreshold; Optim::check from the second) on grids with
@@ -239,13 +181,13 @@ def test_whole_loop_on_ragged_grids(case):
     masks = np.full((nv, H, W), 255, np.uint8)
     masks[:, :, : W // 7] = 0
     masks[0, H - 1, :] = 0
-    o, e = _pair_sized(sc, masks=masks, full_cells=csize == 3, level=level, csize=csize, wsize=wsize, minImageNum=mi, seed=7, enable_check=1,
+    o, e = pair_sized(sc, masks=masks, full_cells=csize == 3, level=level, csize=csize, wsize=wsize, minImageNum=mi, seed=7, enable_check=1,
                        view_propagation=vprop, max_propag=maxp)
     gw, gh = e.grid_dims(0)
     assert (gw, gh) == o.grid_dims(0)
     Wl, Hl = e.pyramid(0, level).shape[1], e.pyramid(0, level).shape[0]
     assert gw % 2 == 1 or gh % 2 == 1 or Wl % csize or Hl % csize, (gw, gh, Wl, Hl)
-    po = _loop_two_iterations(o, e, sc, seeds, table, f"case {case}")
+    po = loop_two_iterations(o, e, sc, seeds, table, f"case {case}")
     k0, k1 = _edge_counts(o, nv)
     grids = [o.grid_dims(v) for v in range(nv)]
     li = _list_entries_in_outer_cells(sc, po, level, csize, grids, "images", "nimages")
@@ -310,7 +252,7 @@ def test_window_test_at_coarser_levels_of_an_odd_image():
     levels: Optim::preProcess keeps a two-view patch only if the second view passes, and the flag must equal the oracle's for
     every seed."""
     sc = synth.make_scene(nviews=3, W=383, H=217, arc_deg=80.0, radius=2.0, kind="plane")
-    o, e = _pair(sc, level=0, minImageNum=2)
+    o, e = pair(sc, level=0, minImageNum=2)
     assert [e.pyramid(2, l).shape[:2] for l in range(3)] == [(217, 383), (108, 191), (54, 95)]
     seeds = np.concatenate([_border_seeds(sc, 0, 2), _border_seeds(sc, 2, 0), _border_seeds(sc, 1, 2), _border_seeds(sc, 0, 1)[::3]])
     cams = [RefCam(sc.P[v], 0) for v in range(sc.nviews)]
@@ -321,7 +263,7 @@ def test_window_test_at_coarser_levels_of_an_odd_image():
         flags[i], r = o.preprocess(s)
         assert flags[i] == pre_flag[i], (i, levels[i], s["coord"], flags[i], pre_flag[i])
         if flags[i] == 0:
-            _cmp_records(pre_rec[i], r, f"pre {i}")
+            cmp_records(pre_rec[i], r, f"pre {i}")
     coarse = levels >= 1
     print("seeds", len(seeds), "sampled at level >= 1:", int(coarse.sum()), "accepted", int((flags == 0).sum()), "rejected", int((flags != 0).sum()),
           "coarse accepted", int((coarse & (flags == 0)).sum()), "coarse rejected", int((coarse & (flags != 0)).sum()))
@@ -338,37 +280,11 @@ def test_window_test_at_coarser_levels_of_an_odd_image():
 
 # ------------------------------------------------------------------ 6. views of unequal size
 # (W, H, arc, level, csize, seed stride, the views' sizes): 128x88, 128x88, 121x80, 128x86 cells; 64x44, 64x44, 60x40, 64x43 cells
-# last: (patches, inserted) of the oracle in iterations 0 and 1 when the cases were chosen, with the seed lists of _seeds_for_sizes
+# last: (patches, inserted) of the oracle in iterations 0 and 1 when the cases were chosen, with the seed lists of seeds_for_sizes
 UNEQUAL_CASES = [
     (256, 176, 45.0, 0, 2, 3, [(256, 176), (255, 175), (241, 160), (256, 171)], ((34320, 33016), (101584, 81801))),
     (384, 264, 30.0, 1, 3, 1, [(384, 264), (383, 263), (361, 240), (384, 257)], ((59059, 46551), (51282, 35095))),
 ]
-
-
-def _seeds_for_sizes(sc, seeds, sizes, level):
-    """make_seeds lists every view that sees the point inside the scene's full image; a view cropped to sizes[v] sees less.  The
-    same rule with the view's own size: a view is listed only if the point projects at least 8 pixels inside its image, and a seed
-    whose reference view is not is dropped -- the reference indexes m_pgrids with a patch's m_grids unchecked (filter.cpp:113-119),
-    so a record that lists a view outside whose grid it lies is not an input it takes."""
-    P = sc.P.astype(np.float64)
-    out = []
-    for s in seeds:
-        keep = []
-        for v in s["images"][: s["nimages"]]:
-            x = P[v] @ s["coord"].astype(np.float64)
-            u, w = x[0] / x[2], x[1] / x[2]
-            if x[2] > 0 and 8 <= u < sizes[v][0] - 8 and 8 <= w < sizes[v][1] - 8:
-                keep.append(int(v))
-            elif v == s["images"][0]:
-                keep = []
-                break
-        if len(keep) >= 2:
-            r = s.copy()
-            r["images"][:] = 0
-            r["images"][: len(keep)] = keep
-            r["nimages"] = len(keep)
-            out.append(r)
-    return np.array(out, dtype=seeds.dtype)
 
 
 @pytest.mark.parametrize("case", range(len(UNEQUAL_CASES)))
@@ -380,20 +296,20 @@ def test_views_of_unequal_size(case):
     whose colours are sampled per listed view, against the restatement of tests/test_gpu_ply_export.py."""
     W, H, arc, level, csize, stride, sizes, table = UNEQUAL_CASES[case]
     sc = synth.make_scene(nviews=4, W=W, H=H, arc_deg=arc, radius=4.0, kind="multi")
-    o, e = _pair_sized(sc, sizes=sizes, full_cells=csize == 3, level=level, csize=csize, wsize=7, minImageNum=2, seed=7, enable_check=1)
+    o, e = pair_sized(sc, sizes=sizes, full_cells=csize == 3, level=level, csize=csize, wsize=7, minImageNum=2, seed=7, enable_check=1)
     grids = []
     for v, (w, h) in enumerate(sizes):
         for l in range(level + 3):
             pe, po = e.pyramid(v, l), o.pyramid(v, l)
             assert pe.shape == po.shape == (h >> l, w >> l, 3), (v, l)
             np.testing.assert_array_equal(pe, po, err_msg=f"view {v} level {l}")
-        want = _grid(w, h, level, csize)
+        want = grid_of(w, h, level, csize)
         assert e.grid_dims(v) == o.grid_dims(v) == want, v
         grids.append(want)
     assert len(set(grids)) >= 3 and len({g[0] for g in grids}) >= 2 and len({g[1] for g in grids}) >= 2
-    seeds = _seeds_for_sizes(sc, synth.make_seeds(sc, level=level, csize=csize, stride=stride, seed=5), sizes, level)
+    seeds = seeds_for_sizes(sc, synth.make_seeds(sc, level=level, csize=csize, stride=stride, seed=5), sizes, level)
     assert seeds.shape[0] > 1500
-    po = _loop_two_iterations(o, e, sc, seeds, table, f"unequal sizes, level {level}")
+    po = loop_two_iterations(o, e, sc, seeds, table, f"unequal sizes, level {level}")
     refs = np.bincount(po["images"][:, 0], minlength=4)
     print("reference views of the survivors", refs)
     assert refs.min() >= 1000, refs

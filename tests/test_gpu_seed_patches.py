@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from mvskit_amd import build, engine, synth
-from test_seed_plys import GOLDEN_JPG, H, W, euler_camera, write_ply
+from ply_support import GOLDEN_JPG, H, W, euler_camera, write_ply
 
 pytestmark = pytest.mark.gpu
 F = np.float32

@@ -1,6 +1,6 @@
 """The warm start on the GPU: mvs_engine_seed_points against code from before it, mvs_engine_probe's ops 1, 0, 2 and 3.
 
-The yardstick chain (_yardstick): the hypotheses of every point (mvs_engine_seed_points_hypotheses) go through MVS_PROBE_PREPROCESS and
+The yardstick chain (points_yardstick of tests/scene_support.py): the hypotheses of every point (mvs_engine_seed_points_hypotheses) go through MVS_PROBE_PREPROCESS and
 MVS_PROBE_NCC; numpy picks each point's winner among its count[i] hypotheses -- preProcess flag 0, the highest score strictly above
 min_ncc, the lowest k among equals; the winner of point i sits at batch index i of a batch of npoints records (a valid record in the
 other slots), so that MVS_PROBE_REFINE's key (0, 0, i, 0) is the kernel's; then MVS_PROBE_REFINE and MVS_PROBE_POSTPROCESS, and the
@@ -15,9 +15,10 @@ pixel of every view, concatenated: what structure-from-motion would hand over, w
 import numpy as np
 import pytest
 
+from maps_reading import center64, oaxis64
 from mvskit_amd import engine, synth
-from test_gpu_parity import REL_TOL, _pair
-from test_gpu_seed_random import COUNTERS, PLAIN, _mask_at, _scene, _strip
+from parity_support import COUNTERS, REL_TOL, pair
+from scene_support import PLAIN, cached_scene, mask_at, points_yardstick, strip
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -24  # the unit roundoff of float32
@@ -26,46 +27,6 @@ U = 2.0 ** -24  # the unit roundoff of float32
 def _points(sc, stride):
     pts = np.concatenate([sc.points[v, stride // 2::stride, stride // 2::stride].reshape(-1, 3) for v in range(sc.nviews)])
     return np.ascontiguousarray(pts[np.isfinite(pts).all(axis=1)], dtype=np.float32)
-
-
-def _yardstick(e, pts, K, min_images, min_ncc=None):
-    """-> (the records the chain keeps, in point order; the number of points that at least min_images views qualify for)"""
-    thr = np.float32(e.thresholds()[1] if min_ncc is None else min_ncc)
-    n = pts.shape[0]
-    if n == 0:
-        return np.zeros(0, e.dtype), 0
-    hyp, count = e.seed_points_hypotheses(pts, hypotheses=K, min_ncc=min_ncc)
-    assert hyp.shape[0] == n * K and count.shape[0] == n
-    _, views = e.seed_points_hypotheses(pts, hypotheses=e.cfg.nviews)
-    denom = int((views >= min_images).sum())
-    assert (count == np.minimum(views, K)).all()
-    slot = (np.arange(K)[None, :] < count[:, None]).ravel()
-    assert not hyp[~slot].view(np.uint8).any(), "a slot behind count[i] is not zero bytes"
-    idx = np.nonzero(slot)[0]
-    if idx.size == 0:
-        return np.zeros(0, e.dtype), denom
-    p, _, f = e.probe(engine.PROBE_PREPROCESS, hyp[idx])
-    _, s, _ = e.probe(engine.PROBE_NCC, p)
-    pre = np.zeros(n * K, e.dtype)
-    flag = np.ones(n * K, np.int32)
-    ncc = np.full(n * K, np.nan, np.float32)
-    pre[idx], flag[idx], ncc[idx] = p, f, s
-    best = np.full(n, thr, np.float32)
-    win = np.full(n, -1)
-    for k in range(K):  # ascending k and a strict comparison: the lowest k among equals; a NaN never wins
-        with np.errstate(invalid="ignore"):
-            take = slot[k::K] & (flag[k::K] == 0) & (ncc[k::K] > best)
-        best[take] = ncc[k::K][take]
-        win[take] = k
-    who = np.nonzero(win >= 0)[0]
-    if who.size == 0:
-        return np.zeros(0, e.dtype), denom
-    first = who[0] * K + win[who[0]]
-    batch = np.repeat(pre[first:first + 1], n)
-    batch[who] = pre[who * K + win[who]]
-    ref, _, _ = e.probe(engine.PROBE_REFINE, batch)
-    post, _, pflag = e.probe(engine.PROBE_POSTPROCESS, ref)
-    return post[who[pflag[who] == 0]], denom
 
 
 def _case(sc, ekw, K, stride=4, pts=None, masks=None, sizes=None, list_cap=None, seeds=None, refiner=None, min_kept=0.5):
@@ -88,12 +49,12 @@ def _case(sc, ekw, K, stride=4, pts=None, masks=None, sizes=None, list_cap=None,
     e.clear_patches()
     if seeds is not None:
         e.upload_patches(seeds)
-    want, denom = _yardstick(e, pts, K, ekw["minImageNum"])
+    want, denom = points_yardstick(e, pts, K, ekw["minImageNum"])
     e.close()
     print(f"seed_points: {pts.shape[0]} points, {added} appended, chain keeps {want.shape[0]} of {denom} points with enough views "
           f"({want.shape[0] / max(denom, 1):.3f})")
     assert got.shape[0] == want.shape[0], (got.shape[0], want.shape[0])
-    assert _strip(got).tobytes() == _strip(want).tobytes()
+    assert strip(got).tobytes() == strip(want).tobytes()
     if min_kept:
         assert want.shape[0] >= min_kept * denom, f"the yardstick chain keeps {want.shape[0]} patches for {denom} points: the case shows too little"
     return got
@@ -103,7 +64,7 @@ def _case(sc, ekw, K, stride=4, pts=None, masks=None, sizes=None, list_cap=None,
 @pytest.mark.parametrize("K", [3, 1])
 def test_plain(K):
     """3 views of 96 x 64, csize 2, level 0, depth 0, every 4th pixel: 1152 points"""
-    sc = _scene(3, 96, 64, 30.0)
+    sc = cached_scene(3, 96, 64, 30.0)
     assert _points(sc, 4).shape[0] == 1152
     got = _case(sc, PLAIN, K=K)
     assert (got["nvimages"] == 0).all()
@@ -111,7 +72,7 @@ def test_plain(K):
 
 def test_level_and_depth():
     """level 1 and depth 1 over a few uploaded patches: postProcess reads the depth maps of the pool as it was at entry"""
-    sc = _scene(3, 192, 128, 30.0)
+    sc = cached_scene(3, 192, 128, 30.0)
     seeds = synth.make_seeds(sc, level=1, csize=2, stride=8)
     assert 10 < seeds.shape[0] < 200
     _case(sc, dict(level=1, csize=2, minImageNum=2, depth=1), K=3, stride=8, seeds=seeds)
@@ -119,24 +80,24 @@ def test_level_and_depth():
 
 def test_ragged_grids():
     """97 x 63 and csize 3: 33 x 21 cells"""
-    _case(_scene(3, 97, 63, 30.0), dict(level=0, csize=3, minImageNum=2, depth=0), K=3)
+    _case(cached_scene(3, 97, 63, 30.0), dict(level=0, csize=3, minImageNum=2, depth=0), K=3)
 
 
 def test_unequal_views():
     """views of 96 x 64 and 80 x 56: a point outside the smaller crop qualifies for one view only and leaves the denominator"""
-    _case(_scene(2, 96, 64, 15.0), PLAIN, K=2, sizes=[(96, 64), (80, 56)])
+    _case(cached_scene(2, 96, 64, 15.0), PLAIN, K=2, sizes=[(96, 64), (80, 56)])
 
 
 @pytest.mark.parametrize("list_cap", [16, 64])
 def test_many_views(list_cap):
     """20 views of 48 x 32, every view a hypothesis: the 16-view library cuts the lists, the 64-view library (192-byte records) holds them"""
-    _case(_scene(20, 48, 32, 60.0), dict(level=0, csize=2, minImageNum=3, depth=0), K=20, list_cap=list_cap)
+    _case(cached_scene(20, 48, 32, 60.0), dict(level=0, csize=2, minImageNum=3, depth=0), K=20, list_cap=list_cap)
 
 
 # ---- further cases, each held to bit-equality with the chain
 def test_mask_band():
     """view 0 with a background band, views 1 and 2 without a mask: no hypothesis with reference view 0 projects into the band"""
-    sc = _scene(3, 96, 64, 30.0)
+    sc = cached_scene(3, 96, 64, 30.0)
     band = np.full((sc.H, sc.W), 255, np.uint8)
     band[:, 20:31] = 0
     masks = [band, None, None]
@@ -159,7 +120,7 @@ def test_mask_band():
 
 
 def test_converged_refiner():
-    _case(_scene(3, 96, 64, 30.0), PLAIN, K=3, refiner=dict(mode="converged", max_evals=200, xtol=1e-3))
+    _case(cached_scene(3, 96, 64, 30.0), PLAIN, K=3, refiner=dict(mode="converged", max_evals=200, xtol=1e-3))
 
 
 def _bad_points(sc):
@@ -172,7 +133,7 @@ def test_points_that_give_nothing():
     """bad points interleaved with good ones get count 0 and give nothing; the good points' hypotheses are those of the call without the
     bad ones, and so are -- in records and order -- their patches under the CONVERGED refiner.  (HALVING draws under the point's index
     in the call, which the interleaving shifts: there the chain on the mixed list is the yardstick.)"""
-    sc = _scene(3, 96, 64, 30.0)
+    sc = cached_scene(3, 96, 64, 30.0)
     good = _points(sc, 4)
     bad = _bad_points(sc)
     at = np.array([0, 5, 300, 301, 302, 1151, 1152])  # positions in `good` a bad point goes in front of (1152: behind the last)
@@ -191,14 +152,14 @@ def test_points_that_give_nothing():
     n = e.seed_points(good, hypotheses=3)
     assert n > 500 and e.seed_points(mixed, hypotheses=3) == n
     pool = e.patches()
-    assert _strip(pool[:n]).tobytes() == _strip(pool[n:]).tobytes()
+    assert strip(pool[:n]).tobytes() == strip(pool[n:]).tobytes()
     assert e.seed_points(bad, hypotheses=3) == 0
     e.close()
 
 
 def test_perturbed_points():
     """every point moved by 0.1 scene units along the ray to its own view: held to bit-equality only"""
-    sc = _scene(3, 96, 64, 30.0)
+    sc = cached_scene(3, 96, 64, 30.0)
     pts, rays = [], []
     for v in range(3):
         p = sc.points[v, 2::4, 2::4].reshape(-1, 3)
@@ -212,7 +173,7 @@ def test_perturbed_points():
 
 
 def _engine(monkeypatch=None, grid=None, **kw):
-    sc = _scene(3, 96, 64, 30.0)
+    sc = cached_scene(3, 96, 64, 30.0)
     if grid:
         monkeypatch.setenv("MVS_SWEEP_GRID", grid)
     e = engine.Engine(3, enable_check=0, **{**PLAIN, **kw})
@@ -234,7 +195,7 @@ def test_determinism_chunks_and_sweep_grid(monkeypatch):
         assert n > 500 and e.seed_points(pts) == n
         pools.append(e.patches())
         assert pools[-1].shape[0] == 2 * n
-        assert _strip(pools[-1][:n]).tobytes() == _strip(pools[-1][n:]).tobytes()
+        assert strip(pools[-1][:n]).tobytes() == strip(pools[-1][n:]).tobytes()
         hyp = e.seed_points_hypotheses(pts)
         pools.append(hyp[0].tobytes() + hyp[1].tobytes())  # the window streams in chunks too
         e.close()
@@ -287,25 +248,6 @@ def test_state_and_empty():
 
 
 # ---- steps 1 and 2 against a float64 reading
-def _center64(P32):
-    """the camera centre as the engine derives it from the level-0 projection: in double, in this order, rounded to float32"""
-    P = P32.astype(np.float64)
-    a, b, c, d, ee, f, g, h, i = P[0, 0], P[0, 1], P[0, 2], P[1, 0], P[1, 1], P[1, 2], P[2, 0], P[2, 1], P[2, 2]
-    A, B, C = ee * i - f * h, -(d * i - f * g), d * h - ee * g
-    det = a * A + b * B + c * C
-    inv = [A, -(b * i - c * h), b * f - c * ee, B, a * i - c * g, -(a * f - c * d), C, -(a * h - b * g), a * ee - b * d]
-    q = P[:, 3]
-    return np.array([-(inv[3 * r] * q[0] + inv[3 * r + 1] * q[1] + inv[3 * r + 2] * q[2]) / det for r in range(3)]).astype(np.float32).astype(np.float64)
-
-
-def _oaxis64(P32):
-    """the optical axis row as the engine holds it: the third row of the projection over the float32 norm of its first three entries
-    (the engine's norm can differ from this one in the last bit: one unit roundoff on every term of the depth)"""
-    r = P32[2].astype(np.float64)
-    n = np.float32(np.sqrt(np.float32((r[:3] ** 2).sum())))
-    return (P32[2] / n).astype(np.float32).astype(np.float64)
-
-
 def _reading(sc, pts, level, sizes, masks):
     """float64: per (point, view) the gate, the depth, the squared camera distance, the sum of the depth's term magnitudes, and whether
     the pair keeps the margins inside which the float32 gate must agree: the projection more than 1e-3 pixel from a rounding boundary
@@ -320,7 +262,7 @@ def _reading(sc, pts, level, sizes, masks):
         P = P32.astype(np.float64).copy()
         P[:2] /= 2.0 ** level
         w, h = sizes[v][0] >> level, sizes[v][1] >> level
-        o = _oaxis64(P32)
+        o = oaxis64(P32)
         depth[:, v] = X @ o[:3] + o[3]
         mag[:, v] = np.abs(X * o[:3]).sum(axis=1) + abs(o[3])
         x = X @ P[:, :3].T + P[:, 3]
@@ -330,12 +272,12 @@ def _reading(sc, pts, level, sizes, masks):
         inside = (x[:, 2] > 0) & (fx >= 0) & (fx < w) & (fy >= 0) & (fy < h)
         fg = np.ones(n, bool)
         if masks is not None and masks[v] is not None:
-            m = _mask_at(masks[v], sizes[v], level)
+            m = mask_at(masks[v], sizes[v], level)
             fg = m[np.clip(fy, 0, h - 1).astype(int), np.clip(fx, 0, w - 1).astype(int)]
         ok[:, v] = inside & fg & (depth[:, v] > 0)
         edge = np.minimum(np.abs(px - np.rint(px)), np.abs(py - np.rint(py)))
         safe[:, v] = (edge > 1e-3) & (np.abs(depth[:, v]) > 1e-3 * mag[:, v]) & (np.abs(x[:, 2]) > 1e-3 * (np.abs(X * P[2, :3]).sum(axis=1) + abs(P[2, 3])))
-        c = _center64(P32)
+        c = center64(P32)
         centers.append(c)
         dist[:, v] = ((c - X) ** 2).sum(axis=1)
     return ok, safe, depth, dist, mag, np.array(centers)
@@ -359,7 +301,7 @@ HYP_CASES = {
 
 def _hyp_setup(name):
     cs = HYP_CASES[name]
-    sc = _scene(*cs["scene"])
+    sc = cached_scene(*cs["scene"])
     masks = None
     if cs["band"]:
         band = np.full((sc.H, sc.W), 255, np.uint8)
@@ -465,7 +407,7 @@ def test_depth_ranges(name):
 
 
 def test_depth_ranges_of_a_fully_masked_view():
-    sc = _scene(3, 96, 64, 30.0)
+    sc = cached_scene(3, 96, 64, 30.0)
     e = engine.Engine(3, enable_check=0, **PLAIN)
     e.set_scene(sc, masks=[np.zeros((sc.H, sc.W), np.uint8), None, None])
     pts = _points(sc, 4)
@@ -492,7 +434,7 @@ def test_warm_then_cold_then_propagate():
     pool = e.patches()
     assert pool.shape[0] == n + m
     e.close()
-    o, e2 = _pair(sc, minImageNum=2, seed=7)
+    o, e2 = pair(sc, minImageNum=2, seed=7)
     o.add_patches(pool)
     e2.upload_patches(pool)
     co, ce = o.propagate(0), e2.propagate(0)

@@ -8,9 +8,7 @@ import numpy as np
 import pytest
 
 from mvskit_amd import engine, synth
-from test_gpu_parity import REL_TOL, _dense_pool, _pair
-from test_gpu_ragged_shapes import COUNTERS, _grid, _pair_sized, _seeds_for_sizes
-from test_gpu_sweep_resident import _pools_match_oracle, _sweep_grid
+from parity_support import COUNTERS, GRID_KW, REL_TOL, SEEDED, dense_pool, grid_of, pair, pair_sized, pools_match_oracle, seeds_for_sizes, sweep_grid
 
 pytestmark = pytest.mark.gpu
 
@@ -33,9 +31,6 @@ def _propagate_by_passes(e, it):
 
 
 # ------------------------------------------------------------------ 1. listing too few jobs; view propagation
-SEEDED = (0, 2)
-
-
 @pytest.fixture(scope="module")
 def two_of_five(small_multi_scene):
     """Seeds in views 0 and 2 of 5: the cells of views 1, 3 and 4 hold memberships of those patches but no patch whose reference
@@ -47,7 +42,7 @@ def two_of_five(small_multi_scene):
 
 def test_two_seeded_views_of_five_with_check(two_of_five):
     sc, seeds = two_of_five
-    o, e = _pair(sc, seed=5, enable_check=1)
+    o, e = pair(sc, seed=5, enable_check=1)
     o.add_patches(seeds)
     e.upload_patches(seeds)
     bound = sum(_jobs_of_view(e, v) for v in SEEDED)
@@ -65,14 +60,14 @@ def test_two_seeded_views_of_five_with_check(two_of_five):
         o.update_threshold()
         e.update_threshold()  # m_depth 2: Optim::check in the second iteration
     assert co["patches"] > 0
-    _pools_match_oracle(o.patches(), e.patches())
+    pools_match_oracle(o.patches(), e.patches())
     o.close()
     e.close()
 
 
 def test_view_propagation_lists_the_own_cell_sources(two_of_five):
     sc, seeds = two_of_five
-    o, e = _pair(sc, seed=5, view_propagation=1)
+    o, e = pair(sc, seed=5, view_propagation=1)
     e0 = engine.Engine(sc.nviews, level=0, csize=2, wsize=7, minImageNum=3, enable_check=0, seed=5)
     e0.set_scene(sc)
     o.add_patches(seeds)
@@ -135,7 +130,7 @@ def _case_odd_width():
     """65 x 49 cells: a ghost job (cx == gw) in every other row; 4851 jobs per colour = 37 chunks of 128 and one of 115, 38 chunks
     over 8 queues (queues 0-5 hold five, 6-7 four)"""
     sc = synth.make_scene(nviews=3, W=130, H=98, arc_deg=30.0, radius=4.0, kind="plane")
-    o, e = _pair(sc, minImageNum=2, seed=11)
+    o, e = pair(sc, minImageNum=2, seed=11)
     assert e.grid_dims(0) == (65, 49) and sum(_jobs_of_view(e, v) for v in range(3)) == 4851 and 4851 % 128 == 115
     return o, e, synth.make_seeds(sc, stride=3, seed=5)
 
@@ -143,7 +138,7 @@ def _case_odd_width():
 def _case_less_than_a_chunk():
     """8 x 6 cells in 2 views: 48 jobs, one partial chunk in queue 0 and seven empty queues"""
     sc = synth.make_scene(nviews=2, W=16, H=12, arc_deg=10.0, radius=4.0, kind="plane")
-    o, e = _pair(sc, minImageNum=2, seed=5)
+    o, e = pair(sc, minImageNum=2, seed=5)
     assert sum(_jobs_of_view(e, v) for v in range(2)) == 48
     return o, e, synth.make_seeds(sc, stride=1, seed=5)
 
@@ -152,10 +147,10 @@ def _case_unequal_views():
     """1376 + 1240 + 1344 jobs: chunks 10 and 20 of the 31 straddle two views"""
     sizes = [(128, 86), (121, 80), (128, 83)]
     sc = synth.make_scene(nviews=3, W=128, H=88, arc_deg=30.0, radius=4.0, kind="multi")
-    o, e = _pair_sized(sc, sizes=sizes, level=0, csize=2, wsize=7, minImageNum=2, seed=7)
-    assert [e.grid_dims(v) for v in range(3)] == [_grid(w, h, 0, 2) for w, h in sizes]
+    o, e = pair_sized(sc, sizes=sizes, level=0, csize=2, wsize=7, minImageNum=2, seed=7)
+    assert [e.grid_dims(v) for v in range(3)] == [grid_of(w, h, 0, 2) for w, h in sizes]
     assert [_jobs_of_view(e, v) for v in range(3)] == [1376, 1240, 1344]
-    return o, e, _seeds_for_sizes(sc, synth.make_seeds(sc, level=0, csize=2, stride=2, seed=5), sizes, 0)
+    return o, e, seeds_for_sizes(sc, synth.make_seeds(sc, level=0, csize=2, stride=2, seed=5), sizes, 0)
 
 
 @pytest.mark.parametrize("make", [_case_odd_width, _case_less_than_a_chunk, _case_unequal_views])
@@ -169,15 +164,12 @@ def test_awkward_shapes(make):
     print("seeds", seeds.shape[0], "oracle", co, "engine", ce, "listed", listed, "of", 2 * njobs)
     assert set(COUNTERS) <= set(co) and co == ce, (co, ce)
     assert co["inserted"] > 0 and 0 < listed <= 2 * njobs
-    _pools_match_oracle(o.patches(), e.patches())
+    pools_match_oracle(o.patches(), e.patches())
     o.close()
     e.close()
 
 
 # ------------------------------------------------------------------ 4. the grid size must not matter
-GRID_KW = dict(level=0, csize=2, wsize=7, minImageNum=2, seed=11, enable_check=1)
-
-
 def _two_iterations(e, seeds):
     e.upload_patches(seeds)
     c = [e.propagate(0)]
@@ -194,7 +186,7 @@ def grid_default():
     seeds = synth.make_seeds(sc, stride=3, seed=5)
     e = engine.Engine(sc.nviews, **GRID_KW)
     e.set_scene(sc)
-    with _sweep_grid(None):
+    with sweep_grid(None):
         res = _two_iterations(e, seeds)
     e.close()
     return sc, seeds, res
@@ -207,7 +199,7 @@ def test_lists_are_drained_at_any_grid_size(grid_default, grid):
     sc, seeds, (cd, ld, pd) = grid_default
     e = engine.Engine(sc.nviews, **GRID_KW)
     e.set_scene(sc)
-    with _sweep_grid(grid):
+    with sweep_grid(grid):
         c, listed, p = _two_iterations(e, seeds)
     e.close()
     print("grid", grid, "listed", listed, "counters", c)
@@ -221,21 +213,21 @@ def test_cell_that_gives_up_is_followed_by_listed_cells(small_plane_scene):
     """The scene of test_gpu_sweep_resident.py::test_cell_that_gives_up_is_followed_by_clean_cells: a wave whose cell goes to the
     second tier takes the next entry of its list; the second tier runs the cells of retry_jobs as before."""
     sc = small_plane_scene
-    pool = _dense_pool(sc, per_cell=30, window=5)
-    o, e = _pair(sc, seed=4, enable_check=1, minImageNum=2, max_propag=8)
+    pool = dense_pool(sc, per_cell=30, window=5)
+    o, e = pair(sc, seed=4, enable_check=1, minImageNum=2, max_propag=8)
     o.add_patches(pool)
     e.upload_patches(pool)
     o.update_threshold()
     e.update_threshold()
     co = o.propagate(1)
-    with _sweep_grid(2):
+    with sweep_grid(2):
         ce = e.propagate(1)
         t = e.timing()
     print("oracle", co, "engine", ce, "timing", t)
     assert t["check_retried_cells"] > 0 and t["sweep_jobs_listed"] > t["check_retried_cells"], t
     assert set(COUNTERS) <= set(co) and co == ce, (co, ce)
     po, pe = o.patches(), e.patches()
-    _pools_match_oracle(po, pe)
+    pools_match_oracle(po, pe)
     assert (pe["coord"] == po["coord"]).all(axis=1).mean() > 0.99
     o.close()
     e.close()

@@ -2,7 +2,7 @@
 to find room (refine_patch_pair).  Which trials are refined together must not change a bit of the result: every case
 runs the HIP engine with the pairing on and with MVS_SWEEP_PAIR=0 (read on every launch: every trial alone) and asserts that the two pools
 are the same bytes, the two counter lists equal, and both equal to the CPU oracle's (ENGINE schedule) with the pool matching it as
-test_gpu_sweep_resident.py::_pools_match_oracle does.
+parity_support.pools_match_oracle does.
 
 mvs_engine_sweep_pairs (Engine.sweep_pairs) says how the trials were refined; every case asserts the statistic it is about, so that
 none passes without having met what it is named for, and that nothing is refined as a pair with the switch off."""
@@ -14,10 +14,7 @@ import pytest
 
 import oracle_binding as ob
 from mvskit_amd import engine, synth
-from test_gpu_parity import _dense_pool
-from test_gpu_ragged_shapes import COUNTERS
-from test_gpu_sweep_joblist import SEEDED
-from test_gpu_sweep_resident import GRID_KW, REMOVALS, _pools_match_oracle, _sweep_grid, _two_iterations
+from parity_support import COUNTERS, GRID_KW, REMOVALS, SEEDED, dense_pool, pools_match_oracle, sweep_grid, two_iterations
 
 pytestmark = pytest.mark.gpu
 
@@ -59,7 +56,7 @@ def _engine_run(sc, pool, plan, on, grid=None, refiner=None, before=None, **ekw)
     if refiner:
         e.set_refiner(refiner)
     e.set_scene(sc)
-    with _pairing(on), _sweep_grid(grid):
+    with _pairing(on), sweep_grid(grid):
         e.upload_patches(pool)
         if before:
             before(e)
@@ -73,7 +70,7 @@ def _engine_run(sc, pool, plan, on, grid=None, refiner=None, before=None, **ekw)
 
 
 def _oracle_run(sc, pool, plan, before=None, **kw):
-    """-> (counters, removals, pool) of the CPU oracle as test_gpu_parity.py::_pair sets it up"""
+    """-> (counters, removals, pool) of the CPU oracle as parity_support.pair sets it up"""
     okw = dict(level=0, csize=2, wsize=7, minImageNum=3, schedule=ob.SCHEDULE_ENGINE, sum_mode=ob.SUM_TREE64, enable_check=0, nthreads=8)
     okw.update(kw)
     o = ob.Oracle(sc.nviews, **okw)
@@ -100,7 +97,7 @@ def _check_case(oracle, on, off):
     for it in range(len(oc)):
         assert set(COUNTERS) <= set(oc[it]) and oc[it] == c1[it], (it, oc[it], c1[it])
     assert orem == r1
-    _pools_match_oracle(po, p1)
+    pools_match_oracle(po, p1)
     # with the switch off the same trials wait for each other and are then refined one by one
     assert s0["paired"] == 0 and s0["can_pair"] == s1["can_pair"] == s1["paired"], (s0, s1)
     for k in engine.Engine.SWEEP_PAIR_KEYS[1:5]:
@@ -116,8 +113,8 @@ def plane_case():
     Optim::check): the oracle and the engine without pairing, computed once and left unchanged"""
     sc = synth.make_scene(nviews=3, W=130, H=98, arc_deg=30.0, radius=4.0, kind="plane")
     seeds = synth.make_seeds(sc, stride=3, seed=5)
-    oracle = _oracle_run(sc, seeds, _two_iterations, **GRID_KW)
-    off = _engine_run(sc, seeds, _two_iterations, False, **GRID_KW)
+    oracle = _oracle_run(sc, seeds, two_iterations, **GRID_KW)
+    off = _engine_run(sc, seeds, two_iterations, False, **GRID_KW)
     return sc, seeds, oracle, off
 
 
@@ -127,7 +124,7 @@ def test_plain_pairs_with_check(plane_case, grid):
     wave (MVS_SWEEP_GRID=1) runs every cell, pairs and all, one after the other: the stash and the working block of one cell's pair must
     not leak into the next cell."""
     sc, seeds, oracle, off = plane_case
-    on = _engine_run(sc, seeds, _two_iterations, True, grid=grid, **GRID_KW)
+    on = _engine_run(sc, seeds, two_iterations, True, grid=grid, **GRID_KW)
     s, tot = _check_case(oracle, on, off)
     assert s["paired"] > 1000 and tot["patches"] > 2000
     assert oracle[0][1]["patches"] > 1000  # the iteration with Optim::check has its share of them
@@ -191,7 +188,7 @@ def test_cell_that_gives_up_with_a_candidate_pending(small_plane_scene):
     max_propag 8, two resident waves): a cell whose Optim::check outgrows the LDS id set gives up in the middle of finishing a pair --
     the second candidate is dropped with everything else of the cell, and the second tier runs the cell again, pairs and all."""
     sc = small_plane_scene
-    pool = _dense_pool(sc, per_cell=30, window=5)
+    pool = dense_pool(sc, per_cell=30, window=5)
     kw = dict(seed=4, enable_check=1, minImageNum=2, max_propag=8)
 
     def before(x):

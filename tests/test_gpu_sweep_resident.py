@@ -4,49 +4,16 @@ test_gpu_parity.py::test_mixed_configurations, at grid sizes set through the dev
 
 Every cell runs the same instructions on the same inputs whatever wave takes it, so the number of resident waves must not change
 a bit of the result: counters, the order of the pool and every field of every record."""
-import os
-from contextlib import contextmanager
-
 import numpy as np
 import pytest
 
 from mvskit_amd import engine, synth
-from test_gpu_parity import REL_TOL, _cmp_records, _dense_pool, _pair
-from test_gpu_ragged_shapes import COUNTERS, _grid, _pair_sized, _seeds_for_sizes
+from parity_support import COUNTERS, GRID_KW, dense_pool, grid_of, pair, pair_sized, pools_match_oracle, seeds_for_sizes, sweep_grid, two_iterations
 
 pytestmark = pytest.mark.gpu
-REMOVALS = ("outside", "exact", "neighbor", "groups")
-
-
-@contextmanager
-def _sweep_grid(n):
-    """MVS_SWEEP_GRID=<n> around the engine calls of the block (None: the default grid), restored afterwards"""
-    old = os.environ.pop("MVS_SWEEP_GRID", None)
-    if n is not None:
-        os.environ["MVS_SWEEP_GRID"] = str(n)
-    try:
-        yield
-    finally:
-        os.environ.pop("MVS_SWEEP_GRID", None)
-        if old is not None:
-            os.environ["MVS_SWEEP_GRID"] = old
-
-
-def _pools_match_oracle(po, pe):
-    assert po.shape == pe.shape and po.shape[0] > 0
-    np.testing.assert_array_equal(po["nimages"], pe["nimages"])
-    np.testing.assert_array_equal(po["images"], pe["images"])
-    np.testing.assert_array_equal(po["vimages"], pe["vimages"])
-    np.testing.assert_allclose(pe["coord"], po["coord"], rtol=REL_TOL, atol=1e-6)
-    np.testing.assert_allclose(pe["normal"], po["normal"], rtol=0, atol=REL_TOL)
-    for k in range(0, po.shape[0], max(po.shape[0] // 64, 1)):
-        _cmp_records(pe[k], po[k], f"record {k}")
 
 
 # ------------------------------------------------------------------ 1. the grid size must not matter
-GRID_KW = dict(level=0, csize=2, wsize=7, minImageNum=2, seed=11, enable_check=1)
-
-
 @pytest.fixture(scope="module")
 def grid_scene():
     """3 views of 130 x 98 at csize 2: a 65 x 49 grid, ceil(65 / 2) * 49 = 1617 jobs per view and 4851 per colour, i.e. 38 chunks of
@@ -54,31 +21,20 @@ def grid_scene():
     (the second with Optim::check) and the engine's at the default grid are computed once and left unchanged."""
     sc = synth.make_scene(nviews=3, W=130, H=98, arc_deg=30.0, radius=4.0, kind="plane")
     seeds = synth.make_seeds(sc, stride=3, seed=5)
-    o, e = _pair(sc, **GRID_KW)
-    assert e.grid_dims(0) == o.grid_dims(0) == _grid(130, 98, 0, 2) == (65, 49)
+    o, e = pair(sc, **GRID_KW)
+    assert e.grid_dims(0) == o.grid_dims(0) == grid_of(130, 98, 0, 2) == (65, 49)
     njobs = sum(((gw + 1) // 2) * gh for gw, gh in (e.grid_dims(v) for v in range(3)))
     assert njobs == 4851 and njobs % 128 != 0 and (-(-njobs // 128)) % 8 != 0
     o.add_patches(seeds)
-    oc, orem = _two_iterations(o)
+    oc, orem = two_iterations(o)
     po = o.patches()
     o.close()
-    with _sweep_grid(None):
+    with sweep_grid(None):
         e.upload_patches(seeds)
-        ec, erem = _two_iterations(e)
+        ec, erem = two_iterations(e)
         pe = e.patches()
     e.close()
     return dict(scene=sc, seeds=seeds, oracle=(oc, orem, po), default=(ec, erem, pe))
-
-
-def _two_iterations(x):
-    """Propagate::run(0), Filter::run, updateThreshold (m_depth 2: Optim::check from here), Propagate::run(1)"""
-    counters, removed = [], []
-    counters.append(x.propagate(0))
-    r = x.filter()
-    removed.append([r[k] for k in REMOVALS])
-    x.update_threshold()
-    counters.append(x.propagate(1))
-    return counters, removed
 
 
 def test_default_grid_matches_oracle(grid_scene):
@@ -90,7 +46,7 @@ def test_default_grid_matches_oracle(grid_scene):
         assert oc[it] == ec[it], (it, oc[it], ec[it])
     assert orem == erem
     assert oc[0]["inserted"] > 1000 and oc[1]["patches"] > 1000  # both iterations have work in most chunks
-    _pools_match_oracle(po, pe)
+    pools_match_oracle(po, pe)
 
 
 @pytest.mark.parametrize("grid", [1, 3, 8, 9])
@@ -103,16 +59,16 @@ def test_grid_size_does_not_matter(grid_scene, grid):
     _, _, pd = grid_scene["default"]
     e = engine.Engine(sc.nviews, **GRID_KW)
     e.set_scene(sc)
-    with _sweep_grid(grid):
+    with sweep_grid(grid):
         e.upload_patches(seeds)
-        ec, erem = _two_iterations(e)
+        ec, erem = two_iterations(e)
         pe = e.patches()
     e.close()
     for it in range(2):
         assert all(oc[it][k] == ec[it][k] for k in COUNTERS), (grid, it, oc[it], ec[it])
         assert oc[it] == ec[it], (grid, it, oc[it], ec[it])
     assert orem == erem
-    _pools_match_oracle(po, pe)
+    pools_match_oracle(po, pe)
     assert pe.shape == pd.shape
     np.testing.assert_array_equal(pe["coord"].view(np.uint32), pd["coord"].view(np.uint32))
     for f in pe.dtype.names:
@@ -126,7 +82,7 @@ def test_fewer_jobs_than_one_chunk():
     without any.  First a pass in which no cell has a source (the empty pool): all-zero counters, nothing staged (job_nstage zero
     everywhere: inserted + replaced == 0 and the pool as it was).  Then one iteration on seeds."""
     sc = synth.make_scene(nviews=2, W=16, H=12, arc_deg=10.0, radius=4.0, kind="plane")
-    o, e = _pair(sc, minImageNum=2, seed=5)
+    o, e = pair(sc, minImageNum=2, seed=5)
     assert e.grid_dims(0) == o.grid_dims(0) == (8, 6)
     c0 = e.propagate(0)
     assert all(c0[k] == 0 for k in COUNTERS), c0
@@ -138,7 +94,7 @@ def test_fewer_jobs_than_one_chunk():
     co, ce = o.propagate(0), e.propagate(0)
     print("seeds", seeds.shape[0], "oracle", co, "engine", ce)
     assert set(COUNTERS) <= set(co) and co == ce, (co, ce)
-    _pools_match_oracle(o.patches(), e.patches())
+    pools_match_oracle(o.patches(), e.patches())
     o.close()
     e.close()
 
@@ -149,21 +105,21 @@ def test_cell_that_gives_up_is_followed_by_clean_cells(small_plane_scene):
     Optim::check too large for its LDS id set hands the cell to the second tier and goes on with later cells, whose results must
     not carry anything of the abandoned cell (its counts, its live list, its staged records)."""
     sc = small_plane_scene
-    pool = _dense_pool(sc, per_cell=30, window=5)
-    o, e = _pair(sc, seed=4, enable_check=1, minImageNum=2, max_propag=8)
+    pool = dense_pool(sc, per_cell=30, window=5)
+    o, e = pair(sc, seed=4, enable_check=1, minImageNum=2, max_propag=8)
     o.add_patches(pool)
     e.upload_patches(pool)
     o.update_threshold()
     e.update_threshold()  # m_depth 2: Optim::check runs
     co = o.propagate(1)
-    with _sweep_grid(2):
+    with sweep_grid(2):
         ce = e.propagate(1)
         t = e.timing()
     print("oracle", co, "engine", ce, "retried cells", t["check_retried_cells"])
     assert t["check_retried_cells"] > 0, t
     assert set(COUNTERS) <= set(co) and co == ce, (co, ce)
     po, pe = o.patches(), e.patches()
-    _pools_match_oracle(po, pe)
+    pools_match_oracle(po, pe)
     assert (pe["coord"] == po["coord"]).all(axis=1).mean() > 0.99
     o.close()
     e.close()
@@ -177,23 +133,23 @@ def test_views_of_unequal_size_on_three_waves():
     the oracle's."""
     sizes = [(128, 86), (121, 80), (128, 83)]
     sc = synth.make_scene(nviews=3, W=128, H=88, arc_deg=30.0, radius=4.0, kind="multi")
-    o, e = _pair_sized(sc, sizes=sizes, level=0, csize=2, wsize=7, minImageNum=2, seed=7)
+    o, e = pair_sized(sc, sizes=sizes, level=0, csize=2, wsize=7, minImageNum=2, seed=7)
     grids = [e.grid_dims(v) for v in range(3)]
-    assert grids == [o.grid_dims(v) for v in range(3)] == [_grid(w, h, 0, 2) for w, h in sizes]
+    assert grids == [o.grid_dims(v) for v in range(3)] == [grid_of(w, h, 0, 2) for w, h in sizes]
     bases = np.cumsum([0] + [((gw + 1) // 2) * gh for gw, gh in grids])
     assert len(set(grids)) == 3 and list(bases) == [0, 1376, 2616, 3960] and all(b % 128 for b in bases[1:])
-    seeds = _seeds_for_sizes(sc, synth.make_seeds(sc, level=0, csize=2, stride=2, seed=5), sizes, 0)
+    seeds = seeds_for_sizes(sc, synth.make_seeds(sc, level=0, csize=2, stride=2, seed=5), sizes, 0)
     assert seeds.shape[0] > 300
     o.add_patches(seeds)
     co = o.propagate(0)
-    with _sweep_grid(3):
+    with sweep_grid(3):
         e.upload_patches(seeds)
         ce = e.propagate(0)
     print("oracle", co, "engine", ce)
     assert set(COUNTERS) <= set(co) and co == ce, (co, ce)
     assert co["inserted"] > 500
     po, pe = o.patches(), e.patches()
-    _pools_match_oracle(po, pe)
+    pools_match_oracle(po, pe)
     assert len(set(np.unique(po["images"][:, 0]))) == 3  # every view is the reference view of some patch
     o.close()
     e.close()

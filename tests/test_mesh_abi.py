@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 from mvskit_amd import build, engine
+from mvskit_amd.engine import MVS_ERR_ARG
 
-MVS_ERR_ARG = -1
 SYMBOLS = ("mvs_engine_tsdf", "mvs_engine_extract_mesh", "mvs_engine_mesh")
 
 

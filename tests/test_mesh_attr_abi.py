@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 from mvskit_amd import build, engine
+from mvskit_amd.engine import MVS_ERR_ARG
 
-MVS_ERR_ARG = -1
 SYMBOLS = ("mvs_default_mesh_colouring", "mvs_engine_mesh_normals", "mvs_engine_mesh_colours")
 HEADER = os.path.join(build.ROOT, "include", "mvskit_engine.h")
 

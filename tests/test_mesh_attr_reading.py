@@ -3,18 +3,9 @@ import numpy as np
 
 import mesh_attr_reading as ar
 import mesh_reading as mr
+from maps_reading import cameras64, render_agree64
 from mvskit_amd import synth
-from test_gpu_maps import _agree64, _cams, _render64
-
-
-def grid_mesh(nx, ny, z=None):
-    """nx x ny vertices at integer (x, y) and height z[y, x] (default 0), two counter-clockwise triangles a cell: normals towards +z"""
-    y, x = np.mgrid[0:ny, 0:nx]
-    zz = np.zeros((ny, nx)) if z is None else z
-    verts = np.stack([x, y, zz], axis=-1).reshape(-1, 3).astype(np.float32)
-    p = (y[:-1, :-1] * nx + x[:-1, :-1]).ravel()
-    tris = np.concatenate([np.stack([p, p + 1, p + nx + 1], 1), np.stack([p, p + nx + 1, p + nx], 1)]).astype(np.int32)
-    return verts, tris
+from scene_support import grid_mesh
 
 
 def test_flat_grid_gives_the_axis_exactly():
@@ -66,13 +57,12 @@ def _plane_setup(colour):
     """three views of the plane z = 0 behind one exact patch that every pixel renders, images of one colour"""
     sc = synth.make_scene(nviews=3, W=48, H=32, arc_deg=30.0, radius=4.0, kind="plane")
     sizes = [(sc.W, sc.H)] * 3
-    cams = _cams(sc, 0, sizes)
+    cams = cameras64(sc, 0, sizes)
     pat = np.zeros(1, synth.PATCH_DTYPE)
     pat["coord"][0, :4] = (0, 0, 0, 1)
     pat["normal"][0, :3] = (0, 0, 1)
     ids = [np.zeros((sc.H, sc.W), np.int32) for _ in range(3)]
-    X = [_render64(pat, ids[v], cams[v])[1] for v in range(3)]
-    bits, unsure = zip(*[_agree64(pat, ids, X, cams, v, 0.004, 0.98) for v in range(3)])
+    bits, unsure = render_agree64(pat, ids, cams, 0.004, 0.98)
     images = [np.full((sc.H, sc.W, 3), colour, np.uint8) for _ in range(3)]
     return pat, ids, bits, unsure, cams, images
 

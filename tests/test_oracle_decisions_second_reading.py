@@ -1,7 +1,7 @@
 """Second reading of the DECISION stages of the hot path -- which views a patch keeps, which view becomes its reference, whether a
 view sees it, what it gains, which patch a depth-map cell names, what Filter::filterOutside / filterExact remove -- written in numpy
 straight from the reference's source text (file:line cited per function) and sharing no code with oracle/pmmvs_oracle.cpp; the
-arithmetic underneath (projection, axes, textures, INCC, isNeighbor) is the second reading of tests/test_oracle_second_reading.py.
+arithmetic underneath (projection, axes, textures, INCC, isNeighbor) is the second reading of tests/second_reading.py.
 Compared with the oracle (ENGINE schedule, reference summation order) on a populated scene: the decisions must be IDENTICAL.
 The reference ships no vectors and cannot be built here (Eigen / CImg / NLopt absent): two independent restatements of the same
 source agreeing is as far as pinning goes."""
@@ -10,8 +10,8 @@ import pytest
 
 import oracle_binding as ob
 from mvskit_amd import synth
-from test_oracle_second_reading import (F, RefCam, ref_dot, ref_get_paxes, ref_get_tex, ref_get_unit, ref_is_neighbor, ref_normalize,
-                                        ref_compute_incc, ref_project, ref_pyr_down, ref_quad_residual, ref_robustincc, ref_set_scales)
+from second_reading import (F, RefCam, ref_compute_incc, ref_dot, ref_get_paxes, ref_get_tex, ref_get_unit, ref_is_neighbor, ref_normalize,
+                            ref_project, ref_pyr_down, ref_quad_residual, ref_robustincc, ref_set_scales)
 
 LEVEL, CSIZE, WSIZE, MIN_IMAGE_NUM = 0, 2, 7, 2
 COS60 = F(np.cos(F(60.0 * np.pi / 180.0)))  # cosf(m_angleThreshold0) = cosf(m_angleThreshold1), pmmvps.cpp:54-55

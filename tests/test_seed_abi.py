@@ -6,8 +6,7 @@ import numpy as np
 import pytest
 
 from mvskit_amd import build, engine
-
-MVS_ERR_ARG = -1
+from mvskit_amd.engine import MVS_ERR_ARG
 
 
 @pytest.mark.parametrize("cap", [16, 32, 64])

@@ -6,16 +6,14 @@ import ctypes as C
 import math
 import os
 import shutil
-import struct
 
 import numpy as np
 import pytest
 
 from mvskit_amd import build, engine
+from ply_support import GOLDEN_JPG, H, NV, W, euler_camera, write_ply
 
 F = np.float32
-GOLDEN_JPG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jpeg", "baseline_444.jpg")  # 40 x 30
-W, H, NV = 40, 30, 4
 
 
 @pytest.fixture(scope="module")
@@ -29,51 +27,6 @@ def host():
     L.mvshost_ply_probe.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(C.c_int)]
     L.mvshost_ply_probe.restype = C.c_longlong
     return L
-
-
-def write_ply(path, fmt, xyz, normals=None, extra_colour=False, faces=None):
-    n = len(xyz)
-    head = ["ply", f"format {fmt} 1.0", "comment written by tests/test_seed_plys.py", f"element vertex {n}",
-            "property float x", "property float y", "property double z" if fmt != "ascii" else "property float z"]
-    if extra_colour:
-        head += ["property uchar red", "property uchar green", "property uchar blue"]
-    if normals is not None:
-        head += ["property float nx", "property float ny", "property float nz"]
-    if faces is not None:
-        head += [f"element face {len(faces)}", "property list uchar int vertex_indices"]
-    head.append("end_header")
-    with open(path, "wb") as f:
-        f.write(("\n".join(head) + "\n").encode())
-        e = "<" if fmt == "binary_little_endian" else ">"
-        for i in range(n):
-            if fmt == "ascii":
-                vals = [repr(float(v)) for v in xyz[i]]
-                if extra_colour:
-                    vals += ["10", "20", "30"]
-                if normals is not None:
-                    vals += [repr(float(v)) for v in normals[i]]
-                f.write((" ".join(vals) + "\n").encode())
-            else:
-                f.write(struct.pack(e + "ffd", *[float(v) for v in xyz[i]]))
-                if extra_colour:
-                    f.write(bytes([10, 20, 30]))
-                if normals is not None:
-                    f.write(struct.pack(e + "fff", *[float(v) for v in normals[i]]))
-        for face in faces or []:
-            if fmt == "ascii":
-                f.write((f"{len(face)} " + " ".join(str(v) for v in face) + "\n").encode())
-            else:
-                f.write(struct.pack(e + "B" + "i" * len(face), len(face), *face))
-
-
-def euler_camera(a, b, g, t, fx=60.0, fy=60.0, cx=W / 2.0, cy=H / 2.0):
-    """CONTOUR2 line of a camera (camera.cpp:117-134, quat2proj 241-261) and its rotation."""
-    s1, s2, s3, c1, c2, c3 = (math.sin(math.radians(a)), math.sin(math.radians(b)), math.sin(math.radians(g)),
-                              math.cos(math.radians(a)), math.cos(math.radians(b)), math.cos(math.radians(g)))
-    R = np.array([[c2 * c3, c3 * s2 * s1 - s3 * c1, c3 * s2 * c1 + s3 * s1], [s3 * c2, s3 * s2 * s1 + c3 * c1, s3 * s2 * c1 - c3 * s1],
-                  [-s2, c2 * s1, c2 * c1]])
-    text = "CONTOUR2\n%r %r 0 %r %r 0\n%r %r %r\n%r %r %r\n" % tuple(float(v) for v in (fx, fy, cx, cy, a, b, g, t[0], t[1], t[2]))
-    return text, R
 
 
 @pytest.fixture(scope="module")

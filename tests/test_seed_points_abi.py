@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 from mvskit_amd import build, engine
+from mvskit_amd.engine import MVS_ERR_ARG
 
-MVS_ERR_ARG = -1
 SYMBOLS = ("mvs_default_seed_points", "mvs_engine_seed_points", "mvs_engine_seed_points_hypotheses", "mvs_engine_depth_ranges")
 
 

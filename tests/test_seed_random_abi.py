@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 from mvskit_amd import build, engine
+from mvskit_amd.engine import MVS_ERR_ARG
 
-MVS_ERR_ARG = -1
 SYMBOLS = ("mvs_default_seed_random", "mvs_engine_seed_random", "mvs_engine_seed_random_hypotheses")
 
 

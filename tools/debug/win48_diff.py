@@ -9,13 +9,13 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle_binding as ob  # noqa: E402
 from mvskit_amd import engine, synth  # noqa: E402
-from test_gpu_fullsize import _cells_in_ref_view  # noqa: E402
+from parity_support import cells_in_ref_view  # noqa: E402
 
 W, H = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (3840, 2160)
 sc = synth.make_scene(nviews=48, W=W, H=H, arc_deg=110.0, radius=4.0, kind="multi")
 views = [47, 46, 44, 40, 33, 20]
 seeds = synth.make_seeds(sc, level=0, csize=2, stride=3, seed=31, views=views)
-cx, cy = _cells_in_ref_view(sc, seeds)
+cx, cy = cells_in_ref_view(sc, seeds)
 ref = seeds["images"][:, 0].astype(np.int64)
 gw, gh = W // 2, H // 2
 corners = {47: (gw - 70 - 64, gh - 70 - 64), 46: (70, gh - 70 - 64), 44: (gw - 70 - 64, 70), 40: (70, 70), 33: (gw - 150 - 64, gh // 2), 20: (gw // 2, gh - 150 - 64)}

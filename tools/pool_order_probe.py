@@ -1,8 +1,8 @@
 """What would a pool ordered by (reference view, cell) buy?  Times one Propagate::run and one Filter::run on the pool as the
 engine leaves it (creation order) and on the same patches re-uploaded in cell order."""
-import sys, time
+import os, sys, time
 import numpy as np
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mvskit_amd import engine, synth
 
 sc = synth.make_scene(nviews=12, W=1920, H=1080, arc_deg=110.0, radius=4.0, kind="multi")

@@ -1,8 +1,9 @@
 """Reconstruction quality on a synthetic scene: every patch against the analytic surface at the pixel of its reference
 view it projects to (depth along the optical axis, normal)."""
+import os
 import sys
 import numpy as np
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mvskit_amd import engine, synth
 
 
