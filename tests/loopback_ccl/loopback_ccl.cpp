@@ -2,7 +2,7 @@
 //
 // RCCL refuses a communicator whose ranks share one device, and a gpurun box has one MI355X, so the engine's multi-rank
 // exchange (mvs_engine_exchange: count all-gather, in-place block broadcasts, commit of the union) could only ever run
-// there with world = 1.  This library exports the eight nccl* entry points the engine binds (mvs_engine.cpp, struct Rccl)
+// there with world = 1.  This library exports the eight nccl* entry points the engine binds (rccl() in mvs_engine_comm.cpp, struct Rccl)
 // and moves the bytes through a POSIX shared-memory segment between PROCESSES OF ONE HOST: every collective is executed
 // eagerly and synchronously (stream sync, device -> segment, barrier, segment -> device, barrier), group calls are no-ops.
 // tests/test_gpu_dist.py points MVS_CCL_LIBRARY at it to run 2 and 3 engine ranks on the one GPU through the real C ABI.

@@ -79,7 +79,7 @@ def test_struct_sizes_of_the_binding():
 
 def test_loopback_transport_exports_what_the_engine_binds():
     """tests/loopback_ccl (the shared-memory stand-in for RCCL that lets several engine ranks share the one GPU of a test box)
-    must export exactly the eight entry points mvs_engine.cpp binds through MVS_CCL_LIBRARY."""
+    must export exactly the eight entry points mvs_engine_comm.cpp binds through MVS_CCL_LIBRARY."""
     import subprocess
 
     d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "loopback_ccl")
@@ -88,6 +88,6 @@ def test_loopback_transport_exports_what_the_engine_binds():
     have = {line.split()[-1] for line in out.splitlines() if " T " in line}
     want = {"ncclGetUniqueId", "ncclCommInitRank", "ncclCommDestroy", "ncclAllGather", "ncclBroadcast", "ncclGroupStart", "ncclGroupEnd", "ncclGetErrorString"}
     assert want <= have
-    src = open(os.path.join(os.path.dirname(d), "..", "mvskit_amd", "csrc", "mvs_engine.cpp")).read()
+    src = open(os.path.join(os.path.dirname(d), "..", "mvskit_amd", "csrc", "mvs_engine_comm.cpp")).read()
     for name in want:
         assert f'"{name}"' in src, name

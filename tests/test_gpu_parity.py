@@ -394,7 +394,7 @@ def test_filter_run_matches_oracle(small_multi_scene):
 
 
 def test_filter_packed_geometry_gives_what_the_records_give(small_multi_scene, monkeypatch):
-    """Inside Filter::run the stages read the patches they meet from a 32-byte packed copy (DParams::geo, mvs_engine.cpp pack_geometry)
+    """Inside Filter::run the stages read the patches they meet from a 32-byte packed copy (DParams::geo, mvs_engine_filter.cpp pack_geometry)
     instead of the records.  The fault-injection build can switch the copy off (MVS_FAULT_NOPACK): both ways the same removals and the
     same pool, byte for byte, as the oracle's.  A pool with a seed whose coord.w is not 1 cannot be packed (the copy leaves w out): the
     engine must notice and read the records."""
