@@ -501,6 +501,78 @@ int mvs_engine_mesh_normals(mvs_engine* e, int64_t n_v, const float* verts, int6
 int mvs_engine_mesh_colours(mvs_engine* e, const mvs_maps_config* c, const mvs_mesh_colouring* m, int64_t n_v, const float* verts,
                             const float* normals /* or NULL */, uint8_t* rgb /* [n_v][3] */, uint8_t* used /* [n_v] or NULL */);
 
+/* Mesh clean-up (no reference counterpart): connected components, the removal of small components and unused vertices, and Taubin
+ * smoothing of a triangle mesh -- that of mvs_engine_mesh, or any caller's.  verts: n_v x 3 floats, tris: n_t x 3 int32 vertex ids.  The
+ * three calls are stateless, only read the engine and need a device but no views, like mvs_engine_extract_mesh; all pointers may be host
+ * or device memory (hipMemcpyDefault).  Every result is an integer or comes from an integer sum: it does not depend on the order in which
+ * the triangles are listed or in which the hardware meets them, and two calls give the same bytes.  A refused call writes nothing.
+ * mvs_engine_mesh_components:
+ *     GRAPH         the vertices are 0 .. n_v-1; every triangle joins its three ids.  A triangle with repeated ids joins what it names and
+ *                   still counts as a triangle.  Components are those of this graph: two pieces that touch in one vertex are one component.
+ *     LABEL         label[i] = the smallest vertex id of i's component (a lock-free union-find in which the smaller id becomes the root,
+ *                   then flattened): canonical.  A vertex that no triangle names is its own component.
+ *     NTRIS         ntris[i] = the number of triangles of i's component; 0 for an unused vertex.
+ *     n_components  the number of components with at least one triangle.
+ *   label, ntris and n_components may each be NULL.  LIMITS: n_v, n_t in 0 .. 2^30.  Device memory for the call: 8 bytes a vertex and 12 a
+ *   triangle.
+ *   MVS_ERR_ARG, checked in this order before the handle is read: a negative count or a count over the limit; tris NULL with n_t > 0; no
+ *   engine.  Then, after one validating pass on the device: an id outside 0 .. n_v - 1.  MVS_ERR_HIP: an allocation or copy failed.
+ * mvs_engine_mesh_prune:
+ *     KEEP          a triangle is kept when its component has ntris >= min_triangles and, with largest_only, is the component with the most
+ *                   triangles (among equals the one with the smaller label: a 64-bit maximum over (ntris << 32) | (0xffffffff - label)).
+ *     VERTICES      a vertex is kept when a kept triangle names it: min_triangles = 1 already drops the rim vertices of
+ *                   mvs_engine_extract_mesh that no triangle uses.
+ *     ORDER         kept vertices and kept triangles stay in their input order; the new ids are the exclusive scan of the keep flags.
+ *                   Position bytes are copied unchanged; triangle ids are rewritten, their corner order unchanged.
+ *     vmap          vmap[i] = the new id of vertex i, or -1; may be NULL.  Where whole components go, the normals of the pruned mesh are
+ *                   the kept rows of the normals of the full mesh.
+ *   Sizes follow mvs_engine_extract_mesh: with out_verts == NULL, out_tris == NULL or a cap (in vertices / triangles) too small, *n_v_out
+ *   and *n_t_out are the exact counts and nothing else is written, vmap neither; MVS_ERR_CAPACITY when a non-NULL output is too small.  An
+ *   output that ALIASES an input is not supported.  LIMITS: as above.  Device memory for the call: 16 bytes a vertex and 20 a triangle
+ *   (labels, counts, flags and their scans), and with outputs the positions (12 bytes a vertex) and the pruned mesh (12 bytes a kept vertex, 12 a kept triangle).
+ *   MVS_ERR_ARG, checked in this order before the handle is read: p NULL; min_triangles < 1; largest_only outside 0/1; a negative count or a
+ *   count over the limit; verts NULL with n_v > 0; tris NULL with n_t > 0; n_v_out or n_t_out NULL; a negative cap; no engine.  Then, after
+ *   the validating pass: an id outside 0 .. n_v - 1.
+ * mvs_engine_mesh_smooth: Taubin lambda|mu smoothing as an ORDER-FREE INTEGER SUM.  An iteration is a STEP with factor lambda, then, when
+ *   mu != 0, a STEP with factor mu (mu == 0: plain Laplacian smoothing, which shrinks).  A STEP with factor f on positions x:
+ *     TERMS         for every corner occurrence of vertex i in a triangle (i, j, k) the two terms x_j - x_i and x_k - x_i, per component in
+ *                   fp32: the other end of an interior edge counts twice, that of a boundary edge once (umbrella weights).  A term with a
+ *                   non-finite component contributes nothing and is not counted.
+ *     SCALE         M = the largest |component| over all contributing terms of this step.  M == 0: the step leaves every position as it
+ *                   is.  Otherwise E = floor(log2 M) and S = 2^(30 - E), as for the normals.
+ *     SUM           q = llrint((double)term_c * S), round-half-even; A_i = the int64 sum of q per component, by 64-bit integer atomic adds
+ *                   (the two terms of a corner may be added first: integer addition is associative); c_i = the int32 count of contributing
+ *                   terms.
+ *     UPDATE        in fp64 without contraction: u = ((double)A_i * 2^(E-30)) / (double)c_i, x_i' = (float)((double)x_i + (double)f * u).  A
+ *                   vertex with c_i == 0 keeps its bytes.
+ *   The positions of a step are read from one buffer and written to another (Jacobi, not in place).  iterations == 0 copies.  Triangles
+ *   are never changed, and boundaries are NOT PINNED: the rim of an open mesh shrinks.  out_verts may be verts itself.  The ids are
+ *   validated once, before the first step.  LIMITS: as above.  Device memory for the call: 52 bytes a vertex (two position buffers, three
+ *   int64, the count) and 12 a triangle.
+ *   MVS_ERR_ARG, checked in this order before the handle is read: s NULL; iterations outside 0..1000; lambda not finite or outside (0, 1); mu
+ *   not finite or outside (-1, 0]; a negative count or a count over the limit; verts or out_verts NULL with n_v > 0, or tris NULL with
+ *   n_t > 0; no engine.  Then: an id outside 0 .. n_v - 1. */
+typedef struct mvs_mesh_pruning {
+    int64_t min_triangles;   /* keep a component with at least this many triangles; >= 1 */
+    int32_t largest_only;    /* 1: keep only the component with most triangles (ties: the smaller label) */
+    int32_t pad;
+} mvs_mesh_pruning;          /* 16 bytes */
+void mvs_default_mesh_pruning(mvs_mesh_pruning* p); /* min_triangles 1, largest_only 0 */
+typedef struct mvs_mesh_smoothing {
+    int32_t iterations;  /* 0 .. 1000 */
+    float lambda;        /* shrinking step, in (0, 1) */
+    float mu;            /* inflating step, in (-1, 0]; 0: plain Laplacian, no second step */
+    int32_t pad;
+} mvs_mesh_smoothing;    /* 16 bytes */
+void mvs_default_mesh_smoothing(mvs_mesh_smoothing* s); /* 10, 0.5, -0.53 */
+int mvs_engine_mesh_components(mvs_engine* e, int64_t n_v, int64_t n_t, const int32_t* tris, int32_t* label /* [n_v] or NULL */,
+                               int32_t* ntris /* [n_v] or NULL */, int64_t* n_components /* or NULL */);
+int mvs_engine_mesh_prune(mvs_engine* e, const mvs_mesh_pruning* p, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris,
+                          int64_t cap_v, float* out_verts, int64_t cap_t, int32_t* out_tris, int32_t* vmap /* [n_v] or NULL */,
+                          int64_t* n_v_out, int64_t* n_t_out);
+int mvs_engine_mesh_smooth(mvs_engine* e, const mvs_mesh_smoothing* s, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris,
+                           float* out_verts /* [n_v][3] */);
+
 /* Propagate::run(iter), propagate.cpp:28-64: two colour passes, each = index build + sweep + commit */
 int mvs_engine_propagate(mvs_engine* e, int iter, mvs_counters* out);
 

@@ -1,6 +1,6 @@
 // mvs_engine_output.cpp -- what the C ABI in include/mvskit_engine.h makes of the finished pool: the PLY point cloud (mvs_ply.hip), the
-// dense per-view maps and their fusion (mvs_maps.hip), the triangle mesh (mvs_mesh.hip) and its vertex normals and colours
-// (mvs_mesh_attr.hip).  Every entry point is stateless: its working arrays live in buffers of the call, and nothing of the engine's
+// dense per-view maps and their fusion (mvs_maps.hip), the triangle mesh (mvs_mesh.hip), its vertex normals and colours
+// (mvs_mesh_attr.hip) and its clean-up (mvs_mesh_clean.hip).  Every entry point is stateless: its working arrays live in buffers of the call, and nothing of the engine's
 // state changes.
 #include <climits>
 #include <cmath>
@@ -484,6 +484,151 @@ int mvs_engine_mesh_colours(mvs_engine* e, const mvs_maps_config* c, const mvs_m
     if (used) HIPCHK(hipMemcpyAsync(used, d_used.p, (size_t)n_v, hipMemcpyDefault, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
+    return MVS_OK;
+}
+
+// Mesh clean-up (mvs_mesh_clean.hip; the definitions are in mvskit_engine.h): components, pruning, smoothing.  Stateless like the
+// attribute calls: the caller's arrays come into buffers of the call from wherever they lie, the results leave from there.
+static_assert(sizeof(mvs_mesh_pruning) == 16, "mvs_mesh_pruning is 16 bytes");
+static_assert(sizeof(mvs_mesh_smoothing) == 16, "mvs_mesh_smoothing is 16 bytes");
+namespace {
+int mesh_counts(int64_t n_v, int64_t n_t, const char* who) {
+    if (n_v < 0 || n_t < 0 || n_v > MESH_ATTR_MAX || n_t > MESH_ATTR_MAX) { g_err = std::string(who) + ": a count negative or over 2^30"; return MVS_ERR_ARG; }
+    return MVS_OK;
+}
+// the caller's triangles into d_tris, their ids checked (words: one zeroed word of scratch); the stream is idle on return
+int mesh_take_tris(mvs_engine* e, int64_t n_v, int64_t n_t, const int32_t* tris, DevBuf<int32_t>& d_tris, DevBuf<uint32_t>& words, const char* who) {
+    hipStream_t st = e->stream;
+    if (d_tris.ensure(3 * n_t) || words.ensure(2)) return MVS_ERR_HIP;
+    if (n_t > 0) HIPCHK(hipMemcpyAsync(d_tris.p, tris, (size_t)n_t * 3 * sizeof(int32_t), hipMemcpyDefault, st));
+    HIPCHK(hipMemsetAsync(words.p, 0, 2 * sizeof(uint32_t), st));
+    mvsk_mesh_check_ids(n_v, n_t, d_tris.p, words.p, st);
+    uint32_t bad = 0;
+    if (int r = read_back(e, words.p, &bad)) return r;
+    HIPCHK(hipGetLastError());
+    if (bad) { g_err = std::string(who) + ": a vertex index outside 0 .. n_v - 1"; return MVS_ERR_ARG; }
+    return MVS_OK;
+}
+// labels and per-vertex triangle counts of valid triangles on the device (launched, not waited for); ncomp: one word, zeroed here
+int mesh_label(mvs_engine* e, int64_t n_v, int64_t n_t, const int32_t* d_tris, DevBuf<int32_t>& parent, DevBuf<int32_t>& size, DevBuf<unsigned long long>& ncomp) {
+    if (parent.ensure(n_v) || size.ensure(n_v) || ncomp.ensure(2)) return MVS_ERR_HIP;
+    HIPCHK(hipMemsetAsync(ncomp.p, 0, 2 * sizeof(unsigned long long), e->stream));
+    mvsk_mesh_components(n_v, n_t, d_tris, parent.p, size.p, ncomp.p, e->stream);
+    return MVS_OK;
+}
+}  // namespace
+
+int mvs_engine_mesh_components(mvs_engine* e, int64_t n_v, int64_t n_t, const int32_t* tris, int32_t* label, int32_t* ntris, int64_t* n_components) {
+    const char* who = "mvs_engine_mesh_components";
+    if (int r = mesh_counts(n_v, n_t, who)) return r;
+    if (!tris && n_t > 0) { g_err = std::string(who) + ": tris null"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
+    if (n_v == 0 && n_t == 0) { if (n_components) *n_components = 0; return MVS_OK; }
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:mesh_components");
+    hipStream_t st = e->stream;
+    DevBuf<int32_t> d_tris, parent, size;
+    DevBuf<uint32_t> words;
+    DevBuf<unsigned long long> ncomp;
+    if (int r = mesh_take_tris(e, n_v, n_t, tris, d_tris, words, who)) return r;
+    if (int r = mesh_label(e, n_v, n_t, d_tris.p, parent, size, ncomp)) return r;
+    unsigned long long nc = 0;
+    if (int r = read_back(e, ncomp.p, &nc)) return r;  // a failure is known before anything is written
+    HIPCHK(hipGetLastError());
+    if (label && n_v > 0) HIPCHK(hipMemcpyAsync(label, parent.p, (size_t)n_v * sizeof(int32_t), hipMemcpyDefault, st));
+    if (ntris && n_v > 0) HIPCHK(hipMemcpyAsync(ntris, size.p, (size_t)n_v * sizeof(int32_t), hipMemcpyDefault, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (n_components) *n_components = (int64_t)nc;
+    return MVS_OK;
+}
+
+void mvs_default_mesh_pruning(mvs_mesh_pruning* p) {
+    if (!p) return;
+    p->min_triangles = 1; p->largest_only = 0; p->pad = 0;
+}
+
+int mvs_engine_mesh_prune(mvs_engine* e, const mvs_mesh_pruning* p, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, int64_t cap_v,
+                          float* out_verts, int64_t cap_t, int32_t* out_tris, int32_t* vmap, int64_t* n_v_out, int64_t* n_t_out) {
+    const char* who = "mvs_engine_mesh_prune";
+    if (!p) { g_err = std::string(who) + ": pruning null"; return MVS_ERR_ARG; }
+    if (p->min_triangles < 1) { g_err = std::string(who) + ": min_triangles < 1"; return MVS_ERR_ARG; }
+    if (p->largest_only != 0 && p->largest_only != 1) { g_err = std::string(who) + ": largest_only not 0 or 1"; return MVS_ERR_ARG; }
+    if (int r = mesh_counts(n_v, n_t, who)) return r;
+    if (!verts && n_v > 0) { g_err = std::string(who) + ": verts null"; return MVS_ERR_ARG; }
+    if (!tris && n_t > 0) { g_err = std::string(who) + ": tris null"; return MVS_ERR_ARG; }
+    if (int r = mesh_out_args(cap_v, cap_t, n_v_out, n_t_out, who)) return r;
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
+    if (n_v == 0 && n_t == 0) { *n_v_out = 0; *n_t_out = 0; return MVS_OK; }
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:mesh_prune");
+    hipStream_t st = e->stream;
+    DevBuf<int32_t> d_tris, parent, size, vflag, vbase, tflag, tbase, scan, d_out_tris;
+    DevBuf<uint32_t> words;
+    DevBuf<unsigned long long> ncomp;  // [0] the components, [1] the largest one's key
+    DevBuf<float> d_verts, d_out_verts;
+    if (int r = mesh_take_tris(e, n_v, n_t, tris, d_tris, words, who)) return r;
+    if (int r = mesh_label(e, n_v, n_t, d_tris.p, parent, size, ncomp)) return r;
+    if (vflag.ensure(n_v) || vbase.ensure(n_v + 1) || tflag.ensure(n_t) || tbase.ensure(n_t + 1) || scan.ensure(std::max(n_v, n_t) / 256 + 4096)) return MVS_ERR_HIP;
+    if (n_v > 0) HIPCHK(hipMemsetAsync(vflag.p, 0, (size_t)n_v * sizeof(int32_t), st));
+    if (p->largest_only) mvsk_mesh_largest(n_v, parent.p, size.p, ncomp.p + 1, st);
+    mvsk_mesh_keep(n_t, d_tris.p, parent.p, size.p, p->min_triangles, p->largest_only, ncomp.p + 1, tflag.p, vflag.p, st);
+    int64_t nv = 0, nt = 0;
+    if (int r = scan_total(e, vflag.p, vbase.p, scan.p, n_v, &nv)) return r;
+    if (int r = scan_total(e, tflag.p, tbase.p, scan.p, n_t, &nt)) return r;
+    *n_v_out = nv; *n_t_out = nt;
+    if ((out_verts && cap_v < nv) || (out_tris && cap_t < nt)) { g_err = std::string(who) + ": a cap is smaller than the pruned mesh (*n_v_out, *n_t_out)"; return MVS_ERR_CAPACITY; }
+    if (!out_verts || !out_tris) return MVS_OK;
+    if (d_verts.ensure(3 * n_v) || d_out_verts.ensure(3 * nv) || d_out_tris.ensure(3 * nt)) return MVS_ERR_HIP;
+    if (n_v > 0) HIPCHK(hipMemcpyAsync(d_verts.p, verts, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
+    mvsk_mesh_gather(n_v, d_verts.p, vflag.p, vbase.p, d_out_verts.p, nv, n_t, d_tris.p, tflag.p, tbase.p, d_out_tris.p, nt, st);
+    if (nv > 0) HIPCHK(hipMemcpyAsync(out_verts, d_out_verts.p, (size_t)nv * 3 * sizeof(float), hipMemcpyDefault, st));
+    if (nt > 0) HIPCHK(hipMemcpyAsync(out_tris, d_out_tris.p, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDefault, st));
+    if (vmap && n_v > 0) HIPCHK(hipMemcpyAsync(vmap, vflag.p, (size_t)n_v * sizeof(int32_t), hipMemcpyDefault, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return MVS_OK;
+}
+
+void mvs_default_mesh_smoothing(mvs_mesh_smoothing* s) {
+    if (!s) return;
+    s->iterations = 10; s->lambda = 0.5f; s->mu = -0.53f; s->pad = 0;
+}
+
+int mvs_engine_mesh_smooth(mvs_engine* e, const mvs_mesh_smoothing* s, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, float* out_verts) {
+    const char* who = "mvs_engine_mesh_smooth";
+    if (!s) { g_err = std::string(who) + ": smoothing null"; return MVS_ERR_ARG; }
+    if (s->iterations < 0 || s->iterations > 1000) { g_err = std::string(who) + ": iterations outside 0..1000"; return MVS_ERR_ARG; }
+    if (!std::isfinite(s->lambda) || !(s->lambda > 0.0f && s->lambda < 1.0f)) { g_err = std::string(who) + ": lambda not finite or outside (0, 1)"; return MVS_ERR_ARG; }
+    if (!std::isfinite(s->mu) || !(s->mu > -1.0f && s->mu <= 0.0f)) { g_err = std::string(who) + ": mu not finite or outside (-1, 0]"; return MVS_ERR_ARG; }
+    if (int r = mesh_counts(n_v, n_t, who)) return r;
+    if (((!verts || !out_verts) && n_v > 0) || (!tris && n_t > 0)) { g_err = std::string(who) + ": verts, tris or out_verts null"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
+    if (n_v == 0 && n_t == 0) return MVS_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:mesh_smooth");
+    hipStream_t st = e->stream;
+    const bool two = s->mu != 0.0f;
+    const int steps = s->iterations * (two ? 2 : 1);
+    DevBuf<int32_t> d_tris, cnt;
+    DevBuf<uint32_t> words, mbits;  // mbits: the bits of the largest component, a word per step
+    DevBuf<float> xa, xb;
+    DevBuf<long long> acc;
+    if (int r = mesh_take_tris(e, n_v, n_t, tris, d_tris, words, who)) return r;
+    if (n_v == 0) return MVS_OK;
+    if (xa.ensure(3 * n_v) || xb.ensure(3 * n_v) || acc.ensure(3 * n_v) || cnt.ensure(n_v) || mbits.ensure(steps + 1)) return MVS_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(xa.p, verts, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
+    HIPCHK(hipMemsetAsync(acc.p, 0, (size_t)n_v * 3 * sizeof(long long), st));
+    HIPCHK(hipMemsetAsync(cnt.p, 0, (size_t)n_v * sizeof(int32_t), st));
+    HIPCHK(hipMemsetAsync(mbits.p, 0, (size_t)(steps + 1) * sizeof(uint32_t), st));
+    float *from = xa.p, *to = xb.p;
+    for (int k = 0; k < steps; ++k) {
+        mvsk_mesh_smooth_step(n_v, from, to, (two && (k & 1)) ? s->mu : s->lambda, n_t, d_tris.p, mbits.p + k, acc.p, cnt.p, st);
+        std::swap(from, to);
+    }
+    HIPCHK(hipStreamSynchronize(st));  // a failure is known before anything is written
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_verts, from, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
+    HIPCHK(hipStreamSynchronize(st));
     return MVS_OK;
 }
 

@@ -145,3 +145,20 @@ void mvsk_mesh_normals_finish(int64_t n_v, const long long* acc, float* normals,
 struct MeshColourArgs { float occl_tol, min_cos; };
 void mvsk_mesh_colours(const DParams& prm, const MapsArgs& a, const MeshColourArgs& m, int64_t n_v, const float* verts, const float* normals,
                        const int32_t* ids, const uint8_t* usable, uint8_t* rgb, uint8_t* used, hipStream_t st);
+// mvs_engine_mesh_components / mvs_engine_mesh_prune / mvs_engine_mesh_smooth (mvs_mesh_clean.hip): connected components by union-find,
+// pruning behind two scans, Taubin smoothing as an order-free integer sum.  verts: 3 floats a vertex, tris: 3 ids a triangle.
+// *bad != 0 when an id of a triangle lies outside 0 .. n_v - 1 (zero before the launch); every launcher below wants valid ids
+void mvsk_mesh_check_ids(int64_t n_v, int64_t n_t, const int32_t* tris, uint32_t* bad, hipStream_t st);
+// parent[i] = the smallest id of i's component, size[i] = the triangles of that component, *ncomp += the components with a triangle
+void mvsk_mesh_components(int64_t n_v, int64_t n_t, const int32_t* tris, int32_t* parent, int32_t* size, unsigned long long* ncomp, hipStream_t st);
+// *best = max over the components with a triangle of (size << 32) | (0xffffffff - label) (zero before the launch)
+void mvsk_mesh_largest(int64_t n_v, const int32_t* parent, const int32_t* size, unsigned long long* best, hipStream_t st);
+// tflag[t] = triangle t is kept; vflag[i] = 1 where a kept triangle names vertex i (vflag zero before the launch); best is read with largest_only
+void mvsk_mesh_keep(int64_t n_t, const int32_t* tris, const int32_t* parent, const int32_t* size, int64_t min_triangles, int largest_only,
+                    const unsigned long long* best, int32_t* tflag, int32_t* vflag, hipStream_t st);
+// with vbase / tbase = the exclusive scans of the flags: the kept rows in input order, ids rewritten; vflag becomes the vertex map (-1: dropped)
+void mvsk_mesh_gather(int64_t n_v, const float* verts, int32_t* vflag, const int32_t* vbase, float* out_verts, int64_t cap_v, int64_t n_t, const int32_t* tris,
+                      const int32_t* tflag, const int32_t* tbase, int32_t* out_tris, int64_t cap_t, hipStream_t st);
+// one STEP with factor f from xin to xout: *mbits zero before the launch, acc (3 int64 a vertex) and cnt zero before and after it
+void mvsk_mesh_smooth_step(int64_t n_v, const float* xin, float* xout, float f, int64_t n_t, const int32_t* tris, uint32_t* mbits, long long* acc, int32_t* cnt,
+                           hipStream_t st);

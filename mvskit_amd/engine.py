@@ -33,6 +33,7 @@ EXPORTS = [
     "mvs_default_maps_config", "mvs_engine_render_maps", "mvs_engine_fused_points",
     "mvs_engine_tsdf", "mvs_engine_extract_mesh", "mvs_engine_mesh", "mvs_engine_sweep_pairs",
     "mvs_default_mesh_colouring", "mvs_engine_mesh_normals", "mvs_engine_mesh_colours",
+    "mvs_default_mesh_pruning", "mvs_default_mesh_smoothing", "mvs_engine_mesh_components", "mvs_engine_mesh_prune", "mvs_engine_mesh_smooth",
 ]
 PLY_ASCII, PLY_BINARY_LE = 0, 1  # mvs_ply_format
 #: one vertex of the binary PLY file (mvs_engine_export_ply): 27 packed bytes
@@ -102,6 +103,16 @@ class Volume(C.Structure):
 class MeshColouring(C.Structure):
     """mvs_mesh_colouring: the two thresholds of mvs_engine_mesh_colours, 8 bytes."""
     _fields_ = [("occl_tol", C.c_float), ("min_cos", C.c_float)]
+
+
+class MeshPruning(C.Structure):
+    """mvs_mesh_pruning: what mvs_engine_mesh_prune keeps, 16 bytes."""
+    _fields_ = [("min_triangles", C.c_int64), ("largest_only", C.c_int32), ("pad", C.c_int32)]
+
+
+class MeshSmoothing(C.Structure):
+    """mvs_mesh_smoothing: the steps of mvs_engine_mesh_smooth, 16 bytes."""
+    _fields_ = [("iterations", C.c_int32), ("lam", C.c_float), ("mu", C.c_float), ("pad", C.c_int32)]
 
 
 class Counters(C.Structure):
@@ -221,6 +232,15 @@ def load_library(cap32: bool = False, cap: int = 0):
         L.mvs_default_mesh_colouring.restype = None
         L.mvs_engine_mesh_normals.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp]
         L.mvs_engine_mesh_colours.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(MeshColouring), C.c_int64, vp, vp, vp, vp]
+    if hasattr(L, "mvs_engine_mesh_components"):
+        L.mvs_default_mesh_pruning.argtypes = [C.POINTER(MeshPruning)]
+        L.mvs_default_mesh_pruning.restype = None
+        L.mvs_default_mesh_smoothing.argtypes = [C.POINTER(MeshSmoothing)]
+        L.mvs_default_mesh_smoothing.restype = None
+        L.mvs_engine_mesh_components.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp, C.POINTER(C.c_int64)]
+        L.mvs_engine_mesh_prune.argtypes = [vp, C.POINTER(MeshPruning), C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp,
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.mvs_engine_mesh_smooth.argtypes = [vp, C.POINTER(MeshSmoothing), C.c_int64, vp, C.c_int64, vp, vp]
     _libs[LIB_PATH] = L
     return L
 
@@ -584,11 +604,57 @@ class Engine:
         self._check(self.L.mvs_engine_mesh_colours(self.h, C.byref(c), C.byref(m), verts.shape[0], _ptr(verts), _ptr(normals), _ptr(rgb), _ptr(used)))
         return rgb, used
 
-    def coloured_mesh(self, volume, source=0, min_consistent=1, depth_tol=0.01, normal_cos=0.9, occl_tol=0.01, min_cos=0.1, cap_v=0, cap_t=0):
+    # ---- mesh clean-up
+    def mesh_components(self, n_v, tris):
+        """The connected components of the mesh's vertex graph (include/mvskit_engine.h, mvs_engine_mesh_components): (label [n_v] int32,
+        the smallest vertex id of each vertex's component; ntris [n_v] int32, the triangles of that component; the number of components
+        with a triangle).  Needs no views."""
+        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        label, ntris, n = np.zeros(int(n_v), np.int32), np.zeros(int(n_v), np.int32), C.c_int64()
+        self._check(self.L.mvs_engine_mesh_components(self.h, int(n_v), tris.shape[0], _ptr(tris), _ptr(label), _ptr(ntris), C.byref(n)))
+        return label, ntris, n.value
+
+    def prune_mesh(self, verts, tris, min_triangles=1, largest_only=False):
+        """The mesh without the components of fewer than min_triangles triangles (largest_only: without all but the largest) and without
+        the vertices that no kept triangle names (include/mvskit_engine.h, mvs_engine_mesh_prune): (verts, tris, vmap [n] int32, the new
+        id of every input vertex or -1).  What stays keeps its order and its bytes.  The size call comes first.  Needs no views."""
+        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        p = MeshPruning(int(min_triangles), int(bool(largest_only)), 0)
+        nv, nt = C.c_int64(), C.c_int64()
+
+        def call(cap_v, out_v, cap_t, out_t, vmap):
+            return self.L.mvs_engine_mesh_prune(self.h, C.byref(p), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), cap_v, _ptr(out_v), cap_t,
+                                                _ptr(out_t), _ptr(vmap), C.byref(nv), C.byref(nt))
+
+        self._check(call(0, None, 0, None, None))
+        out_v, out_t = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
+        vmap = np.full(verts.shape[0], -1, np.int32)
+        self._check(call(nv.value, out_v, nt.value, out_t, vmap))
+        return out_v, out_t, vmap
+
+    def smooth_mesh(self, verts, tris, iterations=10, lam=0.5, mu=-0.53):
+        """Taubin smoothing of the positions (include/mvskit_engine.h, mvs_engine_mesh_smooth): float32 [n, 3].  Every iteration moves
+        each vertex by lam towards the mean of its triangles' other corners and then, unless mu is 0, by mu away from it again; an
+        order-free integer sum, the same bytes whatever order the triangles are listed in.  Boundaries are not pinned.  Needs no views."""
+        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        s = MeshSmoothing(int(iterations), float(lam), float(mu), 0)
+        out = np.zeros((verts.shape[0], 3), np.float32)
+        self._check(self.L.mvs_engine_mesh_smooth(self.h, C.byref(s), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), _ptr(out)))
+        return out
+
+    def coloured_mesh(self, volume, source=0, min_consistent=1, depth_tol=0.01, normal_cos=0.9, occl_tol=0.01, min_cos=0.1, cap_v=0, cap_t=0,
+                      min_triangles=0, largest_only=False, smooth_iterations=0):
         """mesh, mesh_normals and mesh_colours chained: (verts, tris, normals, rgb, used), what write_mesh_ply takes.  Every step renders
-        the maps it needs itself."""
+        the maps it needs itself.  With min_triangles >= 1 or largest_only the mesh is pruned (prune_mesh), with smooth_iterations > 0
+        smoothed (smooth_mesh with its default steps), in that order, before the normals and colours are taken."""
         kw = dict(source=source, min_consistent=min_consistent, depth_tol=depth_tol, normal_cos=normal_cos)
         verts, tris = self.mesh(volume, cap_v=cap_v, cap_t=cap_t, **kw)
+        if min_triangles > 0 or largest_only:
+            verts, tris, _ = self.prune_mesh(verts, tris, max(1, int(min_triangles)), largest_only)
+        if smooth_iterations > 0:
+            verts = self.smooth_mesh(verts, tris, smooth_iterations)
         normals = self.mesh_normals(verts, tris)
         rgb, used = self.mesh_colours(verts, normals, occl_tol=occl_tol, min_cos=min_cos, **kw)
         return verts, tris, normals, rgb, used
