@@ -691,6 +691,16 @@ int mvs_engine_last_timing(mvs_engine* e, mvs_timing* t);
  *          trial alone: out[0] is then 0 and out[5] says what would pair); out[1] + ... + out[5] = all trials */
 int mvs_engine_sweep_pairs(mvs_engine* e, int64_t out[6]);
 
+/* Trials of the sweep that reused what the trial before them had computed, summed over every pass since the engine was created.  A trial
+ * into a FULL cell (the replace-worst branch) draws nothing before Optim::refinePatch: generatePatch, the pre-filter and preProcess
+ * depend on the source patch, the cell's worst patch and the index alone, so while nothing is staged the next trial of the same source
+ * entry would compute the same again.  Such trials are counted in every work counter (evals and view_evals included) as if they had run.
+ *   out[0] trials skipped because the trial before them ended before the refinement (generatePatch failed, pre-filtered, preProcess
+ *          failed): they end the same way
+ *   out[1] trials that took the candidate the trial before them had brought through preProcess and went straight to their own
+ *          refinement (always 0: this engine runs those trials in full) */
+int mvs_engine_sweep_repeats(mvs_engine* e, int64_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif

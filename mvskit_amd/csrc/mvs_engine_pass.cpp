@@ -268,6 +268,7 @@ static int pass_impl(mvs_engine* e, int iter, int pass, mvs_counters* out) {
     for (const DCounters& c : hcs) {
         add_counters(sum, c);
         for (int k = 0; k < 6; ++k) e->sweep_pairs[k] += (int64_t)c.pair[k];
+        for (int k = 0; k < 2; ++k) e->sweep_repeats[k] += (int64_t)c.repeats[k];
     }
     sum.evals += fill[0]; sum.view_evals += fill[1]; sum.trimmed = (int64_t)trimmed;
     float ms = 0.0f;

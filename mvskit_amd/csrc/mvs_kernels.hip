@@ -508,6 +508,7 @@ struct SweepAcc {
     unsigned cand, pref, patch, f0, f1, ins, rep;
     unsigned long long evals, view_evals;
     unsigned pair[6];  // DCounters::pair
+    unsigned skip;     // DCounters::repeats[0]
 #ifdef MVS_STAGE_TIMING
     unsigned long long stage[16];
 #endif
@@ -517,6 +518,7 @@ DEV SweepAcc sweep_acc_zero() {
     acc.cand = acc.pref = acc.patch = acc.f0 = acc.f1 = acc.ins = acc.rep = 0u;
     acc.evals = acc.view_evals = 0ull;
     for (int k = 0; k < 6; ++k) acc.pair[k] = 0u;
+    acc.skip = 0u;
 #ifdef MVS_STAGE_TIMING
     for (int k = 0; k < 16; ++k) acc.stage[k] = 0ull;
 #endif
@@ -534,6 +536,7 @@ DEV void sweep_acc_flush(const SweepArgs& a, const SweepAcc& acc, unsigned slot)
     if (acc.evals) atomicAdd(&C->evals, acc.evals);
     if (acc.view_evals) atomicAdd(&C->view_evals, acc.view_evals);
     for (int k = 0; k < 6; ++k) if (acc.pair[k]) atomicAdd(&C->pair[k], (unsigned long long)acc.pair[k]);
+    if (acc.skip) atomicAdd(&C->repeats[0], (unsigned long long)acc.skip);
 #ifdef MVS_STAGE_TIMING
     for (int k = 0; k < 12; ++k) if (acc.stage[k]) atomicAdd(&C->stage[k], acc.stage[k]);
     atomicMax(&C->stage[12], acc.stage[12]); atomicMax(&C->stage[13], acc.stage[13]);
@@ -591,6 +594,7 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WaveCtx& wc, SweepAc
     uint32_t pend_k3 = 0u;
     int pend_sz = 0;
     unsigned n_pair = 0, n_elig = 0, n_last = 0, n_noroom = 0, n_lost = 0, n_long = 0;  // DCounters::pair
+    unsigned n_skip = 0;                                                                // DCounters::repeats[0]
     for (int sidx = 0; sidx <= nsrc; ++sidx) {
         const bool flush = sidx == nsrc;
         const int scx = sidx < 2 ? sxs[sidx] : cx, scy = sidx < 2 ? sys[sidx] : cy;
@@ -636,19 +640,30 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WaveCtx& wc, SweepAc
                         const DPatch* wp = worst >= MVS_NEWBASE ? a.staging + (worst - MVS_NEWBASE) : prm.pool + worst;
                         ic = project(vw, ld4(wp->coord), prm.level);
                     }
+                    // A trial into a FULL cell draws nothing before the refinement: what follows, up to and including preProcess, is a function
+                    // of the source record, the worst patch and the index.  If it ends there it has staged nothing, the live list is what it
+                    // was, and the `rest` trials of this source entry still to come would compute the same and end the same way: their counts
+                    // (the evaluations included) are added here and they are not run.  (Nothing waits in such a cell: `pend` is false.)
+                    const unsigned rest = np >= prm.cap ? (unsigned)(ntrial - 1 - it) : 0u;
+                    const unsigned ev0 = wc.evals, vev0 = wc.view_evals;
+                    auto skip_rest = [&]() {
+                        n_skip += rest;
+                        wc.evals += rest * (wc.evals - ev0); wc.view_evals += rest * (wc.view_evals - vev0);
+                        it += (int)rest;
+                    };
                     {
                         Cand src;  // loaded per trial: its registers are free again during the refinement
                         load_cand(sp, wc, src);
                         const bool gen_ok = generate_patch(prm, wc, s_scratch, src, ic, c, as_view, np >= prm.cap);
                         ST_ADD(1, st_t)
-                        if (!gen_ok) { pend_failed |= pend; continue; }
+                        if (!gen_ok) { pend_failed |= pend; skip_rest(); continue; }
                     }
                     ++n_cand;
-                    if (np >= prm.cap && c.ncc < worst_ncc) { ++n_pref; continue; }
+                    if (np >= prm.cap && c.ncc < worst_ncc) { ++n_pref; n_cand += rest; n_pref += rest; skip_rest(); continue; }
                     ++n_patch;
                     const int pre_r = pre_process(prm, wc, s_scratch, c);
                     ST_ADD(2, st_t)
-                    if (pre_r == -1) { ++n_f0; pend_failed |= pend; continue; }
+                    if (pre_r == -1) { ++n_f0; pend_failed |= pend; n_cand += rest; n_patch += rest; n_f0 += rest; skip_rest(); continue; }
                     if (!pend && np + 1 < prm.cap) {
                         // Room for this trial AND the next: the next one, whatever becomes of this one, still takes the np < cap branch above and
                         // reads nothing of the live list before Optim::check -- it may be generated first and refined together with this one.
@@ -756,6 +771,7 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WaveCtx& wc, SweepAc
         acc->evals += wc.evals; acc->view_evals += wc.view_evals;
         acc->pair[0] += n_pair; acc->pair[5] += n_elig;
         acc->pair[1] += n_last; acc->pair[2] += n_noroom; acc->pair[3] += n_lost; acc->pair[4] += n_long;
+        acc->skip += n_skip;
 #ifdef MVS_STAGE_TIMING
         st_acc[0] = ST_NOW() - st_begin;
         for (int k = 0; k < 12; ++k) acc->stage[k] += st_acc[k];

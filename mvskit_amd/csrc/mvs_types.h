@@ -110,6 +110,9 @@ struct DCounters {
     // failed generate / preProcess, 4 one of the two lists was longer than 8 views; 5 trials that can pair, whether or not they did
     // (MVS_SWEEP_PAIR=0, the CONVERGED refiner) -- 1 + 2 + 3 + 4 + 5 = the trials refined
     unsigned long long pair[6];
+    // trials of a full cell that reused what the trial before them had computed (mvs_engine_sweep_repeats): 0 skipped after an early
+    // outcome, 1 started from the stashed candidate (none: those trials run in full)
+    unsigned long long repeats[2];
 };
 
 // Arguments of one sweep launch (one colour pass over the owned views).
