@@ -112,7 +112,19 @@ typedef struct mvs_refiner {
 
 /* One view: PhotoSet::m_photos[i] (image/photoSet.hpp:62).  P is the row-major 3x4 level-0 projection
  * (`CONTOUR` camera text, image/camera.cpp:110-116); rgb is the level-0 image as Image::m_images[0]
- * holds it, interleaved uint8 RGB, H rows of W pixels (image/image.hpp:76); mask is H*W uint8 or NULL. */
+ * holds it, interleaved uint8 RGB, H rows of W pixels (image/image.hpp:76); mask is H*W uint8 or NULL.
+ *
+ * Precondition on P: its third row has unit norm in its first three entries, |(P[8], P[9], P[10])| = 1, as K [R | t] with K's last
+ * row (0, 0, 1) has (the `CONTOUR2` text always gives that, camera.cpp:117-134; a `CONTOUR` text holds any matrix).  The engine, like
+ * the reference, takes P[8..11] . X for the depth along the optical axis without dividing by that norm, and these rely on it:
+ *   - Propagate::generatePatch (propagate.cpp:220-237) computes depth = oaxis . X with the normalised axis and then
+ *     unproject(depth * (u, v, 1)), whose third coordinate is P[8..11] . X: with another norm the new patch lies at another depth;
+ *   - the depth arguments of mvs_engine_seed_random: a hypothesis at depth d is unproject(d * (px, py, 1));
+ *   - mvs_engine_depth_ranges, which returns oaxis . X (normalised) and whose ranges are meant for seed_random;
+ *   - ipscale = P_row0 . xaxis + P_row1 . yaxis (Optim::setAxesScales, optim.cpp:43-65), fx + fy only at that scale, and with it
+ *     Optim::getUnit, the patch axes and every threshold in pixels.
+ * mvs_engine_set_views does not check or rescale P.  A caller that holds a general `CONTOUR` matrix divides all twelve entries by
+ * |(P[8], P[9], P[10])| first: a projection matrix is defined up to scale, so no pixel moves. */
 typedef struct mvs_view_desc {
     int32_t width, height;
     float P[12];

@@ -277,15 +277,25 @@ def _raycast(P, C, W, H, objects):
 
 
 def make_scene(nviews=12, W=1920, H=1080, arc_deg=110.0, radius=4.0, kind="multi", keep_geometry=True, tex_seed=12345,
-               noise_sigma=2.0, geometry_views=None):
+               noise_sigma=2.0, geometry_views=None, cameras=None, objects=None, focal=None, target=(0.0, 0.0, 0.0)):
     """cfg2-style scene: `nviews` cameras on an arc looking at 3 textured planes + a sphere
     (kind="multi") or one textured plane z = 0 (kind="plane").  geometry_views: keep the ground-truth points / normals
     (needed by make_seeds for reference views and occlusion tests) only for these views -- the others hold NaN, which
-    make_seeds reads as "not visible there" (48 views of 4K would need 19 GB otherwise)."""
-    P, C = make_cameras(nviews, W, H, arc_deg, radius)
-    focal = 765.702941895 * W / 640.0
-    basis = _texture_basis(radius / focal, seed=tex_seed)
-    objects = default_objects(kind)
+    make_seeds reads as "not visible there" (48 views of 4K would need 19 GB otherwise).
+    cameras=(P[n,3,4] float32, C[n,3]): these cameras instead of the arc's (the third row of every P of unit norm in its first three
+    entries, include/mvskit_engine.h); objects: these instead of default_objects(kind); focal: what meta["focal"] holds for them, one
+    number or (fx + fy) / 2 per view (make_seeds' unit); target: the point the scene lies around, kept in meta["target"]."""
+    nominal = 765.702941895 * W / 640.0
+    if cameras is None:
+        P, C = make_cameras(nviews, W, H, arc_deg, radius)
+    else:
+        P, C = np.ascontiguousarray(cameras[0], dtype=np.float32), np.asarray(cameras[1], dtype=np.float64)
+        assert P.shape == (nviews, 3, 4) and C.shape == (nviews, 3)
+    if focal is None:
+        focal = nominal
+    basis = _texture_basis(radius / nominal, seed=tex_seed)
+    if objects is None:
+        objects = default_objects(kind)
     imgs = np.empty((nviews, H, W, 3), dtype=np.uint8)
     pts_all = np.empty((nviews, H, W, 3), dtype=np.float32) if keep_geometry else None
     nrm_all = np.empty((nviews, H, W, 3), dtype=np.float32) if keep_geometry else None
@@ -317,7 +327,7 @@ def make_scene(nviews=12, W=1920, H=1080, arc_deg=110.0, radius=4.0, kind="multi
     if pool is not None:
         pool.shutdown()
     return Scene(W=W, H=H, P=P, images=imgs, centers=C, points=pts_all, normals=nrm_all,
-                 meta={"kind": kind, "arc_deg": arc_deg, "radius": radius, "focal": focal})
+                 meta={"kind": kind, "arc_deg": arc_deg, "radius": radius, "focal": focal, "target": tuple(float(t) for t in target)})
 
 
 def _project(P, X):
@@ -341,6 +351,7 @@ def make_seeds(scene: Scene, level=0, csize=2, stride=16, depth_noise=0.5, norma
     out = []
     cosmax = math.cos(math.radians(max_cone_deg))
     Pd = scene.P.astype(np.float64)
+    focal = scene.meta["focal"]
     for v in (range(n) if views is None else views):
         rng = np.random.RandomState(seed + v)
         cx, cy = np.meshgrid(np.arange(stride // 2, gw, stride), np.arange(stride // 2, gh, stride))
@@ -360,7 +371,8 @@ def make_seeds(scene: Scene, level=0, csize=2, stride=16, depth_noise=0.5, norma
         ray = X - C
         dist = np.linalg.norm(ray, axis=1, keepdims=True)
         ray /= dist
-        unit = 2.0 * dist * scale / (2.0 * scene.meta["focal"])  # Optim::getUnit, optim.cpp:34-41
+        fv = float(focal[v]) if np.ndim(focal) else focal  # one focal, or (fx + fy) / 2 of the reference view
+        unit = 2.0 * dist * scale / (2.0 * fv)  # Optim::getUnit, optim.cpp:34-41
         X = X + ray * unit * depth_noise * rng.normal(size=(X.shape[0], 1))
         # normal noise: rotate towards a random tangent direction
         tang = rng.normal(size=N.shape)

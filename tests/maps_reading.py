@@ -4,6 +4,26 @@ tests/test_gpu_maps.py holds the device to it, and mesh_reading.py and mesh_attr
 import numpy as np
 
 DEPTH_TOL, NORMAL_COS = 0.004, 0.98
+EDGE_PX, S_MARGIN, COS_MARGIN = 1e-3, 1e-5, 1e-5  # the margins where the world lies about as far from the origin as from the cameras
+U = 2.0 ** -24  # float32 unit roundoff
+
+
+def margins(kappa, W, H):
+    """The margins of the float64 readings for a world whose coordinates are `kappa` times its depths (camera_scenes.kappa), images of
+    W x H: dict(edge=pixels, s=, cos=), never below the module's defaults.
+    edge: the device projects in float32, px = (P0 . X + p03) / (P2 . X + p23) + 0.5.  Each sum has four terms, three products and three
+    additions: its error is at most 4 U of the sum of the terms' magnitudes.  For the numerator that sum is at most
+    2 sqrt(3) (fx + |skew| + cx) |X|_inf (p03 = -P0 . C is as large as P0 . X), with fx + |skew| + cx <= (1.5 + 0.6) max(W, H) in the
+    scenes of camera_scenes.py (fx <= 1.25 * 1.196 W, cx <= 0.575 W), and |X|_inf <= kappa w: 4 U * 7.3 kappa max(W, H) = 29 U kappa max(W, H) pixels after
+    the division by w.  For the denominator it is 2 sqrt(3) |X|_inf: relative 4 U * 3.5 kappa = 14 U kappa, times |px| <= max(W, H).
+    The division and the addition of 0.5 add 2 U max(W, H).  In all (29 + 14 + 2) U kappa max(W, H): c = 48 with the sum rounded up.
+    s: s = n_q . (X0q - C) / n_q . (X - C).  Each difference rounds relative to |X|_inf, U kappa of the depth, each dot product of three
+    terms adds 3 U kappa: 8 U kappa for the quotient; X itself comes from the rendering, about 30 float32 operations (the depth
+    bound of tests/test_gpu_maps.py), 30 U kappa.  All of it over |cos(n_q, ray)| > 0.3, which the cases assert: 38 / 0.3 = 127,
+    c = 128.  With kappa = 1 that is 7.6e-6, inside the default 1e-5.
+    cos: n . n_q is a sum of three products of numbers both sides read exactly, 3 U |n| |n_q| = 1.8e-7 whatever the world's offset: the
+    default stays."""
+    return dict(edge=max(EDGE_PX, 48.0 * kappa * U * max(W, H)), s=max(S_MARGIN, 128.0 * kappa * U), cos=COS_MARGIN)
 
 
 def cameras64(sc, level, sizes):
@@ -45,8 +65,9 @@ def render64(pat, ids, cam):
     return depth, X, cos, t
 
 
-def agree64(pat, ids, X, cams, v, tol, ncos):
-    """step 3 in float64 for view v -> (bits, unsure): uint64 maps, bit u of `unsure` = the pair (pixel, u) lies inside a margin"""
+def agree64(pat, ids, X, cams, v, tol, ncos, edge_px=EDGE_PX, s_margin=S_MARGIN, cos_margin=COS_MARGIN):
+    """step 3 in float64 for view v -> (bits, unsure): uint64 maps, bit u of `unsure` = the pair (pixel, u) lies inside a margin (of
+    edge_px pixels around a rounding boundary, s_margin around depth_tol, cos_margin around normal_cos: margins())"""
     bits, unsure = np.zeros(ids[v].shape, np.uint64), np.zeros(ids[v].shape, np.uint64)
     ok = ids[v] >= 0
     Xv = X[v][ok]
@@ -57,7 +78,7 @@ def agree64(pat, ids, X, cams, v, tol, ncos):
         h = Xv @ cu["P"][:, :3].T + cu["P"][:, 3]
         assert (h[:, 2] > 0.1).all(), f"view {u}: smallest w {h[:, 2].min()}"  # every point lies well in front of every camera in these scenes
         px, py = h[:, 0] / h[:, 2] + 0.5, h[:, 1] / h[:, 2] + 0.5
-        edge = np.minimum(np.abs(px - np.rint(px)), np.abs(py - np.rint(py))) <= 1e-3
+        edge = np.minimum(np.abs(px - np.rint(px)), np.abs(py - np.rint(py))) <= edge_px
         fx, fy = np.floor(px).astype(int), np.floor(py).astype(int)
         inside = (fx >= 0) & (fx < cu["W"]) & (fy >= 0) & (fy < cu["H"])
         idq = np.where(inside, ids[u][np.clip(fy, 0, cu["H"] - 1), np.clip(fx, 0, cu["W"] - 1)], -1)
@@ -69,7 +90,7 @@ def agree64(pat, ids, X, cams, v, tol, ncos):
         nn = (n * nq).sum(1)
         with np.errstate(invalid="ignore"):
             bit = met & (ds <= tol) & ((nn >= ncos) if ncos > -1 else True)
-            margin = edge | (met & ((np.abs(ds - tol) < 1e-5) | ((np.abs(nn - ncos) < 1e-5) if ncos > -1 else False)))
+            margin = edge | (met & ((np.abs(ds - tol) < s_margin) | ((np.abs(nn - ncos) < cos_margin) if ncos > -1 else False)))
         b, m = np.zeros(ids[v].shape, np.uint64), np.zeros(ids[v].shape, np.uint64)
         b[ok], m[ok] = bit.astype(np.uint64) << np.uint64(u), margin.astype(np.uint64) << np.uint64(u)
         bits |= b
@@ -77,10 +98,10 @@ def agree64(pat, ids, X, cams, v, tol, ncos):
     return bits, unsure
 
 
-def render_agree64(pat, ids, cams, tol=DEPTH_TOL, ncos=NORMAL_COS):
+def render_agree64(pat, ids, cams, tol=DEPTH_TOL, ncos=NORMAL_COS, edge_px=EDGE_PX, s_margin=S_MARGIN, cos_margin=COS_MARGIN):
     """steps 2 and 3 over every view: render each id map, then agree each view against the others -> (bits, unsure), one map per view"""
     X = [render64(pat, ids[v], cams[v])[1] for v in range(len(cams))]
-    bits, unsure = zip(*[agree64(pat, ids, X, cams, v, tol, ncos) for v in range(len(cams))])
+    bits, unsure = zip(*[agree64(pat, ids, X, cams, v, tol, ncos, edge_px, s_margin, cos_margin) for v in range(len(cams))])
     return bits, unsure
 
 

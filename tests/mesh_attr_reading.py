@@ -6,7 +6,7 @@ colours64() restates mvs_engine_mesh_colours in float64 on render64 / agree64 of
 masks), as mesh_reading.tsdf64 does for the volume, and says which vertices have a (vertex, view) pair inside a margin."""
 import numpy as np
 
-from maps_reading import popcount
+from maps_reading import COS_MARGIN, EDGE_PX, S_MARGIN, popcount
 
 
 def normals_exact(verts, tris):
@@ -50,10 +50,11 @@ def _bilinear64(img, x, y):
     return (im[ly, lx] * (dx0 * dy0) + im[ly + 1, lx] * (dx0 * dy1)) + (im[ly, lx + 1] * (dx1 * dy0) + im[ly + 1, lx + 1] * (dx1 * dy1))
 
 
-def colours64(pat, ids, bits, unsure, cams, images, masks, verts, normals, min_consistent=1, occl_tol=0.01, min_cos=0.1):
+def colours64(pat, ids, bits, unsure, cams, images, masks, verts, normals, min_consistent=1, occl_tol=0.01, min_cos=0.1, edge_px=EDGE_PX,
+              s_margin=S_MARGIN, cos_margin=COS_MARGIN):
     """mvs_engine_mesh_colours in float64.  pat: the records by pool index; ids[v], bits[v], unsure[v]: view v's id map and the agree
     words of agree64 with their margins; cams: cameras64 of tests/maps_reading.py; images[v]: the level-L pyramid [H, W, 3] uint8; masks[v]:
-    the level-L mask as booleans, or None; normals: [n, 3] or None.
+    the level-L mask as booleans, or None; normals: [n, 3] or None; edge_px, s_margin, cos_margin: maps_reading.margins().
     -> dict of per-vertex arrays: mean [n, 3] (the unrounded weighted mean; NaN with no view), used (uint8), sure (no pair of the vertex
     lies inside a margin), reached (some view has the vertex in its sampling window), confirmed (the confirmed tier was chosen)"""
     X = np.asarray(verts, np.float64).reshape(-1, 3)
@@ -70,8 +71,8 @@ def colours64(pat, ids, bits, unsure, cams, images, masks, verts, normals, min_c
             front = h[:, 2] > 0
             win = front & (x >= 0) & (y >= 0) & (x < W - 1) & (y < H - 1)
             # within 1e-3 pixel of the window's edge, on either side of it
-            near_win = front & (x > -1e-3) & (y > -1e-3) & (x < W - 1 + 1e-3) & (y < H - 1 + 1e-3)
-            edge_win = near_win & ((np.abs(x) <= 1e-3) | (np.abs(y) <= 1e-3) | (np.abs(x - (W - 1)) <= 1e-3) | (np.abs(y - (H - 1)) <= 1e-3))
+            near_win = front & (x > -edge_px) & (y > -edge_px) & (x < W - 1 + edge_px) & (y < H - 1 + edge_px)
+            edge_win = near_win & ((np.abs(x) <= edge_px) | (np.abs(y) <= edge_px) | (np.abs(x - (W - 1)) <= edge_px) | (np.abs(y - (H - 1)) <= edge_px))
         sure &= ~edge_win
         reached |= win
         xs, ys = np.where(win, x, 0.0), np.where(win, y, 0.0)
@@ -85,8 +86,8 @@ def colours64(pat, ids, bits, unsure, cams, images, masks, verts, normals, min_c
         state = np.where(fg, np.where(use, ids[v], -1), -2)
         # a projection within 1e-3 pixel of a rounding boundary across which that differs
         differs = np.zeros(N, bool)
-        for yy in (np.floor(ys + 0.5 - 1e-3).astype(int), np.floor(ys + 0.5 + 1e-3).astype(int)):
-            for xx in (np.floor(xs + 0.5 - 1e-3).astype(int), np.floor(xs + 0.5 + 1e-3).astype(int)):
+        for yy in (np.floor(ys + 0.5 - edge_px).astype(int), np.floor(ys + 0.5 + edge_px).astype(int)):
+            for xx in (np.floor(xs + 0.5 - edge_px).astype(int), np.floor(xs + 0.5 + edge_px).astype(int)):
                 cy, cx = np.clip(yy, 0, H - 1), np.clip(xx, 0, W - 1)
                 differs |= (state[cy, cx] != state[fy, fx]) | (use_lo != use_hi)[cy, cx]
         sure &= ~(win & differs)
@@ -99,7 +100,7 @@ def colours64(pat, ids, bits, unsure, cams, images, masks, verts, normals, min_c
             with np.errstate(divide="ignore", invalid="ignore"):
                 wf = (nrm * d).sum(1) / np.sqrt((d * d).sum(1))
             w = np.where(facing, wf, 1.0)
-            sure &= ~(ok & facing & (np.abs(wf - min_cos) < 1e-5))
+            sure &= ~(ok & facing & (np.abs(wf - min_cos) < cos_margin))
             with np.errstate(invalid="ignore"):
                 ok &= ~facing | (wf >= min_cos)
         usable = ok & use[fy, fx]
@@ -109,7 +110,7 @@ def colours64(pat, ids, bits, unsure, cams, images, masks, verts, normals, min_c
             den = (nq * (X - cam["C"])).sum(1)
             s = (nq * (X0q - cam["C"])).sum(1) / den
             good = np.isfinite(den) & (den != 0) & (np.abs(s - 1.0) <= occl_tol)
-            sure &= ~(usable & (np.abs(np.abs(s - 1.0) - occl_tol) < 1e-5))
+            sure &= ~(usable & (np.abs(np.abs(s - 1.0) - occl_tol) < s_margin))
         conf = usable & good
         unconf = ok & ~use[fy, fx]
         sample = _bilinear64(images[v], xs, ys)

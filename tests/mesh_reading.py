@@ -7,7 +7,7 @@ the normal against the direction from the centroid of the inside corners to that
 tsdf64() restates mvs_engine_tsdf in float64 and says which (point, view) pairs lie inside a margin."""
 import numpy as np
 
-from maps_reading import popcount
+from maps_reading import EDGE_PX, S_MARGIN, popcount
 
 #: the Kuhn split of a cube along its main diagonal, as corner tuples (corner c = dx + 2 dy + 4 dz)
 TETS = ((0, 1, 3, 7), (0, 1, 5, 7), (0, 2, 3, 7), (0, 2, 6, 7), (0, 4, 5, 7), (0, 4, 6, 7))
@@ -138,9 +138,9 @@ def sphere_volume(dims, centers, radius, origin=(0.0, 0.0, 0.0), voxel=1.0):
     return d.astype(np.float32)
 
 
-def tsdf64(pat, ids, bits, unsure, cams, min_consistent, origin, voxel, dims, trunc):
+def tsdf64(pat, ids, bits, unsure, cams, min_consistent, origin, voxel, dims, trunc, edge_px=EDGE_PX, s_margin=S_MARGIN):
     """mvs_engine_tsdf in float64.  pat: the records by pool index; ids[v], bits[v], unsure[v]: view v's id map and the agree words of
-    agree64 with their margins; cams: cameras64 of tests/maps_reading.py.
+    agree64 with their margins; cams: cameras64 of tests/maps_reading.py; edge_px, s_margin: maps_reading.margins().
     -> dict of [nz, ny, nx] arrays: tsdf, count, sure (no pair of the point lies inside a margin), reached (some view takes the point to
     a usable pixel), bound (max over the contributing views of dz / (|cos(n_q, ray)| trunc))"""
     nx, ny, nz = dims
@@ -152,7 +152,7 @@ def tsdf64(pat, ids, bits, unsure, cams, min_consistent, origin, voxel, dims, tr
         h = X @ cam["P"][:, :3].T + cam["P"][:, 3]
         assert (h[:, 2] > 0.1).all()
         px, py = h[:, 0] / h[:, 2] + 0.5, h[:, 1] / h[:, 2] + 0.5
-        edge = np.minimum(np.abs(px - np.rint(px)), np.abs(py - np.rint(py))) <= 1e-3
+        edge = np.minimum(np.abs(px - np.rint(px)), np.abs(py - np.rint(py))) <= edge_px
         fx, fy = np.floor(px).astype(int), np.floor(py).astype(int)
         inside = (fx >= 0) & (fx < cam["W"]) & (fy >= 0) & (fy < cam["H"])
         cy, cx = np.clip(fy, 0, cam["H"] - 1), np.clip(fx, 0, cam["W"] - 1)
@@ -166,8 +166,8 @@ def tsdf64(pat, ids, bits, unsure, cams, min_consistent, origin, voxel, dims, tr
         # a projection within 1e-3 pixel of a rounding boundary may be taken to the pixel across it: that matters unless none of the
         # pixels it can be taken to could be usable
         any_use = np.zeros(N, bool)
-        for yy in (np.floor(py - 1e-3).astype(int), np.floor(py + 1e-3).astype(int)):
-            for xx in (np.floor(px - 1e-3).astype(int), np.floor(px + 1e-3).astype(int)):
+        for yy in (np.floor(py - edge_px).astype(int), np.floor(py + edge_px).astype(int)):
+            for xx in (np.floor(px - edge_px).astype(int), np.floor(px + edge_px).astype(int)):
                 ok = (xx >= 0) & (xx < cam["W"]) & (yy >= 0) & (yy < cam["H"])
                 any_use |= ok & use_hi[np.clip(yy, 0, cam["H"] - 1), np.clip(xx, 0, cam["W"] - 1)]
         sure &= ~(edge & any_use)
@@ -181,7 +181,7 @@ def tsdf64(pat, ids, bits, unsure, cams, min_consistent, origin, voxel, dims, tr
             sd = (s - 1.0) * dz
             cos = np.abs(den) / (np.linalg.norm(nq, axis=1) * np.linalg.norm(ray, axis=1))
         assert (dz > 0.1).all() and (cos[met] > 0.2).all(), "the scene has a grazing plane or a point behind a camera"
-        sure &= ~(met & (np.abs(sd + trunc) < 1e-5 * dz))
+        sure &= ~(met & (np.abs(sd + trunc) < s_margin * dz))
         add = met & (sd >= -trunc)
         total[add] += np.minimum(sd[add] / trunc, 1.0)
         cnt[add] += 1

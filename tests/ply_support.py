@@ -123,11 +123,12 @@ def write_ply(path, fmt, xyz, normals=None, extra_colour=False, faces=None):
                 f.write(struct.pack(e + "B" + "i" * len(face), len(face), *face))
 
 
-def euler_camera(a, b, g, t, fx=60.0, fy=60.0, cx=W / 2.0, cy=H / 2.0):
-    """CONTOUR2 line of a camera (camera.cpp:117-134, quat2proj 241-261) and its rotation."""
+def euler_camera(a, b, g, t, fx=60.0, fy=60.0, cx=W / 2.0, cy=H / 2.0, skew=0.0):
+    """CONTOUR2 line of a camera (camera.cpp:117-134: K = [[fx, skew, cx], [0, fy, cy], [0, 0, 1]]; quat2proj 241-261) and its rotation."""
     s1, s2, s3, c1, c2, c3 = (math.sin(math.radians(a)), math.sin(math.radians(b)), math.sin(math.radians(g)),
                               math.cos(math.radians(a)), math.cos(math.radians(b)), math.cos(math.radians(g)))
     R = np.array([[c2 * c3, c3 * s2 * s1 - s3 * c1, c3 * s2 * c1 + s3 * s1], [s3 * c2, s3 * s2 * s1 + c3 * c1, s3 * s2 * c1 - c3 * s1],
                   [-s2, c2 * s1, c2 * c1]])
-    text = "CONTOUR2\n%r %r 0 %r %r 0\n%r %r %r\n%r %r %r\n" % tuple(float(v) for v in (fx, fy, cx, cy, a, b, g, t[0], t[1], t[2]))
+    text = "CONTOUR2\n%r %r %s %r %r 0\n%r %r %r\n%r %r %r\n" % ((float(fx), float(fy), "0" if skew == 0 else repr(float(skew)))
+                                                            + tuple(float(v) for v in (cx, cy, a, b, g, t[0], t[1], t[2])))
     return text, R

@@ -159,10 +159,13 @@ def engine_with_pool(sc, ekw, masks, sizes, list_cap, seeds):
 
 
 def lattice(sc, level, min_count=1):
-    """the case's mvs_volume: 1.5 pixel footprints at the scene's radius of 4, around the origin"""
-    foot = 4.0 / (765.702941895 * sc.W / 640.0 / 2 ** level)
+    """the case's mvs_volume: 1.5 pixel footprints at the scene's radius of 4 (with the scene's focal: the largest where the views'
+    differ, so the smallest footprint), around the scene's target"""
+    focal = float(np.max(sc.meta.get("focal", 765.702941895 * sc.W / 640.0)))
+    target = sc.meta.get("target", (0.0, 0.0, 0.0))
+    foot = 4.0 / (focal / 2 ** level)
     voxel = 1.5 * foot
-    origin = [(-DIMS[c] / 2 + SHIFT[c]) * voxel for c in range(3)]
+    origin = [target[c] + (-DIMS[c] / 2 + SHIFT[c]) * voxel for c in range(3)]
     return engine.make_volume(origin, voxel, DIMS, TRUNC_VOXELS * voxel, min_count)
 
 

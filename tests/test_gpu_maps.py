@@ -10,13 +10,19 @@ fused-point comparison.  Every case asserts that the reading leaves out fewer th
 with no agreeing view and at least 10 % with all other views agreeing: a vacuous or one-sided case fails.
 
 Depth bound: the reading is about 30 float32 operations at unit roundoff 2^-24 divided by the cosine between the normal and the ray, about
-2e-6 / cos; the bound 2e-5 / |cos| relative keeps a tenfold margin."""
+2e-6 / cos; the bound 2e-5 / |cos| relative keeps a tenfold margin.
+
+Cameras off the arc (camera_scenes.py): where the world lies off the origin every one of those roundings is relative to the coordinates,
+kappa(sc) times the depths, so the depth bound is 2e-5 kappa / |cos|, and the margins are maps_reading.margins(kappa, W, H), which
+derives them from the operation counts: max(1e-3, 48 kappa 2^-24 max(W, H)) pixels, max(1e-5, 128 kappa 2^-24) on s, 1e-5 on n . n_q.
+The caps do not move."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from maps_reading import DEPTH_TOL, NORMAL_COS, agree64, cameras64, expected_ids, fused64, popcount, render64
+import camera_scenes as cs
+from maps_reading import DEPTH_TOL, NORMAL_COS, agree64, cameras64, expected_ids, fused64, margins, popcount, render64
 from mvskit_amd import engine, synth
 from mvskit_amd.engine import MVS_ERR_CAPACITY, MVS_ERR_STATE
 from scene_support import PLAIN, cached_scene, engine_with_pool, mask_at
@@ -24,7 +30,7 @@ from scene_support import PLAIN, cached_scene, engine_with_pool, mask_at
 pytestmark = pytest.mark.gpu
 
 
-def _check_fused(e, pts, maps, cams, want, source, dedupe):
+def _check_fused(e, pts, maps, cams, want, source, dedupe, edge_px=1e-3):
     """the records of one fused_points call against the reading's (emit, sure) masks; -> the set of (view, y, x) emitted"""
     got = set()
     last = (-1, -1, -1)
@@ -36,7 +42,7 @@ def _check_fused(e, pts, maps, cams, want, source, dedupe):
         h = r["xyz"].astype(np.float64) @ cam["P"][:, :3].T + cam["P"][:, 3]
         px, py = h[:, 0] / h[:, 2], h[:, 1] / h[:, 2]
         x, y = np.rint(px).astype(int), np.rint(py).astype(int)
-        assert np.abs(px - x).max() < 1e-3 and np.abs(py - y).max() < 1e-3, "xyz does not project onto its pixel"
+        assert np.abs(px - x).max() < edge_px and np.abs(py - y).max() < edge_px, "xyz does not project onto its pixel"
         assert (x >= 0).all() and (x < cam["W"]).all() and (y >= 0).all() and (y < cam["H"]).all()
         assert (r["rgb"] == e.pyramid(v, e.cfg.level)[y, x]).all()
         assert r["normal"].tobytes() == maps[v]["normal"][y, x].tobytes() and r["conf"].tobytes() == maps[v]["conf"][y, x].tobytes()
@@ -53,8 +59,9 @@ def _check_fused(e, pts, maps, cams, want, source, dedupe):
     return got
 
 
-def _case(sc, ekw, source=0, masks=None, sizes=None, list_cap=None, seeds=None, twin=True):
+def _case(sc, ekw, source=0, masks=None, sizes=None, list_cap=None, seeds=None, twin=True, kappa=1.0):
     level, csize = ekw["level"], ekw["csize"]
+    mg = margins(kappa, sc.W >> level, sc.H >> level)
     sizes = sizes or [(sc.W, sc.H)] * sc.nviews
     seeds = synth.make_seeds(sc, level, csize, stride=1) if seeds is None else seeds
     e = engine_with_pool(sc, ekw, masks, sizes, list_cap, seeds)
@@ -81,7 +88,7 @@ def _case(sc, ekw, source=0, masks=None, sizes=None, list_cap=None, seeds=None, 
         for k in ("depth", "normal", "conf"):
             assert np.isnan(m[k][~have]).all() and not np.isnan(m[k][have]).any()
         assert (m["agree"][~have] == 0).all()
-        ratio = np.abs(m["depth"][have].astype(np.float64) - depth[have]) / np.abs(depth[have]) / (2e-5 / cos[have])
+        ratio = np.abs(m["depth"][have].astype(np.float64) - depth[have]) / np.abs(depth[have]) / (2e-5 * kappa / cos[have])
         worst = max(worst, float(ratio.max()) if have.any() else 0.0)
         ids.append(want_ids)
         X.append(Xv)
@@ -92,7 +99,7 @@ def _case(sc, ekw, source=0, masks=None, sizes=None, list_cap=None, seeds=None, 
     nvalid = nout = none = full = 0
     hist = np.zeros(sc.nviews, int)
     for v in range(sc.nviews):
-        b, u = agree64(pat, ids, X, cams, v, DEPTH_TOL, NORMAL_COS)
+        b, u = agree64(pat, ids, X, cams, v, DEPTH_TOL, NORMAL_COS, mg["edge"], mg["s"], mg["cos"])
         got = maps[v]["agree"]
         assert (((got >> np.uint64(v)) & np.uint64(1)) == 0).all(), f"view {v}: its own bit is set"
         assert ((got >> np.uint64(sc.nviews)) == 0).all(), f"view {v}: a bit beyond the last view is set"
@@ -119,9 +126,9 @@ def _case(sc, ekw, source=0, masks=None, sizes=None, list_cap=None, seeds=None, 
     m = C.c_int64()
     assert e.L.mvs_engine_fused_points(e.h, C.byref(c), n.value - 1, small.ctypes.data_as(C.c_void_p), C.byref(m)) == MVS_ERR_CAPACITY
     assert m.value == n.value and small.tobytes() == keep, "a call with cap = n - 1 wrote to out"
-    deduped = _check_fused(e, pts, maps, cams, fused64(ids, bits, unsure, 1, True), source, True)
+    deduped = _check_fused(e, pts, maps, cams, fused64(ids, bits, unsure, 1, True), source, True, mg["edge"])
     all_pts = e.fused_points(source=source, min_consistent=1, depth_tol=DEPTH_TOL, normal_cos=NORMAL_COS, dedupe=False)
-    everyone = _check_fused(e, all_pts, maps, cams, fused64(ids, bits, unsure, 1, False), source, False)
+    everyone = _check_fused(e, all_pts, maps, cams, fused64(ids, bits, unsure, 1, False), source, False, mg["edge"])
     assert deduped <= everyone and len(everyone) > len(deduped), "dedupe = 0 does not emit a superset"
     print(f"maps: {pts.shape[0]} fused points, {all_pts.shape[0]} without dedupe")
     # nothing of the engine's state moved: the pool, the thresholds, and the pass that follows against a twin that never rendered
@@ -140,6 +147,15 @@ def _case(sc, ekw, source=0, masks=None, sizes=None, list_cap=None, seeds=None, 
 def test_plain(source):
     """3 views of 96 x 64, csize 2, level 0: the plain path, both selections"""
     _case(cached_scene(3, 96, 64, 30.0), PLAIN, source=source)
+
+
+@pytest.mark.parametrize("family", cs.FAMILIES)
+def test_camera_families(family):
+    """3 views of 96 x 64 on the plane, off the arc: rolled views (the agreement gather takes a pixel of a view turned by 90 degrees to
+    a column of another), per-view intrinsics and distances (P_L, Minv, centre and oaxis indexed by view), the world at (6, -4, 8)
+    (`far`, and `mixed` with all three)"""
+    sc = cs.reading_scene(family)
+    _case(sc, PLAIN, kappa=cs.kappa(sc))
 
 
 def test_ragged_grid():

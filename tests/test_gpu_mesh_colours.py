@@ -13,14 +13,19 @@ the usability or the patch differs, or of the window's edge; when |s - 1| lies w
 when the pixel's usability rests on an unsure agree pair.  A vertex with such a pair is left out, and every case asserts that these are
 fewer than 5 % of the vertices that any view reaches (the figures are in DESIGN.md, f-8).  On the others `used` is exact and
 |rgb - mean64| <= 0.51 per channel: half a unit of rounding plus 0.01 -- the fp32 chain of about 20 operations on values up to 255 errs
-by under 1e-3."""
+by under 1e-3.
+
+Cameras off the arc (camera_scenes.py): the caller's set lies on the plane z = target_z around the target, the margins are
+maps_reading.margins(kappa, W, H) (min_cos keeps 1e-5: w is a dot product of a unit normal with C - X, 8 roundings relative to
+kappa times the depth, 3e-6 at kappa = 7).  The colour bound stays 0.51: the worst seen on the families is 0.49999."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import camera_scenes as cs
 import mesh_attr_reading as ar
-from maps_reading import DEPTH_TOL, NORMAL_COS, cameras64, render_agree64
+from maps_reading import DEPTH_TOL, NORMAL_COS, cameras64, margins, render_agree64
 from mvskit_amd import engine, synth
 from mvskit_amd.engine import MVS_ERR_STATE
 from scene_support import PLAIN, cached_scene, engine_with_pool, lattice, many_view_seeds, mask_at
@@ -34,17 +39,18 @@ GREY = np.array([128, 128, 128], np.uint8)
 
 def caller_set(sc, level, band_view=None, band=None):
     """-> (verts [n, 3] float32, normals [n, 3] float32, {name: slice})"""
-    foot = 4.0 / (765.702941895 * sc.W / 640.0 / 2 ** level)
+    foot = 4.0 / (float(np.max(sc.meta.get("focal", 765.702941895 * sc.W / 640.0))) / 2 ** level)
+    target = np.asarray(sc.meta.get("target", (0.0, 0.0, 0.0)))
     W, H = sc.W >> level, sc.H >> level
     rng = np.random.default_rng(17)
     gx, gy = np.meshgrid(np.linspace(-0.56, 0.56, 24) * W * foot, np.linspace(-0.56, 0.56, 16) * H * foot)
     step = 1.12 * W * foot / 23
-    xy = np.stack([gx.ravel(), gy.ravel()], 1) + rng.uniform(-0.3, 0.3, (gx.size, 2)) * step
+    xy = np.stack([gx.ravel(), gy.ravel()], 1) + rng.uniform(-0.3, 0.3, (gx.size, 2)) * step + target[:2]
     n = xy.shape[0]
     up, zero = np.tile([0.0, 0.0, 1.0], (n, 1)), np.zeros((n, 3))
 
     def at(z):
-        return np.concatenate([xy, np.full((n, 1), z)], 1)
+        return np.concatenate([xy, np.full((n, 1), target[2] + z)], 1)
 
     parts = [("plane", at(0.0), up), ("above", at(0.2), up), ("below", at(-0.2), up), ("facing_away", at(0.0), -up), ("zero_normal", at(0.0), zero),
              ("outside", at(0.0)[:24] + [60.0, 0.0, 0.0], up[:24])]
@@ -80,7 +86,7 @@ def check_colours(name, r, rgb, used, cap=0.05):
     return worst
 
 
-def _case(sc, ekw, masks=None, list_cap=None, seeds=None, band=None):
+def _case(sc, ekw, masks=None, list_cap=None, seeds=None, band=None, kappa=1.0):
     level, csize = ekw["level"], ekw["csize"]
     sizes = [(sc.W, sc.H)] * sc.nviews
     seeds = synth.make_seeds(sc, level, csize, stride=1) if seeds is None else seeds
@@ -91,13 +97,14 @@ def _case(sc, ekw, masks=None, list_cap=None, seeds=None, band=None):
     thr = e.thresholds()
     cams = cameras64(sc, level, sizes)
     ids = [m["ids"] for m in e.render_maps(depth_tol=DEPTH_TOL, normal_cos=NORMAL_COS)]
-    bits, unsure = render_agree64(pat, ids, cams)
+    mg = margins(kappa, sc.W >> level, sc.H >> level)
+    bits, unsure = render_agree64(pat, ids, cams, edge_px=mg["edge"], s_margin=mg["s"], cos_margin=mg["cos"])
     images = [e.pyramid(v, level) for v in range(sc.nviews)]
     lmasks = None if masks is None else [None if m is None else mask_at(m, sizes[v], level) for v, m in enumerate(masks)]
     vol = lattice(sc, level)
 
     def reading(verts, normals):
-        return ar.colours64(pat, ids, bits, unsure, cams, images, lmasks, verts, normals, 1, DEPTH_TOL, MIN_COS)
+        return ar.colours64(pat, ids, bits, unsure, cams, images, lmasks, verts, normals, 1, DEPTH_TOL, MIN_COS, mg["edge"], mg["s"], mg["cos"])
 
     # (a) the engine's own mesh
     verts, tris = e.mesh(vol, **KW)
@@ -149,6 +156,14 @@ def _case(sc, ekw, masks=None, list_cap=None, seeds=None, band=None):
 def test_plain():
     """3 views of 96 x 64 on the textured plane, csize 2"""
     _case(cached_scene(3, 96, 64, 30.0), PLAIN)
+
+
+@pytest.mark.parametrize("family", cs.FAMILIES)
+def test_camera_families(family):
+    """3 views of 96 x 64 on the plane, off the arc: k_mattr_colours' projection, window and image indexed by views that differ, rolled
+    views, and vertices around (6, -4, 8) (`far`, `mixed`)"""
+    sc = cs.reading_scene(family)
+    _case(sc, PLAIN, kappa=cs.kappa(sc))
 
 
 def test_ragged_grid_with_a_mask_band():

@@ -17,12 +17,16 @@ The 40-view case differs from the maps test's in two ways, both found on the CPU
 lattice point, unlike a rendered pixel's point, projects anywhere in a pixel, and over an arc of 1 degree its 40 projections spread over
 a tenth of a pixel, which leaves 6 % of the reached points within 1e-3 pixel of a boundary in some view (no shift of the lattice and no
 spacing from 1.45 to 1.55 footprints brought that below 5 %); at 0.25 degrees it is 2.2 %.  And its seeds are exact everywhere
-(many_view_seeds).  The volume is two-sided all the same: 16 % of the reached points at 1, 67 % inside the band, 17 % silent."""
+(many_view_seeds).  The volume is two-sided all the same: 16 % of the reached points at 1, 67 % inside the band, 17 % silent.
+
+Cameras off the arc (camera_scenes.py): the plane is z = target_z, the lattice lies around the target, the margins are
+maps_reading.margins(kappa, W, H) and the bound is 2e-5 kappa times the same maximum, as in tests/test_gpu_maps.py."""
 import numpy as np
 import pytest
 
+import camera_scenes as cs
 import mesh_reading as mr
-from maps_reading import DEPTH_TOL, NORMAL_COS, cameras64, render_agree64
+from maps_reading import DEPTH_TOL, NORMAL_COS, cameras64, margins, render_agree64
 from mvskit_amd import engine, synth
 from mvskit_amd.engine import MVS_ERR_STATE
 from scene_support import DIMS, PLAIN, cached_scene, engine_with_pool, lattice, many_view_seeds
@@ -30,13 +34,14 @@ from scene_support import DIMS, PLAIN, cached_scene, engine_with_pool, lattice, 
 pytestmark = pytest.mark.gpu
 
 
-def reading(pat, ids, cams, vol, min_consistent=1):
+def reading(pat, ids, cams, vol, min_consistent=1, kappa=1.0):
     """tsdf64 of the volume over the pool `pat` (records by pool index) and the id maps"""
-    bits, unsure = render_agree64(pat, ids, cams)
-    return mr.tsdf64(pat, ids, bits, unsure, cams, min_consistent, vol.origin[:], vol.voxel, vol.dims[:], vol.trunc)
+    mg = margins(kappa, max(c["W"] for c in cams), max(c["H"] for c in cams))
+    bits, unsure = render_agree64(pat, ids, cams, edge_px=mg["edge"], s_margin=mg["s"], cos_margin=mg["cos"])
+    return mr.tsdf64(pat, ids, bits, unsure, cams, min_consistent, vol.origin[:], vol.voxel, vol.dims[:], vol.trunc, mg["edge"], mg["s"])
 
 
-def check_volume(r, tsdf, count, cap=0.05):
+def check_volume(r, tsdf, count, cap=0.05, kappa=1.0):
     """the engine's volume against the reading r; cap: the share of the reached points the reading may leave out; -> the largest
     fraction of the bound"""
     sure, reached = r["sure"], r["reached"]
@@ -47,7 +52,7 @@ def check_volume(r, tsdf, count, cap=0.05):
     assert (count[sure] == r["count"][sure]).all(), "count differs from the float64 reading outside the margins"
     assert (np.isnan(tsdf) == (count == 0)).all()
     have = sure & (r["count"] > 0)
-    ratio = np.abs(tsdf[have].astype(np.float64) - r["tsdf"][have]) / (2e-5 * r["bound"][have])
+    ratio = np.abs(tsdf[have].astype(np.float64) - r["tsdf"][have]) / (2e-5 * kappa * r["bound"][have])
     worst = float(ratio.max())
     print(f"mesh: tsdf error at most {worst:.4f} of its bound")
     assert worst <= 1.0
@@ -60,7 +65,7 @@ def check_volume(r, tsdf, count, cap=0.05):
     return worst
 
 
-def _case(sc, ekw, masks=None, list_cap=None, seeds=None):
+def _case(sc, ekw, masks=None, list_cap=None, seeds=None, kappa=1.0):
     level, csize = ekw["level"], ekw["csize"]
     sizes = [(sc.W, sc.H)] * sc.nviews
     seeds = synth.make_seeds(sc, level, csize, stride=1) if seeds is None else seeds
@@ -77,7 +82,7 @@ def _case(sc, ekw, masks=None, list_cap=None, seeds=None):
     assert tsdf.shape == count.shape == (DIMS[2], DIMS[1], DIMS[0]) and tsdf.dtype == np.float32 and count.dtype == np.int32
     again = e.tsdf(vol, **kw)
     assert again[0].tobytes() == tsdf.tobytes() and again[1].tobytes() == count.tobytes(), "two calls give different bytes"
-    check_volume(reading(pat, ids, cams, vol), tsdf, count)
+    check_volume(reading(pat, ids, cams, vol, kappa=kappa), tsdf, count, kappa=kappa)
     assert count.max() <= sc.nviews and count.max() >= 2
     # the chained call: the bytes of the two calls, which are the reading's of that volume
     verts, tris = e.mesh(vol, **kw)
@@ -94,10 +99,11 @@ def _case(sc, ekw, masks=None, list_cap=None, seeds=None):
     v2, t2 = e.mesh(vol2, **kw)
     w2, u2 = mr.extract(vol.origin[:], vol.voxel, DIMS, tsdf, count, 2)
     assert v2.tobytes() == w2.tobytes() and t2.tobytes() == u2.tobytes() and 0 < t2.shape[0] <= tris.shape[0]
-    # on the plane z = 0: a crossing lies on the edge that brackets it
-    dist = np.abs(verts[:, 2].astype(np.float64))
+    # on the plane z = 0 (z = the target's where the scene has one): a crossing lies on the edge that brackets it
+    z0 = sc.meta.get("target", (0.0, 0.0, 0.0))[2]
+    dist = np.abs(verts[:, 2].astype(np.float64) - z0)
     pts = e.fused_points(**kw)
-    pdist = np.abs(pts["xyz"][:, 2].astype(np.float64))
+    pdist = np.abs(pts["xyz"][:, 2].astype(np.float64) - z0)
     print(f"mesh: {verts.shape[0]} vertices, {tris.shape[0]} triangles; distance to the plane in voxels: median {np.median(dist) / vol.voxel:.4f}, "
           f"max {dist.max() / vol.voxel:.4f}; fused points: median {np.median(pdist) / vol.voxel:.4f}, max {pdist.max() / vol.voxel:.4f}")
     assert np.median(dist) < vol.voxel
@@ -114,6 +120,14 @@ def _case(sc, ekw, masks=None, list_cap=None, seeds=None):
 def test_plain():
     """3 views of 96 x 64 on the textured plane, csize 2"""
     _case(cached_scene(3, 96, 64, 30.0), PLAIN)
+
+
+@pytest.mark.parametrize("family", cs.FAMILIES)
+def test_camera_families(family):
+    """3 views of 96 x 64 on the plane, off the arc: the projection, the image size and the centre of k_mesh_tsdf indexed by views
+    that differ, rolled views, and the lattice around (6, -4, 8) (`far`, `mixed`)"""
+    sc = cs.reading_scene(family)
+    _case(sc, PLAIN, kappa=cs.kappa(sc))
 
 
 def test_ragged_grid_with_a_mask_band():

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import camera_scenes as cs
 from mvskit_amd import build, engine, synth
 from ply_support import level_inputs, parse_ascii, restate_ply
 
@@ -28,7 +29,17 @@ def host():
 @pytest.mark.parametrize("level", [0, 1])
 def test_mirror_writeply_is_the_restatement(host, small_plane_scene, tmp_path, level):
     """PatchManager::writePly of the host mirror (now mvs_engine_export_ply) writes, byte for byte, the file of the restatement."""
-    sc = small_plane_scene
+    _mirror_writeply(host, small_plane_scene, tmp_path, level)
+
+
+@pytest.mark.gpu
+def test_mirror_writeply_on_mixed_cameras(host, tmp_path):
+    """the same at level 0 on the `mixed` family of camera_scenes.py, 3 views of 160 x 120 of the plane: k_ply_colour's projection and
+    image indexed by views whose intrinsics, roll and distance differ, around (12, -8, 16)"""
+    _mirror_writeply(host, cs.family_scene("mixed", 3, 160, 120, 30.0, "plane"), tmp_path, 0)
+
+
+def _mirror_writeply(host, sc, tmp_path, level):
     seeds = synth.make_seeds(sc, level=level, stride=4, seed=21)
     out = np.zeros(200000, dtype=engine.PATCH_DTYPE)
     nout, ptot = C.c_longlong(), C.c_longlong()

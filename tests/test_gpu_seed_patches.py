@@ -63,13 +63,13 @@ def members(ds, X, views=None):
     return out
 
 
-def make_dataset(root, host, nv, pts, no_mask=(), near=(), holes_for=(), arc=(-15.0, 15.0), seed=5, sizes=None):
+def make_dataset(root, host, nv, pts, no_mask=(), near=(), holes_for=(), arc=(-15.0, 15.0), seed=5, sizes=None, intrinsics=None):
     """A dataset directory in the layout of tests/test_seed_plys.py: CONTOUR2 cameras on an arc 4 units from a plane through the origin
     (`near`: 1 unit), the 40 x 30 JPEG as every image, PGM masks with a background band and sub-threshold greys (`no_mask`: no file),
     the point cloud, one binary normal-map PLY per view with holes.  holes_for: points whose pixels carry no normal in any view.
     sizes: one (width, height) per view instead of 40 x 30 -- a binary PPM of that size as the view's image (PhotoSet::init takes
     <name>.ppm before <name>.jpg), masks and maps of that size; the cameras share the intrinsics of sizes[0], so a smaller view is a
-    top-left crop.  Returns the projections the mirror derives, the level-0 masks as stored, and the maps readNormals leaves (R * n in float32)."""
+    top-left crop.  intrinsics: one dict(fx, fy, cx, cy, skew) per view instead of the shared one.  Returns the projections the mirror derives, the level-0 masks as stored, and the maps readNormals leaves (R * n in float32)."""
     for d in ("txt", "image", "mask", "ply"):
         os.makedirs(root / d)
     (root / "option").write_text(f"level 0\ncsize 2\nthreshold 0.7\nwsize 7\nminImageNum 2\nimages -1 0 {nv}\n")
@@ -85,7 +85,7 @@ def make_dataset(root, host, nv, pts, no_mask=(), near=(), holes_for=(), arc=(-1
         angles = (3.0 * (v % 7) - 4.0, ang, 2.0 * (v % 3))
         _, R = euler_camera(*angles, (0.0, 0.0, 0.0))
         t = -R @ centre
-        text, _ = euler_camera(*angles, t, **intr)
+        text, _ = euler_camera(*angles, t, **(intr if intrinsics is None else intrinsics[v]))
         ds["P"].append(probe_camera(host, root / "txt" / f"{v:08d}.txt", text))
         # Photo::m_R itself: with K = identity the projection the mirror derives is [R | t] exactly
         unit_k, _ = euler_camera(*angles, t, fx=1.0, fy=1.0, cx=0.0, cy=0.0)
@@ -341,4 +341,31 @@ def test_case7_odd_and_unequal_view_sizes(tmp_path, sizes):
             e.seed_patches(ds["pts"], [ds["maps"][0]] * 4, ds["masks"])  # view 2's map must have view 2's shape
     ce, co = e.propagate(0), o.propagate(0)
     assert ce == co, (ce, co)
+    assert_same_pool(e.patches(), o.patches())
+
+
+def test_case8_unequal_intrinsics(tmp_path):
+    """4 views 40 x 30 whose intrinsics differ (the `intrinsics` family of tests/camera_scenes.py at this size: fx = 60 * (1, 1.25, 0.85,
+    1.1), fy = 1.07 fx, skew 0.02 fx, the principal point off centre by (0, 0), (9.5, -6.25), (-12, 4), (3, 3) pixels at W = 160): the
+    kernel's SeedCam table read per view, records byte for byte against the mirror's loop, and the same pool after one Propagate::run.
+    The view lists differ from those the same points get when every view has the shared intrinsics of the other cases."""
+    host = host_lib(16)
+    intr = []
+    for v in range(4):
+        fx = 60.0 * (1.0, 1.25, 0.85, 1.1)[v]
+        dx, dy = ((0.0, 0.0), (9.5, -6.25), (-12.0, 4.0), (3.0, 3.0))[v]
+        intr.append(dict(fx=fx, fy=1.07 * fx, skew=0.02 * fx, cx=W / 2.0 + dx * W / 160.0, cy=H / 2.0 + dy * W / 160.0))
+    pts = plane_points(300)
+    ds = make_dataset(tmp_path / "d", host, 4, pts, intrinsics=intr)
+    for v in range(4):  # the mirror derived what the family asks for: rows 0 and 1 of P differ in scale by 1.07 and by view
+        K = ds["P"][v][:, :3].astype(np.float64) @ ds["R"][v].astype(np.float64).T
+        np.testing.assert_allclose(K, [[intr[v]["fx"], intr[v]["skew"], intr[v]["cx"]], [0, intr[v]["fy"], intr[v]["cy"]], [0, 0, 1]], rtol=0, atol=1e-4)
+    e, o, got, exp = device_and_mirror(ds, 16)
+    assert 100 < len(got) < 300 - 5  # case 1's bounds: points are dropped, and not only the five far ones
+    assert len(set(got["nimages"].tolist())) > 1
+    shared = make_dataset(tmp_path / "s", host, 4, pts)
+    moved = sum([v for v, _ in members(shared, X)] != [v for v, _ in members(ds, X)] for X in ds["pts"])
+    assert moved > 20, moved
+    ce, co = e.propagate(0), o.propagate(0)
+    assert ce == co and ce["patches"] > 0, (ce, co)
     assert_same_pool(e.patches(), o.patches())

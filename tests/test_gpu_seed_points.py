@@ -15,6 +15,7 @@ pixel of every view, concatenated: what structure-from-motion would hand over, w
 import numpy as np
 import pytest
 
+import camera_scenes as cams_off_arc
 from maps_reading import center64, oaxis64
 from mvskit_amd import engine, synth
 from parity_support import COUNTERS, REL_TOL, pair
@@ -92,6 +93,14 @@ def test_unequal_views():
 def test_many_views(list_cap):
     """20 views of 48 x 32, every view a hypothesis: the 16-view library cuts the lists, the 64-view library (192-byte records) holds them"""
     _case(cached_scene(20, 48, 32, 60.0), dict(level=0, csize=2, minImageNum=3, depth=0), K=20, list_cap=list_cap)
+
+
+@pytest.mark.parametrize("family", cams_off_arc.FAMILIES)
+def test_camera_families(family):
+    """3 views of 96 x 64 off the arc (camera_scenes.py; `far` at (300, -150, 500), `mixed` at (12, -8, 16)): the SeedCam table differs
+    by view, the nearest views are not the arc's neighbours, the unit vector to the camera is a difference of coordinates hundreds of
+    units large"""
+    _case(cams_off_arc.family_scene(family, 3, 96, 64, 30.0, "plane"), PLAIN, K=3)
 
 
 # ---- further cases, each held to bit-equality with the chain
@@ -248,10 +257,11 @@ def test_state_and_empty():
 
 
 # ---- steps 1 and 2 against a float64 reading
-def _reading(sc, pts, level, sizes, masks):
+def _reading(sc, pts, level, sizes, masks, off_arc=False):
     """float64: per (point, view) the gate, the depth, the squared camera distance, the sum of the depth's term magnitudes, and whether
     the pair keeps the margins inside which the float32 gate must agree: the projection more than 1e-3 pixel from a rounding boundary
-    (image and mask edges are such boundaries), the depth more than 1e-3 of its magnitude from zero"""
+    (image and mask edges are such boundaries), the depth more than 1e-3 of its magnitude from zero.  off_arc: the margin in pixels is
+    maps_reading.margins' with the pair's own kappa, max(|X|_inf, |C|_inf) / |depth|: 48 kappa 2^-24 max(w, h) where that exceeds 1e-3"""
     X = pts.astype(np.float64)
     n, nv = X.shape[0], sc.nviews
     ok, safe = np.zeros((n, nv), bool), np.zeros((n, nv), bool)
@@ -276,8 +286,12 @@ def _reading(sc, pts, level, sizes, masks):
             fg = m[np.clip(fy, 0, h - 1).astype(int), np.clip(fx, 0, w - 1).astype(int)]
         ok[:, v] = inside & fg & (depth[:, v] > 0)
         edge = np.minimum(np.abs(px - np.rint(px)), np.abs(py - np.rint(py)))
-        safe[:, v] = (edge > 1e-3) & (np.abs(depth[:, v]) > 1e-3 * mag[:, v]) & (np.abs(x[:, 2]) > 1e-3 * (np.abs(X * P[2, :3]).sum(axis=1) + abs(P[2, 3])))
         c = center64(P32)
+        px_margin = 1e-3
+        if off_arc:
+            big = np.maximum(np.abs(X).max(axis=1), np.abs(c).max())
+            px_margin = np.maximum(1e-3, 48.0 * U * max(w, h) * big / np.maximum(np.abs(depth[:, v]), 1e-30))
+        safe[:, v] = (edge > px_margin) & (np.abs(depth[:, v]) > 1e-3 * mag[:, v]) & (np.abs(x[:, 2]) > 1e-3 * (np.abs(X * P[2, :3]).sum(axis=1) + abs(P[2, 3])))
         centers.append(c)
         dist[:, v] = ((c - X) ** 2).sum(axis=1)
     return ok, safe, depth, dist, mag, np.array(centers)
@@ -287,7 +301,8 @@ def _probe_points(sc, stride):
     """the scene's points, and copies pushed sideways and towards / beyond the cameras so that views drop out for every reason"""
     base = _points(sc, stride)
     side = base + np.array([1.2, 0.4, 0.0], np.float32)
-    near = base * np.float32(0.3) + np.array([0.0, 0.0, 2.5], np.float32)
+    target = np.asarray(sc.meta.get("target", (0.0, 0.0, 0.0)), np.float32)  # (0, 0, 0) on the arc: the same bits as without it
+    near = (base - target) * np.float32(0.3) + np.array([0.0, 0.0, 2.5], np.float32) + target
     far = base + np.array([0.0, 0.0, 6.0], np.float32)
     return np.ascontiguousarray(np.concatenate([base, side, near, far]), dtype=np.float32)
 
@@ -296,12 +311,16 @@ HYP_CASES = {
     "masked_level1": dict(scene=(3, 192, 128, 30.0), level=1, K=2, stride=8, band=(41, 89)),
     "twenty_views": dict(scene=(20, 48, 32, 60.0), level=0, K=20, stride=4, band=None),
     "three_of_twenty": dict(scene=(20, 48, 32, 60.0), level=0, K=3, stride=4, band=None),
+    # cameras off the arc (camera_scenes.py): 4 views of 96 x 64 of the plane, `mixed` at (12, -8, 16)
+    "intrinsics": dict(scene="intrinsics", level=0, K=4, stride=4, band=None),
+    "mixed": dict(scene="mixed", level=0, K=4, stride=4, band=None),
 }
 
 
 def _hyp_setup(name):
     cs = HYP_CASES[name]
-    sc = cached_scene(*cs["scene"])
+    off_arc = isinstance(cs["scene"], str)
+    sc = cams_off_arc.family_scene(cs["scene"], 4, 96, 64, 30.0, "plane") if off_arc else cached_scene(*cs["scene"])
     masks = None
     if cs["band"]:
         band = np.full((sc.H, sc.W), 255, np.uint8)
@@ -311,7 +330,7 @@ def _hyp_setup(name):
     e.set_scene(sc, masks=masks)
     pts = _probe_points(sc, cs["stride"])
     sizes = [(sc.W, sc.H)] * sc.nviews
-    ok, safe, depth, dist, mag, centers = _reading(sc, pts, cs["level"], sizes, masks)
+    ok, safe, depth, dist, mag, centers = _reading(sc, pts, cs["level"], sizes, masks, off_arc)
     # the points of the test: every (point, view) pair inside the margins, camera distances more than 1e-4 apart (relative)
     sd = np.sort(dist, axis=1)
     apart = ((sd[:, 1:] - sd[:, :-1]) > 1e-4 * sd[:, 1:]).all(axis=1)
@@ -362,7 +381,7 @@ def test_hypotheses_against_float64(name):
     assert (werr <= 4).all(), werr.max()
 
 
-@pytest.mark.parametrize("name", ["masked_level1", "twenty_views"])
+@pytest.mark.parametrize("name", ["masked_level1", "twenty_views", "intrinsics", "mixed"])
 def test_depth_ranges(name):
     e, sc, cs, pts, ok, depth, dist, mag, centers = _hyp_setup(name)
     before = (e.patches().tobytes(), e.thresholds())

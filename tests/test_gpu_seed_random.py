@@ -14,6 +14,7 @@ import math
 import numpy as np
 import pytest
 
+import camera_scenes as cs
 from mvskit_amd import engine, synth
 from parity_support import COUNTERS, pair
 from scene_support import PLAIN, cached_scene, mask_at, random_yardstick, ranges, strip
@@ -58,6 +59,13 @@ def test_plain():
     sc = cached_scene(3, 96, 64, 30.0)
     got = _case(sc, PLAIN, K=4)
     assert (got["nvimages"] == 0).all()
+
+
+@pytest.mark.parametrize("family", cs.FAMILIES)
+def test_camera_families(family):
+    """3 views of 96 x 64 off the arc (camera_scenes.py; `far` at (300, -150, 500), `mixed` at (12, -8, 16)), depths from
+    scene_support.ranges: unproject(d (px, py, 1)) where rows 0 and 1 of P differ in scale, carry a skew and a roll, and differ by view"""
+    _case(cs.family_scene(family, 3, 96, 64, 30.0, "plane"), PLAIN, K=4)
 
 
 def test_wide_range():

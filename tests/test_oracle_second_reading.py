@@ -3,32 +3,21 @@ source text (file:line cited per function), with no code shared with oracle/pmmv
 its reference summation order (ORC_SUM_SEQ).  The reference ships no golden vectors and cannot be built here (Eigen, CImg,
 NLopt absent), so this is what stands between "the oracle agrees with itself" and "two restatements of the same source
 agree": pyramids byte for byte, projections / patch axes / sampling / normalisation / NCC to float rounding (the oracle's
-documented deviations are reciprocal-multiplies and fused multiply-adds)."""
+documented deviations are reciprocal-multiplies and fused multiply-adds).  The checks that involve a camera live
+in reading_checks.py, which tests/test_camera_families.py runs on cameras off the arc."""
 import numpy as np
 import pytest
 
 import oracle_binding as ob
 from mvskit_amd import synth
-from second_reading import (F, RefCam, ref_compute_incc, ref_cost_func, ref_decode, ref_dot, ref_encode, ref_get_color, ref_get_mask_all,
-                            ref_get_paxes, ref_get_tex, ref_get_unit, ref_is_neighbor, ref_mask_down, ref_normalize, ref_project, ref_pyr_down,
-                            ref_quad_residual, ref_robustincc, ref_set_scales, ref_unproject)
+import reading_checks as rc
+from second_reading import F, RefCam, ref_get_color, ref_get_mask_all, ref_get_unit, ref_mask_down, ref_pyr_down, ref_quad_residual, ref_robustincc
 
 
 # ------------------------------------------------------------------ the comparison
 @pytest.fixture(scope="module")
 def setup():
-    sc = synth.make_scene(nviews=4, W=160, H=120, arc_deg=45.0, radius=4.0, kind="multi")
-    o = ob.Oracle(sc.nviews, level=0, csize=2, wsize=7, minImageNum=2, schedule=ob.SCHEDULE_ENGINE, sum_mode=ob.SUM_SEQ, enable_check=0, seed=1)
-    o.set_scene(sc)
-    cams = [RefCam(sc.P[v], 0) for v in range(sc.nviews)]
-    pyrs = []
-    for v in range(sc.nviews):
-        levels = [sc.images[v]]
-        for _ in range(2):
-            levels.append(ref_pyr_down(levels[-1]))
-        pyrs.append(levels)
-    seeds = synth.make_seeds(sc, stride=9, seed=4)
-    return sc, o, cams, pyrs, seeds
+    return rc.make_setup(synth.make_scene(nviews=4, W=160, H=120, arc_deg=45.0, radius=4.0, kind="multi"))
 
 
 def test_pyramid_second_reading(setup):
@@ -112,39 +101,13 @@ def test_mask_pyramid_second_reading_odd_sizes():
 
 
 def test_camera_second_reading(setup):
-    sc, o, cams, _, seeds = setup
-    for v in range(sc.nviews):
-        c = o.camera(v)
-        np.testing.assert_allclose(c["center"], cams[v].center, rtol=1e-5, atol=1e-6)
-        np.testing.assert_allclose(c["oaxis"], cams[v].oaxis, rtol=1e-6, atol=1e-7)
-        np.testing.assert_allclose(c["xaxis"], cams[v].xaxis, rtol=1e-5, atol=1e-6)
-        np.testing.assert_allclose(c["yaxis"], cams[v].yaxis, rtol=1e-5, atol=1e-6)
-        np.testing.assert_allclose(c["zaxis"], cams[v].zaxis, rtol=1e-5, atol=1e-6)
-        assert abs(c["ipscale"] - cams[v].ipscale) <= 1e-5 * abs(cams[v].ipscale)
-    for s in seeds[:40]:
-        X = s["coord"].astype(F)
-        for v in (0, 2):
-            for level in (0, 1):
-                P = cams[v].P[level]
-                ic = ref_project(P, X)
-                np.testing.assert_allclose(o.project(v, X, level), ic, rtol=2e-6, atol=1e-4)
-                homog = (ic * F(np.dot(P[2], X))).astype(F)  # (u*w, v*w, w): unproject inverts P exactly
-                back = ref_unproject(P, homog)
-                np.testing.assert_allclose(o.unproject(v, np.append(homog, F(1)), level), back, rtol=1e-4, atol=1e-4)
-                np.testing.assert_allclose(back[:3], X[:3], rtol=1e-3, atol=1e-3)
+    rc.check_camera(setup)
 
 
 def test_units_axes_and_samples_second_reading(setup):
     sc, o, cams, pyrs, seeds = setup
+    rc.check_units_and_axes(setup)
     rng = np.random.RandomState(3)
-    for s in seeds[:30]:
-        X, N = s["coord"].astype(F), s["normal"].astype(F)
-        v = int(s["images"][0])
-        assert abs(o.get_unit(v, X) - ref_get_unit(cams[v], X, 0)) <= 2e-6 * ref_get_unit(cams[v], X, 0)
-        px, py = o.get_paxes(v, X, N)
-        rx, ry = ref_get_paxes(cams[v], X, N, 0)
-        np.testing.assert_allclose(px, rx, rtol=2e-5, atol=1e-9)
-        np.testing.assert_allclose(py, ry, rtol=2e-5, atol=1e-9)
     for _ in range(200):
         v, level = rng.randint(sc.nviews), rng.randint(3)
         H, W = pyrs[v][level].shape[:2]
@@ -153,114 +116,22 @@ def test_units_axes_and_samples_second_reading(setup):
 
 
 def test_texture_and_incc_second_reading(setup):
-    sc, o, cams, pyrs, seeds = setup
-    cos_thr = F(np.cos(F(60.0 * np.pi / 180.0)))
-    checked = 0
-    for s in seeds[:60]:
-        X, N = s["coord"].astype(F), s["normal"].astype(F)
-        idx = [int(i) for i in s["images"][: s["nimages"]]]
-        if len(idx) < 2:
-            continue
-        px, py = ref_get_paxes(cams[idx[0]], X, N, 0)
-        t = ref_get_tex(cams[idx[1]], pyrs[idx[1]], X, px, py, N, 0, 7, cos_thr)
-        flag, tex = o.get_tex(X, px, py, N, idx[1], normalize=False)
-        assert (t is None) == (flag != 0)
-        if t is not None:
-            np.testing.assert_allclose(tex.reshape(49, 3), t, rtol=1e-5, atol=2e-3)  # positions differ by float rounding of the axes
-            flag, texn = o.get_tex(X, px, py, N, idx[1], normalize=True)
-            np.testing.assert_allclose(texn.reshape(49, 3), ref_normalize(t), rtol=1e-3, atol=2e-3)
-        for robust in (0, 1):
-            got = o.compute_incc(s, robust=robust)
-            exp = ref_compute_incc(cams, pyrs, X, N, idx, 0, 7, min(2 * 2, sc.nviews), robust, cos_thr)  # m_tau, pmmvps.cpp:32
-            assert abs(got - exp) <= 5e-5 * max(1.0, abs(exp)), (got, exp)  # measured worst case 6.4e-6
-            checked += 1
-    assert checked > 60
+    rc.check_texture_and_incc(setup)
     for r in np.linspace(0, 0.33, 12):
         assert abs(ob.lib().orc_robustincc(float(r)) - ref_robustincc(r)) < 1e-7
 
 
 # ------------------------------------------------------------------ refinement variables, cost, scales, neighbours
 def test_encode_decode_and_cost_second_reading(setup):
-    sc, o, cams, pyrs, seeds = setup
-    cos_thr = F(np.cos(F(60.0 * np.pi / 180.0)))
-    rng = np.random.RandomState(7)
-    checked = 0
-    for s in seeds[:40]:
-        idx = [int(i) for i in s["images"][: s["nimages"]]]
-        if len(idx) < 2:
-            continue
-        X, N = s["coord"].astype(F), s["normal"].astype(F)
-        rec = s.copy()
-        rec["dscale"] = F(0.01)
-        cam = cams[idx[0]]
-        ray = (X - cam.center).astype(F)
-        ray = (ray / np.linalg.norm(ray).astype(F)).astype(F)
-        x = ref_encode(cam, X, ray, rec["dscale"], X, N)
-        np.testing.assert_allclose(o.encode(rec), x, rtol=0, atol=2e-4)  # angles in units of pi/48: 2e-4 units = 1.3e-5 rad
-        x2 = (x + rng.uniform(-1.5, 1.5, 3)).astype(F)
-        c, n = o.decode(rec, x2)
-        rc, rn = ref_decode(cam, X, ray, rec["dscale"], x2)
-        np.testing.assert_allclose(c, rc, rtol=1e-6, atol=1e-6)
-        np.testing.assert_allclose(n, rn, rtol=0, atol=2e-6)
-        got = o.cost(rec, x2)
-        exp = ref_cost_func(cams, pyrs, X, ray, rec["dscale"], idx, x2, 0, 7, min(4, sc.nviews), 2, cos_thr)
-        assert abs(got - exp) <= 5e-5 * max(1.0, abs(exp)), (got, exp)
-        checked += 1
-    assert checked > 25
+    rc.check_encode_decode_and_cost(setup)
 
 
 def test_scales_and_neighbours_second_reading(setup):
-    sc, o, cams, pyrs, seeds = setup
-    tau = min(4, sc.nviews)
-    done = []
-    for s in seeds[:60]:
-        f, rec = o.preprocess(s)
-        if f != 0:
-            continue
-        idx = [int(i) for i in rec["images"][: rec["nimages"]]]
-        ds, asc = ref_set_scales(cams, rec["coord"].astype(F), idx, 0, 7, tau)
-        # m_dscale is a quotient of ~1-pixel differences of projections ~100 pixels large: rounding of the projections (fused or not)
-        # shows at 1e-5 relative
-        assert abs(rec["dscale"] - ds) <= 2e-4 * ds and abs(rec["ascale"] - asc) <= 2e-4 * asc, (rec["dscale"], ds, rec["ascale"], asc)
-        done.append(rec)
-    assert len(done) > 30
-    pairs = same = 0
-    for i in range(0, len(done) - 1):
-        for j in (i + 1, (i + 7) % len(done)):
-            if i == j:
-                continue
-            for thr in (0.25, 1.0, 4.0):
-                pairs += 1
-                same += o.is_neighbor(done[i], done[j], thr) == ref_is_neighbor(cams, done[i], done[j], 2, 0, thr)
-    assert pairs > 100 and same == pairs
+    rc.check_scales_and_neighbours(setup)
 
 
 def test_generate_patch_second_reading(setup):
-    """Propagate::generatePatch, propagate.cpp:220-237: depth along the optical axis of the source's reference view, the pixel
-    unprojected at that depth, the source's normal; views whose cell falls outside the grid are dropped (setGridsImages)."""
-    sc, o, cams, pyrs, seeds = setup
-    rng = np.random.RandomState(11)
-    checked = 0
-    for s in seeds[:60]:
-        v = int(s["images"][0])
-        X = s["coord"].astype(F)
-        ic0 = ref_project(cams[v].P[0], X)
-        ic = np.array([ic0[0] + rng.uniform(-3, 3), ic0[1] + rng.uniform(-3, 3), 1.0], F)
-        f, rec = o.generate_patch(s, ic)
-        if f != 0:
-            continue
-        depth = F(np.dot(cams[v].oaxis, X))
-        exp = ref_unproject(cams[v].P[0], (depth * ic).astype(F))
-        np.testing.assert_allclose(rec["coord"], exp, rtol=2e-5, atol=2e-5)
-        np.testing.assert_array_equal(rec["normal"], s["normal"])
-        kept = [int(i) for i in rec["images"][: rec["nimages"]]]
-        assert kept and kept[0] == v and set(kept) <= {int(i) for i in s["images"][: s["nimages"]]}
-        for i in kept:  # every kept view sees the new point inside its grid (cells of csize 2 at level 0)
-            p = ref_project(cams[i].P[0], exp)
-            gx, gy = int(np.floor(p[0] + F(0.5))) // 2, int(np.floor(p[1] + F(0.5))) // 2
-            assert 0 <= gx < (sc.W + 1) // 2 and 0 <= gy < (sc.H + 1) // 2
-        checked += 1
-    assert checked > 40
+    rc.check_generate_patch(setup)
 
 
 def test_filter_quad_second_reading(setup):
@@ -290,29 +161,4 @@ def test_filter_quad_second_reading(setup):
 
 
 def test_set_inccs_matrix_second_reading(setup):
-    """Optim::setINCCs (matrix form, optim.cpp:748-783), what Optim::setRefImage (348-383) sums by rows to pick the reference view."""
-    sc, o, cams, pyrs, seeds = setup
-    cos_thr = F(np.cos(F(60.0 * np.pi / 180.0)))
-    checked = 0
-    for s in seeds[:40]:
-        idx = [int(i) for i in s["images"][: s["nimages"]]]
-        if len(idx) < 3:
-            continue
-        X, N = s["coord"].astype(F), s["normal"].astype(F)
-        px, py = ref_get_paxes(cams[idx[0]], X, N, 0)
-        texs = []
-        for v in idx:
-            t = ref_get_tex(cams[v], pyrs[v], X, px, py, N, 0, 7, cos_thr)
-            texs.append(None if t is None else ref_normalize(t))
-        n = len(idx)
-        exp = np.zeros((n, n), F)
-        for i in range(n):
-            for j in range(i + 1, n):
-                exp[i, j] = exp[j, i] = F(2) if texs[i] is None or texs[j] is None else ref_robustincc(F(1) - ref_dot(texs[i], texs[j]))
-        got = o.set_inccs_matrix(s, robust=1)
-        np.testing.assert_allclose(got, exp, rtol=0, atol=5e-5)
-        sums_e, sums_g = exp.sum(1), got.sum(1)
-        if np.sort(sums_e)[1] - np.sort(sums_e)[0] > 1e-3:  # away from ties both readings choose the same reference view
-            assert int(np.argmin(sums_e)) == int(np.argmin(sums_g))
-        checked += 1
-    assert checked > 15
+    rc.check_set_inccs_matrix(setup)

@@ -13,6 +13,7 @@ import pytest
 
 import oracle_binding as ob
 import refiner_restatement as rr
+from parity_support import probe_vs_restatement, refiner_candidates, refiner_oracle
 from mvskit_amd import build, engine, synth
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
@@ -21,25 +22,6 @@ from quality_probe import patch_errors  # noqa: E402
 F = np.float32
 RD0 = RA0 = 4.0  # mvs_default_config: refine_rd0, refine_ra0
 BOUNDS = [(None, None), (-23.99999, 23.99999), (-23.99999, 23.99999)]  # optim.cpp:496-506
-
-
-def _oracle(nviews, minImageNum=3, list_cap=0):
-    kw = dict(level=0, csize=2, wsize=7, minImageNum=minImageNum, schedule=ob.SCHEDULE_ENGINE, sum_mode=ob.SUM_TREE64, enable_check=0, nthreads=8)
-    if list_cap:
-        kw["list_cap"] = list_cap
-    return ob.Oracle(nviews, **kw)
-
-
-def _candidates(o, scene, n=200, stride=6, seed=31):
-    """seeds that pass Optim::preProcess, as the refiner receives them"""
-    out = []
-    for s in synth.make_seeds(scene, stride=stride, seed=seed):
-        f, r = o.preprocess(s)
-        if f == 0:
-            out.append(r)
-        if len(out) >= n:
-            break
-    return np.array(out, dtype=o.dtype)
 
 
 def _in_input_frame(o, inp, out):
@@ -77,9 +59,9 @@ def test_restatement_against_a_converged_optimiser(small_multi_scene):
     (maxfev 500, xtol 1e-7), on the oracle's cost_func; the halving search (Oracle.refine) for scale."""
     from scipy.optimize import minimize
 
-    o = _oracle(small_multi_scene.nviews)
+    o = refiner_oracle(small_multi_scene.nviews)
     o.set_scene(small_multi_scene)
-    cands = _candidates(o, small_multi_scene)
+    cands = refiner_candidates(o, small_multi_scene)
     assert cands.shape[0] >= 150
     gap_s, gap_h, evals, ok, worse = [], [], [], 0, 0
     for j, c in enumerate(cands):
@@ -121,61 +103,23 @@ def test_restatement_budget_semantics():
 
 
 # ------------------------------------------------------------------ GPU
-def _probe_vs_restatement(scene, minImageNum, list_cap):
-    o = _oracle(scene.nviews, minImageNum, list_cap)
-    o.set_scene(scene)
-    cands = _candidates(o, scene, n=120)
-    assert cands.shape[0] >= 60
-    e = engine.Engine(scene.nviews, list_cap=list_cap or None, level=0, csize=2, wsize=7, minImageNum=minImageNum, enable_check=0)
-    e.set_scene(scene)
-    e.set_refiner("converged")
-    rec, xf, ni = e.probe(engine.PROBE_REFINE_X, cands)
-    rec2, xf2, ni2 = e.probe(engine.PROBE_REFINE_X, cands)
-    assert rec.tobytes() == rec2.tobytes() and xf.tobytes() == xf2.tobytes() and ni.tobytes() == ni2.tobytes()  # deterministic
-    agree, same_cost, worst, ev_e, ev_r = 0, 0, 0.0, [], []
-    for j, c in enumerate(cands):
-        x = rr.clamp_angles(o.encode(c))
-        f0 = o.cost(c, x)
-        fe = o.cost(c, xf[j, :3])
-        worst = max(worst, abs(float(xf[j, 3]) - fe))
-        assert abs(float(xf[j, 3]) - fe) <= 1e-5, (j, xf[j], fe)
-        assert fe <= f0 + 1e-5, (j, fe, f0)
-        assert 0 < abs(int(ni[j])) <= 500
-        xs, fs, n, conv = rr.refine_converged(lambda y, c=c: o.cost(c, np.asarray(y, F)), x, RD0, RA0, 500, 1e-4)
-        same_x = np.all(np.abs(xf[j, :3] - xs) <= 1e-5 * np.maximum(1.0, np.abs(xs)))
-        agree += int(same_x and (n if conv else -n) == int(ni[j]))
-        same_cost += int(abs(fe - fs) <= 1e-5)
-        ev_e.append(abs(int(ni[j])))
-        ev_r.append(n)
-    print(f"{scene.nviews} views, list cap {e.list_cap}: same trajectory {agree}/{cands.shape[0]}, same final cost (1e-5) {same_cost}, "
-          f"worst reported-cost difference {worst:.3g}, evals median {np.median(ev_e):.0f} (restatement {np.median(ev_r):.0f})")
-    # The kernel's four-proposal passes use the class-lane pivot sums, orc_cost the two-pass form: they differ by ~1e-7, and near the
-    # minimum the costs of the vertices differ by less than that, so most trajectories part in their last iterations and end at other
-    # points of the same flat valley (same trajectory 8/120 and 18/120 on the GPU; the restatement with 2e-7 of noise
-    # added to its costs agrees with itself on none).  What must agree is where they end: the cost, and about how long it takes.
-    assert same_cost >= 0.9 * cands.shape[0]
-    assert abs(np.median(ev_e) - np.median(ev_r)) <= 0.1 * np.median(ev_r)
-    assert agree >= 0.05 * cands.shape[0]
-    assert (ni > 0).mean() >= 0.9
-
-
 @pytest.mark.gpu
 def test_probe_matches_restatement(small_multi_scene):
-    _probe_vs_restatement(small_multi_scene, 3, 0)
+    probe_vs_restatement(small_multi_scene, 3, 0)
 
 
 @pytest.mark.gpu
 def test_probe_matches_restatement_32_view_library():
     """20 views, minImageNum 8: tau = 16 views per proposal, all 64 lanes of the four-proposal passes busy."""
     sc = synth.make_scene(nviews=20, W=256, H=160, arc_deg=120.0, radius=4.0, kind="multi")
-    _probe_vs_restatement(sc, 8, 32)
+    probe_vs_restatement(sc, 8, 32)
 
 
 @pytest.mark.gpu
 def test_budget_exhausted_keeps_the_input(small_multi_scene):
-    o = _oracle(small_multi_scene.nviews)
+    o = refiner_oracle(small_multi_scene.nviews)
     o.set_scene(small_multi_scene)
-    cands = _candidates(o, small_multi_scene, n=80)
+    cands = refiner_candidates(o, small_multi_scene, n=80)
     e = engine.Engine(small_multi_scene.nviews, level=0, csize=2, wsize=7, minImageNum=3, enable_check=0)
     e.set_scene(small_multi_scene)
     e.set_refiner("converged", max_evals=9)
