@@ -585,6 +585,61 @@ int mvs_engine_mesh_prune(mvs_engine* e, const mvs_mesh_pruning* p, int64_t n_v,
 int mvs_engine_mesh_smooth(mvs_engine* e, const mvs_mesh_smoothing* s, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris,
                            float* out_verts /* [n_v][3] */);
 
+/* Mesh decimation (no reference counterpart): VERTEX CLUSTERING (Rossignac-Borrel) on a uniform grid the caller gives -- one output vertex
+ * per occupied cell, the triangles that still join three different cells, each set of three cells once.  The marching-tetrahedra mesh has
+ * a vertex count set by the voxel, not by the shape; this thins it out on the device.  verts: n_v x 3 floats, tris: n_t x 3 int32 vertex
+ * ids.  The call is stateless, only reads the engine and needs a device but no views, like the clean-up calls; all pointers may be host or
+ * device memory (hipMemcpyDefault).  Every result is an integer, comes from an integer sum or is a copy of input bytes: two calls give the
+ * same bytes, whatever order the hardware meets the triangles in.  A refused call writes nothing.
+ * mvs_engine_mesh_decimate:
+ *     MEMBERS       vertex i is a member when at least one input triangle names it.  An unused vertex takes no part, and its bytes may be
+ *                   anything, a NaN included.
+ *     CELL          per component in fp32: g_c = floorf((x_c - origin_c) / cell), IEEE subtraction and division.  Every g_c of a member
+ *                   must lie in -2^20 .. 2^20 - 1.  The cell of a member is the triple (g_x, g_y, g_z).
+ *     CLUSTER       the members of one cell form one cluster; its representative rep is the smallest member id: canonical.
+ *     TRIANGLES     a triangle (a, b, c) becomes (rep(a), rep(b), rep(c)), the corner order kept.  COLLAPSED: a triangle two of whose
+ *                   corners fall into one cluster is dropped (a triangle with repeated ids is one).  DUPLICATE: of the surviving
+ *                   triangles that name the same unordered set of three clusters only the one with the smallest input index is kept;
+ *                   orientation plays no part.  Kept triangles stay in input order.
+ *     VERTICES      a cluster becomes an output vertex when a kept triangle names it.  Output vertices are in ascending order of rep; the
+ *                   new ids are the exclusive scan of those flags over 0 .. n_v - 1, as in mvs_engine_mesh_prune.
+ *     POSITION, placement 0 (the mean), by the scheme of the normals and the smoothing: M = the largest |component| over all members'
+ *                   positions, E = floor(log2 M), S = 2^(30 - E); q = llrint((double)x_c * S), round-half-even; A = the int64 sum of q
+ *                   over the cluster's members, by 64-bit integer atomic adds; n = the int32 member count; p = (float)(((double)A *
+ *                   2^(E-30)) / (double)n) in fp64 without contraction.  A cluster with n == 1 copies its member's bytes: a cell so
+ *                   small that nothing merges gives back the input positions.  M == 0: every member is a zero of either sign, all of
+ *                   them share one cell whatever the grid, and every triangle collapses.
+ *     POSITION, placement 1 (a member): with p the placement-0 position in fp32, for every member d = x - p per component and d2 =
+ *                   (dx*dx + dy*dy) + dz*dz in fp32 without contraction; the output is the bytes of the member with the smallest d2, among
+ *                   equals the smallest id: one 64-bit unsigned minimum over (bits(d2) << 32) | id.
+ *     vmap          vmap[i] = the output id of i's cluster; -1 for an unused vertex and for a member whose cluster no kept triangle names;
+ *                   may be NULL.  It lets the caller carry attributes over; the call itself carries none.
+ *   WHAT CLUSTERING DOES NOT PROMISE: the result of a closed manifold need not be manifold.  A surface that passes the same three cells
+ *   twice (a thin wall, two sheets closer than a cell) leaves, once the duplicate is dropped, edges with one or three triangles; a
+ *   cluster may join parts of the surface that were not neighbours.  No target count: the count follows from `cell`.
+ *   Sizes follow mvs_engine_mesh_prune: with out_verts == NULL, out_tris == NULL or a cap (in vertices / triangles) too small, *n_v_out
+ *   and *n_t_out are the exact counts and nothing else is written, vmap neither; MVS_ERR_CAPACITY when a non-NULL output is too small.  An
+ *   output that ALIASES an input is not supported.  LIMITS: n_v, n_t in 0 .. 2^30.  Device memory for the call: 36 bytes a vertex (position,
+ *   used flag, cell key, representative, flag and scan), 32 a triangle (ids, key, table answer, flag and scan) and ONE TABLE of 12 bytes a
+ *   slot with the power of two of slots that is >= 2 max(n_v, n_t) (24 to 48 bytes per vertex or triangle, whichever are more); with
+ *   outputs 28 bytes a vertex more (three int64, the count), 8 more for placement 1, and the decimated mesh (12 bytes a kept vertex, 12 a
+ *   kept triangle, 4 a vertex for vmap).
+ *   MVS_ERR_ARG, checked in this order before the handle is read: d NULL; cell not finite or <= 0; an origin component not finite; placement
+ *   outside 0/1; a negative count or a count over the limit; verts NULL with n_v > 0; tris NULL with n_t > 0; n_v_out or n_t_out NULL; a
+ *   negative cap; no engine.  Then, after the validating pass on the device: an id outside 0 .. n_v - 1.  Then: a member with a non-finite
+ *   component, or with a cell index outside the range.  MVS_ERR_HIP: an allocation or copy failed (or a probe of the table found no slot,
+ *   which a correct build never does). */
+typedef struct mvs_mesh_decimation {
+    float origin[3];   /* a corner of the clustering grid; finite */
+    float cell;        /* edge of a grid cell; finite, > 0 */
+    int32_t placement; /* 0: the mean of the cell's members; 1: the member nearest to that mean */
+    int32_t pad;
+} mvs_mesh_decimation; /* 24 bytes */
+void mvs_default_mesh_decimation(mvs_mesh_decimation* d); /* origin 0, cell 1, placement 0 */
+int mvs_engine_mesh_decimate(mvs_engine* e, const mvs_mesh_decimation* d, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris,
+                             int64_t cap_v, float* out_verts, int64_t cap_t, int32_t* out_tris, int32_t* vmap /* [n_v] or NULL */,
+                             int64_t* n_v_out, int64_t* n_t_out);
+
 /* Propagate::run(iter), propagate.cpp:28-64: two colour passes, each = index build + sweep + commit */
 int mvs_engine_propagate(mvs_engine* e, int iter, mvs_counters* out);
 

@@ -632,4 +632,101 @@ int mvs_engine_mesh_smooth(mvs_engine* e, const mvs_mesh_smoothing* s, int64_t n
     return MVS_OK;
 }
 
+// Mesh decimation (mvs_mesh_decimate.hip; the definition is in mvskit_engine.h): vertex clustering on the caller's grid.  Stateless like
+// the clean-up calls.  One table serves three fills: the cells of the members, then the two keys that find the duplicate triangles.
+static_assert(sizeof(mvs_mesh_decimation) == 24, "mvs_mesh_decimation is 24 bytes");
+namespace {
+int64_t mdec_slots(int64_t n) {
+    int64_t s = 1024;
+    while (s < 2 * n) s <<= 1;
+    return s;
+}
+// an empty table of `slots` slots, then out[i] = the smallest item that carries key[i]
+int mdec_fill(mvs_engine* e, int64_t n, const unsigned long long* key, DevBuf<unsigned long long>& tkey, DevBuf<int32_t>& tval, int32_t* out, uint32_t* fail) {
+    if (n == 0) return MVS_OK;
+    const int64_t slots = mdec_slots(n);
+    HIPCHK(hipMemsetAsync(tkey.p, 0xff, (size_t)slots * sizeof(unsigned long long), e->stream));
+    HIPCHK(hipMemsetAsync(tval.p, 0x7f, (size_t)slots * sizeof(int32_t), e->stream));
+    mvsk_mdec_table(n, key, tkey.p, tval.p, slots, out, fail, e->stream);
+    return MVS_OK;
+}
+}  // namespace
+
+void mvs_default_mesh_decimation(mvs_mesh_decimation* d) {
+    if (!d) return;
+    d->origin[0] = d->origin[1] = d->origin[2] = 0.0f;
+    d->cell = 1.0f; d->placement = 0; d->pad = 0;
+}
+
+int mvs_engine_mesh_decimate(mvs_engine* e, const mvs_mesh_decimation* d, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, int64_t cap_v,
+                             float* out_verts, int64_t cap_t, int32_t* out_tris, int32_t* vmap, int64_t* n_v_out, int64_t* n_t_out) {
+    const char* who = "mvs_engine_mesh_decimate";
+    if (!d) { g_err = std::string(who) + ": decimation null"; return MVS_ERR_ARG; }
+    if (!std::isfinite(d->cell) || !(d->cell > 0.0f)) { g_err = std::string(who) + ": cell not finite or <= 0"; return MVS_ERR_ARG; }
+    if (!std::isfinite(d->origin[0]) || !std::isfinite(d->origin[1]) || !std::isfinite(d->origin[2])) { g_err = std::string(who) + ": origin not finite"; return MVS_ERR_ARG; }
+    if (d->placement != 0 && d->placement != 1) { g_err = std::string(who) + ": placement not 0 or 1"; return MVS_ERR_ARG; }
+    if (int r = mesh_counts(n_v, n_t, who)) return r;
+    if (!verts && n_v > 0) { g_err = std::string(who) + ": verts null"; return MVS_ERR_ARG; }
+    if (!tris && n_t > 0) { g_err = std::string(who) + ": tris null"; return MVS_ERR_ARG; }
+    if (int r = mesh_out_args(cap_v, cap_t, n_v_out, n_t_out, who)) return r;
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
+    if (n_v == 0 && n_t == 0) { *n_v_out = 0; *n_t_out = 0; return MVS_OK; }
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:mesh_decimate");
+    hipStream_t st = e->stream;
+    DevBuf<int32_t> d_tris, used, rep, tval, tans, tflag, tbase, vflag, vbase, scan, cnt, d_out_tris;
+    DevBuf<uint32_t> words, flags;  // flags: [0] the bits of the members' largest component, [1] a member not finite or outside the grid, [2] a probe that ran out
+    DevBuf<unsigned long long> vkey, tkeys, tkey, best;
+    DevBuf<long long> acc;
+    DevBuf<float> d_verts, d_out_verts;
+    if (int r = mesh_take_tris(e, n_v, n_t, tris, d_tris, words, who)) return r;
+    const int64_t slots = mdec_slots(std::max(n_v, n_t));
+    if (d_verts.ensure(3 * n_v) || used.ensure(n_v) || vkey.ensure(n_v) || rep.ensure(n_v) || flags.ensure(4) || tkey.ensure(slots) || tval.ensure(slots)) return MVS_ERR_HIP;
+    if (n_v > 0) HIPCHK(hipMemcpyAsync(d_verts.p, verts, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
+    if (n_v > 0) HIPCHK(hipMemsetAsync(used.p, 0, (size_t)n_v * sizeof(int32_t), st));
+    HIPCHK(hipMemsetAsync(flags.p, 0, 4 * sizeof(uint32_t), st));
+    mvsk_mdec_members(n_v, d_verts.p, n_t, d_tris.p, d->origin, d->cell, used.p, vkey.p, flags.p, flags.p + 1, st);
+    if (int r = mdec_fill(e, n_v, vkey.p, tkey, tval, rep.p, flags.p + 2)) return r;  // a refused member has no key
+    uint32_t hf[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(hf, flags.p, sizeof(hf), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    if (hf[1]) { g_err = std::string(who) + ": a member with a non-finite component or a cell index outside -2^20 .. 2^20 - 1"; return MVS_ERR_ARG; }
+    if (hf[2]) { g_err = std::string(who) + ": the cell table found no slot"; return MVS_ERR_HIP; }
+    if (tkeys.ensure(n_t) || tans.ensure(n_t) || tflag.ensure(n_t) || tbase.ensure(n_t + 1) || vflag.ensure(n_v) || vbase.ensure(n_v + 1) ||
+        scan.ensure(std::max(n_v, n_t) / 256 + 4096))
+        return MVS_ERR_HIP;
+    mvsk_mdec_tkey1(n_t, d_tris.p, rep.p, tkeys.p, st);
+    if (int r = mdec_fill(e, n_t, tkeys.p, tkey, tval, tans.p, flags.p + 2)) return r;
+    mvsk_mdec_tkey2(n_t, d_tris.p, rep.p, tans.p, tkeys.p, st);
+    if (int r = mdec_fill(e, n_t, tkeys.p, tkey, tval, tans.p, flags.p + 2)) return r;
+    if (n_v > 0) HIPCHK(hipMemsetAsync(vflag.p, 0, (size_t)n_v * sizeof(int32_t), st));
+    mvsk_mdec_keep(n_t, d_tris.p, rep.p, tans.p, tflag.p, vflag.p, st);
+    int64_t nv = 0, nt = 0;
+    if (int r = scan_total(e, vflag.p, vbase.p, scan.p, n_v, &nv)) return r;
+    if (int r = scan_total(e, tflag.p, tbase.p, scan.p, n_t, &nt)) return r;
+    if (int r = read_back(e, flags.p + 2, &hf[2])) return r;
+    HIPCHK(hipGetLastError());
+    if (hf[2]) { g_err = std::string(who) + ": the triangle table found no slot"; return MVS_ERR_HIP; }
+    *n_v_out = nv; *n_t_out = nt;
+    if ((out_verts && cap_v < nv) || (out_tris && cap_t < nt)) { g_err = std::string(who) + ": a cap is smaller than the decimated mesh (*n_v_out, *n_t_out)"; return MVS_ERR_CAPACITY; }
+    if (!out_verts || !out_tris) return MVS_OK;
+    if (acc.ensure(3 * n_v) || cnt.ensure(n_v) || (d->placement == 1 && best.ensure(n_v)) || d_out_verts.ensure(3 * nv) || d_out_tris.ensure(3 * nt)) return MVS_ERR_HIP;
+    if (n_v > 0) {
+        HIPCHK(hipMemsetAsync(acc.p, 0, (size_t)n_v * 3 * sizeof(long long), st));
+        HIPCHK(hipMemsetAsync(cnt.p, 0, (size_t)n_v * sizeof(int32_t), st));
+        if (d->placement == 1) HIPCHK(hipMemsetAsync(best.p, 0xff, (size_t)n_v * sizeof(unsigned long long), st));
+    }
+    mvsk_mdec_positions(d->placement, n_v, d_verts.p, rep.p, vflag.p, vbase.p, flags.p, acc.p, cnt.p, best.p, d_out_verts.p, nv, st);
+    mvsk_mdec_gather(n_v, rep.p, vflag.p, vbase.p, used.p, n_t, d_tris.p, tflag.p, tbase.p, d_out_tris.p, nt, st);  // used becomes the vertex map
+    HIPCHK(hipStreamSynchronize(st));  // a failure is known before anything is written
+    HIPCHK(hipGetLastError());
+    if (nv > 0) HIPCHK(hipMemcpyAsync(out_verts, d_out_verts.p, (size_t)nv * 3 * sizeof(float), hipMemcpyDefault, st));
+    if (nt > 0) HIPCHK(hipMemcpyAsync(out_tris, d_out_tris.p, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDefault, st));
+    if (vmap && n_v > 0) HIPCHK(hipMemcpyAsync(vmap, used.p, (size_t)n_v * sizeof(int32_t), hipMemcpyDefault, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return MVS_OK;
+}
+
 }  // extern "C"

@@ -162,3 +162,26 @@ void mvsk_mesh_gather(int64_t n_v, const float* verts, int32_t* vflag, const int
 // one STEP with factor f from xin to xout: *mbits zero before the launch, acc (3 int64 a vertex) and cnt zero before and after it
 void mvsk_mesh_smooth_step(int64_t n_v, const float* xin, float* xout, float f, int64_t n_t, const int32_t* tris, uint32_t* mbits, long long* acc, int32_t* cnt,
                            hipStream_t st);
+// mvs_engine_mesh_decimate (mvs_mesh_decimate.hip): vertex clustering on a grid.  One open-addressing table (tkey: `slots` 64-bit keys,
+// all ones = empty; tval: their values, at least 2^30 before a fill; slots a power of two >= twice the items) finds the clusters and
+// the duplicate triangles.  Every launcher wants valid ids.
+// used[i] = 1 where a triangle names vertex i (zero before); key[i] = the packed cell of member i, all ones for an unused vertex; *mbits =
+// the bits of the members' largest |component|, *bad != 0 when a member is not finite or lies outside the grid (both zero before)
+void mvsk_mdec_members(int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, const float* origin, float cell, int32_t* used,
+                       unsigned long long* key, uint32_t* mbits, uint32_t* bad, hipStream_t st);
+// out[i] = the smallest item index that carries key[i] (-1 for an item whose key is all ones); *fail != 0 when a probe ran out of slots
+void mvsk_mdec_table(int64_t n, const unsigned long long* key, unsigned long long* tkey, int32_t* tval, int64_t slots, int32_t* out, uint32_t* fail,
+                     hipStream_t st);
+// key[t] = (a << 30) | b of the sorted representatives a < b < c, all ones for a collapsed triangle; then, with first[t] = the table's
+// answer to that key, key[t] = (first[t] << 30) | c
+void mvsk_mdec_tkey1(int64_t n_t, const int32_t* tris, const int32_t* rep, unsigned long long* key, hipStream_t st);
+void mvsk_mdec_tkey2(int64_t n_t, const int32_t* tris, const int32_t* rep, const int32_t* first, unsigned long long* key, hipStream_t st);
+// tflag[t] = (winner[t] == t), winner the table's answer to the second key; vflag[r] = 1 on the representatives of a kept triangle (zero before)
+void mvsk_mdec_keep(int64_t n_t, const int32_t* tris, const int32_t* rep, const int32_t* winner, int32_t* tflag, int32_t* vflag, hipStream_t st);
+// the output positions at out_verts[3 vbase[r] ..] of the flagged representatives r; acc (3 int64 a vertex) and cnt zero before, best
+// (read with placement 1) all ones
+void mvsk_mdec_positions(int placement, int64_t n_v, const float* verts, const int32_t* rep, const int32_t* vflag, const int32_t* vbase, const uint32_t* mbits,
+                         long long* acc, int32_t* cnt, unsigned long long* best, float* out_verts, int64_t cap_v, hipStream_t st);
+// the vertex map and the kept triangles in input order, ids rewritten
+void mvsk_mdec_gather(int64_t n_v, const int32_t* rep, const int32_t* vflag, const int32_t* vbase, int32_t* vmap, int64_t n_t, const int32_t* tris,
+                      const int32_t* tflag, const int32_t* tbase, int32_t* out_tris, int64_t cap_t, hipStream_t st);

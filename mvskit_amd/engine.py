@@ -34,6 +34,7 @@ EXPORTS = [
     "mvs_engine_tsdf", "mvs_engine_extract_mesh", "mvs_engine_mesh", "mvs_engine_sweep_pairs", "mvs_engine_sweep_repeats",
     "mvs_default_mesh_colouring", "mvs_engine_mesh_normals", "mvs_engine_mesh_colours",
     "mvs_default_mesh_pruning", "mvs_default_mesh_smoothing", "mvs_engine_mesh_components", "mvs_engine_mesh_prune", "mvs_engine_mesh_smooth",
+    "mvs_default_mesh_decimation", "mvs_engine_mesh_decimate",
 ]
 PLY_ASCII, PLY_BINARY_LE = 0, 1  # mvs_ply_format
 #: one vertex of the binary PLY file (mvs_engine_export_ply): 27 packed bytes
@@ -113,6 +114,11 @@ class MeshPruning(C.Structure):
 class MeshSmoothing(C.Structure):
     """mvs_mesh_smoothing: the steps of mvs_engine_mesh_smooth, 16 bytes."""
     _fields_ = [("iterations", C.c_int32), ("lam", C.c_float), ("mu", C.c_float), ("pad", C.c_int32)]
+
+
+class MeshDecimation(C.Structure):
+    """mvs_mesh_decimation: the grid and the placement of mvs_engine_mesh_decimate, 24 bytes."""
+    _fields_ = [("origin", C.c_float * 3), ("cell", C.c_float), ("placement", C.c_int32), ("pad", C.c_int32)]
 
 
 class Counters(C.Structure):
@@ -243,6 +249,11 @@ def load_library(cap32: bool = False, cap: int = 0):
         L.mvs_engine_mesh_prune.argtypes = [vp, C.POINTER(MeshPruning), C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp,
                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.mvs_engine_mesh_smooth.argtypes = [vp, C.POINTER(MeshSmoothing), C.c_int64, vp, C.c_int64, vp, vp]
+    if hasattr(L, "mvs_engine_mesh_decimate"):
+        L.mvs_default_mesh_decimation.argtypes = [C.POINTER(MeshDecimation)]
+        L.mvs_default_mesh_decimation.restype = None
+        L.mvs_engine_mesh_decimate.argtypes = [vp, C.POINTER(MeshDecimation), C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp,
+                                               C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     _libs[LIB_PATH] = L
     return L
 
@@ -646,17 +657,45 @@ class Engine:
         self._check(self.L.mvs_engine_mesh_smooth(self.h, C.byref(s), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), _ptr(out)))
         return out
 
+    # ---- mesh decimation
+    def decimate_mesh(self, verts, tris, cell, origin=(0.0, 0.0, 0.0), placement="mean"):
+        """Vertex clustering on the grid of edge `cell` with a corner at `origin` (include/mvskit_engine.h, mvs_engine_mesh_decimate):
+        (verts, tris, vmap [n] int32, the output id of every input vertex's cluster or -1).  One vertex per occupied cell, at the mean of
+        the cell's vertices (placement "mean") or at the one of them nearest to that mean ("member"); triangles that no longer join
+        three cells go, and of those that join the same three only the first stays.  The result of a closed surface need not be closed.
+        The same bytes whatever order the hardware meets the triangles in.  The size call comes first.  Needs no views."""
+        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        if placement not in ("mean", "member"):
+            raise ValueError("decimate_mesh: placement is 'mean' or 'member'")
+        d = MeshDecimation((C.c_float * 3)(*[float(o) for o in origin]), float(cell), 1 if placement == "member" else 0, 0)
+        nv, nt = C.c_int64(), C.c_int64()
+
+        def call(cap_v, out_v, cap_t, out_t, vmap):
+            return self.L.mvs_engine_mesh_decimate(self.h, C.byref(d), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), cap_v, _ptr(out_v), cap_t,
+                                                   _ptr(out_t), _ptr(vmap), C.byref(nv), C.byref(nt))
+
+        self._check(call(0, None, 0, None, None))
+        out_v, out_t = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
+        vmap = np.full(verts.shape[0], -1, np.int32)
+        self._check(call(nv.value, out_v, nt.value, out_t, vmap))
+        return out_v, out_t, vmap
+
     def coloured_mesh(self, volume, source=0, min_consistent=1, depth_tol=0.01, normal_cos=0.9, occl_tol=0.01, min_cos=0.1, cap_v=0, cap_t=0,
-                      min_triangles=0, largest_only=False, smooth_iterations=0):
+                      min_triangles=0, largest_only=False, smooth_iterations=0, decimate_cell=0.0, decimate_placement="mean"):
         """mesh, mesh_normals and mesh_colours chained: (verts, tris, normals, rgb, used), what write_mesh_ply takes.  Every step renders
         the maps it needs itself.  With min_triangles >= 1 or largest_only the mesh is pruned (prune_mesh), with smooth_iterations > 0
-        smoothed (smooth_mesh with its default steps), in that order, before the normals and colours are taken."""
+        smoothed (smooth_mesh with its default steps), with decimate_cell > 0 decimated (decimate_mesh), in that order, before the normals
+        and colours are taken.  The decimation grid starts at volume.origin - voxel / 2: marching tetrahedra leaves lattice coordinates in
+        two of a vertex's three components, and with a cell that is a multiple of the voxel none of them sits on a cell boundary."""
         kw = dict(source=source, min_consistent=min_consistent, depth_tol=depth_tol, normal_cos=normal_cos)
         verts, tris = self.mesh(volume, cap_v=cap_v, cap_t=cap_t, **kw)
         if min_triangles > 0 or largest_only:
             verts, tris, _ = self.prune_mesh(verts, tris, max(1, int(min_triangles)), largest_only)
         if smooth_iterations > 0:
             verts = self.smooth_mesh(verts, tris, smooth_iterations)
+        if decimate_cell > 0:
+            verts, tris, _ = self.decimate_mesh(verts, tris, decimate_cell, decimation_origin(volume), decimate_placement)
         normals = self.mesh_normals(verts, tris)
         rgb, used = self.mesh_colours(verts, normals, occl_tol=occl_tol, min_cos=min_cos, **kw)
         return verts, tris, normals, rgb, used
@@ -777,6 +816,12 @@ def make_volume(origin, voxel, dims, trunc, min_count=1):
         v.origin[k], v.dims[k] = float(origin[k]), int(dims[k])
     v.voxel, v.trunc, v.min_count, v.pad = float(voxel), float(trunc), int(min_count), 0
     return v
+
+
+def decimation_origin(volume):
+    """The grid corner Engine.coloured_mesh gives decimate_mesh: volume.origin - voxel / 2 per component, in float32."""
+    half = np.float32(volume.voxel) / np.float32(2)
+    return tuple(float(np.float32(volume.origin[k]) - half) for k in range(3))
 
 
 def volume_around(xyz, voxel, trunc_voxels=4, pad_voxels=2, min_count=1):
