@@ -768,6 +768,13 @@ int mvs_engine_sweep_pairs(mvs_engine* e, int64_t out[6]);
  *          refinement (always 0: this engine runs those trials in full) */
 int mvs_engine_sweep_repeats(mvs_engine* e, int64_t out[2]);
 
+/* Sweep launches by kernel, summed over every pass since the engine was created.  A window whose samples fill all three slots of every
+ * class lane and leave one extra (3 x 16 + 1 samples: wsize 7) runs on an instantiation of the sweep without the slot-mask arithmetic;
+ * results do not depend on it.  MVS_SWEEP_FULLWINDOW=0 in the environment (read at every launch) keeps such a window on the generic
+ * kernel.  The CONVERGED refiner and the second tier of Optim::check always run generic kernels (the latter is not counted here).
+ *   out[0] launches of a generic kernel      out[1] launches of the full-window kernel */
+int mvs_engine_sweep_kernels(mvs_engine* e, int64_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -411,7 +411,21 @@ struct ClsConst {
     unsigned cs[3];  // per slot j: fx | fy << 8 | valid << 16
     int fb;          // first lane of this lane's row (16 r)
     int xbase, nx;   // the extra: sample xbase if nx == 1 (wave-uniform)
+    unsigned xcs;    // the extra's fx | fy << 8 | 1 << 16 (wave-uniform; meaningless if nx == 0)
 };
+// How a window of wsz samples falls on the three slots of a row's 16 lanes; make_cls on the device and the sweep's launcher on the host.
+struct ClsLayout { int njx, lim, xbase, nx; };  // slots j < njx hold the samples q = c + 16 j < lim; the extra as in ClsConst
+__host__ __device__ inline ClsLayout cls_layout(int wsz) {
+    const int nj = wsz >> 4, rem = wsz & 15;
+    return {nj + (rem > 1 ? 1 : 0), rem > 1 ? wsz : 16 * nj, 16 * nj, rem == 1 ? 1 : 0};
+}
+// Every slot of every lane holds a sample and the window has its extra (3 x 16 + 1 samples: 7x7).  The valid bit of a slot is then 1
+// on every lane, and the arithmetic that applies it as a factor 1.0f is the identity: x * 1.0f, fma(-p, 1.0f, r) = r - p and
+// 1.0f - dx1 round once either way, so code that leaves the factor out computes the same bits.
+__host__ __device__ inline bool cls_full_window(int wsz) {
+    const ClsLayout l = cls_layout(wsz);
+    return l.njx >= 3 && l.lim >= 48 && l.nx == 1;
+}
 // Per-wave working state.
 struct WaveCtx {
     int lane;
@@ -422,6 +436,11 @@ struct WaveCtx {
     unsigned long long st_t;
 #endif
 };
+// The same state in a launch whose window is full (cls_full_window): the functions that sample are templates on the context's type and
+// leave out the slot-mask arithmetic for this one; everything else takes it as a WaveCtx.
+struct WaveCtxFull : WaveCtx {};
+template <class WC> struct wc_full_window { static constexpr bool value = false; };
+template <> struct wc_full_window<WaveCtxFull> { static constexpr bool value = true; };
 #ifdef MVS_STAGE_TIMING
 #define WC_T0(wc) { (wc).st_t = (unsigned long long)__builtin_amdgcn_s_memtime(); }
 #define WC_ADD(wc, k) { const unsigned long long t1_ = (unsigned long long)__builtin_amdgcn_s_memtime(); (wc).st_acc[k] += t1_ - (wc).st_t; (wc).st_t = t1_; }
@@ -469,17 +488,17 @@ DEV float inv_msd(const DParams& prm, float ssd) {
 struct ClsPend { Texel2 q0, q1; float dx1, dy1; };
 DEV ClsConst make_cls(const DParams& prm, int lane) {
     ClsConst cc;
-    const int wsz = prm.wsz, nj = wsz >> 4, rem = wsz & 15;
-    const int njx = nj + (rem > 1 ? 1 : 0), lim = rem > 1 ? wsz : 16 * nj;
+    const ClsLayout l = cls_layout(prm.wsz);
     const int row = lane >> 4, c = lane & 15;
     cc.fb = 16 * row;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const int q = c + 16 * j;
-        const bool valid = j < njx && q < lim;
+        const bool valid = j < l.njx && q < l.lim;
         cc.cs[j] = valid ? (unsigned)(q % prm.wsize) | ((unsigned)(q / prm.wsize) << 8) | (1u << 16) : 0u;
     }
-    cc.xbase = 16 * nj; cc.nx = rem == 1 ? 1 : 0;
+    cc.xbase = l.xbase; cc.nx = l.nx;
+    cc.xcs = (unsigned)(l.xbase % prm.wsize) | ((unsigned)(l.xbase / prm.wsize) << 8) | (1u << 16);
     return cc;
 }
 DEV float cvt_ub0(unsigned x) { return (float)(x & 255u); }
@@ -516,15 +535,18 @@ DEV ClsPend cls_issue(const ClsFrame& f, unsigned cs) {
     return p;
 }
 // bilinear blend (Image::getColor, image.cpp:447-472) minus the pivot; 0 on lanes whose sample does not exist
+// FULL (a full window, cls_full_window): the slot holds a sample, the factor below is 1.0f and is left out
+template <bool FULL = false>
 DEV void cls_colour(const ClsPend& p, unsigned cs, float pr, float pg, float pb, float& r, float& g, float& b) {
     const Texel2 q0 = p.q0, q1 = p.q1;
-    const float fm = cvt_ub2(cs);  // 1, or 0 for a slot without a sample: both column weights vanish, and with them all four
-    const float dx1 = p.dx1 * fm, dx0 = fm - dx1, dy1 = p.dy1, dy0 = 1.0f - dy1;
+    const float fm = FULL ? 1.0f : cvt_ub2(cs);  // 1, or 0 for a slot without a sample: both column weights vanish, and with them all four
+    const float dx1 = FULL ? p.dx1 : p.dx1 * fm, dx0 = fm - dx1, dy1 = p.dy1, dy0 = 1.0f - dy1;
     const float f00 = dx0 * dy0, f01 = dx0 * dy1, f10 = dx1 * dy0, f11 = dx1 * dy1;
     r = fma_((float)(q1.b & 255u), f11, fma_((float)(q0.b & 255u), f10, fma_((float)(q1.a & 255u), f01, (float)(q0.a & 255u) * f00)));
     g = fma_((float)((q1.b >> 8) & 255u), f11, fma_((float)((q0.b >> 8) & 255u), f10, fma_((float)((q1.a >> 8) & 255u), f01, (float)((q0.a >> 8) & 255u) * f00)));
     b = fma_((float)((q1.b >> 16) & 255u), f11, fma_((float)((q0.b >> 16) & 255u), f10, fma_((float)((q1.a >> 16) & 255u), f01, (float)((q0.a >> 16) & 255u) * f00)));
-    r = fma_(-pr, fm, r); g = fma_(-pg, fm, g); b = fma_(-pb, fm, b);
+    if (FULL) { r = r - pr; g = g - pg; b = b - pb; }
+    else { r = fma_(-pr, fm, r); g = fma_(-pg, fm, g); b = fma_(-pb, fm, b); }
 }
 DEV float bperm_f(int addr, float x) { return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(x))); }
 #define MVS_ROW_STEP(x, C) x = x + dpp_f<C>(x);
@@ -537,7 +559,11 @@ DEV float bperm_f(int addr, float x) { return __int_as_float(__builtin_amdgcn_ds
 // Leaves in frame lane 16 g + k (k >= 1) the INCC of view k against the reference view of proposal g.
 // Straight-line per view (always three sample slots per lane; a slot without a sample contributes exact zeros), the
 // reference view peeled off, and the loads of view k + 1 issued as the slots of view k are consumed.
-DEV void eval_steps4(const DParams& prm, WaveCtx& wc, const ClsConst& cc, const Frame& f, int n, unsigned (&okm)[4], float& incc_l) {
+template <class WC>
+DEV void eval_steps4(const DParams& prm, WC& wc, const ClsConst& cc, const Frame& f, int n, unsigned (&okm)[4], float& incc_l) {
+    constexpr bool FULL = wc_full_window<WC>::value;
+    // (the extra's test stays a run-time one here even for a full window: known true, this loop's scalar reloads go from 17 to 20 -- DESIGN.md section 5)
+    const bool has_x = cc.nx > 0;
     frames_publish(wc, f, 64);
     const unsigned long long okb = ballot(f.ok != 0);
 #pragma unroll
@@ -563,7 +589,7 @@ DEV void eval_steps4(const DParams& prm, WaveCtx& wc, const ClsConst& cc, const 
         for (int j = 0; j < 3; ++j) {
             const unsigned cs = cls_opaque(cc.cs[j]);
             float r, g, b;
-            cls_colour(pend[j], cs, pv.x, pv.y, pv.z, r, g, b);
+            cls_colour<FULL>(pend[j], cs, pv.x, pv.y, pv.z, r, g, b);
             pend[j] = cls_issue(fn, cs);
             c0[j][0] = r; c0[j][1] = g; c0[j][2] = b;
             s1r += r; s1g += g; s1b += b;
@@ -580,7 +606,7 @@ DEV void eval_steps4(const DParams& prm, WaveCtx& wc, const ClsConst& cc, const 
         for (int j = 0; j < 3; ++j) {
             const unsigned cs = cls_opaque(cc.cs[j]);
             float r, g, b;
-            cls_colour(pend[j], cs, pv.x, pv.y, pv.z, r, g, b);
+            cls_colour<FULL>(pend[j], cs, pv.x, pv.y, pv.z, r, g, b);
             pend[j] = cls_issue(fn, cs);
             s1r += r; s1g += g; s1b += b;
             s2 = fma_(r, r, s2); s2 = fma_(g, g, s2); s2 = fma_(b, b, s2);
@@ -592,17 +618,16 @@ DEV void eval_steps4(const DParams& prm, WaveCtx& wc, const ClsConst& cc, const 
     const int a0 = (wc.lane & 48) << 2;  // ds_bpermute address of lane 16 g: the reference view of this lane's proposal
     // the extras: frame lane 16 g + k samples them in its own frame (a frame that does not sample holds a harmless address
     // and its sums are never looked at) and adds them to the sums of (proposal g, view k) it holds
-    if (cc.nx > 0) {
+    if (has_x) {
         const float4 pv = mvs_dyn_lds4[MVS_PIVOT_LDS4 + lc];
         ClsFrame fr;
         fr.tlx = f.tlx; fr.tly = f.tly; fr.dxx = f.dxx; fr.dxy = f.dxy; fr.dyx = f.dyx; fr.dyy = f.dyy; fr.w = f.w;
         fr.base = ((unsigned long long)f.img_hi << 32) | (unsigned long long)f.img_lo;
         {
-            const int q = cc.xbase;
-            const unsigned cs = (unsigned)(q % prm.wsize) | ((unsigned)(q / prm.wsize) << 8) | (1u << 16);
+            const unsigned cs = cc.xcs;
             const ClsPend pe = cls_issue(fr, cs);
             float r, g, b;
-            cls_colour(pe, cs, pv.x, pv.y, pv.z, r, g, b);
+            cls_colour<FULL>(pe, cs, pv.x, pv.y, pv.z, r, g, b);
             const float r0 = bperm_f(a0, r), g0 = bperm_f(a0, g), b0 = bperm_f(a0, b);
             P1r += r; P1g += g; P1b += b;
             P2 = fma_(r, r, P2); P2 = fma_(g, g, P2); P2 = fma_(b, b, P2);
@@ -622,7 +647,10 @@ DEV void eval_steps4(const DParams& prm, WaveCtx& wc, const ClsConst& cc, const 
 // One publication; the sampling -- the peeled reference view and the view loop, the very code above -- once per candidate, from the frames
 // fb + 8 s + k and the pivots 8 s + k into the lanes lc == 8 s + k; then ONE pass of the extras, the per-view scalars (reference lane 16 g + 8 s)
 // and, in the caller, the robust INCCs.  okm[s][g]: the views of (candidate s, proposal g) that sample; returns the same bits by frame lane.
-DEV unsigned long long eval_steps4_pair(const DParams& prm, WaveCtx& wc, const ClsConst& cc, const Frame& f, int n0, int n1, unsigned (&okm)[2][4], float& incc_l) {
+template <class WC>
+DEV unsigned long long eval_steps4_pair(const DParams& prm, WC& wc, const ClsConst& cc, const Frame& f, int n0, int n1, unsigned (&okm)[2][4], float& incc_l) {
+    constexpr bool FULL = wc_full_window<WC>::value;
+    const bool has_x = FULL || cc.nx > 0;
     frames_publish(wc, f, 64);
     const unsigned long long okb = ballot(f.ok != 0);
 #pragma unroll
@@ -652,7 +680,7 @@ DEV unsigned long long eval_steps4_pair(const DParams& prm, WaveCtx& wc, const C
             for (int j = 0; j < 3; ++j) {
                 const unsigned cs = cls_opaque(cc.cs[j]);
                 float r, g, b;
-                cls_colour(pend[j], cs, pv.x, pv.y, pv.z, r, g, b);
+                cls_colour<FULL>(pend[j], cs, pv.x, pv.y, pv.z, r, g, b);
                 pend[j] = cls_issue(fn, cs);
                 c0[j][0] = r; c0[j][1] = g; c0[j][2] = b;
                 s1r += r; s1g += g; s1b += b;
@@ -669,7 +697,7 @@ DEV unsigned long long eval_steps4_pair(const DParams& prm, WaveCtx& wc, const C
             for (int j = 0; j < 3; ++j) {
                 const unsigned cs = cls_opaque(cc.cs[j]);
                 float r, g, b;
-                cls_colour(pend[j], cs, pv.x, pv.y, pv.z, r, g, b);
+                cls_colour<FULL>(pend[j], cs, pv.x, pv.y, pv.z, r, g, b);
                 pend[j] = cls_issue(fn, cs);
                 s1r += r; s1g += g; s1b += b;
                 s2 = fma_(r, r, s2); s2 = fma_(g, g, s2); s2 = fma_(b, b, s2);
@@ -680,17 +708,16 @@ DEV unsigned long long eval_steps4_pair(const DParams& prm, WaveCtx& wc, const C
         }
     }
     const int a0 = (wc.lane & 56) << 2;  // ds_bpermute address of lane 16 g + 8 s: the reference view of this lane's candidate and proposal
-    if (cc.nx > 0) {
+    if (has_x) {
         const float4 pv = mvs_dyn_lds4[MVS_PIVOT_LDS4 + lc];
         ClsFrame fr;
         fr.tlx = f.tlx; fr.tly = f.tly; fr.dxx = f.dxx; fr.dxy = f.dxy; fr.dyx = f.dyx; fr.dyy = f.dyy; fr.w = f.w;
         fr.base = ((unsigned long long)f.img_hi << 32) | (unsigned long long)f.img_lo;
         {
-            const int q = cc.xbase;
-            const unsigned cs = (unsigned)(q % prm.wsize) | ((unsigned)(q / prm.wsize) << 8) | (1u << 16);
+            const unsigned cs = cc.xcs;
             const ClsPend pe = cls_issue(fr, cs);
             float r, g, b;
-            cls_colour(pe, cs, pv.x, pv.y, pv.z, r, g, b);
+            cls_colour<FULL>(pe, cs, pv.x, pv.y, pv.z, r, g, b);
             const float r0 = bperm_f(a0, r), g0 = bperm_f(a0, g), b0 = bperm_f(a0, b);
             P1r += r; P1g += g; P1b += b;
             P2 = fma_(r, r, P2); P2 = fma_(g, g, P2); P2 = fma_(b, b, P2);
@@ -720,10 +747,11 @@ DEV unsigned long long eval_steps4_pair(const DParams& prm, WaveCtx& wc, const C
 // pivots of the class-lane steps that follow in refinePatch.
 // texs != nullptr: the centred texture of view k goes to LDS, texs[3 k tstride + 3 sample + channel], and *ssd_out
 // receives, in view lane k, its sum of squares -- what Optim::setRefImage needs.
-DEV void cls_raw(const ClsPend& p, unsigned cs, float& r, float& g, float& b) {  // bilinear blend; 0 on a slot without a sample
+template <bool FULL = false>
+DEV void cls_raw(const ClsPend& p, unsigned cs, float& r, float& g, float& b) {  // bilinear blend; 0 on a slot without a sample (FULL: as cls_colour)
     const Texel2 q0 = p.q0, q1 = p.q1;
-    const float fm = cvt_ub2(cs);
-    const float dx1 = p.dx1 * fm, dx0 = fm - dx1, dy1 = p.dy1, dy0 = 1.0f - dy1;
+    const float fm = FULL ? 1.0f : cvt_ub2(cs);
+    const float dx1 = FULL ? p.dx1 : p.dx1 * fm, dx0 = fm - dx1, dy1 = p.dy1, dy0 = 1.0f - dy1;
     const float f00 = dx0 * dy0, f01 = dx0 * dy1, f10 = dx1 * dy0, f11 = dx1 * dy1;
     r = fma_((float)(q1.b & 255u), f11, fma_((float)(q0.b & 255u), f10, fma_((float)(q1.a & 255u), f01, (float)(q0.a & 255u) * f00)));
     g = fma_((float)((q1.b >> 8) & 255u), f11, fma_((float)((q0.b >> 8) & 255u), f10, fma_((float)((q1.a >> 8) & 255u), f01, (float)((q0.a >> 8) & 255u) * f00)));
@@ -764,8 +792,8 @@ DEV int gram_col(int lane) { return lane & 15; }
 DEV int gram_row(int lane, int r) { return (lane >> 4) * 4 + r; }
 template <int N> struct GramIC { static constexpr int value = N; };
 #endif
-template <bool PIV = false>
-DEV void eval_views(const DParams& prm, WaveCtx& wc, const Frame& f, int n, vmask_t (&okm)[1], float& incc_l, float* piv = nullptr,
+template <bool PIV = false, class WC>
+DEV void eval_views(const DParams& prm, WC& wc, const Frame& f, int n, vmask_t (&okm)[1], float& incc_l, float* piv = nullptr,
                     float* texs = nullptr, int tstride = 0, float* ssd_out = nullptr) {
 #if MVS_PAIR_MFMA
     // texs != nullptr: the Gram matrix of the centred textures is left at texs[a * LD + b] (see MVS_GRAM_CH above)
@@ -783,7 +811,9 @@ DEV void eval_views(const DParams& prm, WaveCtx& wc, const Frame& f, int n, vmas
     const int gk0 = wc.lane / MVS_GRAM_CH;                       // this lane's k within an MFMA
     const float* const grow = texs + (wc.lane & (MVS_GRAM_CH - 1)) * gtp;  // this lane's view of the chunk in LDS
 #endif
+    constexpr bool FULL = wc_full_window<WC>::value;
     const ClsConst& cc = wc.cc;
+    const bool has_x = FULL || cc.nx > 0;
     frames_publish(wc, f, MVS_LISTCAP > 16 ? MVS_LISTCAP : 16);
     okm[0] = vballot(f.ok != 0);  // a frame is only ever valid on a lane < n <= MVS_LISTCAP
     wc.view_evals += (okm[0] & 1u) ? (unsigned)vpop(okm[0]) : 0u;
@@ -792,11 +822,11 @@ DEV void eval_views(const DParams& prm, WaveCtx& wc, const Frame& f, int n, vmas
     float fxr = 0.0f, fxg = 0.0f, fxb = 0.0f;
     unsigned xcs = 0u;
     ClsPend pe;
-    if (cc.nx > 0) {
+    if (has_x) {
         ClsFrame fr;
         fr.tlx = f.tlx; fr.tly = f.tly; fr.dxx = f.dxx; fr.dxy = f.dxy; fr.dyx = f.dyx; fr.dyy = f.dyy; fr.w = f.w;
         fr.base = ((unsigned long long)f.img_hi << 32) | (unsigned long long)f.img_lo;
-        xcs = (unsigned)(cc.xbase % prm.wsize) | ((unsigned)(cc.xbase / prm.wsize) << 8) | (1u << 16);
+        xcs = cc.xcs;
         pe = cls_issue(fr, xcs);
     }
     float d0[3][3], d0x[3] = {0.0f, 0.0f, 0.0f};
@@ -808,7 +838,7 @@ DEV void eval_views(const DParams& prm, WaveCtx& wc, const Frame& f, int n, vmas
 #pragma unroll
         for (int j = 0; j < 3; ++j) pend[j] = cls_issue(fr, cls_opaque(cc.cs[j]));
     }
-    if (cc.nx > 0) cls_raw(pe, xcs, fxr, fxg, fxb);
+    if (has_x) cls_raw<FULL>(pe, xcs, fxr, fxg, fxb);
     const int rounds = (n + 3) >> 2;
     auto round_body = [&](const int t) {
         const int v = 4 * t + row, vq = min(v, max(n - 1, 0));
@@ -818,13 +848,13 @@ DEV void eval_views(const DParams& prm, WaveCtx& wc, const Frame& f, int n, vmas
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const unsigned cs = cls_opaque(cc.cs[j]);
-            cls_raw(pend[j], cs, cr[j], cg[j], cb[j]);
+            cls_raw<FULL>(pend[j], cs, cr[j], cg[j], cb[j]);
             pend[j] = cls_issue(fn, cs);
             s1r += cr[j]; s1g += cg[j]; s1b += cb[j];
         }
         MVS_ROW_STEP3(0xB1) MVS_ROW_STEP3(0x4E) MVS_ROW_STEP3(0x141) MVS_ROW_STEP3(0x140)
         float xr = 0.0f, xg = 0.0f, xb = 0.0f;
-        if (cc.nx > 0) {
+        if (has_x) {
             xr = bperm_f(4 * vq, fxr); xg = bperm_f(4 * vq, fxg); xb = bperm_f(4 * vq, fxb);
             s1r += xr; s1g += xg; s1b += xb;
         }
@@ -832,15 +862,18 @@ DEV void eval_views(const DParams& prm, WaveCtx& wc, const Frame& f, int n, vmas
         float er[3], eg[3], eb[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            const float fm = cvt_ub2(cls_opaque(cc.cs[j]));
-            er[j] = fma_(-mr, fm, cr[j]); eg[j] = fma_(-mg, fm, cg[j]); eb[j] = fma_(-mb, fm, cb[j]);
+            if (FULL) { er[j] = cr[j] - mr; eg[j] = cg[j] - mg; eb[j] = cb[j] - mb; }
+            else {
+                const float fm = cvt_ub2(cls_opaque(cc.cs[j]));
+                er[j] = fma_(-mr, fm, cr[j]); eg[j] = fma_(-mg, fm, cg[j]); eb[j] = fma_(-mb, fm, cb[j]);
+            }
         }
         const float exr = xr - mr, exg = xg - mg, exb = xb - mb;
         if (t == 0) {  // the centred reference texture: from row 0 to every row
             const int a0 = 4 * lc;
 #pragma unroll
             for (int j = 0; j < 3; ++j) { d0[j][0] = bperm_f(a0, er[j]); d0[j][1] = bperm_f(a0, eg[j]); d0[j][2] = bperm_f(a0, eb[j]); }
-            if (cc.nx > 0) { d0x[0] = bperm_f(0, exr); d0x[1] = bperm_f(0, exg); d0x[2] = bperm_f(0, exb); }
+            if (has_x) { d0x[0] = bperm_f(0, exr); d0x[1] = bperm_f(0, exg); d0x[2] = bperm_f(0, exb); }
         }
         float sq = 0.0f, dt = 0.0f;
 #pragma unroll
@@ -849,7 +882,7 @@ DEV void eval_views(const DParams& prm, WaveCtx& wc, const Frame& f, int n, vmas
             dt += fma_(d0[j][2], eb[j], fma_(d0[j][1], eg[j], d0[j][0] * er[j]));
         }
         MVS_ROW_STEP2(0xB1) MVS_ROW_STEP2(0x4E) MVS_ROW_STEP2(0x141) MVS_ROW_STEP2(0x140)
-        if (cc.nx > 0) {
+        if (has_x) {
             sq += fma_(exb, exb, fma_(exg, exg, exr * exr));
             dt += fma_(d0x[2], exb, fma_(d0x[1], exg, d0x[0] * exr));
         }
@@ -861,7 +894,7 @@ DEV void eval_views(const DParams& prm, WaveCtx& wc, const Frame& f, int n, vmas
 #pragma unroll
             for (int j = 0; j < 3; ++j)
                 if (cc.cs[j] >> 16) { const int q = 3 * (lc + 16 * j); tv[q] = have ? er[j] : 0.0f; tv[q + 1] = have ? eg[j] : 0.0f; tv[q + 2] = have ? eb[j] : 0.0f; }
-            if (cc.nx > 0 && lc == 0) { tv[3 * cc.xbase] = have ? exr : 0.0f; tv[3 * cc.xbase + 1] = have ? exg : 0.0f; tv[3 * cc.xbase + 2] = have ? exb : 0.0f; }
+            if (has_x && lc == 0) { tv[3 * cc.xbase] = have ? exr : 0.0f; tv[3 * cc.xbase + 1] = have ? exg : 0.0f; tv[3 * cc.xbase + 2] = have ? exb : 0.0f; }
         }
 #else
         if (texs && v < n) {  // sample-major: element 3 q + channel of view v's row of 3 * tstride floats (the k order of the pair sums)
@@ -869,7 +902,7 @@ DEV void eval_views(const DParams& prm, WaveCtx& wc, const Frame& f, int n, vmas
 #pragma unroll
             for (int j = 0; j < 3; ++j)
                 if (cc.cs[j] >> 16) { const int q = 3 * (lc + 16 * j); tv[q] = er[j]; tv[q + 1] = eg[j]; tv[q + 2] = eb[j]; }
-            if (cc.nx > 0 && lc == 0) { tv[3 * cc.xbase] = exr; tv[3 * cc.xbase + 1] = exg; tv[3 * cc.xbase + 2] = exb; }
+            if (has_x && lc == 0) { tv[3 * cc.xbase] = exr; tv[3 * cc.xbase + 1] = exg; tv[3 * cc.xbase + 2] = exb; }
         }
 #endif
     };
@@ -1054,7 +1087,8 @@ DEV float compute_weights(const DParams& prm, const WaveCtx& wc, F4 coord, F4 no
 }
 
 // Optim::computeINCC, optim.cpp:630-706
-DEV float compute_incc(const DParams& prm, WaveCtx& wc, F4 coord, F4 normal, int img, int n, float weights, int robust) {
+template <class WC>
+DEV float compute_incc(const DParams& prm, WC& wc, F4 coord, F4 normal, int img, int n, float weights, int robust) {
     if (n < 2) return 2.0f;
     const int ref = rli(img, 0);
     F4 px, py;
@@ -1092,13 +1126,15 @@ DEV float weighted_incc(const DParams& prm, vmask_t okm, float val_l, float weig
     return div_rn(score, total);
 }
 // PatchManager::computeNcc, patch_manager.cpp:401-404
-DEV float compute_ncc(const DParams& prm, WaveCtx& wc, F4 coord, F4 normal, int img, int n) {
+template <class WC>
+DEV float compute_ncc(const DParams& prm, WC& wc, F4 coord, F4 normal, int img, int n) {
     const float w = compute_weights(prm, wc, coord, normal, img, n);
     return 1.0f - unrobustincc(compute_incc(prm, wc, coord, normal, img, n, w, 1));
 }
 
 // Optim::setINCCs (vector), optim.cpp:708-746: returns the view-lane INCC array (reference vs every view)
-DEV float set_inccs(const DParams& prm, WaveCtx& wc, F4 coord, F4 normal, int img, int n, int robust, vmask_t* okm_out = nullptr,
+template <class WC>
+DEV float set_inccs(const DParams& prm, WC& wc, F4 coord, F4 normal, int img, int n, int robust, vmask_t* okm_out = nullptr,
                     float* texs = nullptr, int tstride = 0, float* ssd_out = nullptr) {
     const int ref = rli(img, 0);
     F4 px, py;
@@ -1167,7 +1203,8 @@ struct KeptTex {
     int orig;        // view lanes (current index) -> old index
     int n_eval;      // length of the list at the time of the evaluation
 };
-DEV void constraint_images(const DParams& prm, WaveCtx& wc, int* scratch, Cand& c, float nccThreshold, float keep_w = 0.0f, int keep_n = 0,
+template <class WC>
+DEV void constraint_images(const DParams& prm, WC& wc, int* scratch, Cand& c, float nccThreshold, float keep_w = 0.0f, int keep_n = 0,
                            KeptTex* kt = nullptr) {
     vmask_t okm = 0u;
     float ssd = 1.0f;
@@ -1264,7 +1301,8 @@ DEV int check_angles(const DParams& prm, const WaveCtx& wc, const Cand& c) {
 }
 
 // Optim::preProcess, optim.cpp:137-163
-DEV int pre_process(const DParams& prm, WaveCtx& wc, int* scratch, Cand& c) {
+template <class WC>
+DEV int pre_process(const DParams& prm, WC& wc, int* scratch, Cand& c) {
     add_images(prm, wc, scratch, c);
     constraint_images(prm, wc, scratch, c, prm.nccThresholdBefore);
     sort_images(prm, wc, c);
@@ -1338,7 +1376,8 @@ DEV double cost_of_group(const DParams& prm, const WaveCtx& wc, unsigned okm, fl
     return ans / (double)denom;
 }
 // rows (four proposals): bit g = proposal g is evaluated; a proposal left out samples nothing, costs 2 and is not counted.
-DEV void cost_func4(const DParams& prm, WaveCtx& wc, const RefineCtx& rc, int imgx, int n, bool four, float x0, float x1, float x2,
+template <class WC>
+DEV void cost_func4(const DParams& prm, WC& wc, const RefineCtx& rc, int imgx, int n, bool four, float x0, float x1, float x2,
                     double (&fv)[4], float* piv = nullptr, const ClsConst* cc = nullptr, unsigned rows = 0xFu) {
     F4 coord, normal, px, py;
     decode(prm, rc, x0, x1, x2, coord, normal);
@@ -1381,7 +1420,8 @@ DEV void cost_func4(const DParams& prm, WaveCtx& wc, const RefineCtx& rc, int im
 }
 // Optim::refinePatch, optim.cpp:480-547, BOBYQA replaced by the halving random search
 // w_out != nullptr (inside the sweep): the weights go out and the final m_ncc is left to postProcess
-DEV void refine_patch(const DParams& prm, WaveCtx& wc, Cand& c, uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3, float* w_out = nullptr) {
+template <class WC>
+DEV void refine_patch(const DParams& prm, WC& wc, Cand& c, uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3, float* w_out = nullptr) {
     RefineCtx rc;
     rc.center = c.coord;
     rc.ref = rli(c.img, 0);
@@ -1474,7 +1514,8 @@ DEV void pend_load(const int* st, const WaveCtx& wc, Cand& c, float& w) {
 // cost_func4 for the four proposals of TWO candidates: lane 16 g + 8 s + k decodes proposal g of candidate s (rc, imgx, szl and x0..x2 are
 // that lane's), builds its patch axes and the frame of view k < szl = min(tau, nimg) of candidate s (<= 8).  fv[s][g]: the cost of proposal g
 // of candidate s -- the eight means in lanes j < 8 (candidate j >> 2, proposal j & 3), added in cost_func's order, one fp64 division.
-DEV void cost_func4_pair(const DParams& prm, WaveCtx& wc, const RefineCtx& rc, int imgx, int sz0, int sz1, int szl, float x0, float x1, float x2,
+template <class WC>
+DEV void cost_func4_pair(const DParams& prm, WC& wc, const RefineCtx& rc, int imgx, int sz0, int sz1, int szl, float x0, float x1, float x2,
                          double (&fv)[2][4], const ClsConst& cc) {
     F4 coord, normal, px, py;
     decode(prm, rc, x0, x1, x2, coord, normal);
@@ -1511,7 +1552,8 @@ DEV void cost_func4_pair(const DParams& prm, WaveCtx& wc, const RefineCtx& rc, i
 // changes is where the work of the frame lanes runs -- decode, getPAxes, the frames, the extra sample, the per-view scalars, the robust
 // INCCs and the cost means are issued once for both, candidate s in lanes 16 g + 8 s + k (refine_patch leaves the lanes 16 g + 8 .. 15 idle).
 // Leaves the refined coord / normal of candidate 0 and its weights in the stash, those of candidate 1 in c1 and w1.
-DEV void refine_patch_pair(const DParams& prm, WaveCtx& wc, int* st, Cand& c1, uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3a, uint32_t k3b, float& w1) {
+template <class WC>
+DEV void refine_patch_pair(const DParams& prm, WC& wc, int* st, Cand& c1, uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3a, uint32_t k3b, float& w1) {
     float* const ctx = reinterpret_cast<float*>(st + MVS_PEND_CTX);
     int* const ximg = st + MVS_PEND_XIMG;
     const float amin = -23.99999f, amax = 23.99999f;
@@ -1639,7 +1681,8 @@ DEV void refine_patch_pair(const DParams& prm, WaveCtx& wc, int* st, Cand& c1, u
 // or the next pass would take the evaluations beyond max_evals (NLopt's MAXEVAL_REACHED: the reference counts that a failure and
 // leaves the patch as it was, optim.cpp:530-545).  Returns the evaluations made, negated when the budget ran out; x_out / f_out:
 // the best vertex and its cost.  w_out as refine_patch.
-DEV int refine_patch_simplex(const DParams& prm, WaveCtx& wc, Cand& c, int max_evals, float xtol, float* w_out = nullptr,
+template <class WC>
+DEV int refine_patch_simplex(const DParams& prm, WC& wc, Cand& c, int max_evals, float xtol, float* w_out = nullptr,
                                float* x_out = nullptr, double* f_out = nullptr) {
     RefineCtx rc;
     rc.center = c.coord;
@@ -1771,7 +1814,8 @@ DEV int pair_index(int a, int b, int n) { return a * (2 * n - a - 1) / 2 + (b - 
 // work counters do not count a second evaluation); entry i of the list is entry kt->orig of that evaluation.
 // `pre` (Filter::filterExact, which has the frames of four patches made side by side): lane i < nimg holds the finished frame of view c.img
 // -- made by make_frame from getPAxes of the FIRST view of the list, as below.
-DEV void set_ref_image(const DParams& prm, WaveCtx& wc, float* texs, int tstride, Cand& c, const KeptTex* kt = nullptr, const Frame* pre = nullptr) {
+template <class WC>
+DEV void set_ref_image(const DParams& prm, WC& wc, float* texs, int tstride, Cand& c, const KeptTex* kt = nullptr, const Frame* pre = nullptr) {
     if (c.nimg == 0) return;
     const int n = c.nimg;
     const int ref = rli(c.img, 0);
@@ -1944,7 +1988,8 @@ DEV int get_mask_all(const DParams& prm, const WaveCtx& wc, const Cand& c) {
 DEV float score2(const Cand& c, float thr) { return fmaxf(0.0f, c.ncc - thr) * (float)c.nimg; }
 
 // Optim::postProcess, optim.cpp:260-298 (Optim::check is applied by the caller, which owns the cell lists)
-DEV int post_process(const DParams& prm, WaveCtx& wc, int* scratch, float* texs, int tstride, Cand& c, float keep_w = 0.0f, bool keep = false) {
+template <class WC>
+DEV int post_process(const DParams& prm, WC& wc, int* scratch, float* texs, int tstride, Cand& c, float keep_w = 0.0f, bool keep = false) {
     if (c.nimg < prm.minImageNum) return -1;
     if (get_mask_all(prm, wc, c) == 0) return -1;
     const int keep_n = keep ? c.nimg : 0;
@@ -2008,7 +2053,8 @@ DEV WaveCtx make_wave_ctx(const DParams& prm) {
 // (optim.cpp:385-395) makes that view the reference.
 // need_ncc = false (engine schedule, destination cell not full): the initial score is only ever read by the
 // replace-worst pre-filter (propagate.cpp:170); refinePatch overwrites it, so it is not computed when nothing reads it.
-DEV bool generate_patch(const DParams& prm, WaveCtx& wc, int* scratch, const Cand& src, F3 icoord, Cand& out, int as_view = -1, bool need_ncc = true) {
+template <class WC>
+DEV bool generate_patch(const DParams& prm, WC& wc, int* scratch, const Cand& src, F3 icoord, Cand& out, int as_view = -1, bool need_ncc = true) {
     int simg = src.img;
     if (as_view >= 0 && rli(src.img, 0) != as_view) {
         const unsigned long long hit = ballot(0 < wc.lane && wc.lane < src.nimg && src.img == as_view);

@@ -468,6 +468,12 @@ int mvs_engine_sweep_repeats(mvs_engine* e, int64_t out[2]) {
     return MVS_OK;
 }
 
+int mvs_engine_sweep_kernels(mvs_engine* e, int64_t out[2]) {
+    if (!e || !out) return MVS_ERR_ARG;
+    for (int k = 0; k < 2; ++k) out[k] = e->sweep_kernels[k];
+    return MVS_OK;
+}
+
 int mvs_engine_last_timing(mvs_engine* e, mvs_timing* t) {
     if (!e || !t) return MVS_ERR_ARG;
     *t = e->timing;

@@ -179,6 +179,7 @@ struct mvs_engine {
                                              // lie in job_cnt and job_base_scan, which the commit fills only after the sweep
     int64_t sweep_pairs[6] = {0, 0, 0, 0, 0, 0};  // DCounters::pair, summed over the passes since the engine was created (mvs_engine_sweep_pairs)
     int64_t sweep_repeats[2] = {0, 0};            // DCounters::repeats, likewise (mvs_engine_sweep_repeats)
+    int64_t sweep_kernels[2] = {0, 0};            // sweep launches by kernel: generic, full-window (mvs_engine_sweep_kernels)
     int64_t retried_cells = 0;               // destination cells that went to the second tier since the engine was created
     int64_t pass_retried = 0;                // ... in the last pass
     SweepArgs sa{};

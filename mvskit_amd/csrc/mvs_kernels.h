@@ -26,7 +26,9 @@ void mvsk_fill_ncc(const DParams& prm, unsigned long long* evals, hipStream_t st
 // simplex = 1 the CONVERGED refiner (k_sweep_simplex, k_sweep_retry_simplex, k_probe_refine_simplex) with these two arguments
 struct RefineSel { int simplex; int max_evals; float xtol; };
 size_t mvsk_sweep_lds_bytes(const DParams& prm);
-void mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hipStream_t st);
+// -> 1 if the launch went to the full-window instantiation (k_sweep_full: every class-lane slot holds a sample, as for the default 7x7 window,
+// and MVS_SWEEP_FULLWINDOW is not 0), 0 if to a generic kernel, -1 if there was nothing to launch
+int mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hipStream_t st);
 void mvsk_sweep_retry(const DParams& prm, const SweepArgs& a, int nretry, const RefineSel& rs, hipStream_t st);
 void mvsk_job_work(const DParams& prm, const SweepArgs& a, int mode, int shift, int32_t* work, hipStream_t st);
 // The sweep's job lists: clears job_nstage[0, njobs) and lists the jobs of [job_lo, job_hi) that run a trial, per queue.  flags and scan

@@ -548,8 +548,8 @@ DEV void sweep_acc_flush(const SweepArgs& a, const SweepAcc& acc, unsigned slot)
 // counted goes into `acc` when it is done -- nothing of a cell that gives up.
 // SIMPLEX = true: the refinement is refine_patch_simplex with max_evals / xtol (k_sweep_simplex, k_sweep_retry_simplex: the CONVERGED
 // refiner of mvs_engine_set_refiner); the default kernels keep the halving search and never see the two arguments.
-template <bool BIG, bool SIMPLEX = false>
-DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WaveCtx& wc, SweepAcc* acc, const int64_t job, int* s_scratch, int* s_pend, float* s_texs,
+template <bool BIG, bool SIMPLEX = false, class WC>
+DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WC& wc, SweepAcc* acc, const int64_t job, int* s_scratch, int* s_pend, float* s_texs,
                     int* big_table, int max_evals = 0, float xtol = 0.0f) {
 #ifdef MVS_STAGE_TIMING
     unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -801,9 +801,11 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WaveCtx& wc, SweepAc
 // chunk to itself spreads the 384 waves of an XCD over 384 chunks: sweep 333 ms per step against 281 for one block per cell;
 // takes of 64 / 16 / 4 / 1 jobs (of unlisted jobs, a lane per job testing for a source): 309 / 285 / 273.5 / 270.4 ms
 // (profiles/r09_resident_ab.txt).  The cursor's atomic is one per listed job: a round trip in ~430 us of work per cell.
-template <bool SIMPLEX>
+// WC = WaveCtxFull: the instantiation for a full window (k_sweep_full)
+template <bool SIMPLEX, class WC = WaveCtx>
 DEV void sweep_resident(const DParams& prm, const SweepArgs& a, int* s_scratch, int* s_pend, float* s_texs, int max_evals, float xtol) {
-    WaveCtx wc = make_wave_ctx(prm);
+    WC wc;
+    static_cast<WaveCtx&>(wc) = make_wave_ctx(prm);
     SweepAcc acc = sweep_acc_zero();
     for (unsigned step = 0; step < MVS_SWEEP_QUEUES; ++step) {
         const unsigned q = (blockIdx.x + step) & (MVS_SWEEP_QUEUES - 1u);
@@ -827,6 +829,13 @@ __global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep(DParams prm, Swee
     __shared__ __attribute__((aligned(16))) int s_pend[MVS_PEND_INTS];  // a waiting candidate, the working block of a pair (mvs_device.cuh)
     extern __shared__ float s_texs[];
     sweep_resident<false>(prm, a, s_scratch, s_pend, s_texs, 0, 0.0f);
+}
+// k_sweep for a launch whose window fills every slot of every lane (cls_full_window: the default 7x7), chosen by mvsk_sweep
+__global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep_full(DParams prm, SweepArgs a) {
+    __shared__ int s_scratch[192];
+    __shared__ __attribute__((aligned(16))) int s_pend[MVS_PEND_INTS];  // a waiting candidate, the working block of a pair (mvs_device.cuh)
+    extern __shared__ float s_texs[];
+    sweep_resident<false, WaveCtxFull>(prm, a, s_scratch, s_pend, s_texs, 0, 0.0f);
 }
 __global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep_simplex(DParams prm, SweepArgs a, int max_evals, float xtol) {
     __shared__ int s_scratch[192];
@@ -1493,9 +1502,14 @@ static SweepArgs sweep_args_with_switches(const SweepArgs& a) {
     b.pair = (p && atoi(p) == 0) ? 0 : 1;
     return b;
 }
-void mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hipStream_t st) {
+// A/B and test switch, read on every launch: MVS_SWEEP_FULLWINDOW=0 keeps a full window on the generic kernel (the result does not depend on it)
+static bool sweep_full_window(const DParams& prm) {
+    const char* p = getenv("MVS_SWEEP_FULLWINDOW");
+    return cls_full_window(prm.wsz) && !(p && atoi(p) == 0);
+}
+int mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hipStream_t st) {
     const int64_t nloc = a.job_hi - a.job_lo;
-    if (nloc <= 0) return;
+    if (nloc <= 0) return -1;
     // development knob: MVS_SWEEP_LDS_PAD=<bytes> raises the block's LDS allocation, i.e. lowers the waves per SIMD
     static const size_t pad = getenv("MVS_SWEEP_LDS_PAD") ? (size_t)atol(getenv("MVS_SWEEP_LDS_PAD")) : 0;
     const size_t lds = mvsk_sweep_lds_bytes(prm) + pad;
@@ -1512,7 +1526,9 @@ void mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hip
     }
     const SweepArgs b = sweep_args_with_switches(a);
     if (rs.simplex) hipLaunchKernelGGL(k_sweep_simplex, dim3((unsigned)nblocks), dim3(64), lds, st, prm, b, rs.max_evals, rs.xtol);
+    else if (sweep_full_window(prm)) { hipLaunchKernelGGL(k_sweep_full, dim3((unsigned)nblocks), dim3(64), lds, st, prm, b); return 1; }
     else hipLaunchKernelGGL(k_sweep, dim3((unsigned)nblocks), dim3(64), lds, st, prm, b);
+    return 0;
 }
 void mvsk_job_work(const DParams& prm, const SweepArgs& a, int mode, int shift, int32_t* work, hipStream_t st) {
     if (a.njobs > 0) hipLaunchKernelGGL(k_job_work, dim3(nblk(a.njobs, 256)), dim3(256), 0, st, prm, a, mode, shift, work);

@@ -31,7 +31,7 @@ EXPORTS = [
     "mvs_default_seed_random", "mvs_engine_seed_random", "mvs_engine_seed_random_hypotheses",
     "mvs_default_seed_points", "mvs_engine_seed_points", "mvs_engine_seed_points_hypotheses", "mvs_engine_depth_ranges",
     "mvs_default_maps_config", "mvs_engine_render_maps", "mvs_engine_fused_points",
-    "mvs_engine_tsdf", "mvs_engine_extract_mesh", "mvs_engine_mesh", "mvs_engine_sweep_pairs", "mvs_engine_sweep_repeats",
+    "mvs_engine_tsdf", "mvs_engine_extract_mesh", "mvs_engine_mesh", "mvs_engine_sweep_pairs", "mvs_engine_sweep_repeats", "mvs_engine_sweep_kernels",
     "mvs_default_mesh_colouring", "mvs_engine_mesh_normals", "mvs_engine_mesh_colours",
     "mvs_default_mesh_pruning", "mvs_default_mesh_smoothing", "mvs_engine_mesh_components", "mvs_engine_mesh_prune", "mvs_engine_mesh_smooth",
     "mvs_default_mesh_decimation", "mvs_engine_mesh_decimate",
@@ -231,6 +231,8 @@ def load_library(cap32: bool = False, cap: int = 0):
         L.mvs_engine_sweep_pairs.argtypes = [vp, C.POINTER(C.c_int64)]
     if hasattr(L, "mvs_engine_sweep_repeats"):
         L.mvs_engine_sweep_repeats.argtypes = [vp, C.POINTER(C.c_int64)]
+    if hasattr(L, "mvs_engine_sweep_kernels"):
+        L.mvs_engine_sweep_kernels.argtypes = [vp, C.POINTER(C.c_int64)]
     if hasattr(L, "mvs_engine_tsdf"):
         L.mvs_engine_tsdf.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(Volume), vp, vp]
         L.mvs_engine_extract_mesh.argtypes = [vp, C.POINTER(Volume), vp, vp, C.c_int64, vp, C.c_int64, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -784,6 +786,14 @@ class Engine:
         out = (C.c_int64 * 2)()
         self._check(self.L.mvs_engine_sweep_repeats(self.h, out))
         return dict(zip(self.SWEEP_REPEAT_KEYS, (int(x) for x in out)))
+
+    #: mvs_engine_sweep_kernels: sweep launches by the kernel the launcher chose, since the engine was created
+    SWEEP_KERNEL_KEYS = ("generic", "full_window")
+
+    def sweep_kernels(self):
+        out = (C.c_int64 * 2)()
+        self._check(self.L.mvs_engine_sweep_kernels(self.h, out))
+        return dict(zip(self.SWEEP_KERNEL_KEYS, (int(x) for x in out)))
 
     def depth_normal_map(self, view, kind):
         gw, gh = self.grid_dims(view)
