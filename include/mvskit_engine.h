@@ -775,6 +775,15 @@ int mvs_engine_sweep_repeats(mvs_engine* e, int64_t out[2]);
  *   out[0] launches of a generic kernel      out[1] launches of the full-window kernel */
 int mvs_engine_sweep_kernels(mvs_engine* e, int64_t out[2]);
 
+/* Launches by the form of their texture samplers, since the engine was created.  The RGBA8 pyramids of all views lie in one device
+ * allocation.  While it is below 4 GiB the full-window sweep kernel and the refine probe (mvs_engine_probe, MVS_PROBE_REFINE with the
+ * default refiner) address a texel by the allocation's base, one value for the whole launch, plus a 32-bit byte offset per lane (the
+ * narrow form); otherwise, and in every other kernel, by a 64-bit address per lane (the wide form).  The texels read are the same and
+ * so are the results.  MVS_SAMPLER_WIDE=1 in the environment (read at every launch) keeps the wide form.
+ *   out[0] sweep launches with wide samplers      out[1] sweep launches with narrow samplers
+ *   out[2] refine probes with wide samplers       out[3] refine probes with narrow samplers */
+int mvs_engine_sampler_launches(mvs_engine* e, int64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -341,7 +341,10 @@ struct Frame {
     float tlx, tly, dxx, dxy, dyx, dyy;
     int w;               // width of the chosen level
     int ok;              // 1 = the view passed the angle gate and getTexSafe
-    unsigned img_lo, img_hi;  // RGBA8 pyramid level base address
+    // where the RGBA8 texels of the chosen level lie, in the form of the sampler that reads the frame (WaveCtx::narrow):
+    //   narrow  a_lo = the level's byte offset in the pyramid block (DView::img_off), a_hi = its row pitch in bytes (4 w)
+    //   wide    a_lo, a_hi = the halves of the level's address (DView::img)
+    unsigned a_lo, a_hi;
 };
 // levelDiff = clamp(floor(log2(ratio) + .5)) (optim.cpp:808) as comparisons against 2^(k - .5), k = -3 .. 2 ("level
 // pick").  Those six thresholds are ONE float mantissa (that of sqrt 2, 0x3504F3) under six exponents, so for ratio = 2^e * 1.m the
@@ -358,6 +361,8 @@ DEV int level_diff(const DParams& prm, float ratio) {
 DEV float pow2_level(int ld) { return __int_as_float((127 + ld) << 23); }  // Optim::myPow2, exact powers of two
 // Straight-line: every load of the view's constants is issued at the top (one wait instead of one per early exit --
 // a lane that leaves early saves nothing while its neighbours go on), the gates only select the result.
+// NARROW: the frame is for a sampler that addresses the pyramid block by 32-bit byte offsets (Frame::a_lo / a_hi)
+template <bool NARROW = false>
 DEV Frame make_frame(const DParams& prm, F4 coord, F4 px, F4 py, F4 pz, int v, bool active) {
     const DView* vw = prm.views + (active ? v : 0);
     const F4 ctr = ld4(vw->center);
@@ -365,7 +370,7 @@ DEV Frame make_frame(const DParams& prm, F4 coord, F4 px, F4 py, F4 pz, int v, b
 #pragma unroll
     for (int k = 0; k < 12; ++k) P[k] = vw->P[prm.level][k];
     const int W0 = vw->W[0], H0 = vw->H[0];
-    const unsigned long long base_level = (unsigned long long)vw->img[prm.level];
+    const unsigned long long base_level = NARROW ? (unsigned long long)vw->img_off[prm.level] : (unsigned long long)vw->img[prm.level];
     const F4 ray = nrm4(sub4(ctr, coord));
     const float weight = fmaxf(0.0f, dot4(ray, pz));
     F3 center = project_regs(P, coord);
@@ -375,7 +380,8 @@ DEV Frame make_frame(const DParams& prm, F4 coord, F4 px, F4 py, F4 pz, int v, b
     const int ld = level_diff(prm, ratio);
     const float iscale = pow2_level(-ld);  // exact reciprocal of a power of two
     const int newLevel = prm.level + ld;
-    const unsigned long long base_new = (unsigned long long)vw->img[newLevel];  // the one load that depends on the arithmetic
+    // the one load that depends on the arithmetic
+    const unsigned long long base_new = NARROW ? (unsigned long long)vw->img_off[newLevel] : (unsigned long long)vw->img[newLevel];
     center = scl3(center, iscale);
     dx = scl3(dx, iscale);
     dy = scl3(dy, iscale);
@@ -398,7 +404,8 @@ DEV Frame make_frame(const DParams& prm, F4 coord, F4 px, F4 py, F4 pz, int v, b
     f.w = ok ? W : (W0 >> prm.level);
     f.ok = ok ? 1 : 0;
     const unsigned long long a = ok ? base_new : base_level;
-    f.img_lo = (unsigned)(a & 0xffffffffull); f.img_hi = (unsigned)(a >> 32);
+    f.a_lo = (unsigned)(a & 0xffffffffull);
+    f.a_hi = NARROW ? 4u * (unsigned)f.w : (unsigned)(a >> 32);
     return f;
 }
 
@@ -441,6 +448,18 @@ struct WaveCtx {
 struct WaveCtxFull : WaveCtx {};
 template <class WC> struct wc_full_window { static constexpr bool value = false; };
 template <> struct wc_full_window<WaveCtxFull> { static constexpr bool value = true; };
+// How a launch addresses the texels it samples is a property of the context's type as well.  WIDE (WaveCtx, WaveCtxFull): a 64-bit address
+// per lane, for a pyramid block of any size.  NARROW (WaveCtxOfs, WaveCtxFullOfs): the block's base, one value for the whole launch
+// (DParams::pyr32, scalar registers), plus a 32-bit byte offset per lane -- the address arithmetic of a sample slot is then 32-bit
+// (v_mad_u32_u24, v_lshl_add_u32, v_add_u32 in place of v_mad_u64_u32 and three v_lshl_add_u64) and the loads take the form
+// global_load v, v_off, s[base].  The texels read are the same, so the results are.  The launcher picks a narrow instantiation where
+// the block is below 4 GiB (DParams::pyr32 is set).  A Frame is made (make_frame) and consumed by functions of ONE context type.
+struct WaveCtxOfs : WaveCtx {};
+struct WaveCtxFullOfs : WaveCtx {};
+template <> struct wc_full_window<WaveCtxFullOfs> { static constexpr bool value = true; };
+template <class WC> struct wc_narrow { static constexpr bool value = false; };
+template <> struct wc_narrow<WaveCtxOfs> { static constexpr bool value = true; };
+template <> struct wc_narrow<WaveCtxFullOfs> { static constexpr bool value = true; };
 #ifdef MVS_STAGE_TIMING
 #define WC_T0(wc) { (wc).st_t = (unsigned long long)__builtin_amdgcn_s_memtime(); }
 #define WC_ADD(wc, k) { const unsigned long long t1_ = (unsigned long long)__builtin_amdgcn_s_memtime(); (wc).st_acc[k] += t1_ - (wc).st_t; (wc).st_t = t1_; }
@@ -461,7 +480,7 @@ DEV void frames_publish(const WaveCtx& wc, const Frame& f, int nlanes) {
         float4* d = mvs_dyn_lds4 + 3 * wc.lane;
         d[0] = make_float4(f.tlx, f.tly, f.dxx, f.dxy);
         d[1] = make_float4(f.dyx, f.dyy, __int_as_float(f.w), __int_as_float(f.ok));
-        d[2] = make_float4(__int_as_float((int)f.img_lo), __int_as_float((int)f.img_hi), 0.0f, 0.0f);
+        d[2] = make_float4(__int_as_float((int)f.a_lo), __int_as_float((int)f.a_hi), 0.0f, 0.0f);
     }
     __syncthreads();
 }
@@ -507,26 +526,48 @@ DEV float cvt_ub2(unsigned x) { return (float)((x >> 16) & 255u); }
 // The sample constants are unpacked where they are used (three v_cvt_f32_ubyte): hoisted out of the refinement loop as nine
 // floats they only turn into scratch traffic.  The empty asm hides the loop invariance from the optimiser.
 DEV unsigned cls_opaque(unsigned x) { asm volatile("" : "+v"(x)); return x; }
-struct ClsFrame { float tlx, tly, dxx, dxy, dyx, dyy; int w; unsigned long long base; };
+struct ClsFrame { float tlx, tly, dxx, dxy, dyx, dyy; int w; unsigned a_lo, a_hi; };  // a_lo, a_hi: as in Frame
 DEV ClsFrame cls_frame(int fidx) {
     const float4* s = mvs_dyn_lds4 + 3 * fidx;
     const float4 A = s[0], B = s[1];
     const float2 Cc = *reinterpret_cast<const float2*>(s + 2);
     ClsFrame f;
     f.tlx = A.x; f.tly = A.y; f.dxx = A.z; f.dxy = A.w; f.dyx = B.x; f.dyy = B.y; f.w = __float_as_int(B.z);
-    f.base = ((unsigned long long)(unsigned)__float_as_int(Cc.y) << 32) | (unsigned long long)(unsigned)__float_as_int(Cc.x);
+    f.a_lo = (unsigned)__float_as_int(Cc.x); f.a_hi = (unsigned)__float_as_int(Cc.y);
     return f;
 }
-DEV ClsPend cls_issue(const ClsFrame& f, unsigned cs) {
+DEV ClsFrame cls_frame_of(const Frame& f) {  // a frame lane's own frame (the extra sample)
+    ClsFrame fr;
+    fr.tlx = f.tlx; fr.tly = f.tly; fr.dxx = f.dxx; fr.dxy = f.dxy; fr.dyx = f.dyx; fr.dyy = f.dyy; fr.w = f.w;
+    fr.a_lo = f.a_lo; fr.a_hi = f.a_hi;
+    return fr;
+}
+// NARROW (wc_narrow): pyr = DParams::pyr32, the launch's one base; the byte offsets of the two texel rows are formed in 32-bit unsigned
+// arithmetic -- row number and pitch are below 2^24 and the block below 2^32 (mvs_engine_set_views), so the 24-bit multiply and the
+// sums are exact -- and the address is the base plus the zero-extended offset, which the compiler turns into scalar-base loads.
+template <bool NARROW> DEV const uint8_t* sampler_base(const DParams& prm) { return NARROW ? prm.pyr32 : nullptr; }
+template <bool NARROW>
+DEV ClsPend cls_issue(const uint8_t* pyr, const ClsFrame& f, unsigned cs) {
     typedef const __attribute__((address_space(1))) uint32_t* GlobalTexels;
+    typedef const __attribute__((address_space(1))) uint8_t* GlobalBytes;
     // a slot without a sample has cs = 0: it reads the window's first texels (a valid address) and is weighted out in
     // cls_colour, so no select is needed here
     const float fx = cvt_ub0(cs), fy = cvt_ub1(cs);
     const float sx = fma_(f.dyx, fy, fma_(f.dxx, fx, f.tlx));
     const float sy = fma_(f.dyy, fy, fma_(f.dxy, fx, f.tly));
     const int lx = (int)sx, ly = (int)sy;
-    const unsigned long long a0 = f.base + 4ull * (unsigned long long)(unsigned)(ly * f.w + lx);
-    const GlobalTexels t0 = (GlobalTexels)a0, t1 = (GlobalTexels)(a0 + 4ull * (unsigned long long)(unsigned)f.w);
+    GlobalTexels t0, t1;
+    if (NARROW) {
+        // (the empty asm keeps the row's offset one v_mad_u32_u24: reassociated, the sum costs a shift and a three-operand add more)
+        unsigned row = __umul24((unsigned)ly, f.a_hi) + f.a_lo;
+        asm("" : "+v"(row));
+        const unsigned o0 = row + ((unsigned)lx << 2), o1 = o0 + f.a_hi;
+        t0 = (GlobalTexels)((GlobalBytes)pyr + (unsigned long long)o0); t1 = (GlobalTexels)((GlobalBytes)pyr + (unsigned long long)o1);
+    } else {
+        const unsigned long long base = ((unsigned long long)f.a_hi << 32) | (unsigned long long)f.a_lo;
+        const unsigned long long a0 = base + 4ull * (unsigned long long)(unsigned)(ly * f.w + lx);
+        t0 = (GlobalTexels)a0; t1 = (GlobalTexels)(a0 + 4ull * (unsigned long long)(unsigned)f.w);
+    }
     ClsPend p;
     p.q0.a = t0[0]; p.q0.b = t0[1];
     p.q1.a = t1[0]; p.q1.b = t1[1];
@@ -561,7 +602,8 @@ DEV float bperm_f(int addr, float x) { return __int_as_float(__builtin_amdgcn_ds
 // reference view peeled off, and the loads of view k + 1 issued as the slots of view k are consumed.
 template <class WC>
 DEV void eval_steps4(const DParams& prm, WC& wc, const ClsConst& cc, const Frame& f, int n, unsigned (&okm)[4], float& incc_l) {
-    constexpr bool FULL = wc_full_window<WC>::value;
+    constexpr bool FULL = wc_full_window<WC>::value, NARROW = wc_narrow<WC>::value;
+    const uint8_t* const pyr = sampler_base<NARROW>(prm);
     // (the extra's test stays a run-time one here even for a full window: known true, this loop's scalar reloads go from 17 to 20 -- DESIGN.md section 5)
     const bool has_x = cc.nx > 0;
     frames_publish(wc, f, 64);
@@ -579,7 +621,7 @@ DEV void eval_steps4(const DParams& prm, WC& wc, const ClsConst& cc, const Frame
     {
         const ClsFrame fr = cls_frame(fb);
 #pragma unroll
-        for (int j = 0; j < 3; ++j) pend[j] = cls_issue(fr, cls_opaque(cc.cs[j]));
+        for (int j = 0; j < 3; ++j) pend[j] = cls_issue<NARROW>(pyr, fr, cls_opaque(cc.cs[j]));
     }
     {   // the reference view
         const float4 pv = mvs_dyn_lds4[MVS_PIVOT_LDS4];
@@ -590,7 +632,7 @@ DEV void eval_steps4(const DParams& prm, WC& wc, const ClsConst& cc, const Frame
             const unsigned cs = cls_opaque(cc.cs[j]);
             float r, g, b;
             cls_colour<FULL>(pend[j], cs, pv.x, pv.y, pv.z, r, g, b);
-            pend[j] = cls_issue(fn, cs);
+            pend[j] = cls_issue<NARROW>(pyr, fn, cs);
             c0[j][0] = r; c0[j][1] = g; c0[j][2] = b;
             s1r += r; s1g += g; s1b += b;
             s2 = fma_(r, r, s2); s2 = fma_(g, g, s2); s2 = fma_(b, b, s2);
@@ -607,7 +649,7 @@ DEV void eval_steps4(const DParams& prm, WC& wc, const ClsConst& cc, const Frame
             const unsigned cs = cls_opaque(cc.cs[j]);
             float r, g, b;
             cls_colour<FULL>(pend[j], cs, pv.x, pv.y, pv.z, r, g, b);
-            pend[j] = cls_issue(fn, cs);
+            pend[j] = cls_issue<NARROW>(pyr, fn, cs);
             s1r += r; s1g += g; s1b += b;
             s2 = fma_(r, r, s2); s2 = fma_(g, g, s2); s2 = fma_(b, b, s2);
             s01 = fma_(r, c0[j][0], s01); s01 = fma_(g, c0[j][1], s01); s01 = fma_(b, c0[j][2], s01);
@@ -620,12 +662,10 @@ DEV void eval_steps4(const DParams& prm, WC& wc, const ClsConst& cc, const Frame
     // and its sums are never looked at) and adds them to the sums of (proposal g, view k) it holds
     if (has_x) {
         const float4 pv = mvs_dyn_lds4[MVS_PIVOT_LDS4 + lc];
-        ClsFrame fr;
-        fr.tlx = f.tlx; fr.tly = f.tly; fr.dxx = f.dxx; fr.dxy = f.dxy; fr.dyx = f.dyx; fr.dyy = f.dyy; fr.w = f.w;
-        fr.base = ((unsigned long long)f.img_hi << 32) | (unsigned long long)f.img_lo;
+        const ClsFrame fr = cls_frame_of(f);
         {
             const unsigned cs = cc.xcs;
-            const ClsPend pe = cls_issue(fr, cs);
+            const ClsPend pe = cls_issue<NARROW>(pyr, fr, cs);
             float r, g, b;
             cls_colour<FULL>(pe, cs, pv.x, pv.y, pv.z, r, g, b);
             const float r0 = bperm_f(a0, r), g0 = bperm_f(a0, g), b0 = bperm_f(a0, b);
@@ -649,7 +689,8 @@ DEV void eval_steps4(const DParams& prm, WC& wc, const ClsConst& cc, const Frame
 // and, in the caller, the robust INCCs.  okm[s][g]: the views of (candidate s, proposal g) that sample; returns the same bits by frame lane.
 template <class WC>
 DEV unsigned long long eval_steps4_pair(const DParams& prm, WC& wc, const ClsConst& cc, const Frame& f, int n0, int n1, unsigned (&okm)[2][4], float& incc_l) {
-    constexpr bool FULL = wc_full_window<WC>::value;
+    constexpr bool FULL = wc_full_window<WC>::value, NARROW = wc_narrow<WC>::value;
+    const uint8_t* const pyr = sampler_base<NARROW>(prm);
     const bool has_x = FULL || cc.nx > 0;
     frames_publish(wc, f, 64);
     const unsigned long long okb = ballot(f.ok != 0);
@@ -670,7 +711,7 @@ DEV unsigned long long eval_steps4_pair(const DParams& prm, WC& wc, const ClsCon
         {
             const ClsFrame fr = cls_frame(fb);
 #pragma unroll
-            for (int j = 0; j < 3; ++j) pend[j] = cls_issue(fr, cls_opaque(cc.cs[j]));
+            for (int j = 0; j < 3; ++j) pend[j] = cls_issue<NARROW>(pyr, fr, cls_opaque(cc.cs[j]));
         }
         {   // the reference view
             const float4 pv = mvs_dyn_lds4[pb];
@@ -681,7 +722,7 @@ DEV unsigned long long eval_steps4_pair(const DParams& prm, WC& wc, const ClsCon
                 const unsigned cs = cls_opaque(cc.cs[j]);
                 float r, g, b;
                 cls_colour<FULL>(pend[j], cs, pv.x, pv.y, pv.z, r, g, b);
-                pend[j] = cls_issue(fn, cs);
+                pend[j] = cls_issue<NARROW>(pyr, fn, cs);
                 c0[j][0] = r; c0[j][1] = g; c0[j][2] = b;
                 s1r += r; s1g += g; s1b += b;
                 s2 = fma_(r, r, s2); s2 = fma_(g, g, s2); s2 = fma_(b, b, s2);
@@ -698,7 +739,7 @@ DEV unsigned long long eval_steps4_pair(const DParams& prm, WC& wc, const ClsCon
                 const unsigned cs = cls_opaque(cc.cs[j]);
                 float r, g, b;
                 cls_colour<FULL>(pend[j], cs, pv.x, pv.y, pv.z, r, g, b);
-                pend[j] = cls_issue(fn, cs);
+                pend[j] = cls_issue<NARROW>(pyr, fn, cs);
                 s1r += r; s1g += g; s1b += b;
                 s2 = fma_(r, r, s2); s2 = fma_(g, g, s2); s2 = fma_(b, b, s2);
                 s01 = fma_(r, c0[j][0], s01); s01 = fma_(g, c0[j][1], s01); s01 = fma_(b, c0[j][2], s01);
@@ -710,12 +751,10 @@ DEV unsigned long long eval_steps4_pair(const DParams& prm, WC& wc, const ClsCon
     const int a0 = (wc.lane & 56) << 2;  // ds_bpermute address of lane 16 g + 8 s: the reference view of this lane's candidate and proposal
     if (has_x) {
         const float4 pv = mvs_dyn_lds4[MVS_PIVOT_LDS4 + lc];
-        ClsFrame fr;
-        fr.tlx = f.tlx; fr.tly = f.tly; fr.dxx = f.dxx; fr.dxy = f.dxy; fr.dyx = f.dyx; fr.dyy = f.dyy; fr.w = f.w;
-        fr.base = ((unsigned long long)f.img_hi << 32) | (unsigned long long)f.img_lo;
+        const ClsFrame fr = cls_frame_of(f);
         {
             const unsigned cs = cc.xcs;
-            const ClsPend pe = cls_issue(fr, cs);
+            const ClsPend pe = cls_issue<NARROW>(pyr, fr, cs);
             float r, g, b;
             cls_colour<FULL>(pe, cs, pv.x, pv.y, pv.z, r, g, b);
             const float r0 = bperm_f(a0, r), g0 = bperm_f(a0, g), b0 = bperm_f(a0, b);
@@ -811,7 +850,8 @@ DEV void eval_views(const DParams& prm, WC& wc, const Frame& f, int n, vmask_t (
     const int gk0 = wc.lane / MVS_GRAM_CH;                       // this lane's k within an MFMA
     const float* const grow = texs + (wc.lane & (MVS_GRAM_CH - 1)) * gtp;  // this lane's view of the chunk in LDS
 #endif
-    constexpr bool FULL = wc_full_window<WC>::value;
+    constexpr bool FULL = wc_full_window<WC>::value, NARROW = wc_narrow<WC>::value;
+    const uint8_t* const pyr = sampler_base<NARROW>(prm);
     const ClsConst& cc = wc.cc;
     const bool has_x = FULL || cc.nx > 0;
     frames_publish(wc, f, MVS_LISTCAP > 16 ? MVS_LISTCAP : 16);
@@ -823,11 +863,9 @@ DEV void eval_views(const DParams& prm, WC& wc, const Frame& f, int n, vmask_t (
     unsigned xcs = 0u;
     ClsPend pe;
     if (has_x) {
-        ClsFrame fr;
-        fr.tlx = f.tlx; fr.tly = f.tly; fr.dxx = f.dxx; fr.dxy = f.dxy; fr.dyx = f.dyx; fr.dyy = f.dyy; fr.w = f.w;
-        fr.base = ((unsigned long long)f.img_hi << 32) | (unsigned long long)f.img_lo;
+        const ClsFrame fr = cls_frame_of(f);
         xcs = cc.xcs;
-        pe = cls_issue(fr, xcs);
+        pe = cls_issue<NARROW>(pyr, fr, xcs);
     }
     float d0[3][3], d0x[3] = {0.0f, 0.0f, 0.0f};
     float ssd_l = 1.0f, dot_l = 0.0f, mr_l = 128.0f, mg_l = 128.0f, mb_l = 128.0f;
@@ -836,7 +874,7 @@ DEV void eval_views(const DParams& prm, WC& wc, const Frame& f, int n, vmask_t (
         const int last = max(n - 1, 0);  // an empty list never reaches this point; the clamps below stay inside the frames all the same
         const ClsFrame fr = cls_frame(min(row, last));
 #pragma unroll
-        for (int j = 0; j < 3; ++j) pend[j] = cls_issue(fr, cls_opaque(cc.cs[j]));
+        for (int j = 0; j < 3; ++j) pend[j] = cls_issue<NARROW>(pyr, fr, cls_opaque(cc.cs[j]));
     }
     if (has_x) cls_raw<FULL>(pe, xcs, fxr, fxg, fxb);
     const int rounds = (n + 3) >> 2;
@@ -849,7 +887,7 @@ DEV void eval_views(const DParams& prm, WC& wc, const Frame& f, int n, vmask_t (
         for (int j = 0; j < 3; ++j) {
             const unsigned cs = cls_opaque(cc.cs[j]);
             cls_raw<FULL>(pend[j], cs, cr[j], cg[j], cb[j]);
-            pend[j] = cls_issue(fn, cs);
+            pend[j] = cls_issue<NARROW>(pyr, fn, cs);
             s1r += cr[j]; s1g += cg[j]; s1b += cb[j];
         }
         MVS_ROW_STEP3(0xB1) MVS_ROW_STEP3(0x4E) MVS_ROW_STEP3(0x141) MVS_ROW_STEP3(0x140)
@@ -1095,7 +1133,7 @@ DEV float compute_incc(const DParams& prm, WC& wc, F4 coord, F4 normal, int img,
     get_paxes(prm, prm.views + ref, coord, normal, px, py);
     const int sz = min(prm.tau, n);
     wc.evals++;
-    const Frame f = make_frame(prm, coord, px, py, normal, img, wc.lane < sz);
+    const Frame f = make_frame<wc_narrow<WC>::value>(prm, coord, px, py, normal, img, wc.lane < sz);
     vmask_t okm[1];
     float incc_l;
     eval_views(prm, wc, f, sz, okm, incc_l);
@@ -1140,7 +1178,7 @@ DEV float set_inccs(const DParams& prm, WC& wc, F4 coord, F4 normal, int img, in
     F4 px, py;
     get_paxes(prm, prm.views + ref, coord, normal, px, py);
     wc.evals++;
-    const Frame f = make_frame(prm, coord, px, py, normal, img, wc.lane < n);
+    const Frame f = make_frame<wc_narrow<WC>::value>(prm, coord, px, py, normal, img, wc.lane < n);
     vmask_t okm[1];
     float incc_l;
     eval_views(prm, wc, f, n, okm, incc_l, nullptr, texs, tstride, ssd_out);
@@ -1385,7 +1423,7 @@ DEV void cost_func4(const DParams& prm, WC& wc, const RefineCtx& rc, int imgx, i
     const int sz = min(prm.tau, n);
     const int minimum = min(prm.minImageNum, sz);
     const int g = wc.lane >> 4, i = wc.lane & 15;
-    const Frame f = make_frame(prm, coord, px, py, normal, imgx, (four ? ((rows >> g) & 1u) != 0u : g < 1) && i < sz);
+    const Frame f = make_frame<wc_narrow<WC>::value>(prm, coord, px, py, normal, imgx, (four ? ((rows >> g) & 1u) != 0u : g < 1) && i < sz);
     float incc_l;
     fv[1] = fv[2] = fv[3] = 2.0;
     if (four) {
@@ -1520,7 +1558,7 @@ DEV void cost_func4_pair(const DParams& prm, WC& wc, const RefineCtx& rc, int im
     F4 coord, normal, px, py;
     decode(prm, rc, x0, x1, x2, coord, normal);
     get_paxes<true>(prm, prm.views + rc.ref, coord, normal, px, py);
-    const Frame f = make_frame(prm, coord, px, py, normal, imgx, (wc.lane & 7) < szl);
+    const Frame f = make_frame<wc_narrow<WC>::value>(prm, coord, px, py, normal, imgx, (wc.lane & 7) < szl);
     wc.evals += 8u;
     unsigned okm[2][4];
     float incc_l;
@@ -1835,7 +1873,7 @@ DEV void set_ref_image(const DParams& prm, WC& wc, float* texs, int tstride, Can
     else {
         F4 px, py;
         get_paxes(prm, prm.views + ref, c.coord, c.normal, px, py);
-        f = make_frame(prm, c.coord, px, py, c.normal, c.img, wc.lane < n);
+        f = make_frame<wc_narrow<WC>::value>(prm, c.coord, px, py, c.normal, c.img, wc.lane < n);
     }
     wc.evals++;
     WC_ADD(wc, 1)

@@ -41,6 +41,7 @@ RefineSel refine_sel(const mvs_engine* e) {
 DParams current_params(mvs_engine* e) {
     DParams p = e->prm;
     p.views = e->dviews.p;
+    p.pyr32 = e->pyr_narrow ? e->pyr.p : nullptr;
     p.pool = e->pool.p;
     p.pool_n = e->pool_n;
     p.total_cells = e->total_cells;
@@ -239,7 +240,7 @@ int mvs_engine_set_views(mvs_engine* e, int nviews, const mvs_view_desc* views) 
     HIPCHK(hipSetDevice(e->cfg.device));
     hipStream_t st = e->stream;
     Range rg("mvs:set_views (upload + pyramids)");
-    e->img_bufs.clear(); e->mask_bufs.clear();
+    e->mask_bufs.clear();
     e->have_views = false;
     const int maxLevel = e->cfg.level + 3;
     e->hviews.assign(nviews, DView{});
@@ -250,18 +251,35 @@ int mvs_engine_set_views(mvs_engine* e, int nviews, const mvs_view_desc* views) 
         max_bytes = std::max(max_bytes, (size_t)views[v].width * views[v].height * 3);
     }
     if (int r = e->tmp_bytes.ensure((int64_t)max_bytes)) return r;
+    // The pyramids: every level of every view at a fixed offset (a multiple of 256 bytes) of ONE block, view after view, level after level.
+    // A block below 4 GiB can be addressed by a 32-bit byte offset from its base (DView::img_off, the sweep's narrow samplers); their
+    // 24-bit multiply of a row number by a row pitch in bytes is exact while both stay below 2^24.
+    std::vector<uint64_t> level_off((size_t)nviews * maxLevel);
+    uint64_t pyr_bytes = 0;
+    bool narrow = true;
     for (int v = 0; v < nviews; ++v) {
         DView& vw = e->hviews[v];
         vw.W[0] = views[v].width; vw.H[0] = views[v].height;
         for (int l = 1; l < maxLevel; ++l) { vw.W[l] = vw.W[l - 1] / 2; vw.H[l] = vw.H[l - 1] / 2; }
+        for (int l = 0; l < maxLevel; ++l) {
+            level_off[(size_t)v * maxLevel + l] = pyr_bytes;
+            pyr_bytes += (std::max<uint64_t>((uint64_t)vw.W[l] * vw.H[l], 1) * 4 + 255) / 256 * 256;
+        }
+        if ((int64_t)vw.W[0] * 4 >= (1 << 24) || vw.H[0] >= (1 << 24)) narrow = false;
+    }
+    if (pyr_bytes >= (1ull << 32)) narrow = false;
+    if (int r = e->pyr.ensure((int64_t)pyr_bytes)) return r;
+    e->pyr_narrow = narrow;
+    for (int v = 0; v < nviews; ++v) {
+        DView& vw = e->hviews[v];
         setup_camera(e, vw, views[v].P);
         const size_t n0 = (size_t)vw.W[0] * vw.H[0];
         HIPCHK(hipMemcpyAsync(e->tmp_bytes.p, views[v].rgb, n0 * 3, hipMemcpyHostToDevice, st));
         for (int l = 0; l < maxLevel; ++l) {
-            e->img_bufs.emplace_back();
-            if (int r = e->img_bufs.back().ensure(std::max<int64_t>((int64_t)vw.W[l] * vw.H[l], 1))) return r;
-            uint32_t* buf = e->img_bufs.back().p;
+            const uint64_t off = level_off[(size_t)v * maxLevel + l];
+            uint32_t* buf = reinterpret_cast<uint32_t*>(e->pyr.p + off);
             vw.img[l] = buf;
+            vw.img_off[l] = (uint32_t)off;  // (cut short in a block of 4 GiB or more, where nothing reads it)
             if (l == 0) mvsk_rgb_to_rgba(e->tmp_bytes.p, buf, (int64_t)n0, st);
             else mvsk_pyr_down(vw.img[l - 1], vw.W[l - 1], vw.H[l - 1], buf, vw.W[l], vw.H[l], st);
         }
@@ -474,6 +492,12 @@ int mvs_engine_sweep_kernels(mvs_engine* e, int64_t out[2]) {
     return MVS_OK;
 }
 
+int mvs_engine_sampler_launches(mvs_engine* e, int64_t out[4]) {
+    if (!e || !out) return MVS_ERR_ARG;
+    for (int k = 0; k < 4; ++k) out[k] = e->sampler_launches[k];
+    return MVS_OK;
+}
+
 int mvs_engine_last_timing(mvs_engine* e, mvs_timing* t) {
     if (!e || !t) return MVS_ERR_ARG;
     *t = e->timing;
@@ -525,7 +549,8 @@ int mvs_engine_probe(mvs_engine* e, int op, int64_t n, const mvs_patch* in_rec, 
     }
     HIPCHK(hipMemsetAsync(e->tmp_i.p, 0, (size_t)(n + 1) * sizeof(int32_t), st));
     const DParams p = current_params(e);
-    mvsk_probe(p, op, n, e->tmp_rec_in.p, e->tmp_f_in.p, e->tmp_rec_out.p, e->tmp_f_out.p, e->tmp_i.p, rs, st);
+    const int probe_sampler = mvsk_probe(p, op, n, e->tmp_rec_in.p, e->tmp_f_in.p, e->tmp_rec_out.p, e->tmp_f_out.p, e->tmp_i.p, rs, st);
+    if (probe_sampler >= 0) e->sampler_launches[2 + probe_sampler] += 1;
     if (out_rec && (op == MVS_PROBE_PREPROCESS || op == MVS_PROBE_REFINE || op == MVS_PROBE_POSTPROCESS || op == MVS_PROBE_REFINE_X))
         HIPCHK(hipMemcpyAsync(out_rec, e->tmp_rec_out.p, (size_t)n * sizeof(mvs_patch), hipMemcpyDeviceToHost, st));
     if (out_f && (op == MVS_PROBE_NCC || op == MVS_PROBE_COST || op == MVS_PROBE_MATH || op == MVS_PROBE_REFINE_X))

@@ -141,7 +141,8 @@ struct mvs_engine {
     bool have_views = false;
     std::vector<DView> hviews;
     DevBuf<DView> dviews;
-    std::vector<DevBuf<uint32_t>> img_bufs;  // the pyramid levels (DView::img)
+    DevBuf<uint8_t> pyr;                     // the pyramid levels of all views in one block (DView::img / img_off)
+    bool pyr_narrow = false;                 // ... which 32-bit byte offsets can address (DParams::pyr32)
     std::vector<DevBuf<uint8_t>> mask_bufs;  // and masks (DView::mask) of the views
     int total_cells = 0;
     // pool
@@ -180,6 +181,7 @@ struct mvs_engine {
     int64_t sweep_pairs[6] = {0, 0, 0, 0, 0, 0};  // DCounters::pair, summed over the passes since the engine was created (mvs_engine_sweep_pairs)
     int64_t sweep_repeats[2] = {0, 0};            // DCounters::repeats, likewise (mvs_engine_sweep_repeats)
     int64_t sweep_kernels[2] = {0, 0};            // sweep launches by kernel: generic, full-window (mvs_engine_sweep_kernels)
+    int64_t sampler_launches[4] = {0, 0, 0, 0};   // sweep launches, then refine probes, by the form of their samplers: wide, narrow (mvs_engine_sampler_launches)
     int64_t retried_cells = 0;               // destination cells that went to the second tier since the engine was created
     int64_t pass_retried = 0;                // ... in the last pass
     SweepArgs sa{};

@@ -246,7 +246,7 @@ static int pass_impl(mvs_engine* e, int iter, int pass, mvs_counters* out) {
     HIPCHK(hipEventRecord(e->ev[1], st));
     Range rg_sweep(pass & 1 ? "mvs:sweep colour 1" : "mvs:sweep colour 0");
     const int sweep_kernel = mvsk_sweep(p, a, rs, st);
-    if (sweep_kernel >= 0) e->sweep_kernels[sweep_kernel] += 1;
+    if (sweep_kernel >= 0) { e->sweep_kernels[sweep_kernel & 1] += 1; e->sampler_launches[(sweep_kernel >> 1) & 1] += 1; }
     e->pass_retried = 0;
     if (want_vgrid(e)) {  // cells whose Optim::check outgrew the wave's LDS run again on the second tier (normally none)
         int32_t nretry = 0;

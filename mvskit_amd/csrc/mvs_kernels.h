@@ -27,7 +27,8 @@ void mvsk_fill_ncc(const DParams& prm, unsigned long long* evals, hipStream_t st
 struct RefineSel { int simplex; int max_evals; float xtol; };
 size_t mvsk_sweep_lds_bytes(const DParams& prm);
 // -> 1 if the launch went to the full-window instantiation (k_sweep_full: every class-lane slot holds a sample, as for the default 7x7 window,
-// and MVS_SWEEP_FULLWINDOW is not 0), 0 if to a generic kernel, -1 if there was nothing to launch
+// and MVS_SWEEP_FULLWINDOW is not 0), 0 if to a generic kernel, -1 if there was nothing to launch; + 2 if the kernel has the narrow
+// samplers (k_sweep_full_ofs: the pyramid block is below 4 GiB, DParams::pyr32, and MVS_SAMPLER_WIDE is not set)
 int mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hipStream_t st);
 void mvsk_sweep_retry(const DParams& prm, const SweepArgs& a, int nretry, const RefineSel& rs, hipStream_t st);
 void mvsk_job_work(const DParams& prm, const SweepArgs& a, int mode, int shift, int32_t* work, hipStream_t st);
@@ -58,7 +59,8 @@ void mvsk_gather_i32(const int32_t* src, const int32_t* idx, int32_t* out, int64
 void mvsk_scatter_i32(int32_t* dst, const int32_t* idx, const int32_t* val, int64_t n, hipStream_t st);
 void mvsk_groups_kill(const DParams& prm, const int* parent, const int* size, int threshold, uint8_t* kill, hipStream_t st);
 // op 6 needs rs.simplex (the engine checks it); op 2 follows rs
-void mvsk_probe(const DParams& prm, int op, int64_t n, const DPatch* in, const float* in_f, DPatch* out, float* out_f, int32_t* out_i, const RefineSel& rs,
+// -> for op 2 with the default refiner (k_probe_refine) 1 if the launch has the narrow samplers, 0 if the wide ones, as mvsk_sweep chooses; else -1
+int mvsk_probe(const DParams& prm, int op, int64_t n, const DPatch* in, const float* in_f, DPatch* out, float* out_f, int32_t* out_i, const RefineSel& rs,
                 hipStream_t st);
 // mvs_engine_export_ply (mvs_ply.hip): the alive pool slots of [i0, i1) -> idx (base = exclusive scan of the alive flags); the
 // colour (and ASCII line length) of each listed vertex; the vertex records into out at off[k] (ASCII) or 27 k (binary: off null)

@@ -837,6 +837,14 @@ __global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep_full(DParams prm,
     extern __shared__ float s_texs[];
     sweep_resident<false, WaveCtxFull>(prm, a, s_scratch, s_pend, s_texs, 0, 0.0f);
 }
+// k_sweep_full with the narrow samplers (WaveCtxFullOfs: 32-bit texel offsets from DParams::pyr32), chosen by mvsk_sweep where the pyramid
+// block is below 4 GiB; k_sweep_full itself, with a 64-bit address per lane, serves the larger ones
+__global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep_full_ofs(DParams prm, SweepArgs a) {
+    __shared__ int s_scratch[192];
+    __shared__ __attribute__((aligned(16))) int s_pend[MVS_PEND_INTS];  // a waiting candidate, the working block of a pair (mvs_device.cuh)
+    extern __shared__ float s_texs[];
+    sweep_resident<false, WaveCtxFullOfs>(prm, a, s_scratch, s_pend, s_texs, 0, 0.0f);
+}
 __global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep_simplex(DParams prm, SweepArgs a, int max_evals, float xtol) {
     __shared__ int s_scratch[192];
     __shared__ __attribute__((aligned(16))) int s_pend[MVS_PEND_INTS];  // a waiting candidate, the working block of a pair (mvs_device.cuh)
@@ -1146,7 +1154,7 @@ __global__ __launch_bounds__(64) void k_filter_exact(DParams prm, uint8_t* kill,
                 f.tlx = __shfl(fpre.tlx, src); f.tly = __shfl(fpre.tly, src);
                 f.dxx = __shfl(fpre.dxx, src); f.dxy = __shfl(fpre.dxy, src); f.dyx = __shfl(fpre.dyx, src); f.dyy = __shfl(fpre.dyy, src);
                 f.w = __shfl(fpre.w, src); f.ok = __shfl(fpre.ok, src);
-                f.img_lo = (unsigned)__shfl((int)fpre.img_lo, src); f.img_hi = (unsigned)__shfl((int)fpre.img_hi, src);
+                f.a_lo = (unsigned)__shfl((int)fpre.a_lo, src); f.a_hi = (unsigned)__shfl((int)fpre.a_hi, src);
                 if (!mine) { f.tlx = f.tly = f.dxx = f.dxy = f.dyx = f.dyy = 0.0f; f.ok = 0; }
             }
             WC_ADD(wc, 7)
@@ -1412,6 +1420,17 @@ __global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_probe_refine(DParams pr
     refine_patch(prm, wc, c, 0u, 0u, (uint32_t)i, 0u);
     store_cand(out + i, wc, c, 1, (int)i);
 }
+// ... with the narrow samplers (WaveCtxOfs), chosen by mvsk_probe as mvsk_sweep chooses k_sweep_full_ofs
+__global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_probe_refine_ofs(DParams prm, int64_t n, const DPatch* __restrict__ in, DPatch* __restrict__ out) {
+    const int64_t i = blockIdx.x;
+    if (i >= n) return;
+    WaveCtxOfs wc;
+    static_cast<WaveCtx&>(wc) = make_wave_ctx(prm);
+    Cand c;
+    load_cand(in + i, wc, c);
+    refine_patch(prm, wc, c, 0u, 0u, (uint32_t)i, 0u);
+    store_cand(out + i, wc, c, 1, (int)i);
+}
 // refinePatch with the CONVERGED refiner (probe ops 2 and 6): out_f[4 i ..] = the best vertex and its cost, out_i[i] = evaluations
 // (negative: the budget ran out and the record is the input)
 __global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_probe_refine_simplex(DParams prm, int64_t n, const DPatch* __restrict__ in, DPatch* __restrict__ out,
@@ -1507,6 +1526,12 @@ static bool sweep_full_window(const DParams& prm) {
     const char* p = getenv("MVS_SWEEP_FULLWINDOW");
     return cls_full_window(prm.wsz) && !(p && atoi(p) == 0);
 }
+// The narrow samplers (wc_narrow in mvs_device.cuh) where the pyramid block allows them.  A/B and test switch, read on every launch:
+// MVS_SAMPLER_WIDE=1 keeps the 64-bit per-lane addresses that a block of 4 GiB or more needs (the result does not depend on it)
+static bool sampler_narrow(const DParams& prm) {
+    const char* p = getenv("MVS_SAMPLER_WIDE");
+    return prm.pyr32 && !(p && atoi(p) != 0);
+}
 int mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hipStream_t st) {
     const int64_t nloc = a.job_hi - a.job_lo;
     if (nloc <= 0) return -1;
@@ -1526,7 +1551,11 @@ int mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hipS
     }
     const SweepArgs b = sweep_args_with_switches(a);
     if (rs.simplex) hipLaunchKernelGGL(k_sweep_simplex, dim3((unsigned)nblocks), dim3(64), lds, st, prm, b, rs.max_evals, rs.xtol);
-    else if (sweep_full_window(prm)) { hipLaunchKernelGGL(k_sweep_full, dim3((unsigned)nblocks), dim3(64), lds, st, prm, b); return 1; }
+    else if (sweep_full_window(prm)) {
+        if (sampler_narrow(prm)) { hipLaunchKernelGGL(k_sweep_full_ofs, dim3((unsigned)nblocks), dim3(64), lds, st, prm, b); return 3; }
+        hipLaunchKernelGGL(k_sweep_full, dim3((unsigned)nblocks), dim3(64), lds, st, prm, b);
+        return 1;
+    }
     else hipLaunchKernelGGL(k_sweep, dim3((unsigned)nblocks), dim3(64), lds, st, prm, b);
     return 0;
 }
@@ -1644,12 +1673,17 @@ void mvsk_scatter_i32(int32_t* dst, const int32_t* idx, const int32_t* val, int6
 void mvsk_groups_kill(const DParams& prm, const int* parent, const int* size, int threshold, uint8_t* kill, hipStream_t st) {
     if (prm.pool_n > 0) hipLaunchKernelGGL(k_groups_kill, dim3(nblk(prm.pool_n, 256)), dim3(256), 0, st, prm, parent, size, threshold, kill);
 }
-void mvsk_probe(const DParams& prm, int op, int64_t n, const DPatch* in, const float* in_f, DPatch* out, float* out_f, int32_t* out_i, const RefineSel& rs,
+int mvsk_probe(const DParams& prm, int op, int64_t n, const DPatch* in, const float* in_f, DPatch* out, float* out_f, int32_t* out_i, const RefineSel& rs,
                 hipStream_t st) {
     if (n > 0 && (op == 2 || op == 6) && rs.simplex) {
         hipLaunchKernelGGL(k_probe_refine_simplex, dim3((unsigned)n), dim3(64), MVS_FRAME_LDS_BYTES, st, prm, n, in, out, out_f, out_i, rs.max_evals, rs.xtol);
-        return;
+        return -1;
     }
-    if (n > 0 && op == 2) { hipLaunchKernelGGL(k_probe_refine, dim3((unsigned)n), dim3(64), MVS_FRAME_LDS_BYTES, st, prm, n, in, out); return; }
+    if (n > 0 && op == 2) {
+        if (sampler_narrow(prm)) { hipLaunchKernelGGL(k_probe_refine_ofs, dim3((unsigned)n), dim3(64), MVS_FRAME_LDS_BYTES, st, prm, n, in, out); return 1; }
+        hipLaunchKernelGGL(k_probe_refine, dim3((unsigned)n), dim3(64), MVS_FRAME_LDS_BYTES, st, prm, n, in, out);
+        return 0;
+    }
     if (n > 0) hipLaunchKernelGGL(k_probe, dim3((unsigned)n), dim3(64), mvsk_sweep_lds_bytes(prm), st, prm, op, n, in, in_f, out, out_f, out_i);
+    return -1;
 }

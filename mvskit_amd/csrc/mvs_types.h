@@ -54,12 +54,13 @@ struct DView {
     float xaxis[3], yaxis[3], zaxis[3];
     float ipscale;
     int32_t W[MVS_MAXLEV], H[MVS_MAXLEV];
-    const uint32_t* img[MVS_MAXLEV];
+    const uint32_t* img[MVS_MAXLEV];  // into the one block that holds every level of every view
     const uint8_t* mask;  // level m_level, or null
     int32_t gw, gh;
     int32_t cell_base;  // offset of this view's cells in the concatenated per-cell arrays
-    int32_t pad;
+    uint32_t img_off[MVS_MAXLEV];  // img[l] as a byte offset from the block's base; meaningful where the block is below 4 GiB (DParams::pyr32)
 };
+static_assert(sizeof(DView) % 8 == 0, "DView is an array element with 8-byte members");
 
 // Kernel-constant parameters (Option + PmMvps thresholds, pmmvps.cpp:18-68).
 struct DParams {
@@ -92,6 +93,11 @@ struct DParams {
     const float4* geo;
     const uint8_t* geo_ref;
     const unsigned long long* dpgrid;  // (sortable depth << 32 | id), ~0ull = m_MAXDEPTH
+    // The RGBA8 pyramids of all views lie in one allocation, level l of view v at byte offset views[v].img_off[l].  Its base, if the
+    // block is below 4 GiB -- the launchers may then pick samplers that address it by 32-bit byte offsets -- else null.  (The LAST member: in
+    // front of `views` it moved every later argument and the sweep's step loops reloaded 83 / 104 / 91 spilled scalars instead of 15 / 41 / 24,
+    // profiles/r23_codeobj.txt.)
+    const uint8_t* pyr32;
 };
 
 #ifndef MVS_COUNTER_SLOTS

@@ -32,6 +32,7 @@ EXPORTS = [
     "mvs_default_seed_points", "mvs_engine_seed_points", "mvs_engine_seed_points_hypotheses", "mvs_engine_depth_ranges",
     "mvs_default_maps_config", "mvs_engine_render_maps", "mvs_engine_fused_points",
     "mvs_engine_tsdf", "mvs_engine_extract_mesh", "mvs_engine_mesh", "mvs_engine_sweep_pairs", "mvs_engine_sweep_repeats", "mvs_engine_sweep_kernels",
+    "mvs_engine_sampler_launches",
     "mvs_default_mesh_colouring", "mvs_engine_mesh_normals", "mvs_engine_mesh_colours",
     "mvs_default_mesh_pruning", "mvs_default_mesh_smoothing", "mvs_engine_mesh_components", "mvs_engine_mesh_prune", "mvs_engine_mesh_smooth",
     "mvs_default_mesh_decimation", "mvs_engine_mesh_decimate",
@@ -233,6 +234,8 @@ def load_library(cap32: bool = False, cap: int = 0):
         L.mvs_engine_sweep_repeats.argtypes = [vp, C.POINTER(C.c_int64)]
     if hasattr(L, "mvs_engine_sweep_kernels"):
         L.mvs_engine_sweep_kernels.argtypes = [vp, C.POINTER(C.c_int64)]
+    if hasattr(L, "mvs_engine_sampler_launches"):
+        L.mvs_engine_sampler_launches.argtypes = [vp, C.POINTER(C.c_int64)]
     if hasattr(L, "mvs_engine_tsdf"):
         L.mvs_engine_tsdf.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(Volume), vp, vp]
         L.mvs_engine_extract_mesh.argtypes = [vp, C.POINTER(Volume), vp, vp, C.c_int64, vp, C.c_int64, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -794,6 +797,14 @@ class Engine:
         out = (C.c_int64 * 2)()
         self._check(self.L.mvs_engine_sweep_kernels(self.h, out))
         return dict(zip(self.SWEEP_KERNEL_KEYS, (int(x) for x in out)))
+
+    #: mvs_engine_sampler_launches: sweep launches and refine probes by the form of their texture samplers, since the engine was created
+    SAMPLER_LAUNCH_KEYS = ("sweep_wide", "sweep_narrow", "refine_wide", "refine_narrow")
+
+    def sampler_launches(self):
+        out = (C.c_int64 * 4)()
+        self._check(self.L.mvs_engine_sampler_launches(self.h, out))
+        return dict(zip(self.SAMPLER_LAUNCH_KEYS, (int(x) for x in out)))
 
     def depth_normal_map(self, view, kind):
         gw, gh = self.grid_dims(view)
