@@ -435,6 +435,7 @@ __host__ __device__ inline bool cls_full_window(int wsz) {
 }
 // Per-wave working state.
 struct WaveCtx {
+    static constexpr bool full_window = false, narrow = false;  // the generic window code and the wide samplers (WaveCtxT below)
     int lane;
     ClsConst cc;
     unsigned evals, view_evals;
@@ -443,23 +444,15 @@ struct WaveCtx {
     unsigned long long st_t;
 #endif
 };
-// The same state in a launch whose window is full (cls_full_window): the functions that sample are templates on the context's type and
-// leave out the slot-mask arithmetic for this one; everything else takes it as a WaveCtx.
-struct WaveCtxFull : WaveCtx {};
-template <class WC> struct wc_full_window { static constexpr bool value = false; };
-template <> struct wc_full_window<WaveCtxFull> { static constexpr bool value = true; };
-// How a launch addresses the texels it samples is a property of the context's type as well.  WIDE (WaveCtx, WaveCtxFull): a 64-bit address
-// per lane, for a pyramid block of any size.  NARROW (WaveCtxOfs, WaveCtxFullOfs): the block's base, one value for the whole launch
+// The same state in a launch whose window is full (cls_full_window) has full_window = true: the functions that sample are templates on the
+// context's type and leave out the slot-mask arithmetic for it; everything else takes it as a WaveCtx.
+// How a launch addresses the texels it samples is a property of the context's type as well.  WIDE (narrow = false, plain WaveCtx among
+// them): a 64-bit address per lane, for a pyramid block of any size.  NARROW (narrow = true): the block's base, one value for the whole launch
 // (DParams::pyr32, scalar registers), plus a 32-bit byte offset per lane -- the address arithmetic of a sample slot is then 32-bit
 // (v_mad_u32_u24, v_lshl_add_u32, v_add_u32 in place of v_mad_u64_u32 and three v_lshl_add_u64) and the loads take the form
 // global_load v, v_off, s[base].  The texels read are the same, so the results are.  The launcher picks a narrow instantiation where
 // the block is below 4 GiB (DParams::pyr32 is set).  A Frame is made (make_frame) and consumed by functions of ONE context type.
-struct WaveCtxOfs : WaveCtx {};
-struct WaveCtxFullOfs : WaveCtx {};
-template <> struct wc_full_window<WaveCtxFullOfs> { static constexpr bool value = true; };
-template <class WC> struct wc_narrow { static constexpr bool value = false; };
-template <> struct wc_narrow<WaveCtxOfs> { static constexpr bool value = true; };
-template <> struct wc_narrow<WaveCtxFullOfs> { static constexpr bool value = true; };
+template <bool FULL, bool NARROW> struct WaveCtxT : WaveCtx { static constexpr bool full_window = FULL, narrow = NARROW; };
 #ifdef MVS_STAGE_TIMING
 #define WC_T0(wc) { (wc).st_t = (unsigned long long)__builtin_amdgcn_s_memtime(); }
 #define WC_ADD(wc, k) { const unsigned long long t1_ = (unsigned long long)__builtin_amdgcn_s_memtime(); (wc).st_acc[k] += t1_ - (wc).st_t; (wc).st_t = t1_; }
@@ -542,7 +535,7 @@ DEV ClsFrame cls_frame_of(const Frame& f) {  // a frame lane's own frame (the ex
     fr.a_lo = f.a_lo; fr.a_hi = f.a_hi;
     return fr;
 }
-// NARROW (wc_narrow): pyr = DParams::pyr32, the launch's one base; the byte offsets of the two texel rows are formed in 32-bit unsigned
+// NARROW (WaveCtxT::narrow): pyr = DParams::pyr32, the launch's one base; the byte offsets of the two texel rows are formed in 32-bit unsigned
 // arithmetic -- row number and pitch are below 2^24 and the block below 2^32 (mvs_engine_set_views), so the 24-bit multiply and the
 // sums are exact -- and the address is the base plus the zero-extended offset, which the compiler turns into scalar-base loads.
 template <bool NARROW> DEV const uint8_t* sampler_base(const DParams& prm) { return NARROW ? prm.pyr32 : nullptr; }
@@ -602,7 +595,7 @@ DEV float bperm_f(int addr, float x) { return __int_as_float(__builtin_amdgcn_ds
 // reference view peeled off, and the loads of view k + 1 issued as the slots of view k are consumed.
 template <class WC>
 DEV void eval_steps4(const DParams& prm, WC& wc, const ClsConst& cc, const Frame& f, int n, unsigned (&okm)[4], float& incc_l) {
-    constexpr bool FULL = wc_full_window<WC>::value, NARROW = wc_narrow<WC>::value;
+    constexpr bool FULL = WC::full_window, NARROW = WC::narrow;
     const uint8_t* const pyr = sampler_base<NARROW>(prm);
     // (the extra's test stays a run-time one here even for a full window: known true, this loop's scalar reloads go from 17 to 20 -- DESIGN.md section 5)
     const bool has_x = cc.nx > 0;
@@ -689,7 +682,7 @@ DEV void eval_steps4(const DParams& prm, WC& wc, const ClsConst& cc, const Frame
 // and, in the caller, the robust INCCs.  okm[s][g]: the views of (candidate s, proposal g) that sample; returns the same bits by frame lane.
 template <class WC>
 DEV unsigned long long eval_steps4_pair(const DParams& prm, WC& wc, const ClsConst& cc, const Frame& f, int n0, int n1, unsigned (&okm)[2][4], float& incc_l) {
-    constexpr bool FULL = wc_full_window<WC>::value, NARROW = wc_narrow<WC>::value;
+    constexpr bool FULL = WC::full_window, NARROW = WC::narrow;
     const uint8_t* const pyr = sampler_base<NARROW>(prm);
     const bool has_x = FULL || cc.nx > 0;
     frames_publish(wc, f, 64);
@@ -850,7 +843,7 @@ DEV void eval_views(const DParams& prm, WC& wc, const Frame& f, int n, vmask_t (
     const int gk0 = wc.lane / MVS_GRAM_CH;                       // this lane's k within an MFMA
     const float* const grow = texs + (wc.lane & (MVS_GRAM_CH - 1)) * gtp;  // this lane's view of the chunk in LDS
 #endif
-    constexpr bool FULL = wc_full_window<WC>::value, NARROW = wc_narrow<WC>::value;
+    constexpr bool FULL = WC::full_window, NARROW = WC::narrow;
     const uint8_t* const pyr = sampler_base<NARROW>(prm);
     const ClsConst& cc = wc.cc;
     const bool has_x = FULL || cc.nx > 0;
@@ -1133,7 +1126,7 @@ DEV float compute_incc(const DParams& prm, WC& wc, F4 coord, F4 normal, int img,
     get_paxes(prm, prm.views + ref, coord, normal, px, py);
     const int sz = min(prm.tau, n);
     wc.evals++;
-    const Frame f = make_frame<wc_narrow<WC>::value>(prm, coord, px, py, normal, img, wc.lane < sz);
+    const Frame f = make_frame<WC::narrow>(prm, coord, px, py, normal, img, wc.lane < sz);
     vmask_t okm[1];
     float incc_l;
     eval_views(prm, wc, f, sz, okm, incc_l);
@@ -1178,7 +1171,7 @@ DEV float set_inccs(const DParams& prm, WC& wc, F4 coord, F4 normal, int img, in
     F4 px, py;
     get_paxes(prm, prm.views + ref, coord, normal, px, py);
     wc.evals++;
-    const Frame f = make_frame<wc_narrow<WC>::value>(prm, coord, px, py, normal, img, wc.lane < n);
+    const Frame f = make_frame<WC::narrow>(prm, coord, px, py, normal, img, wc.lane < n);
     vmask_t okm[1];
     float incc_l;
     eval_views(prm, wc, f, n, okm, incc_l, nullptr, texs, tstride, ssd_out);
@@ -1423,7 +1416,7 @@ DEV void cost_func4(const DParams& prm, WC& wc, const RefineCtx& rc, int imgx, i
     const int sz = min(prm.tau, n);
     const int minimum = min(prm.minImageNum, sz);
     const int g = wc.lane >> 4, i = wc.lane & 15;
-    const Frame f = make_frame<wc_narrow<WC>::value>(prm, coord, px, py, normal, imgx, (four ? ((rows >> g) & 1u) != 0u : g < 1) && i < sz);
+    const Frame f = make_frame<WC::narrow>(prm, coord, px, py, normal, imgx, (four ? ((rows >> g) & 1u) != 0u : g < 1) && i < sz);
     float incc_l;
     fv[1] = fv[2] = fv[3] = 2.0;
     if (four) {
@@ -1558,7 +1551,7 @@ DEV void cost_func4_pair(const DParams& prm, WC& wc, const RefineCtx& rc, int im
     F4 coord, normal, px, py;
     decode(prm, rc, x0, x1, x2, coord, normal);
     get_paxes<true>(prm, prm.views + rc.ref, coord, normal, px, py);
-    const Frame f = make_frame<wc_narrow<WC>::value>(prm, coord, px, py, normal, imgx, (wc.lane & 7) < szl);
+    const Frame f = make_frame<WC::narrow>(prm, coord, px, py, normal, imgx, (wc.lane & 7) < szl);
     wc.evals += 8u;
     unsigned okm[2][4];
     float incc_l;
@@ -1873,7 +1866,7 @@ DEV void set_ref_image(const DParams& prm, WC& wc, float* texs, int tstride, Can
     else {
         F4 px, py;
         get_paxes(prm, prm.views + ref, c.coord, c.normal, px, py);
-        f = make_frame<wc_narrow<WC>::value>(prm, c.coord, px, py, c.normal, c.img, wc.lane < n);
+        f = make_frame<WC::narrow>(prm, c.coord, px, py, c.normal, c.img, wc.lane < n);
     }
     wc.evals++;
     WC_ADD(wc, 1)

@@ -549,8 +549,8 @@ int mvs_engine_probe(mvs_engine* e, int op, int64_t n, const mvs_patch* in_rec, 
     }
     HIPCHK(hipMemsetAsync(e->tmp_i.p, 0, (size_t)(n + 1) * sizeof(int32_t), st));
     const DParams p = current_params(e);
-    const int probe_sampler = mvsk_probe(p, op, n, e->tmp_rec_in.p, e->tmp_f_in.p, e->tmp_rec_out.p, e->tmp_f_out.p, e->tmp_i.p, rs, st);
-    if (probe_sampler >= 0) e->sampler_launches[2 + probe_sampler] += 1;
+    const KernelVariant probe_kernel = mvsk_probe(p, op, n, e->tmp_rec_in.p, e->tmp_f_in.p, e->tmp_rec_out.p, e->tmp_f_out.p, e->tmp_i.p, rs, st);
+    if (probe_kernel.launched) e->sampler_launches[probe_kernel.narrow ? 3 : 2] += 1;
     if (out_rec && (op == MVS_PROBE_PREPROCESS || op == MVS_PROBE_REFINE || op == MVS_PROBE_POSTPROCESS || op == MVS_PROBE_REFINE_X))
         HIPCHK(hipMemcpyAsync(out_rec, e->tmp_rec_out.p, (size_t)n * sizeof(mvs_patch), hipMemcpyDeviceToHost, st));
     if (out_f && (op == MVS_PROBE_NCC || op == MVS_PROBE_COST || op == MVS_PROBE_MATH || op == MVS_PROBE_REFINE_X))

@@ -245,8 +245,8 @@ static int pass_impl(mvs_engine* e, int iter, int pass, mvs_counters* out) {
     mvsk_job_list(p, a, e->job_cnt.p, e->job_base_scan.p, reinterpret_cast<int32_t*>(e->scan_tmp.p), e->job_list.p, list_bounds, st);
     HIPCHK(hipEventRecord(e->ev[1], st));
     Range rg_sweep(pass & 1 ? "mvs:sweep colour 1" : "mvs:sweep colour 0");
-    const int sweep_kernel = mvsk_sweep(p, a, rs, st);
-    if (sweep_kernel >= 0) { e->sweep_kernels[sweep_kernel & 1] += 1; e->sampler_launches[(sweep_kernel >> 1) & 1] += 1; }
+    const KernelVariant sweep_kernel = mvsk_sweep(p, a, rs, st);
+    if (sweep_kernel.launched) { e->sweep_kernels[sweep_kernel.full_window ? 1 : 0] += 1; e->sampler_launches[sweep_kernel.narrow ? 1 : 0] += 1; }
     e->pass_retried = 0;
     if (want_vgrid(e)) {  // cells whose Optim::check outgrew the wave's LDS run again on the second tier (normally none)
         int32_t nretry = 0;

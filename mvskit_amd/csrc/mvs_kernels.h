@@ -1,16 +1,20 @@
-// mvs_kernels.h -- launchers of the HIP kernels (internal).
+// mvs_kernels.h -- launchers of the HIP kernels (internal), grouped by the unit that defines them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "mvs_types.h"
 
+// mvs_image.hip: texels, pyramids and masks; the exclusive scan (out has n + 1 slots, tmp at least n / 512 + 64); gather / scatter of int32
 void mvsk_rgb_to_rgba(const uint8_t* rgb, uint32_t* out, int64_t n, hipStream_t st);
 void mvsk_rgba_to_rgb(const uint32_t* in, uint8_t* rgb, int64_t n, hipStream_t st);
 void mvsk_pyr_down(const uint32_t* src, int pw, int ph, uint32_t* dst, int w, int h, hipStream_t st);
 void mvsk_mask_down(const uint8_t* src, int pw, int ph, uint8_t* dst, int w, int h, hipStream_t st);
 void mvsk_mask_binarise(uint8_t* m, int64_t n, hipStream_t st);
 void mvsk_exclusive_scan(const int32_t* in, int32_t* out, int64_t n, int32_t* tmp, hipStream_t st);
-void mvsk_index_count(const DParams& prm, int32_t* cnt, int32_t* vcnt, unsigned long long* total, hipStream_t st);
 void mvsk_exclusive_scan_off(const int32_t* in, csr_off_t* out, int64_t n, csr_off_t* tmp, hipStream_t st);
+void mvsk_gather_i32(const int32_t* src, const int32_t* idx, int32_t* out, int64_t n, hipStream_t st);
+void mvsk_scatter_i32(int32_t* dst, const int32_t* idx, const int32_t* val, int64_t n, hipStream_t st);
+// mvs_index.hip: the cell index and the per-cell maps of the pool
+void mvsk_index_count(const DParams& prm, int32_t* cnt, int32_t* vcnt, unsigned long long* total, hipStream_t st);
 void mvsk_index_fill(const DParams& prm, int vgrid, const csr_off_t* start, int32_t* cursor, unsigned long long* ids, hipStream_t st);
 void mvsk_index_fill_direct(const DParams& prm, int vgrid, const csr_off_t* start, int32_t* cursor, int32_t* id32, hipStream_t st);
 void mvsk_index_sort_trim(const DParams& prm, const csr_off_t* start, unsigned long long* ids, int do_trim, unsigned long long* trimmed, hipStream_t st);
@@ -21,15 +25,20 @@ void mvsk_depth_maps(const DParams& prm, unsigned long long* dp, const uint32_t*
 void mvsk_depth_mark_dirty(const DParams& prm, const uint8_t* kill, unsigned long long* dp, uint32_t* dirty, hipStream_t st);
 void mvsk_best_ncc_map(const DParams& prm, int view, unsigned long long* best, hipStream_t st);
 void mvsk_map_extract(const DParams& prm, int view, int kind, const unsigned long long* sel, float* depth, float* normal, int32_t* ids, int ncells, hipStream_t st);
-void mvsk_fill_ncc(const DParams& prm, unsigned long long* evals, hipStream_t st);
+// mvs_sweep.cuh (in mvs_patch.hip): the job lists, the sweep and its retry tier, the commit of a pass
 // the refiner of a sweep / refine probe (mvs_engine_set_refiner): simplex = 0 is the halving search of the default kernels,
 // simplex = 1 the CONVERGED refiner (k_sweep_simplex, k_sweep_retry_simplex, k_probe_refine_simplex) with these two arguments
 struct RefineSel { int simplex; int max_evals; float xtol; };
+// The variant of a sweep or refine-probe kernel.  full_window: the instantiation for a window in which every class-lane slot holds a
+// sample (cls_full_window: the default 7x7); narrow: the samplers that take 32-bit texel offsets from DParams::pyr32 (a pyramid block
+// below 4 GiB); pair: consecutive trials of a cell are refined two at a time.  mvsk_kernel_variant: what a launch on prm may use, with the
+// switches MVS_SWEEP_FULLWINDOW, MVS_SAMPLER_WIDE and MVS_SWEEP_PAIR applied (launched = false).  mvsk_sweep and mvsk_probe return what
+// they used: launched = false where mvsk_sweep had nothing to launch and where mvsk_probe launched anything but the refine probe of the
+// default refiner (k_probe_refine, k_probe_refine_ofs) -- the engine counts the launched ones by full_window and narrow.
+struct KernelVariant { bool launched, full_window, narrow, pair; };
+KernelVariant mvsk_kernel_variant(const DParams& prm);
 size_t mvsk_sweep_lds_bytes(const DParams& prm);
-// -> 1 if the launch went to the full-window instantiation (k_sweep_full: every class-lane slot holds a sample, as for the default 7x7 window,
-// and MVS_SWEEP_FULLWINDOW is not 0), 0 if to a generic kernel, -1 if there was nothing to launch; + 2 if the kernel has the narrow
-// samplers (k_sweep_full_ofs: the pyramid block is below 4 GiB, DParams::pyr32, and MVS_SAMPLER_WIDE is not set)
-int mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hipStream_t st);
+KernelVariant mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hipStream_t st);
 void mvsk_sweep_retry(const DParams& prm, const SweepArgs& a, int nretry, const RefineSel& rs, hipStream_t st);
 void mvsk_job_work(const DParams& prm, const SweepArgs& a, int mode, int shift, int32_t* work, hipStream_t st);
 // The sweep's job lists: clears job_nstage[0, njobs) and lists the jobs of [job_lo, job_hi) that run a trial, per queue.  flags and scan
@@ -40,6 +49,8 @@ void mvsk_job_list(const DParams& prm, const SweepArgs& a, int32_t* flags, int32
 void mvsk_job_cuts(const int32_t* scan, int64_t njobs, int n, int32_t* cuts, hipStream_t st);
 void mvsk_commit_count(const SweepArgs& a, int32_t* cnt, hipStream_t st);
 void mvsk_commit_copy(const SweepArgs& a, const int32_t* base, DPatch* dst, int64_t dst_cap, int32_t* per_view, int keep_key, hipStream_t st);
+// mvs_filter.cuh (in mvs_patch.hip): pool upkeep (the scores of patches that come without one among it) and Filter::run
+void mvsk_fill_ncc(const DParams& prm, unsigned long long* evals, hipStream_t st);
 void mvsk_kill_count(const uint8_t* kill, int64_t n, int32_t* cnt, hipStream_t st);
 void mvsk_kill_export(const uint8_t* kill, int64_t n, const int32_t* base, int32_t* ids, int64_t cap, hipStream_t st);
 void mvsk_apply_kill_flags(DPatch* pool, uint8_t* kill, int64_t n, hipStream_t st);
@@ -55,13 +66,10 @@ void mvsk_filter_neighbor(const DParams& prm, uint8_t* kill, int32_t* retry, int
 void mvsk_filter_neighbor_retry(const DParams& prm, uint8_t* kill, const int32_t* todo, int32_t ntodo, int32_t* overflow, unsigned long long* stats, hipStream_t st);
 void mvsk_groups(const DParams& prm, int* parent, int* size, int threshold, uint8_t* kill, hipStream_t st);
 void mvsk_groups_literal_edges(const DParams& prm, int* parent, int* size, int* edges2, int* nedges, int cap, hipStream_t st);
-void mvsk_gather_i32(const int32_t* src, const int32_t* idx, int32_t* out, int64_t n, hipStream_t st);
-void mvsk_scatter_i32(int32_t* dst, const int32_t* idx, const int32_t* val, int64_t n, hipStream_t st);
 void mvsk_groups_kill(const DParams& prm, const int* parent, const int* size, int threshold, uint8_t* kill, hipStream_t st);
-// op 6 needs rs.simplex (the engine checks it); op 2 follows rs
-// -> for op 2 with the default refiner (k_probe_refine) 1 if the launch has the narrow samplers, 0 if the wide ones, as mvsk_sweep chooses; else -1
-int mvsk_probe(const DParams& prm, int op, int64_t n, const DPatch* in, const float* in_f, DPatch* out, float* out_f, int32_t* out_i, const RefineSel& rs,
-                hipStream_t st);
+// mvs_probe.cuh (in mvs_patch.hip): op 6 needs rs.simplex (the engine checks it); op 2 follows rs
+KernelVariant mvsk_probe(const DParams& prm, int op, int64_t n, const DPatch* in, const float* in_f, DPatch* out, float* out_f, int32_t* out_i, const RefineSel& rs,
+                         hipStream_t st);
 // mvs_engine_export_ply (mvs_ply.hip): the alive pool slots of [i0, i1) -> idx (base = exclusive scan of the alive flags); the
 // colour (and ASCII line length) of each listed vertex; the vertex records into out at off[k] (ASCII) or 27 k (binary: off null)
 void mvsk_ply_select(const DPatch* pool, const int32_t* base, int64_t i0, int64_t i1, int32_t* idx, hipStream_t st);
@@ -84,7 +92,7 @@ void mvsk_seed_emit(const SeedCam* cams, int nviews, int level, float thr, float
 // in mvs_types.h is what their launches share).  SeedRandomArgs: one view's launch by value -- the call's parameters, the
 // view and its depth range.
 struct SeedRandomArgs { SeedChainArgs chain; uint32_t seed; float max_tilt; int32_t view; float dmin, dmax; };
-size_t mvsk_texs_lds_bytes(const DParams& prm);  // mvs_kernels.hip: the dynamic LDS of a wave that runs postProcess without Optim::check
+size_t mvsk_texs_lds_bytes(const DParams& prm);  // mvs_filter.cuh: the dynamic LDS of a wave that runs postProcess without Optim::check
 // the K hypotheses of cells[i] (cells of the view's grid) as records at out[i * K ..]
 void mvsk_seed_random_hypotheses(const DParams& prm, const SeedRandomArgs& a, int64_t ncells, const int32_t* cells, DPatch* out, hipStream_t st);
 // one wave per cell of the view: the patch of cell c, if it gives one, at stage[c] with keep[c] = 1 (keep zero before the launch)

@@ -12,16 +12,11 @@
 // validity or agreement is written so that a NaN fails it.  Stores are plain vector stores.
 #include <hip/hip_runtime.h>
 
-#include "mvs_device.cuh"
+#include "mvs_common.cuh"
 #include "mvs_kernels.h"
 
 using namespace mvsdev;
 
-// the key of k_best_ncc_map / k_depth_maps (a copy of sortable_f32 in mvs_kernels.hip: that file's machine code stays what it was)
-DEV uint32_t maps_sortable_f32(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 DEV bool maps_finite_nonzero(float a) { return fabsf(a) > 0.0f && fabsf(a) < __int_as_float(0x7f800000); }
 DEV float maps_qnan() { return __int_as_float(0x7fc00000); }
 
@@ -37,7 +32,7 @@ __global__ __launch_bounds__(256) void k_maps_select(DParams prm, unsigned long 
     int ix, iy;
     cell_of(prm, vw, ld4(p->coord), ix, iy);
     if (ix < 0 || vw->gw <= ix || iy < 0 || vw->gh <= iy) return;
-    const unsigned long long key = ((unsigned long long)maps_sortable_f32(p->ncc) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)id);
+    const unsigned long long key = ((unsigned long long)sortable_f32(p->ncc) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)id);
     atomicMax(&sel[vw->cell_base + iy * vw->gw + ix], key);
 }
 
@@ -177,27 +172,26 @@ __global__ __launch_bounds__(256) void k_maps_gather(DParams prm, int view, cons
     out[2 * k + 1] = hi;
 }
 
-static inline unsigned maps_nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 // sel[0, total_cells) must be zero
 void mvsk_maps_select(const DParams& prm, unsigned long long* sel, hipStream_t st) {
-    if (prm.pool_n > 0) hipLaunchKernelGGL(k_maps_select, dim3(maps_nblk(prm.pool_n)), dim3(256), 0, st, prm, sel);
+    if (prm.pool_n > 0) hipLaunchKernelGGL(k_maps_select, dim3(nblk(prm.pool_n, 256)), dim3(256), 0, st, prm, sel);
 }
 void mvsk_maps_render(const DParams& prm, int view, int W, int H, int source, const unsigned long long* sel, int32_t* ids, float* pts, hipStream_t st) {
     hipLaunchKernelGGL(k_maps_render, dim3((unsigned)((W + 31) / 32), (unsigned)((H + 7) / 8)), dim3(256), 0, st, prm, view, source, sel, ids, pts);
 }
 void mvsk_maps_agree(const DParams& prm, const MapsArgs& a, int view, int64_t npix, const int32_t* ids, const float* pts, unsigned long long* agree,
                      float* depth, float* normal, float* conf, hipStream_t st) {
-    hipLaunchKernelGGL(k_maps_agree, dim3(maps_nblk(npix)), dim3(256), 0, st, prm, a, view, ids, pts, agree, depth, normal, conf);
+    hipLaunchKernelGGL(k_maps_agree, dim3(nblk(npix, 256)), dim3(256), 0, st, prm, a, view, ids, pts, agree, depth, normal, conf);
 }
 void mvsk_maps_flag(int64_t npix, int view, const int32_t* ids, const unsigned long long* agree, int min_consistent, int dedupe, int32_t* flag,
                     uint8_t* flag8, hipStream_t st) {
-    hipLaunchKernelGGL(k_maps_flag, dim3(maps_nblk(npix)), dim3(256), 0, st, npix, view, ids, agree, min_consistent, dedupe, flag, flag8);
+    hipLaunchKernelGGL(k_maps_flag, dim3(nblk(npix, 256)), dim3(256), 0, st, npix, view, ids, agree, min_consistent, dedupe, flag, flag8);
 }
 void mvsk_maps_expand(int64_t npix, const uint8_t* flag8, int32_t* flag, hipStream_t st) {
-    hipLaunchKernelGGL(k_maps_expand, dim3(maps_nblk(npix)), dim3(256), 0, st, npix, flag8, flag);
+    hipLaunchKernelGGL(k_maps_expand, dim3(nblk(npix, 256)), dim3(256), 0, st, npix, flag8, flag);
 }
 void mvsk_maps_gather(const DParams& prm, int view, int64_t npix, const int32_t* ids, const float* pts, const int32_t* flag, const int32_t* base,
                       void* out, int64_t cap, hipStream_t st) {
-    hipLaunchKernelGGL(k_maps_gather, dim3(maps_nblk(npix)), dim3(256), 0, st, prm, view, ids, pts, flag, base, reinterpret_cast<uint4*>(out), cap);
+    hipLaunchKernelGGL(k_maps_gather, dim3(nblk(npix, 256)), dim3(256), 0, st, prm, view, ids, pts, flag, base, reinterpret_cast<uint4*>(out), cap);
 }

@@ -12,7 +12,7 @@
 // left-to-right fmaf chains; every deciding comparison is written so that a NaN fails it.  Stores are plain vector stores.
 #include <hip/hip_runtime.h>
 
-#include "mvs_device.cuh"
+#include "mvs_common.cuh"
 #include "mvs_kernels.h"
 
 using namespace mvsdev;
@@ -226,31 +226,30 @@ __global__ __launch_bounds__(256) void k_mesh_tris(MeshVol vol, int64_t npoints,
     }
 }
 
-static inline unsigned mesh_nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 void mvsk_mesh_tsdf(const DParams& prm, const MapsArgs& a, const MeshVol& vol, const int32_t* ids, const uint8_t* usable, float* tsdf, int32_t* count,
                     hipStream_t st) {
     const int64_t n = mesh_npoints(vol);
-    hipLaunchKernelGGL(k_mesh_tsdf, dim3(mesh_nblk(n)), dim3(256), 0, st, prm, a, vol, n, ids, usable, tsdf, count);
+    hipLaunchKernelGGL(k_mesh_tsdf, dim3(nblk(n, 256)), dim3(256), 0, st, prm, a, vol, n, ids, usable, tsdf, count);
 }
 void mvsk_mesh_state(const MeshVol& vol, const float* tsdf, const int32_t* count, uint8_t* state, hipStream_t st) {
     const int64_t n = mesh_npoints(vol);
-    hipLaunchKernelGGL(k_mesh_state, dim3(mesh_nblk(n)), dim3(256), 0, st, n, tsdf, count, vol.min_count, state);
+    hipLaunchKernelGGL(k_mesh_state, dim3(nblk(n, 256)), dim3(256), 0, st, n, tsdf, count, vol.min_count, state);
 }
 void mvsk_mesh_edges(const MeshVol& vol, const uint8_t* state, uint8_t* mask, int32_t* cnt, hipStream_t st) {
     const int64_t n = mesh_npoints(vol);
-    hipLaunchKernelGGL(k_mesh_edges, dim3(mesh_nblk(n)), dim3(256), 0, st, vol, n, state, mask, cnt);
+    hipLaunchKernelGGL(k_mesh_edges, dim3(nblk(n, 256)), dim3(256), 0, st, vol, n, state, mask, cnt);
 }
 void mvsk_mesh_verts(const MeshVol& vol, const float* tsdf, const uint8_t* mask, const int32_t* vbase, float* verts, int64_t cap_v, hipStream_t st) {
     const int64_t n = mesh_npoints(vol);
-    hipLaunchKernelGGL(k_mesh_verts, dim3(mesh_nblk(n)), dim3(256), 0, st, vol, n, tsdf, mask, vbase, verts, cap_v);
+    hipLaunchKernelGGL(k_mesh_verts, dim3(nblk(n, 256)), dim3(256), 0, st, vol, n, tsdf, mask, vbase, verts, cap_v);
 }
 void mvsk_mesh_tcount(const MeshVol& vol, const uint8_t* state, int32_t* cnt, hipStream_t st) {
     const int64_t n = mesh_npoints(vol);
-    hipLaunchKernelGGL(k_mesh_tcount, dim3(mesh_nblk(n)), dim3(256), 0, st, vol, n, state, cnt);
+    hipLaunchKernelGGL(k_mesh_tcount, dim3(nblk(n, 256)), dim3(256), 0, st, vol, n, state, cnt);
 }
 void mvsk_mesh_tris(const MeshVol& vol, const uint8_t* state, const uint8_t* mask, const int32_t* vbase, const int64_t* tbase, int32_t* tris,
                     int64_t cap_t, hipStream_t st) {
     const int64_t n = mesh_npoints(vol);
-    hipLaunchKernelGGL(k_mesh_tris, dim3(mesh_nblk(n)), dim3(256), 0, st, vol, n, state, mask, vbase, tbase, tris, cap_t);
+    hipLaunchKernelGGL(k_mesh_tris, dim3(nblk(n, 256)), dim3(256), 0, st, vol, n, state, mask, vbase, tbase, tris, cap_t);
 }

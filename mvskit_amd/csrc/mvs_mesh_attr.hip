@@ -16,7 +16,7 @@
 // fails it.  Stores are plain vector stores.
 #include <hip/hip_runtime.h>
 
-#include "mvs_device.cuh"
+#include "mvs_common.cuh"
 #include "mvs_kernels.h"
 
 using namespace mvsdev;
@@ -189,19 +189,18 @@ __global__ __launch_bounds__(MATTR_BLOCK) void k_mattr_colours(DParams prm, Maps
     }
 }
 
-static inline unsigned mattr_nblk(int64_t n) { return (unsigned)((n + MATTR_BLOCK - 1) / MATTR_BLOCK); }
 
 void mvsk_mesh_normals_scan(int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, uint32_t* mbits, uint32_t* bad, hipStream_t st) {
-    if (n_t > 0) hipLaunchKernelGGL(k_mattr_scan, dim3(mattr_nblk(n_t)), dim3(MATTR_BLOCK), 0, st, n_v, verts, n_t, tris, mbits, bad);
+    if (n_t > 0) hipLaunchKernelGGL(k_mattr_scan, dim3(nblk(n_t, MATTR_BLOCK)), dim3(MATTR_BLOCK), 0, st, n_v, verts, n_t, tris, mbits, bad);
 }
 void mvsk_mesh_normals_accum(const float* verts, int64_t n_t, const int32_t* tris, const uint32_t* mbits, long long* acc, hipStream_t st) {
     if (n_t > 0)
-        hipLaunchKernelGGL(k_mattr_accum, dim3(mattr_nblk(n_t)), dim3(MATTR_BLOCK), 0, st, verts, n_t, tris, mbits, reinterpret_cast<unsigned long long*>(acc));
+        hipLaunchKernelGGL(k_mattr_accum, dim3(nblk(n_t, MATTR_BLOCK)), dim3(MATTR_BLOCK), 0, st, verts, n_t, tris, mbits, reinterpret_cast<unsigned long long*>(acc));
 }
 void mvsk_mesh_normals_finish(int64_t n_v, const long long* acc, float* normals, hipStream_t st) {
-    if (n_v > 0) hipLaunchKernelGGL(k_mattr_finish, dim3(mattr_nblk(n_v)), dim3(MATTR_BLOCK), 0, st, n_v, acc, normals);
+    if (n_v > 0) hipLaunchKernelGGL(k_mattr_finish, dim3(nblk(n_v, MATTR_BLOCK)), dim3(MATTR_BLOCK), 0, st, n_v, acc, normals);
 }
 void mvsk_mesh_colours(const DParams& prm, const MapsArgs& a, const MeshColourArgs& m, int64_t n_v, const float* verts, const float* normals,
                        const int32_t* ids, const uint8_t* usable, uint8_t* rgb, uint8_t* used, hipStream_t st) {
-    if (n_v > 0) hipLaunchKernelGGL(k_mattr_colours, dim3(mattr_nblk(n_v)), dim3(MATTR_BLOCK), 0, st, prm, a, m, n_v, verts, normals, ids, usable, rgb, used);
+    if (n_v > 0) hipLaunchKernelGGL(k_mattr_colours, dim3(nblk(n_v, MATTR_BLOCK)), dim3(MATTR_BLOCK), 0, st, prm, a, m, n_v, verts, normals, ids, usable, rgb, used);
 }

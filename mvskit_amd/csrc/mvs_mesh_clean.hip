@@ -23,32 +23,12 @@
 // The atomics are vector memory atomics; stores are plain vector stores.  fp32 / fp64 without contraction.
 #include <hip/hip_runtime.h>
 
-#include "mvs_device.cuh"
+#include "mvs_common.cuh"
 #include "mvs_kernels.h"
 
 using namespace mvsdev;
 
 #define MCLEAN_BLOCK 256
-
-// the union-find of mvs_kernels.hip (filterSmallGroups), restated: path halving on the way up, the smaller root adopts the larger
-DEV int mclean_find(int* parent, int a) {
-    while (true) {
-        const int pa = __atomic_load_n(&parent[a], __ATOMIC_RELAXED);
-        if (pa == a) return a;
-        const int gp = __atomic_load_n(&parent[pa], __ATOMIC_RELAXED);
-        if (gp != pa) __atomic_store_n(&parent[a], gp, __ATOMIC_RELAXED);
-        a = pa;
-    }
-}
-DEV void mclean_union(int* parent, int a, int b) {
-    while (true) {
-        a = mclean_find(parent, a);
-        b = mclean_find(parent, b);
-        if (a == b) return;
-        if (a > b) { const int t = a; a = b; b = t; }
-        if (atomicCAS(&parent[b], b, a) == b) return;
-    }
-}
 
 __global__ __launch_bounds__(MCLEAN_BLOCK) void k_mclean_check(int64_t n_v, int64_t n_t, const int32_t* __restrict__ tris, uint32_t* __restrict__ bad) {
     const int64_t t = (int64_t)blockIdx.x * MCLEAN_BLOCK + threadIdx.x;
@@ -69,8 +49,8 @@ __global__ __launch_bounds__(MCLEAN_BLOCK) void k_mclean_union(int64_t n_t, cons
     const int64_t t = (int64_t)blockIdx.x * MCLEAN_BLOCK + threadIdx.x;
     if (t >= n_t) return;
     const int i0 = tris[3 * t], i1 = tris[3 * t + 1], i2 = tris[3 * t + 2];
-    mclean_union(parent, i0, i1);
-    mclean_union(parent, i0, i2);
+    uf_union(parent, i0, i1);
+    uf_union(parent, i0, i2);
 }
 
 __global__ __launch_bounds__(MCLEAN_BLOCK) void k_mclean_flatten(int64_t n_v, int* parent) {
@@ -254,9 +234,8 @@ __global__ __launch_bounds__(MCLEAN_BLOCK) void k_msmooth_update(int64_t n_v, co
     cnt[i] = 0;
 }
 
-static inline unsigned mclean_nblk(int64_t n) { return (unsigned)((n + MCLEAN_BLOCK - 1) / MCLEAN_BLOCK); }
 #define MCLEAN_LAUNCH(kernel, n, ...) \
-    do { if ((n) > 0) hipLaunchKernelGGL(kernel, dim3(mclean_nblk(n)), dim3(MCLEAN_BLOCK), 0, st, __VA_ARGS__); } while (0)
+    do { if ((n) > 0) hipLaunchKernelGGL(kernel, dim3(nblk(n, MCLEAN_BLOCK)), dim3(MCLEAN_BLOCK), 0, st, __VA_ARGS__); } while (0)
 
 void mvsk_mesh_check_ids(int64_t n_v, int64_t n_t, const int32_t* tris, uint32_t* bad, hipStream_t st) { MCLEAN_LAUNCH(k_mclean_check, n_t, n_v, n_t, tris, bad); }
 void mvsk_mesh_components(int64_t n_v, int64_t n_t, const int32_t* tris, int32_t* parent, int32_t* size, unsigned long long* ncomp, hipStream_t st) {

@@ -27,7 +27,7 @@
 // memory atomics, none but the compare-and-swap returns a value; stores are plain vector stores.  fp32 / fp64 without contraction.
 #include <hip/hip_runtime.h>
 
-#include "mvs_device.cuh"
+#include "mvs_common.cuh"
 #include "mvs_kernels.h"
 
 using namespace mvsdev;
@@ -299,9 +299,8 @@ __global__ __launch_bounds__(MDEC_BLOCK) void k_mdec_tgather(int64_t n_t, const 
     out[3 * k] = vbase[r.a]; out[3 * k + 1] = vbase[r.b]; out[3 * k + 2] = vbase[r.c];
 }
 
-static inline unsigned mdec_nblk(int64_t n) { return (unsigned)((n + MDEC_BLOCK - 1) / MDEC_BLOCK); }
 #define MDEC_LAUNCH(kernel, n, ...) \
-    do { if ((n) > 0) hipLaunchKernelGGL(kernel, dim3(mdec_nblk(n)), dim3(MDEC_BLOCK), 0, st, __VA_ARGS__); } while (0)
+    do { if ((n) > 0) hipLaunchKernelGGL(kernel, dim3(nblk(n, MDEC_BLOCK)), dim3(MDEC_BLOCK), 0, st, __VA_ARGS__); } while (0)
 
 void mvsk_mdec_members(int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, const float* origin, float cell, int32_t* used,
                        unsigned long long* key, uint32_t* mbits, uint32_t* bad, hipStream_t st) {

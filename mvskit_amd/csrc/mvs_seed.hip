@@ -13,7 +13,7 @@
 // specified for the sweep's lengths and depths only), Optim::getUnit's division in double.  A record therefore has the mirror's bits.
 #include <hip/hip_runtime.h>
 
-#include "mvs_device.cuh"
+#include "mvs_common.cuh"
 #include "mvs_kernels.h"
 
 using namespace mvsdev;
@@ -150,15 +150,14 @@ __global__ __launch_bounds__(SEED_BLOCK) void k_seed_emit(const SeedCam* __restr
     }
 }
 
-static inline unsigned seed_blocks(int64_t n) { return (unsigned)((n + SEED_BLOCK - 1) / SEED_BLOCK); }
 
 void mvsk_seed_accumulate(const SeedView& sv, const float* map, const uint8_t* mask, const float* xyz, int64_t n, float* sum, unsigned long long* bits,
                           hipStream_t st) {
-    if (n > 0) hipLaunchKernelGGL(k_seed_accumulate, dim3(seed_blocks(n)), dim3(SEED_BLOCK), 0, st, sv, map, mask, xyz, n, sum, bits);
+    if (n > 0) hipLaunchKernelGGL(k_seed_accumulate, dim3(nblk(n, SEED_BLOCK)), dim3(SEED_BLOCK), 0, st, sv, map, mask, xyz, n, sum, bits);
 }
 void mvsk_seed_flags(const SeedCam* cams, int level, const float* xyz, const float* sum, const unsigned long long* bits, int64_t n, int32_t* keep,
                      hipStream_t st) {
-    if (n > 0) hipLaunchKernelGGL(k_seed_flags, dim3(seed_blocks(n)), dim3(SEED_BLOCK), 0, st, cams, level, xyz, sum, bits, n, keep);
+    if (n > 0) hipLaunchKernelGGL(k_seed_flags, dim3(nblk(n, SEED_BLOCK)), dim3(SEED_BLOCK), 0, st, cams, level, xyz, sum, bits, n, keep);
 }
 void mvsk_seed_emit(const SeedCam* cams, int nviews, int level, float thr, float tmp_unit, const float* xyz, const float* sum, const unsigned long long* bits,
                     const int32_t* keep, const int32_t* base, int64_t n, DPatch* dst, hipStream_t st) {

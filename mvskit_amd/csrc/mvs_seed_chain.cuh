@@ -3,7 +3,7 @@
 // and parks them in LDS; seed_chain then walks them through Optim::preProcess and PatchManager::computeNcc, keeps the best one, refines it
 // (the engine's refiner) and runs Optim::postProcess; a patch that passes is staged with its keep flag set.
 // The stages are the device functions of the sweep, called as mvs_engine_probe's ops 1, 0, 2 and 3 call them (k_probe, k_probe_refine,
-// k_probe_refine_simplex in mvs_kernels.hip), and between two stages the candidate goes through a record (store_cand / load_cand, in LDS)
+// k_probe_refine_simplex in mvs_probe.cuh), and between two stages the candidate goes through a record (store_cand / load_cand, in LDS)
 // as it does between two probe calls: a kept record has the bits that chain of probes gives.  Optim::check never runs here.
 #pragma once
 #include "mvs_device.cuh"
