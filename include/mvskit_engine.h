@@ -616,7 +616,8 @@ int mvs_engine_mesh_smooth(mvs_engine* e, const mvs_mesh_smoothing* s, int64_t n
  *                   may be NULL.  It lets the caller carry attributes over; the call itself carries none.
  *   WHAT CLUSTERING DOES NOT PROMISE: the result of a closed manifold need not be manifold.  A surface that passes the same three cells
  *   twice (a thin wall, two sheets closer than a cell) leaves, once the duplicate is dropped, edges with one or three triangles; a
- *   cluster may join parts of the surface that were not neighbours.  No target count: the count follows from `cell`.
+ *   cluster may join parts of the surface that were not neighbours.  No target count: the count follows from `cell`.  Whether a result
+ *   is still closed, mvs_engine_mesh_boundaries says (below); the small holes that are loops, mvs_engine_mesh_fill closes.
  *   Sizes follow mvs_engine_mesh_prune: with out_verts == NULL, out_tris == NULL or a cap (in vertices / triangles) too small, *n_v_out
  *   and *n_t_out are the exact counts and nothing else is written, vmap neither; MVS_ERR_CAPACITY when a non-NULL output is too small.  An
  *   output that ALIASES an input is not supported.  LIMITS: n_v, n_t in 0 .. 2^30.  Device memory for the call: 36 bytes a vertex (position,
@@ -639,6 +640,74 @@ void mvs_default_mesh_decimation(mvs_mesh_decimation* d); /* origin 0, cell 1, p
 int mvs_engine_mesh_decimate(mvs_engine* e, const mvs_mesh_decimation* d, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris,
                              int64_t cap_v, float* out_verts, int64_t cap_t, int32_t* out_tris, int32_t* vmap /* [n_v] or NULL */,
                              int64_t* n_v_out, int64_t* n_t_out);
+
+/* Mesh hole filling (no reference counterpart): the BOUNDARY LOOPS of a triangle mesh and their filling with CENTROID FANS.  The TSDF mesh
+ * is open wherever no usable pixel saw the surface; mvs_engine_mesh_boundaries says where and whether a mesh is closed at all, and
+ * mvs_engine_mesh_fill closes the holes of up to max_edges edges.  verts: n_v x 3 floats, tris: n_t x 3 int32 vertex ids.  Both calls are
+ * stateless, only read the engine and need a device but no views, like the clean-up calls; all pointers may be host or device memory
+ * (hipMemcpyDefault).  Every result is an integer, comes from an integer sum or is a copy of input bytes: two calls give the same bytes,
+ * whatever order the hardware meets the triangles in.  A refused call writes nothing.
+ *     EDGES         a triangle (a, b, c) with three different ids has the directed edges a->b, b->c, c->a.  A triangle with a repeated
+ *                   id has no edges here; mvs_engine_mesh_fill copies it through.  cnt(a,b) = the number of triangles with the directed
+ *                   edge a->b.  Per unordered pair {a, b} with f = cnt(a,b), r = cnt(b,a): (1,1) is INTERIOR; (1,0) makes a->b a BOUNDARY
+ *                   half-edge; anything else (a doubled triangle, a fin) is IRREGULAR: it marks both ends COMPLEX and is not a boundary
+ *                   half-edge.
+ *     VERTICES      out[v] / in[v] = the boundary half-edges leaving / entering v.  v is ON A BOUNDARY when out + in > 0, and SIMPLE when
+ *                   out == 1, in == 1 and it is not complex.
+ *     COMPONENTS    the boundary half-edges join their two ends (the union-find of mvs_engine_mesh_components, in which the smaller id
+ *                   becomes the root); label = the smallest vertex id of the joined set: canonical.  A component all of whose vertices
+ *                   are simple is a LOOP: one directed cycle with as many half-edges as vertices, at least 3.  Any other component is
+ *                   COMPLEX; two holes that meet in one vertex are one complex component.
+ * mvs_engine_mesh_boundaries:
+ *     loop[i]       the label of i's component, -1 for a vertex on no boundary.
+ *     length[i]     the number of half-edges of i's component, NEGATED when the component is complex; 0 where loop[i] is -1 (int32: exact
+ *                   while a component has fewer than 2^31 half-edges).
+ *     n_loops, n_complex   the components of each kind.     n_irregular   the irregular unordered pairs.
+ *   Every output may be NULL.  A mesh is a closed edge-manifold exactly when all three counts are 0.  LIMITS: n_v, n_t in 0 .. 2^30.
+ *   Device memory for the call: 36 bytes a vertex (parent, out, in, complex, next, two words a root, loop, length), 12 a triangle and ONE
+ *   TABLE of 12 bytes a slot with the power of two of slots that is >= 6 n_t, one slot or more per directed edge (72 to 144 bytes a triangle).
+ *   MVS_ERR_ARG, checked in this order before the handle is read: a negative count or a count over the limit; tris NULL with n_t > 0; no
+ *   engine.  Then, after one validating pass on the device: an id outside 0 .. n_v - 1.
+ * mvs_engine_mesh_fill:
+ *     FILLED        a loop is filled when 3 <= length <= max_edges.  Complex components and longer loops stay as they are.  The outer rim
+ *                   of an open surface is a loop too: max_edges is what keeps it open.  *n_filled = the number of filled loops.
+ *     LENGTH 3      the loop a->b->c->a with a its label gets the one triangle (b, a, c).  No vertex is added: a single missing triangle
+ *                   is put back.
+ *     LENGTH >= 4   one new vertex w at the centroid, and for every half-edge a->b of the loop the triangle (b, a, w).  Every new directed
+ *                   edge then has its reverse exactly once: a filled loop disappears from mvs_engine_mesh_boundaries, and nothing else
+ *                   about the boundaries changes, not n_irregular, not the labels and lengths of what stays open.
+ *     POSITION      by the scheme of the decimation's mean: M = the largest |component| over the vertices of the filled loops of length
+ *                   >= 4, E = floor(log2 M), S = 2^(30 - E); q = llrint((double)x_c * S), round-half-even; A = the int64 sum of q over the
+ *                   loop's vertices, by 64-bit integer atomic adds; p = (float)(((double)A * 2^(E-30)) / (double)length) in fp64 without
+ *                   contraction.  M == 0 gives +0 in all three components.
+ *     ORDER         out_verts = the n_v input rows unchanged, unused vertices included, then the new vertices in ascending order of their
+ *                   loop's label.  out_tris = the n_t input rows unchanged, then the fill triangles in ascending order of their
+ *                   half-edge's origin a (the triangle of a loop of 3 at its label): every simple vertex is the origin of exactly one
+ *                   half-edge, so the rows are an exclusive scan over the vertices.  Ids never change: there is no vertex map, and
+ *                   attributes of the input carry over row for row.
+ *   Sizes follow mvs_engine_mesh_prune: with out_verts == NULL, out_tris == NULL or a cap (in vertices / triangles) too small, *n_v_out,
+ *   *n_t_out and *n_filled are the exact counts and nothing else is written; MVS_ERR_CAPACITY when a non-NULL output is too small.  An
+ *   output that ALIASES an input is not supported.  LIMITS: n_v, n_t in 0 .. 2^30; *n_v_out or *n_t_out over 2^30 is MVS_ERR_CAPACITY
+ *   (nothing written).  Device memory for the call: that of mvs_engine_mesh_boundaries and 28 bytes a vertex more (position, two counts
+ *   and their scans); with outputs 24 bytes a vertex more (three int64) and the fans (12 bytes a new vertex, 12 a new triangle).
+ *   MVS_ERR_ARG, checked in this order before the handle is read: f NULL; max_edges < 3; a negative count or a count over the limit; verts
+ *   NULL with n_v > 0; tris NULL with n_t > 0; n_v_out or n_t_out NULL (n_filled may be NULL); a negative cap; no engine.  Then, after the
+ *   validating pass on the device: an id outside 0 .. n_v - 1.  Then: a vertex of a filled loop with a non-finite component
+ *   ("loop vertex").  A NaN anywhere else is ignored: on an unused vertex, on an interior vertex, on a loop that is not filled.
+ *   MVS_ERR_HIP: an allocation or copy failed (or a probe of the table found no slot, which a correct build never does).
+ *   WHAT FILLING DOES NOT DO: no ear clipping or minimal-area triangulation, no refinement of a large fan (a long, bent loop gets a fan
+ *   that may fold over itself), nothing for complex components, and the fan is flat until mvs_engine_mesh_smooth relaxes it. */
+typedef struct mvs_mesh_filling {
+    int32_t max_edges; /* fill the loops of 3 .. max_edges half-edges; >= 3 */
+    int32_t pad;
+} mvs_mesh_filling; /* 8 bytes */
+void mvs_default_mesh_filling(mvs_mesh_filling* f); /* max_edges 64 */
+int mvs_engine_mesh_boundaries(mvs_engine* e, int64_t n_v, int64_t n_t, const int32_t* tris, int32_t* loop /* [n_v] or NULL */,
+                               int32_t* length /* [n_v] or NULL */, int64_t* n_loops /* or NULL */, int64_t* n_complex /* or NULL */,
+                               int64_t* n_irregular /* or NULL */);
+int mvs_engine_mesh_fill(mvs_engine* e, const mvs_mesh_filling* f, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris,
+                         int64_t cap_v, float* out_verts, int64_t cap_t, int32_t* out_tris, int64_t* n_v_out, int64_t* n_t_out,
+                         int64_t* n_filled /* or NULL */);
 
 /* Propagate::run(iter), propagate.cpp:28-64: two colour passes, each = index build + sweep + commit */
 int mvs_engine_propagate(mvs_engine* e, int iter, mvs_counters* out);

@@ -729,4 +729,121 @@ int mvs_engine_mesh_decimate(mvs_engine* e, const mvs_mesh_decimation* d, int64_
     return MVS_OK;
 }
 
+// Mesh hole filling (mvs_mesh_fill.hip; the definitions are in mvskit_engine.h): the boundary loops and their centroid fans.  Stateless
+// like the clean-up calls.  Both calls label the boundary components the same way; the filling goes on from there.
+static_assert(sizeof(mvs_mesh_filling) == 8, "mvs_mesh_filling is 8 bytes");
+namespace {
+struct MfillBufs {
+    DevBuf<int32_t> d_tris, tval, parent, outc, inc, cplx, next, hed, rbad, loop, length;
+    DevBuf<uint32_t> words, flags;        // flags: [0] the bits of the centroids' largest component, [1] a loop vertex not finite, [2] a probe that ran out
+    DevBuf<unsigned long long> tkey, counts;  // counts: [0] loops, [1] complex components, [2] irregular pairs, [3] filled loops
+};
+// the caller's triangles checked and labelled: b.loop, b.length, b.next and hc[0..2] (hc[3] = 0); the stream is idle on return
+int mfill_label(mvs_engine* e, int64_t n_v, int64_t n_t, const int32_t* tris, MfillBufs& b, unsigned long long hc[4], const char* who) {
+    hipStream_t st = e->stream;
+    if (int r = mesh_take_tris(e, n_v, n_t, tris, b.d_tris, b.words, who)) return r;
+    const int64_t slots = mdec_slots(3 * n_t);
+    if (b.parent.ensure(n_v) || b.outc.ensure(n_v) || b.inc.ensure(n_v) || b.cplx.ensure(n_v) || b.next.ensure(n_v) || b.hed.ensure(n_v) || b.rbad.ensure(n_v) ||
+        b.loop.ensure(n_v) || b.length.ensure(n_v) || b.flags.ensure(4) || b.counts.ensure(4) || (n_t > 0 && (b.tkey.ensure(slots) || b.tval.ensure(slots))))
+        return MVS_ERR_HIP;
+    for (DevBuf<int32_t>* z : {&b.outc, &b.inc, &b.cplx, &b.next, &b.hed, &b.rbad})
+        if (n_v > 0) HIPCHK(hipMemsetAsync(z->p, 0, (size_t)n_v * sizeof(int32_t), st));
+    HIPCHK(hipMemsetAsync(b.flags.p, 0, 4 * sizeof(uint32_t), st));
+    HIPCHK(hipMemsetAsync(b.counts.p, 0, 4 * sizeof(unsigned long long), st));
+    if (n_t > 0) {
+        HIPCHK(hipMemsetAsync(b.tkey.p, 0xff, (size_t)slots * sizeof(unsigned long long), st));
+        HIPCHK(hipMemsetAsync(b.tval.p, 0, (size_t)slots * sizeof(int32_t), st));
+    }
+    mvsk_mfill_boundaries(n_v, n_t, b.d_tris.p, b.tkey.p, b.tval.p, slots, b.parent.p, b.outc.p, b.inc.p, b.cplx.p, b.next.p, b.hed.p, b.rbad.p, b.loop.p,
+                          b.length.p, b.counts.p, b.flags.p + 2, st);
+    uint32_t fail = 0;
+    HIPCHK(hipMemcpyAsync(hc, b.counts.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    if (int r = read_back(e, b.flags.p + 2, &fail)) return r;
+    HIPCHK(hipGetLastError());
+    if (fail) { g_err = std::string(who) + ": the edge table found no slot"; return MVS_ERR_HIP; }
+    return MVS_OK;
+}
+}  // namespace
+
+int mvs_engine_mesh_boundaries(mvs_engine* e, int64_t n_v, int64_t n_t, const int32_t* tris, int32_t* loop, int32_t* length, int64_t* n_loops, int64_t* n_complex,
+                               int64_t* n_irregular) {
+    const char* who = "mvs_engine_mesh_boundaries";
+    if (int r = mesh_counts(n_v, n_t, who)) return r;
+    if (!tris && n_t > 0) { g_err = std::string(who) + ": tris null"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
+    unsigned long long hc[4] = {0, 0, 0, 0};
+    if (n_v > 0 || n_t > 0) {
+        HIPCHK(hipSetDevice(e->cfg.device));
+        Range rg("mvs:mesh_boundaries");
+        hipStream_t st = e->stream;
+        MfillBufs b;
+        if (int r = mfill_label(e, n_v, n_t, tris, b, hc, who)) return r;  // a failure is known before anything is written
+        if (loop && n_v > 0) HIPCHK(hipMemcpyAsync(loop, b.loop.p, (size_t)n_v * sizeof(int32_t), hipMemcpyDefault, st));
+        if (length && n_v > 0) HIPCHK(hipMemcpyAsync(length, b.length.p, (size_t)n_v * sizeof(int32_t), hipMemcpyDefault, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    if (n_loops) *n_loops = (int64_t)hc[0];
+    if (n_complex) *n_complex = (int64_t)hc[1];
+    if (n_irregular) *n_irregular = (int64_t)hc[2];
+    return MVS_OK;
+}
+
+void mvs_default_mesh_filling(mvs_mesh_filling* f) {
+    if (!f) return;
+    f->max_edges = 64; f->pad = 0;
+}
+
+int mvs_engine_mesh_fill(mvs_engine* e, const mvs_mesh_filling* f, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, int64_t cap_v,
+                         float* out_verts, int64_t cap_t, int32_t* out_tris, int64_t* n_v_out, int64_t* n_t_out, int64_t* n_filled) {
+    const char* who = "mvs_engine_mesh_fill";
+    if (!f) { g_err = std::string(who) + ": filling null"; return MVS_ERR_ARG; }
+    if (f->max_edges < 3) { g_err = std::string(who) + ": max_edges < 3"; return MVS_ERR_ARG; }
+    if (int r = mesh_counts(n_v, n_t, who)) return r;
+    if (!verts && n_v > 0) { g_err = std::string(who) + ": verts null"; return MVS_ERR_ARG; }
+    if (!tris && n_t > 0) { g_err = std::string(who) + ": tris null"; return MVS_ERR_ARG; }
+    if (int r = mesh_out_args(cap_v, cap_t, n_v_out, n_t_out, who)) return r;
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
+    if (n_v == 0 && n_t == 0) { *n_v_out = 0; *n_t_out = 0; if (n_filled) *n_filled = 0; return MVS_OK; }
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:mesh_fill");
+    hipStream_t st = e->stream;
+    MfillBufs b;
+    DevBuf<int32_t> tcnt, tbase, vcnt, vbase, scan, add_tris;
+    DevBuf<float> d_verts, add_verts;
+    DevBuf<long long> acc;
+    unsigned long long hc[4] = {0, 0, 0, 0};
+    if (int r = mfill_label(e, n_v, n_t, tris, b, hc, who)) return r;
+    if (d_verts.ensure(3 * n_v) || tcnt.ensure(n_v) || tbase.ensure(n_v + 1) || vcnt.ensure(n_v) || vbase.ensure(n_v + 1) || scan.ensure(n_v / 256 + 4096)) return MVS_ERR_HIP;
+    if (n_v > 0) HIPCHK(hipMemcpyAsync(d_verts.p, verts, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
+    mvsk_mfill_plan(n_v, d_verts.p, b.loop.p, b.length.p, f->max_edges, tcnt.p, vcnt.p, b.flags.p, b.flags.p + 1, b.counts.p + 3, st);
+    int64_t nv_add = 0, nt_add = 0;
+    if (int r = scan_total(e, tcnt.p, tbase.p, scan.p, n_v, &nt_add)) return r;
+    if (int r = scan_total(e, vcnt.p, vbase.p, scan.p, n_v, &nv_add)) return r;
+    uint32_t bad = 0;
+    HIPCHK(hipMemcpyAsync(&hc[3], b.counts.p + 3, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    if (int r = read_back(e, b.flags.p + 1, &bad)) return r;
+    HIPCHK(hipGetLastError());
+    if (bad) { g_err = std::string(who) + ": a loop vertex with a non-finite component"; return MVS_ERR_ARG; }
+    const int64_t nv = n_v + nv_add, nt = n_t + nt_add;
+    if (nv > MESH_ATTR_MAX || nt > MESH_ATTR_MAX) { g_err = std::string(who) + ": the filled mesh has more than 2^30 vertices or triangles"; return MVS_ERR_CAPACITY; }
+    *n_v_out = nv; *n_t_out = nt;
+    if (n_filled) *n_filled = (int64_t)hc[3];
+    if ((out_verts && cap_v < nv) || (out_tris && cap_t < nt)) { g_err = std::string(who) + ": a cap is smaller than the filled mesh (*n_v_out, *n_t_out)"; return MVS_ERR_CAPACITY; }
+    if (!out_verts || !out_tris) return MVS_OK;
+    if (nt_add > 0) {
+        if (acc.ensure(3 * n_v) || add_tris.ensure(3 * nt_add) || add_verts.ensure(3 * nv_add)) return MVS_ERR_HIP;
+        HIPCHK(hipMemsetAsync(acc.p, 0, (size_t)n_v * 3 * sizeof(long long), st));
+        mvsk_mfill_emit(n_v, d_verts.p, b.loop.p, b.length.p, f->max_edges, b.next.p, tbase.p, vbase.p, b.flags.p, acc.p, add_tris.p, nt_add, add_verts.p, nv_add, st);
+        HIPCHK(hipStreamSynchronize(st));  // a failure is known before anything is written
+        HIPCHK(hipGetLastError());
+    }
+    if (n_v > 0) HIPCHK(hipMemcpyAsync(out_verts, d_verts.p, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
+    if (n_t > 0) HIPCHK(hipMemcpyAsync(out_tris, b.d_tris.p, (size_t)n_t * 3 * sizeof(int32_t), hipMemcpyDefault, st));
+    if (nv_add > 0) HIPCHK(hipMemcpyAsync(out_verts + 3 * n_v, add_verts.p, (size_t)nv_add * 3 * sizeof(float), hipMemcpyDefault, st));
+    if (nt_add > 0) HIPCHK(hipMemcpyAsync(out_tris + 3 * n_t, add_tris.p, (size_t)nt_add * 3 * sizeof(int32_t), hipMemcpyDefault, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return MVS_OK;
+}
+
 }  // extern "C"

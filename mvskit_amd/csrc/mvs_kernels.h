@@ -197,3 +197,21 @@ void mvsk_mdec_positions(int placement, int64_t n_v, const float* verts, const i
 // the vertex map and the kept triangles in input order, ids rewritten
 void mvsk_mdec_gather(int64_t n_v, const int32_t* rep, const int32_t* vflag, const int32_t* vbase, int32_t* vmap, int64_t n_t, const int32_t* tris,
                       const int32_t* tflag, const int32_t* tbase, int32_t* out_tris, int64_t cap_t, hipStream_t st);
+// mvs_engine_mesh_boundaries / mvs_engine_mesh_fill (mvs_mesh_fill.hip): the boundary loops of a mesh and their centroid fans.  One
+// open-addressing table (tkey: `slots` 64-bit keys, all ones = empty; tval: their counts, zero before the fill; slots a power of two >=
+// six times the triangles) counts the directed edges.  Every launcher wants valid ids.
+// loop[i] = the smallest vertex id of i's boundary component (-1: on no boundary), length[i] = its half-edges, negated when it is
+// complex; counts[0..2] += the loops, the complex components, the irregular pairs; next[a] = b for the boundary half-edge a -> b of a
+// simple vertex a.  outc, inc, cplx, next, hed, rbad (a word a vertex each), counts and *fail zero before; *fail != 0: a probe ran out
+void mvsk_mfill_boundaries(int64_t n_v, int64_t n_t, const int32_t* tris, unsigned long long* tkey, int32_t* tval, int64_t slots, int32_t* parent, int32_t* outc,
+                           int32_t* inc, int32_t* cplx, int32_t* next, int32_t* hed, int32_t* rbad, int32_t* loop, int32_t* length, unsigned long long* counts,
+                           uint32_t* fail, hipStream_t st);
+// tcnt[i] = the fill triangles whose half-edge starts at i, vcnt[i] = 1 at the label of a filled loop of 4 or more; *mbits = the bits of
+// the largest |component| of the vertices of those loops, *bad != 0 when a vertex of a filled loop is not finite, *nfilled += the filled
+// loops (all three zero before)
+void mvsk_mfill_plan(int64_t n_v, const float* verts, const int32_t* loop, const int32_t* length, int32_t max_edges, int32_t* tcnt, int32_t* vcnt, uint32_t* mbits,
+                     uint32_t* bad, unsigned long long* nfilled, hipStream_t st);
+// with tbase / vbase = the exclusive scans of those counts: the fill triangles at add_tris[3 tbase[a] ..], the centroids at
+// add_verts[3 vbase[label] ..] (their ids: n_v + vbase[label]); acc (3 int64 a vertex) zero before
+void mvsk_mfill_emit(int64_t n_v, const float* verts, const int32_t* loop, const int32_t* length, int32_t max_edges, const int32_t* next, const int32_t* tbase,
+                     const int32_t* vbase, const uint32_t* mbits, long long* acc, int32_t* add_tris, int64_t cap_t, float* add_verts, int64_t cap_v, hipStream_t st);

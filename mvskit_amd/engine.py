@@ -36,6 +36,7 @@ EXPORTS = [
     "mvs_default_mesh_colouring", "mvs_engine_mesh_normals", "mvs_engine_mesh_colours",
     "mvs_default_mesh_pruning", "mvs_default_mesh_smoothing", "mvs_engine_mesh_components", "mvs_engine_mesh_prune", "mvs_engine_mesh_smooth",
     "mvs_default_mesh_decimation", "mvs_engine_mesh_decimate",
+    "mvs_default_mesh_filling", "mvs_engine_mesh_boundaries", "mvs_engine_mesh_fill",
 ]
 PLY_ASCII, PLY_BINARY_LE = 0, 1  # mvs_ply_format
 #: one vertex of the binary PLY file (mvs_engine_export_ply): 27 packed bytes
@@ -120,6 +121,11 @@ class MeshSmoothing(C.Structure):
 class MeshDecimation(C.Structure):
     """mvs_mesh_decimation: the grid and the placement of mvs_engine_mesh_decimate, 24 bytes."""
     _fields_ = [("origin", C.c_float * 3), ("cell", C.c_float), ("placement", C.c_int32), ("pad", C.c_int32)]
+
+
+class MeshFilling(C.Structure):
+    """mvs_mesh_filling: the longest loop mvs_engine_mesh_fill closes, 8 bytes."""
+    _fields_ = [("max_edges", C.c_int32), ("pad", C.c_int32)]
 
 
 class Counters(C.Structure):
@@ -259,6 +265,12 @@ def load_library(cap32: bool = False, cap: int = 0):
         L.mvs_default_mesh_decimation.restype = None
         L.mvs_engine_mesh_decimate.argtypes = [vp, C.POINTER(MeshDecimation), C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp,
                                                C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    if hasattr(L, "mvs_engine_mesh_fill"):
+        L.mvs_default_mesh_filling.argtypes = [C.POINTER(MeshFilling)]
+        L.mvs_default_mesh_filling.restype = None
+        L.mvs_engine_mesh_boundaries.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.mvs_engine_mesh_fill.argtypes = [vp, C.POINTER(MeshFilling), C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp,
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     _libs[LIB_PATH] = L
     return L
 
@@ -686,17 +698,54 @@ class Engine:
         self._check(call(nv.value, out_v, nt.value, out_t, vmap))
         return out_v, out_t, vmap
 
+    # ---- mesh hole filling
+    def mesh_boundaries(self, n_v, tris):
+        """The boundary loops of the mesh (include/mvskit_engine.h, mvs_engine_mesh_boundaries): (loop [n_v] int32, the smallest vertex id
+        of each vertex's boundary component or -1; length [n_v] int32, the half-edges of that component, negated when it is no simple
+        loop; the numbers of loops, of complex components and of irregular edges).  A mesh is a closed edge-manifold exactly when the
+        three counts are 0.  Needs no views."""
+        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        loop, length = np.zeros(int(n_v), np.int32), np.zeros(int(n_v), np.int32)
+        nl, nc, ni = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self.L.mvs_engine_mesh_boundaries(self.h, int(n_v), tris.shape[0], _ptr(tris), _ptr(loop), _ptr(length), C.byref(nl), C.byref(nc),
+                                                      C.byref(ni)))
+        return loop, length, nl.value, nc.value, ni.value
+
+    def fill_holes(self, verts, tris, max_edges=64):
+        """The mesh with its boundary loops of 3 .. max_edges edges closed (include/mvskit_engine.h, mvs_engine_mesh_fill): (verts, tris,
+        the number of loops filled).  A loop of 3 gets its triangle back; a longer one a new vertex at its centroid and a fan around
+        it.  The input rows stay where they are, the new ones follow them; ids do not change.  The rim of an open surface is a loop too:
+        max_edges keeps it open.  The same bytes whatever order the hardware meets the triangles in.  The size call comes first.  Needs
+        no views."""
+        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        f = MeshFilling(int(max_edges), 0)
+        nv, nt, nf = C.c_int64(), C.c_int64(), C.c_int64()
+
+        def call(cap_v, out_v, cap_t, out_t):
+            return self.L.mvs_engine_mesh_fill(self.h, C.byref(f), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), cap_v, _ptr(out_v), cap_t,
+                                               _ptr(out_t), C.byref(nv), C.byref(nt), C.byref(nf))
+
+        self._check(call(0, None, 0, None))
+        out_v, out_t = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
+        if nv.value or nt.value:
+            self._check(call(nv.value, out_v, nt.value, out_t))
+        return out_v, out_t, nf.value
+
     def coloured_mesh(self, volume, source=0, min_consistent=1, depth_tol=0.01, normal_cos=0.9, occl_tol=0.01, min_cos=0.1, cap_v=0, cap_t=0,
-                      min_triangles=0, largest_only=False, smooth_iterations=0, decimate_cell=0.0, decimate_placement="mean"):
+                      min_triangles=0, largest_only=False, smooth_iterations=0, decimate_cell=0.0, decimate_placement="mean", fill_max_edges=0):
         """mesh, mesh_normals and mesh_colours chained: (verts, tris, normals, rgb, used), what write_mesh_ply takes.  Every step renders
-        the maps it needs itself.  With min_triangles >= 1 or largest_only the mesh is pruned (prune_mesh), with smooth_iterations > 0
-        smoothed (smooth_mesh with its default steps), with decimate_cell > 0 decimated (decimate_mesh), in that order, before the normals
-        and colours are taken.  The decimation grid starts at volume.origin - voxel / 2: marching tetrahedra leaves lattice coordinates in
+        the maps it needs itself.  With min_triangles >= 1 or largest_only the mesh is pruned (prune_mesh), with fill_max_edges >= 3 its
+        holes of up to that many edges are filled (fill_holes: the floaters are gone first, and the smoothing relaxes the fans), with
+        smooth_iterations > 0 it is smoothed (smooth_mesh with its default steps), with decimate_cell > 0 decimated (decimate_mesh), in
+        that order, before the normals and colours are taken.  The decimation grid starts at volume.origin - voxel / 2: marching tetrahedra leaves lattice coordinates in
         two of a vertex's three components, and with a cell that is a multiple of the voxel none of them sits on a cell boundary."""
         kw = dict(source=source, min_consistent=min_consistent, depth_tol=depth_tol, normal_cos=normal_cos)
         verts, tris = self.mesh(volume, cap_v=cap_v, cap_t=cap_t, **kw)
         if min_triangles > 0 or largest_only:
             verts, tris, _ = self.prune_mesh(verts, tris, max(1, int(min_triangles)), largest_only)
+        if fill_max_edges >= 3:
+            verts, tris, _ = self.fill_holes(verts, tris, fill_max_edges)
         if smooth_iterations > 0:
             verts = self.smooth_mesh(verts, tris, smooth_iterations)
         if decimate_cell > 0:
