@@ -1,7 +1,7 @@
 // mvs_engine.cpp -- the core of the C ABI in include/mvskit_engine.h: the engine and its device memory, camera set-up and the view
 // pyramids, the patch pool's upload / download, and the probes.  The other host units (mvs_engine_impl.h is what they share):
 // mvs_engine_pass.cpp (index build -> sweep -> commit), mvs_engine_comm.cpp (the exchange between ranks), mvs_engine_filter.cpp
-// (Filter::run), mvs_engine_seed.cpp (the seeding front ends), mvs_engine_output.cpp (point cloud, maps, mesh).
+// (Filter::run), mvs_engine_seed.cpp (the seeding front ends), mvs_engine_output.cpp (point cloud, maps), mvs_engine_mesh.cpp (mesh).
 #include <dlfcn.h>
 
 #include <cmath>

@@ -291,4 +291,23 @@ template <typename Blocks> ncclResult_t broadcast_blocks(mvs_engine* e, Blocks&&
     return first == ncclSuccess ? end : first;
 }
 
+// ---- mvs_engine_output.cpp
+// The buffers of a call that starts from the dense maps (the maps calls themselves, and the mesh calls of mvs_engine_mesh.cpp)
+struct MapsBufs {
+    MapsArgs args{};
+    int64_t total_pix = 0, max_pix = 0;
+    DevBuf<int32_t> ids;             // [total_pix] the pool index behind every pixel of every view, -1 = invalid
+    DevBuf<float> pts;               // [3 total_pix] its point
+    DevBuf<unsigned long long> agree;  // the views stream through these: [max_pix] each
+    DevBuf<int32_t> flag, base, scan;
+    DevBuf<float> maps;              // [5 max_pix] depth, normal, conf of the view under way
+    DevBuf<uint8_t> flag8;           // [total_pix] fused_points: the emitted pixels, between its counting and its gathering pass
+    DevBuf<mvs_fused_point> recs;    // fused_points: the records of one view
+};
+int maps_args(const mvs_maps_config* c, const char* who);  // the checks of a mvs_maps_config that need no handle
+int maps_state(const mvs_engine* e, const mvs_maps_config* c, const char* who);
+int64_t maps_npix(const mvs_engine* e, int v);
+int render_all(mvs_engine* e, const mvs_maps_config* c, MapsBufs& b);     // steps 1 and 2 for every view: b.ids and b.pts
+int render_usable(mvs_engine* e, const mvs_maps_config* c, MapsBufs& b);  // and their usability, a byte per pixel of all views: b.flag8
+
 }  // namespace mvseng

@@ -1,7 +1,7 @@
-// mvs_engine_output.cpp -- what the C ABI in include/mvskit_engine.h makes of the finished pool: the PLY point cloud (mvs_ply.hip), the
-// dense per-view maps and their fusion (mvs_maps.hip), the triangle mesh (mvs_mesh.hip), its vertex normals and colours
-// (mvs_mesh_attr.hip) and its clean-up (mvs_mesh_clean.hip).  Every entry point is stateless: its working arrays live in buffers of the call, and nothing of the engine's
-// state changes.
+// mvs_engine_output.cpp -- what the C ABI in include/mvskit_engine.h makes of the finished pool: the PLY point cloud (mvs_ply.hip) and
+// the dense per-view maps and their fusion (mvs_maps.hip).  The mesh calls, which start from the same maps (render_all, render_usable),
+// are in mvs_engine_mesh.cpp.  Every entry point is stateless: its working arrays live in buffers of the call, and nothing of the
+// engine's state changes.
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -101,24 +101,14 @@ int mvs_engine_export_ply(mvs_engine* e, int format, int64_t cap, uint8_t* out, 
     return MVS_OK;
 }
 
+}  // extern "C"
+
 // Dense per-view maps and their fusion (mvs_maps.hip; the definitions are in mvskit_engine.h).  Both entry points are stateless: render_all
 // fills the id and the point of every pixel of every view, the views then stream one at a time through buffers sized for the largest.
 // The selection keys go where mvs_engine_depth_normal_map puts them: `best` (source 0; scratch that every user clears first, sized for
 // the cells of all views) or `dpgrid` (source 1; every pass and Filter::run rebuilds it).
 static_assert(sizeof(mvs_maps_config) == 24 && sizeof(mvs_view_maps) == 40 && sizeof(mvs_fused_point) == 32, "the maps structs are 24, 40 and 32 bytes");
-namespace {
-struct MapsBufs {
-    MapsArgs args{};
-    int64_t total_pix = 0, max_pix = 0;
-    DevBuf<int32_t> ids;             // [total_pix] the pool index behind every pixel of every view, -1 = invalid
-    DevBuf<float> pts;               // [3 total_pix] its point
-    DevBuf<unsigned long long> agree;  // the views stream through these: [max_pix] each
-    DevBuf<int32_t> flag, base, scan;
-    DevBuf<float> maps;              // [5 max_pix] depth, normal, conf of the view under way
-    DevBuf<uint8_t> flag8;           // [total_pix] fused_points: the emitted pixels, between its counting and its gathering pass
-    DevBuf<mvs_fused_point> recs;    // fused_points: the records of one view
-};
-
+namespace mvseng {
 int maps_args(const mvs_maps_config* c, const char* who) {
     if (!c) { g_err = std::string(who) + ": config null"; return MVS_ERR_ARG; }
     if (c->source < 0 || c->source > 1) { g_err = std::string(who) + ": source must be 0 or 1"; return MVS_ERR_ARG; }
@@ -168,7 +158,24 @@ int render_all(mvs_engine* e, const mvs_maps_config* c, MapsBufs& b) {
     HIPCHK(hipGetLastError());
     return MVS_OK;
 }
-}  // namespace
+
+// the maps and their usability into b: b.ids and, a byte per pixel of all views, b.flag8 (launched, not waited for)
+int render_usable(mvs_engine* e, const mvs_maps_config* c, MapsBufs& b) {
+    hipStream_t st = e->stream;
+    if (int r = render_all(e, c, b)) return r;
+    if (b.agree.ensure(b.max_pix) || b.flag8.ensure(b.total_pix)) return MVS_ERR_HIP;
+    const DParams p = current_params(e);
+    // usability: fused_points' counting pass without dedupe, kept as a byte per pixel of all views (the views follow each other in stream order)
+    for (int v = 0; v < e->cfg.nviews; ++v) {
+        const int64_t npix = maps_npix(e, v), pix0 = b.args.pix_base[v];
+        mvsk_maps_agree(p, b.args, v, npix, b.ids.p, b.pts.p, b.agree.p, nullptr, nullptr, nullptr, st);
+        mvsk_maps_flag(npix, v, b.ids.p + pix0, b.agree.p, c->min_consistent, 0, b.flag.p, b.flag8.p + pix0, st);
+    }
+    return MVS_OK;
+}
+}  // namespace mvseng
+
+extern "C" {
 
 void mvs_default_maps_config(mvs_maps_config* c) {
     if (!c) return;
@@ -252,597 +259,6 @@ int mvs_engine_fused_points(mvs_engine* e, const mvs_maps_config* c, int64_t cap
         pos += nv;
     }
     *n = total;
-    return MVS_OK;
-}
-
-// Triangle mesh (mvs_mesh.hip; the definitions are in mvskit_engine.h).  Stateless like the maps calls: the volume and every working
-// array live in buffers of the call.  mesh_tsdf leaves the volume on the device, mesh_extract takes one from there; the three entry
-// points differ in where the volume comes from and goes to.
-static_assert(sizeof(mvs_volume) == 40, "mvs_volume is 40 bytes");
-namespace {
-int volume_args(const mvs_volume* vol, const char* who) {
-    if (!vol) { g_err = std::string(who) + ": volume null"; return MVS_ERR_ARG; }
-    if (!std::isfinite(vol->voxel) || !(vol->voxel > 0.0f)) { g_err = std::string(who) + ": voxel not finite or <= 0"; return MVS_ERR_ARG; }
-    if (!std::isfinite(vol->trunc) || !(vol->trunc > 0.0f)) { g_err = std::string(who) + ": trunc not finite or <= 0"; return MVS_ERR_ARG; }
-    for (int c = 0; c < 3; ++c)
-        if (vol->dims[c] < 2 || vol->dims[c] > 1024) { g_err = std::string(who) + ": a dimension outside 2..1024"; return MVS_ERR_ARG; }
-    if ((int64_t)vol->dims[0] * vol->dims[1] * vol->dims[2] > ((int64_t)1 << 28)) { g_err = std::string(who) + ": more than 2^28 lattice points"; return MVS_ERR_ARG; }
-    if (vol->min_count < 1) { g_err = std::string(who) + ": min_count < 1"; return MVS_ERR_ARG; }
-    return MVS_OK;
-}
-int mesh_out_args(int64_t cap_v, int64_t cap_t, const int64_t* n_v, const int64_t* n_t, const char* who) {
-    if (!n_v || !n_t) { g_err = std::string(who) + ": n_v or n_t null"; return MVS_ERR_ARG; }
-    if (cap_v < 0 || cap_t < 0) { g_err = std::string(who) + ": a negative cap"; return MVS_ERR_ARG; }
-    return MVS_OK;
-}
-MeshVol mesh_vol(const mvs_volume* vol) {
-    return MeshVol{{vol->origin[0], vol->origin[1], vol->origin[2]}, vol->voxel, vol->dims[0], vol->dims[1], vol->dims[2], vol->trunc, vol->min_count};
-}
-struct MeshVolume {
-    DevBuf<float> tsdf;
-    DevBuf<int32_t> count;
-};
-
-// the maps and their usability into b: b.ids and, a byte per pixel of all views, b.flag8 (launched, not waited for)
-int render_usable(mvs_engine* e, const mvs_maps_config* c, MapsBufs& b) {
-    hipStream_t st = e->stream;
-    if (int r = render_all(e, c, b)) return r;
-    if (b.agree.ensure(b.max_pix) || b.flag8.ensure(b.total_pix)) return MVS_ERR_HIP;
-    const DParams p = current_params(e);
-    // usability: fused_points' counting pass without dedupe, kept as a byte per pixel of all views (the views follow each other in stream order)
-    for (int v = 0; v < e->cfg.nviews; ++v) {
-        const int64_t npix = maps_npix(e, v), pix0 = b.args.pix_base[v];
-        mvsk_maps_agree(p, b.args, v, npix, b.ids.p, b.pts.p, b.agree.p, nullptr, nullptr, nullptr, st);
-        mvsk_maps_flag(npix, v, b.ids.p + pix0, b.agree.p, c->min_consistent, 0, b.flag.p, b.flag8.p + pix0, st);
-    }
-    return MVS_OK;
-}
-
-// the volume of the engine's maps into d (the stream is idle on return)
-int mesh_tsdf(mvs_engine* e, const mvs_maps_config* c, const MeshVol& mv, MeshVolume& d) {
-    hipStream_t st = e->stream;
-    const int64_t N = mesh_npoints(mv);
-    MapsBufs b;
-    if (int r = render_usable(e, c, b)) return r;
-    if (d.tsdf.ensure(N) || d.count.ensure(N)) return MVS_ERR_HIP;
-    const DParams p = current_params(e);
-    mvsk_mesh_tsdf(p, b.args, mv, b.ids.p, b.flag8.p, d.tsdf.p, d.count.p, st);
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    return MVS_OK;
-}
-
-// marching tetrahedra over a device volume (count may be null)
-int mesh_extract(mvs_engine* e, const MeshVol& mv, const float* d_tsdf, const int32_t* d_count, int64_t cap_v, float* verts, int64_t cap_t, int32_t* tris,
-                 int64_t* n_v, int64_t* n_t, const char* who) {
-    hipStream_t st = e->stream;
-    const int64_t N = mesh_npoints(mv);
-    DevBuf<uint8_t> state, mask;
-    DevBuf<int32_t> cnt, vbase, d_tris;
-    DevBuf<int64_t> tbase, scan;
-    DevBuf<float> d_verts;
-    if (state.ensure(N) || mask.ensure(N) || cnt.ensure(N + 1) || vbase.ensure(N + 1) || tbase.ensure(N + 1) || scan.ensure(N / 256 + 4096)) return MVS_ERR_HIP;
-    mvsk_mesh_state(mv, d_tsdf, d_count, state.p, st);
-    mvsk_mesh_edges(mv, state.p, mask.p, cnt.p, st);
-    mvsk_exclusive_scan(cnt.p, vbase.p, N, reinterpret_cast<int32_t*>(scan.p), st);
-    mvsk_mesh_tcount(mv, state.p, cnt.p, st);
-    mvsk_exclusive_scan_off(cnt.p, tbase.p, N, scan.p, st);
-    int32_t nv32 = 0;
-    int64_t nt = 0;
-    HIPCHK(hipMemcpyAsync(&nv32, vbase.p + N, sizeof nv32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&nt, tbase.p + N, sizeof nt, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    const int64_t nv = nv32;
-    *n_v = nv; *n_t = nt;
-    if ((verts && cap_v < nv) || (tris && cap_t < nt)) { g_err = std::string(who) + ": a cap is smaller than the mesh (*n_v, *n_t)"; return MVS_ERR_CAPACITY; }
-    if (!verts || !tris) return MVS_OK;
-    if (nv > 0) {
-        if (d_verts.ensure(3 * nv)) return MVS_ERR_HIP;
-        mvsk_mesh_verts(mv, d_tsdf, mask.p, vbase.p, d_verts.p, nv, st);
-        HIPCHK(hipMemcpyAsync(verts, d_verts.p, (size_t)nv * 3 * sizeof(float), hipMemcpyDefault, st));
-    }
-    if (nt > 0) {
-        if (d_tris.ensure(3 * nt)) return MVS_ERR_HIP;
-        mvsk_mesh_tris(mv, state.p, mask.p, vbase.p, tbase.p, d_tris.p, nt, st);
-        HIPCHK(hipMemcpyAsync(tris, d_tris.p, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDefault, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    return MVS_OK;
-}
-}  // namespace
-
-int mvs_engine_tsdf(mvs_engine* e, const mvs_maps_config* c, const mvs_volume* vol, float* tsdf, int32_t* count) {
-    const char* who = "mvs_engine_tsdf";
-    if (int r = maps_args(c, who)) return r;
-    if (int r = volume_args(vol, who)) return r;
-    if (!tsdf || !count) { g_err = std::string(who) + ": tsdf or count null"; return MVS_ERR_ARG; }
-    if (int r = maps_state(e, c, who)) return r;
-    HIPCHK(hipSetDevice(e->cfg.device));
-    Range rg("mvs:tsdf");
-    const MeshVol mv = mesh_vol(vol);
-    const int64_t N = mesh_npoints(mv);
-    MeshVolume d;
-    if (int r = mesh_tsdf(e, c, mv, d)) return r;
-    HIPCHK(hipMemcpyAsync(tsdf, d.tsdf.p, (size_t)N * sizeof(float), hipMemcpyDefault, e->stream));
-    HIPCHK(hipMemcpyAsync(count, d.count.p, (size_t)N * sizeof(int32_t), hipMemcpyDefault, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return MVS_OK;
-}
-
-int mvs_engine_extract_mesh(mvs_engine* e, const mvs_volume* vol, const float* tsdf, const int32_t* count, int64_t cap_v, float* verts, int64_t cap_t,
-                            int32_t* tris, int64_t* n_v, int64_t* n_t) {
-    const char* who = "mvs_engine_extract_mesh";
-    if (int r = volume_args(vol, who)) return r;
-    if (!tsdf) { g_err = std::string(who) + ": tsdf null"; return MVS_ERR_ARG; }
-    if (int r = mesh_out_args(cap_v, cap_t, n_v, n_t, who)) return r;
-    if (int r = need_state(e, NEED_ENGINE, who)) return r;
-    HIPCHK(hipSetDevice(e->cfg.device));
-    Range rg("mvs:extract_mesh");
-    const MeshVol mv = mesh_vol(vol);
-    const int64_t N = mesh_npoints(mv);
-    MeshVolume d;  // the caller's volume, from wherever it lies
-    if (d.tsdf.ensure(N) || (count && d.count.ensure(N))) return MVS_ERR_HIP;
-    HIPCHK(hipMemcpyAsync(d.tsdf.p, tsdf, (size_t)N * sizeof(float), hipMemcpyDefault, e->stream));
-    if (count) HIPCHK(hipMemcpyAsync(d.count.p, count, (size_t)N * sizeof(int32_t), hipMemcpyDefault, e->stream));
-    return mesh_extract(e, mv, d.tsdf.p, count ? d.count.p : nullptr, cap_v, verts, cap_t, tris, n_v, n_t, who);
-}
-
-int mvs_engine_mesh(mvs_engine* e, const mvs_maps_config* c, const mvs_volume* vol, int64_t cap_v, float* verts, int64_t cap_t, int32_t* tris,
-                    int64_t* n_v, int64_t* n_t) {
-    const char* who = "mvs_engine_mesh";
-    if (int r = maps_args(c, who)) return r;
-    if (int r = volume_args(vol, who)) return r;
-    if (int r = mesh_out_args(cap_v, cap_t, n_v, n_t, who)) return r;
-    if (int r = maps_state(e, c, who)) return r;
-    HIPCHK(hipSetDevice(e->cfg.device));
-    Range rg("mvs:mesh");
-    const MeshVol mv = mesh_vol(vol);
-    MeshVolume d;
-    if (int r = mesh_tsdf(e, c, mv, d)) return r;
-    return mesh_extract(e, mv, d.tsdf.p, d.count.p, cap_v, verts, cap_t, tris, n_v, n_t, who);
-}
-
-// Vertex normals and colours of a mesh (mvs_mesh_attr.hip; the definitions are in mvskit_engine.h).  Stateless like the mesh calls: the
-// caller's arrays come into buffers of the call from wherever they lie, the results leave from there.
-static_assert(sizeof(mvs_mesh_colouring) == 8, "mvs_mesh_colouring is 8 bytes");
-#define MESH_ATTR_MAX ((int64_t)1 << 30)
-
-int mvs_engine_mesh_normals(mvs_engine* e, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, float* normals) {
-    const char* who = "mvs_engine_mesh_normals";
-    if (n_v < 0 || n_t < 0 || n_v > MESH_ATTR_MAX || n_t > MESH_ATTR_MAX) { g_err = std::string(who) + ": a count negative or over 2^30"; return MVS_ERR_ARG; }
-    if (!verts && n_v > 0) { g_err = std::string(who) + ": verts null"; return MVS_ERR_ARG; }
-    if (!tris && n_t > 0) { g_err = std::string(who) + ": tris null"; return MVS_ERR_ARG; }
-    if (!normals && n_v > 0) { g_err = std::string(who) + ": normals null"; return MVS_ERR_ARG; }
-    if (int r = need_state(e, NEED_ENGINE, who)) return r;
-    if (n_v == 0 && n_t == 0) return MVS_OK;
-    HIPCHK(hipSetDevice(e->cfg.device));
-    Range rg("mvs:mesh_normals");
-    hipStream_t st = e->stream;
-    DevBuf<float> d_verts, d_normals;
-    DevBuf<int32_t> d_tris;
-    DevBuf<long long> acc;
-    DevBuf<uint32_t> words;  // [0] the bits of the largest component, [1] an index out of range
-    if (d_verts.ensure(3 * n_v) || d_tris.ensure(3 * n_t) || words.ensure(2)) return MVS_ERR_HIP;
-    if (n_v > 0) HIPCHK(hipMemcpyAsync(d_verts.p, verts, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
-    if (n_t > 0) HIPCHK(hipMemcpyAsync(d_tris.p, tris, (size_t)n_t * 3 * sizeof(int32_t), hipMemcpyDefault, st));
-    HIPCHK(hipMemsetAsync(words.p, 0, 2 * sizeof(uint32_t), st));
-    mvsk_mesh_normals_scan(n_v, d_verts.p, n_t, d_tris.p, words.p, words.p + 1, st);
-    uint32_t bad = 0;
-    if (int r = read_back(e, words.p + 1, &bad)) return r;
-    HIPCHK(hipGetLastError());
-    if (bad) { g_err = std::string(who) + ": a vertex index outside 0 .. n_v - 1"; return MVS_ERR_ARG; }
-    if (n_v == 0) return MVS_OK;
-    if (acc.ensure(3 * n_v) || d_normals.ensure(3 * n_v)) return MVS_ERR_HIP;
-    HIPCHK(hipMemsetAsync(acc.p, 0, (size_t)n_v * 3 * sizeof(long long), st));
-    mvsk_mesh_normals_accum(d_verts.p, n_t, d_tris.p, words.p, acc.p, st);
-    mvsk_mesh_normals_finish(n_v, acc.p, d_normals.p, st);
-    HIPCHK(hipMemcpyAsync(normals, d_normals.p, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    return MVS_OK;
-}
-
-void mvs_default_mesh_colouring(mvs_mesh_colouring* m) {
-    if (!m) return;
-    m->occl_tol = 0.01f; m->min_cos = 0.1f;
-}
-
-int mvs_engine_mesh_colours(mvs_engine* e, const mvs_maps_config* c, const mvs_mesh_colouring* m, int64_t n_v, const float* verts, const float* normals,
-                            uint8_t* rgb, uint8_t* used) {
-    const char* who = "mvs_engine_mesh_colours";
-    if (int r = maps_args(c, who)) return r;
-    if (!m) { g_err = std::string(who) + ": colouring null"; return MVS_ERR_ARG; }
-    if (!std::isfinite(m->occl_tol) || !(m->occl_tol > 0.0f)) { g_err = std::string(who) + ": occl_tol not finite or <= 0"; return MVS_ERR_ARG; }
-    if (!std::isfinite(m->min_cos) || !(m->min_cos >= -1.0f && m->min_cos <= 1.0f)) { g_err = std::string(who) + ": min_cos not finite or outside [-1, 1]"; return MVS_ERR_ARG; }
-    if (n_v < 0 || n_v > MESH_ATTR_MAX) { g_err = std::string(who) + ": n_v negative or over 2^30"; return MVS_ERR_ARG; }
-    if ((!verts || !rgb) && n_v > 0) { g_err = std::string(who) + ": verts or rgb null"; return MVS_ERR_ARG; }
-    if (int r = maps_state(e, c, who)) return r;
-    if (n_v == 0) return MVS_OK;
-    HIPCHK(hipSetDevice(e->cfg.device));
-    Range rg("mvs:mesh_colours");
-    hipStream_t st = e->stream;
-    DevBuf<float> d_verts, d_normals;
-    DevBuf<uint8_t> d_rgb, d_used;
-    if (d_rgb.ensure(3 * n_v) || d_used.ensure(n_v)) return MVS_ERR_HIP;
-    int64_t alive = 0;
-    if (int r = mvs_engine_num_patches(e, &alive)) return r;
-    MapsBufs b;
-    if (alive == 0) {  // no surface to hold a vertex against: no view counts
-        HIPCHK(hipMemsetAsync(d_rgb.p, 128, (size_t)n_v * 3, st));
-        HIPCHK(hipMemsetAsync(d_used.p, 0, (size_t)n_v, st));
-    } else {
-        if (int r = render_usable(e, c, b)) return r;
-        if (d_verts.ensure(3 * n_v) || (normals && d_normals.ensure(3 * n_v))) return MVS_ERR_HIP;
-        HIPCHK(hipMemcpyAsync(d_verts.p, verts, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
-        if (normals) HIPCHK(hipMemcpyAsync(d_normals.p, normals, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
-        mvsk_mesh_colours(current_params(e), b.args, MeshColourArgs{m->occl_tol, m->min_cos}, n_v, d_verts.p, normals ? d_normals.p : nullptr, b.ids.p,
-                          b.flag8.p, d_rgb.p, d_used.p, st);
-    }
-    HIPCHK(hipMemcpyAsync(rgb, d_rgb.p, (size_t)n_v * 3, hipMemcpyDefault, st));
-    if (used) HIPCHK(hipMemcpyAsync(used, d_used.p, (size_t)n_v, hipMemcpyDefault, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    return MVS_OK;
-}
-
-// Mesh clean-up (mvs_mesh_clean.hip; the definitions are in mvskit_engine.h): components, pruning, smoothing.  Stateless like the
-// attribute calls: the caller's arrays come into buffers of the call from wherever they lie, the results leave from there.
-static_assert(sizeof(mvs_mesh_pruning) == 16, "mvs_mesh_pruning is 16 bytes");
-static_assert(sizeof(mvs_mesh_smoothing) == 16, "mvs_mesh_smoothing is 16 bytes");
-namespace {
-int mesh_counts(int64_t n_v, int64_t n_t, const char* who) {
-    if (n_v < 0 || n_t < 0 || n_v > MESH_ATTR_MAX || n_t > MESH_ATTR_MAX) { g_err = std::string(who) + ": a count negative or over 2^30"; return MVS_ERR_ARG; }
-    return MVS_OK;
-}
-// the caller's triangles into d_tris, their ids checked (words: one zeroed word of scratch); the stream is idle on return
-int mesh_take_tris(mvs_engine* e, int64_t n_v, int64_t n_t, const int32_t* tris, DevBuf<int32_t>& d_tris, DevBuf<uint32_t>& words, const char* who) {
-    hipStream_t st = e->stream;
-    if (d_tris.ensure(3 * n_t) || words.ensure(2)) return MVS_ERR_HIP;
-    if (n_t > 0) HIPCHK(hipMemcpyAsync(d_tris.p, tris, (size_t)n_t * 3 * sizeof(int32_t), hipMemcpyDefault, st));
-    HIPCHK(hipMemsetAsync(words.p, 0, 2 * sizeof(uint32_t), st));
-    mvsk_mesh_check_ids(n_v, n_t, d_tris.p, words.p, st);
-    uint32_t bad = 0;
-    if (int r = read_back(e, words.p, &bad)) return r;
-    HIPCHK(hipGetLastError());
-    if (bad) { g_err = std::string(who) + ": a vertex index outside 0 .. n_v - 1"; return MVS_ERR_ARG; }
-    return MVS_OK;
-}
-// labels and per-vertex triangle counts of valid triangles on the device (launched, not waited for); ncomp: one word, zeroed here
-int mesh_label(mvs_engine* e, int64_t n_v, int64_t n_t, const int32_t* d_tris, DevBuf<int32_t>& parent, DevBuf<int32_t>& size, DevBuf<unsigned long long>& ncomp) {
-    if (parent.ensure(n_v) || size.ensure(n_v) || ncomp.ensure(2)) return MVS_ERR_HIP;
-    HIPCHK(hipMemsetAsync(ncomp.p, 0, 2 * sizeof(unsigned long long), e->stream));
-    mvsk_mesh_components(n_v, n_t, d_tris, parent.p, size.p, ncomp.p, e->stream);
-    return MVS_OK;
-}
-}  // namespace
-
-int mvs_engine_mesh_components(mvs_engine* e, int64_t n_v, int64_t n_t, const int32_t* tris, int32_t* label, int32_t* ntris, int64_t* n_components) {
-    const char* who = "mvs_engine_mesh_components";
-    if (int r = mesh_counts(n_v, n_t, who)) return r;
-    if (!tris && n_t > 0) { g_err = std::string(who) + ": tris null"; return MVS_ERR_ARG; }
-    if (int r = need_state(e, NEED_ENGINE, who)) return r;
-    if (n_v == 0 && n_t == 0) { if (n_components) *n_components = 0; return MVS_OK; }
-    HIPCHK(hipSetDevice(e->cfg.device));
-    Range rg("mvs:mesh_components");
-    hipStream_t st = e->stream;
-    DevBuf<int32_t> d_tris, parent, size;
-    DevBuf<uint32_t> words;
-    DevBuf<unsigned long long> ncomp;
-    if (int r = mesh_take_tris(e, n_v, n_t, tris, d_tris, words, who)) return r;
-    if (int r = mesh_label(e, n_v, n_t, d_tris.p, parent, size, ncomp)) return r;
-    unsigned long long nc = 0;
-    if (int r = read_back(e, ncomp.p, &nc)) return r;  // a failure is known before anything is written
-    HIPCHK(hipGetLastError());
-    if (label && n_v > 0) HIPCHK(hipMemcpyAsync(label, parent.p, (size_t)n_v * sizeof(int32_t), hipMemcpyDefault, st));
-    if (ntris && n_v > 0) HIPCHK(hipMemcpyAsync(ntris, size.p, (size_t)n_v * sizeof(int32_t), hipMemcpyDefault, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (n_components) *n_components = (int64_t)nc;
-    return MVS_OK;
-}
-
-void mvs_default_mesh_pruning(mvs_mesh_pruning* p) {
-    if (!p) return;
-    p->min_triangles = 1; p->largest_only = 0; p->pad = 0;
-}
-
-int mvs_engine_mesh_prune(mvs_engine* e, const mvs_mesh_pruning* p, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, int64_t cap_v,
-                          float* out_verts, int64_t cap_t, int32_t* out_tris, int32_t* vmap, int64_t* n_v_out, int64_t* n_t_out) {
-    const char* who = "mvs_engine_mesh_prune";
-    if (!p) { g_err = std::string(who) + ": pruning null"; return MVS_ERR_ARG; }
-    if (p->min_triangles < 1) { g_err = std::string(who) + ": min_triangles < 1"; return MVS_ERR_ARG; }
-    if (p->largest_only != 0 && p->largest_only != 1) { g_err = std::string(who) + ": largest_only not 0 or 1"; return MVS_ERR_ARG; }
-    if (int r = mesh_counts(n_v, n_t, who)) return r;
-    if (!verts && n_v > 0) { g_err = std::string(who) + ": verts null"; return MVS_ERR_ARG; }
-    if (!tris && n_t > 0) { g_err = std::string(who) + ": tris null"; return MVS_ERR_ARG; }
-    if (int r = mesh_out_args(cap_v, cap_t, n_v_out, n_t_out, who)) return r;
-    if (int r = need_state(e, NEED_ENGINE, who)) return r;
-    if (n_v == 0 && n_t == 0) { *n_v_out = 0; *n_t_out = 0; return MVS_OK; }
-    HIPCHK(hipSetDevice(e->cfg.device));
-    Range rg("mvs:mesh_prune");
-    hipStream_t st = e->stream;
-    DevBuf<int32_t> d_tris, parent, size, vflag, vbase, tflag, tbase, scan, d_out_tris;
-    DevBuf<uint32_t> words;
-    DevBuf<unsigned long long> ncomp;  // [0] the components, [1] the largest one's key
-    DevBuf<float> d_verts, d_out_verts;
-    if (int r = mesh_take_tris(e, n_v, n_t, tris, d_tris, words, who)) return r;
-    if (int r = mesh_label(e, n_v, n_t, d_tris.p, parent, size, ncomp)) return r;
-    if (vflag.ensure(n_v) || vbase.ensure(n_v + 1) || tflag.ensure(n_t) || tbase.ensure(n_t + 1) || scan.ensure(std::max(n_v, n_t) / 256 + 4096)) return MVS_ERR_HIP;
-    if (n_v > 0) HIPCHK(hipMemsetAsync(vflag.p, 0, (size_t)n_v * sizeof(int32_t), st));
-    if (p->largest_only) mvsk_mesh_largest(n_v, parent.p, size.p, ncomp.p + 1, st);
-    mvsk_mesh_keep(n_t, d_tris.p, parent.p, size.p, p->min_triangles, p->largest_only, ncomp.p + 1, tflag.p, vflag.p, st);
-    int64_t nv = 0, nt = 0;
-    if (int r = scan_total(e, vflag.p, vbase.p, scan.p, n_v, &nv)) return r;
-    if (int r = scan_total(e, tflag.p, tbase.p, scan.p, n_t, &nt)) return r;
-    *n_v_out = nv; *n_t_out = nt;
-    if ((out_verts && cap_v < nv) || (out_tris && cap_t < nt)) { g_err = std::string(who) + ": a cap is smaller than the pruned mesh (*n_v_out, *n_t_out)"; return MVS_ERR_CAPACITY; }
-    if (!out_verts || !out_tris) return MVS_OK;
-    if (d_verts.ensure(3 * n_v) || d_out_verts.ensure(3 * nv) || d_out_tris.ensure(3 * nt)) return MVS_ERR_HIP;
-    if (n_v > 0) HIPCHK(hipMemcpyAsync(d_verts.p, verts, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
-    mvsk_mesh_gather(n_v, d_verts.p, vflag.p, vbase.p, d_out_verts.p, nv, n_t, d_tris.p, tflag.p, tbase.p, d_out_tris.p, nt, st);
-    if (nv > 0) HIPCHK(hipMemcpyAsync(out_verts, d_out_verts.p, (size_t)nv * 3 * sizeof(float), hipMemcpyDefault, st));
-    if (nt > 0) HIPCHK(hipMemcpyAsync(out_tris, d_out_tris.p, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDefault, st));
-    if (vmap && n_v > 0) HIPCHK(hipMemcpyAsync(vmap, vflag.p, (size_t)n_v * sizeof(int32_t), hipMemcpyDefault, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    return MVS_OK;
-}
-
-void mvs_default_mesh_smoothing(mvs_mesh_smoothing* s) {
-    if (!s) return;
-    s->iterations = 10; s->lambda = 0.5f; s->mu = -0.53f; s->pad = 0;
-}
-
-int mvs_engine_mesh_smooth(mvs_engine* e, const mvs_mesh_smoothing* s, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, float* out_verts) {
-    const char* who = "mvs_engine_mesh_smooth";
-    if (!s) { g_err = std::string(who) + ": smoothing null"; return MVS_ERR_ARG; }
-    if (s->iterations < 0 || s->iterations > 1000) { g_err = std::string(who) + ": iterations outside 0..1000"; return MVS_ERR_ARG; }
-    if (!std::isfinite(s->lambda) || !(s->lambda > 0.0f && s->lambda < 1.0f)) { g_err = std::string(who) + ": lambda not finite or outside (0, 1)"; return MVS_ERR_ARG; }
-    if (!std::isfinite(s->mu) || !(s->mu > -1.0f && s->mu <= 0.0f)) { g_err = std::string(who) + ": mu not finite or outside (-1, 0]"; return MVS_ERR_ARG; }
-    if (int r = mesh_counts(n_v, n_t, who)) return r;
-    if (((!verts || !out_verts) && n_v > 0) || (!tris && n_t > 0)) { g_err = std::string(who) + ": verts, tris or out_verts null"; return MVS_ERR_ARG; }
-    if (int r = need_state(e, NEED_ENGINE, who)) return r;
-    if (n_v == 0 && n_t == 0) return MVS_OK;
-    HIPCHK(hipSetDevice(e->cfg.device));
-    Range rg("mvs:mesh_smooth");
-    hipStream_t st = e->stream;
-    const bool two = s->mu != 0.0f;
-    const int steps = s->iterations * (two ? 2 : 1);
-    DevBuf<int32_t> d_tris, cnt;
-    DevBuf<uint32_t> words, mbits;  // mbits: the bits of the largest component, a word per step
-    DevBuf<float> xa, xb;
-    DevBuf<long long> acc;
-    if (int r = mesh_take_tris(e, n_v, n_t, tris, d_tris, words, who)) return r;
-    if (n_v == 0) return MVS_OK;
-    if (xa.ensure(3 * n_v) || xb.ensure(3 * n_v) || acc.ensure(3 * n_v) || cnt.ensure(n_v) || mbits.ensure(steps + 1)) return MVS_ERR_HIP;
-    HIPCHK(hipMemcpyAsync(xa.p, verts, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
-    HIPCHK(hipMemsetAsync(acc.p, 0, (size_t)n_v * 3 * sizeof(long long), st));
-    HIPCHK(hipMemsetAsync(cnt.p, 0, (size_t)n_v * sizeof(int32_t), st));
-    HIPCHK(hipMemsetAsync(mbits.p, 0, (size_t)(steps + 1) * sizeof(uint32_t), st));
-    float *from = xa.p, *to = xb.p;
-    for (int k = 0; k < steps; ++k) {
-        mvsk_mesh_smooth_step(n_v, from, to, (two && (k & 1)) ? s->mu : s->lambda, n_t, d_tris.p, mbits.p + k, acc.p, cnt.p, st);
-        std::swap(from, to);
-    }
-    HIPCHK(hipStreamSynchronize(st));  // a failure is known before anything is written
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out_verts, from, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return MVS_OK;
-}
-
-// Mesh decimation (mvs_mesh_decimate.hip; the definition is in mvskit_engine.h): vertex clustering on the caller's grid.  Stateless like
-// the clean-up calls.  One table serves three fills: the cells of the members, then the two keys that find the duplicate triangles.
-static_assert(sizeof(mvs_mesh_decimation) == 24, "mvs_mesh_decimation is 24 bytes");
-namespace {
-int64_t mdec_slots(int64_t n) {
-    int64_t s = 1024;
-    while (s < 2 * n) s <<= 1;
-    return s;
-}
-// an empty table of `slots` slots, then out[i] = the smallest item that carries key[i]
-int mdec_fill(mvs_engine* e, int64_t n, const unsigned long long* key, DevBuf<unsigned long long>& tkey, DevBuf<int32_t>& tval, int32_t* out, uint32_t* fail) {
-    if (n == 0) return MVS_OK;
-    const int64_t slots = mdec_slots(n);
-    HIPCHK(hipMemsetAsync(tkey.p, 0xff, (size_t)slots * sizeof(unsigned long long), e->stream));
-    HIPCHK(hipMemsetAsync(tval.p, 0x7f, (size_t)slots * sizeof(int32_t), e->stream));
-    mvsk_mdec_table(n, key, tkey.p, tval.p, slots, out, fail, e->stream);
-    return MVS_OK;
-}
-}  // namespace
-
-void mvs_default_mesh_decimation(mvs_mesh_decimation* d) {
-    if (!d) return;
-    d->origin[0] = d->origin[1] = d->origin[2] = 0.0f;
-    d->cell = 1.0f; d->placement = 0; d->pad = 0;
-}
-
-int mvs_engine_mesh_decimate(mvs_engine* e, const mvs_mesh_decimation* d, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, int64_t cap_v,
-                             float* out_verts, int64_t cap_t, int32_t* out_tris, int32_t* vmap, int64_t* n_v_out, int64_t* n_t_out) {
-    const char* who = "mvs_engine_mesh_decimate";
-    if (!d) { g_err = std::string(who) + ": decimation null"; return MVS_ERR_ARG; }
-    if (!std::isfinite(d->cell) || !(d->cell > 0.0f)) { g_err = std::string(who) + ": cell not finite or <= 0"; return MVS_ERR_ARG; }
-    if (!std::isfinite(d->origin[0]) || !std::isfinite(d->origin[1]) || !std::isfinite(d->origin[2])) { g_err = std::string(who) + ": origin not finite"; return MVS_ERR_ARG; }
-    if (d->placement != 0 && d->placement != 1) { g_err = std::string(who) + ": placement not 0 or 1"; return MVS_ERR_ARG; }
-    if (int r = mesh_counts(n_v, n_t, who)) return r;
-    if (!verts && n_v > 0) { g_err = std::string(who) + ": verts null"; return MVS_ERR_ARG; }
-    if (!tris && n_t > 0) { g_err = std::string(who) + ": tris null"; return MVS_ERR_ARG; }
-    if (int r = mesh_out_args(cap_v, cap_t, n_v_out, n_t_out, who)) return r;
-    if (int r = need_state(e, NEED_ENGINE, who)) return r;
-    if (n_v == 0 && n_t == 0) { *n_v_out = 0; *n_t_out = 0; return MVS_OK; }
-    HIPCHK(hipSetDevice(e->cfg.device));
-    Range rg("mvs:mesh_decimate");
-    hipStream_t st = e->stream;
-    DevBuf<int32_t> d_tris, used, rep, tval, tans, tflag, tbase, vflag, vbase, scan, cnt, d_out_tris;
-    DevBuf<uint32_t> words, flags;  // flags: [0] the bits of the members' largest component, [1] a member not finite or outside the grid, [2] a probe that ran out
-    DevBuf<unsigned long long> vkey, tkeys, tkey, best;
-    DevBuf<long long> acc;
-    DevBuf<float> d_verts, d_out_verts;
-    if (int r = mesh_take_tris(e, n_v, n_t, tris, d_tris, words, who)) return r;
-    const int64_t slots = mdec_slots(std::max(n_v, n_t));
-    if (d_verts.ensure(3 * n_v) || used.ensure(n_v) || vkey.ensure(n_v) || rep.ensure(n_v) || flags.ensure(4) || tkey.ensure(slots) || tval.ensure(slots)) return MVS_ERR_HIP;
-    if (n_v > 0) HIPCHK(hipMemcpyAsync(d_verts.p, verts, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
-    if (n_v > 0) HIPCHK(hipMemsetAsync(used.p, 0, (size_t)n_v * sizeof(int32_t), st));
-    HIPCHK(hipMemsetAsync(flags.p, 0, 4 * sizeof(uint32_t), st));
-    mvsk_mdec_members(n_v, d_verts.p, n_t, d_tris.p, d->origin, d->cell, used.p, vkey.p, flags.p, flags.p + 1, st);
-    if (int r = mdec_fill(e, n_v, vkey.p, tkey, tval, rep.p, flags.p + 2)) return r;  // a refused member has no key
-    uint32_t hf[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(hf, flags.p, sizeof(hf), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    if (hf[1]) { g_err = std::string(who) + ": a member with a non-finite component or a cell index outside -2^20 .. 2^20 - 1"; return MVS_ERR_ARG; }
-    if (hf[2]) { g_err = std::string(who) + ": the cell table found no slot"; return MVS_ERR_HIP; }
-    if (tkeys.ensure(n_t) || tans.ensure(n_t) || tflag.ensure(n_t) || tbase.ensure(n_t + 1) || vflag.ensure(n_v) || vbase.ensure(n_v + 1) ||
-        scan.ensure(std::max(n_v, n_t) / 256 + 4096))
-        return MVS_ERR_HIP;
-    mvsk_mdec_tkey1(n_t, d_tris.p, rep.p, tkeys.p, st);
-    if (int r = mdec_fill(e, n_t, tkeys.p, tkey, tval, tans.p, flags.p + 2)) return r;
-    mvsk_mdec_tkey2(n_t, d_tris.p, rep.p, tans.p, tkeys.p, st);
-    if (int r = mdec_fill(e, n_t, tkeys.p, tkey, tval, tans.p, flags.p + 2)) return r;
-    if (n_v > 0) HIPCHK(hipMemsetAsync(vflag.p, 0, (size_t)n_v * sizeof(int32_t), st));
-    mvsk_mdec_keep(n_t, d_tris.p, rep.p, tans.p, tflag.p, vflag.p, st);
-    int64_t nv = 0, nt = 0;
-    if (int r = scan_total(e, vflag.p, vbase.p, scan.p, n_v, &nv)) return r;
-    if (int r = scan_total(e, tflag.p, tbase.p, scan.p, n_t, &nt)) return r;
-    if (int r = read_back(e, flags.p + 2, &hf[2])) return r;
-    HIPCHK(hipGetLastError());
-    if (hf[2]) { g_err = std::string(who) + ": the triangle table found no slot"; return MVS_ERR_HIP; }
-    *n_v_out = nv; *n_t_out = nt;
-    if ((out_verts && cap_v < nv) || (out_tris && cap_t < nt)) { g_err = std::string(who) + ": a cap is smaller than the decimated mesh (*n_v_out, *n_t_out)"; return MVS_ERR_CAPACITY; }
-    if (!out_verts || !out_tris) return MVS_OK;
-    if (acc.ensure(3 * n_v) || cnt.ensure(n_v) || (d->placement == 1 && best.ensure(n_v)) || d_out_verts.ensure(3 * nv) || d_out_tris.ensure(3 * nt)) return MVS_ERR_HIP;
-    if (n_v > 0) {
-        HIPCHK(hipMemsetAsync(acc.p, 0, (size_t)n_v * 3 * sizeof(long long), st));
-        HIPCHK(hipMemsetAsync(cnt.p, 0, (size_t)n_v * sizeof(int32_t), st));
-        if (d->placement == 1) HIPCHK(hipMemsetAsync(best.p, 0xff, (size_t)n_v * sizeof(unsigned long long), st));
-    }
-    mvsk_mdec_positions(d->placement, n_v, d_verts.p, rep.p, vflag.p, vbase.p, flags.p, acc.p, cnt.p, best.p, d_out_verts.p, nv, st);
-    mvsk_mdec_gather(n_v, rep.p, vflag.p, vbase.p, used.p, n_t, d_tris.p, tflag.p, tbase.p, d_out_tris.p, nt, st);  // used becomes the vertex map
-    HIPCHK(hipStreamSynchronize(st));  // a failure is known before anything is written
-    HIPCHK(hipGetLastError());
-    if (nv > 0) HIPCHK(hipMemcpyAsync(out_verts, d_out_verts.p, (size_t)nv * 3 * sizeof(float), hipMemcpyDefault, st));
-    if (nt > 0) HIPCHK(hipMemcpyAsync(out_tris, d_out_tris.p, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDefault, st));
-    if (vmap && n_v > 0) HIPCHK(hipMemcpyAsync(vmap, used.p, (size_t)n_v * sizeof(int32_t), hipMemcpyDefault, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
-    return MVS_OK;
-}
-
-// Mesh hole filling (mvs_mesh_fill.hip; the definitions are in mvskit_engine.h): the boundary loops and their centroid fans.  Stateless
-// like the clean-up calls.  Both calls label the boundary components the same way; the filling goes on from there.
-static_assert(sizeof(mvs_mesh_filling) == 8, "mvs_mesh_filling is 8 bytes");
-namespace {
-struct MfillBufs {
-    DevBuf<int32_t> d_tris, tval, parent, outc, inc, cplx, next, hed, rbad, loop, length;
-    DevBuf<uint32_t> words, flags;        // flags: [0] the bits of the centroids' largest component, [1] a loop vertex not finite, [2] a probe that ran out
-    DevBuf<unsigned long long> tkey, counts;  // counts: [0] loops, [1] complex components, [2] irregular pairs, [3] filled loops
-};
-// the caller's triangles checked and labelled: b.loop, b.length, b.next and hc[0..2] (hc[3] = 0); the stream is idle on return
-int mfill_label(mvs_engine* e, int64_t n_v, int64_t n_t, const int32_t* tris, MfillBufs& b, unsigned long long hc[4], const char* who) {
-    hipStream_t st = e->stream;
-    if (int r = mesh_take_tris(e, n_v, n_t, tris, b.d_tris, b.words, who)) return r;
-    const int64_t slots = mdec_slots(3 * n_t);
-    if (b.parent.ensure(n_v) || b.outc.ensure(n_v) || b.inc.ensure(n_v) || b.cplx.ensure(n_v) || b.next.ensure(n_v) || b.hed.ensure(n_v) || b.rbad.ensure(n_v) ||
-        b.loop.ensure(n_v) || b.length.ensure(n_v) || b.flags.ensure(4) || b.counts.ensure(4) || (n_t > 0 && (b.tkey.ensure(slots) || b.tval.ensure(slots))))
-        return MVS_ERR_HIP;
-    for (DevBuf<int32_t>* z : {&b.outc, &b.inc, &b.cplx, &b.next, &b.hed, &b.rbad})
-        if (n_v > 0) HIPCHK(hipMemsetAsync(z->p, 0, (size_t)n_v * sizeof(int32_t), st));
-    HIPCHK(hipMemsetAsync(b.flags.p, 0, 4 * sizeof(uint32_t), st));
-    HIPCHK(hipMemsetAsync(b.counts.p, 0, 4 * sizeof(unsigned long long), st));
-    if (n_t > 0) {
-        HIPCHK(hipMemsetAsync(b.tkey.p, 0xff, (size_t)slots * sizeof(unsigned long long), st));
-        HIPCHK(hipMemsetAsync(b.tval.p, 0, (size_t)slots * sizeof(int32_t), st));
-    }
-    mvsk_mfill_boundaries(n_v, n_t, b.d_tris.p, b.tkey.p, b.tval.p, slots, b.parent.p, b.outc.p, b.inc.p, b.cplx.p, b.next.p, b.hed.p, b.rbad.p, b.loop.p,
-                          b.length.p, b.counts.p, b.flags.p + 2, st);
-    uint32_t fail = 0;
-    HIPCHK(hipMemcpyAsync(hc, b.counts.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    if (int r = read_back(e, b.flags.p + 2, &fail)) return r;
-    HIPCHK(hipGetLastError());
-    if (fail) { g_err = std::string(who) + ": the edge table found no slot"; return MVS_ERR_HIP; }
-    return MVS_OK;
-}
-}  // namespace
-
-int mvs_engine_mesh_boundaries(mvs_engine* e, int64_t n_v, int64_t n_t, const int32_t* tris, int32_t* loop, int32_t* length, int64_t* n_loops, int64_t* n_complex,
-                               int64_t* n_irregular) {
-    const char* who = "mvs_engine_mesh_boundaries";
-    if (int r = mesh_counts(n_v, n_t, who)) return r;
-    if (!tris && n_t > 0) { g_err = std::string(who) + ": tris null"; return MVS_ERR_ARG; }
-    if (int r = need_state(e, NEED_ENGINE, who)) return r;
-    unsigned long long hc[4] = {0, 0, 0, 0};
-    if (n_v > 0 || n_t > 0) {
-        HIPCHK(hipSetDevice(e->cfg.device));
-        Range rg("mvs:mesh_boundaries");
-        hipStream_t st = e->stream;
-        MfillBufs b;
-        if (int r = mfill_label(e, n_v, n_t, tris, b, hc, who)) return r;  // a failure is known before anything is written
-        if (loop && n_v > 0) HIPCHK(hipMemcpyAsync(loop, b.loop.p, (size_t)n_v * sizeof(int32_t), hipMemcpyDefault, st));
-        if (length && n_v > 0) HIPCHK(hipMemcpyAsync(length, b.length.p, (size_t)n_v * sizeof(int32_t), hipMemcpyDefault, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    if (n_loops) *n_loops = (int64_t)hc[0];
-    if (n_complex) *n_complex = (int64_t)hc[1];
-    if (n_irregular) *n_irregular = (int64_t)hc[2];
-    return MVS_OK;
-}
-
-void mvs_default_mesh_filling(mvs_mesh_filling* f) {
-    if (!f) return;
-    f->max_edges = 64; f->pad = 0;
-}
-
-int mvs_engine_mesh_fill(mvs_engine* e, const mvs_mesh_filling* f, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, int64_t cap_v,
-                         float* out_verts, int64_t cap_t, int32_t* out_tris, int64_t* n_v_out, int64_t* n_t_out, int64_t* n_filled) {
-    const char* who = "mvs_engine_mesh_fill";
-    if (!f) { g_err = std::string(who) + ": filling null"; return MVS_ERR_ARG; }
-    if (f->max_edges < 3) { g_err = std::string(who) + ": max_edges < 3"; return MVS_ERR_ARG; }
-    if (int r = mesh_counts(n_v, n_t, who)) return r;
-    if (!verts && n_v > 0) { g_err = std::string(who) + ": verts null"; return MVS_ERR_ARG; }
-    if (!tris && n_t > 0) { g_err = std::string(who) + ": tris null"; return MVS_ERR_ARG; }
-    if (int r = mesh_out_args(cap_v, cap_t, n_v_out, n_t_out, who)) return r;
-    if (int r = need_state(e, NEED_ENGINE, who)) return r;
-    if (n_v == 0 && n_t == 0) { *n_v_out = 0; *n_t_out = 0; if (n_filled) *n_filled = 0; return MVS_OK; }
-    HIPCHK(hipSetDevice(e->cfg.device));
-    Range rg("mvs:mesh_fill");
-    hipStream_t st = e->stream;
-    MfillBufs b;
-    DevBuf<int32_t> tcnt, tbase, vcnt, vbase, scan, add_tris;
-    DevBuf<float> d_verts, add_verts;
-    DevBuf<long long> acc;
-    unsigned long long hc[4] = {0, 0, 0, 0};
-    if (int r = mfill_label(e, n_v, n_t, tris, b, hc, who)) return r;
-    if (d_verts.ensure(3 * n_v) || tcnt.ensure(n_v) || tbase.ensure(n_v + 1) || vcnt.ensure(n_v) || vbase.ensure(n_v + 1) || scan.ensure(n_v / 256 + 4096)) return MVS_ERR_HIP;
-    if (n_v > 0) HIPCHK(hipMemcpyAsync(d_verts.p, verts, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
-    mvsk_mfill_plan(n_v, d_verts.p, b.loop.p, b.length.p, f->max_edges, tcnt.p, vcnt.p, b.flags.p, b.flags.p + 1, b.counts.p + 3, st);
-    int64_t nv_add = 0, nt_add = 0;
-    if (int r = scan_total(e, tcnt.p, tbase.p, scan.p, n_v, &nt_add)) return r;
-    if (int r = scan_total(e, vcnt.p, vbase.p, scan.p, n_v, &nv_add)) return r;
-    uint32_t bad = 0;
-    HIPCHK(hipMemcpyAsync(&hc[3], b.counts.p + 3, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    if (int r = read_back(e, b.flags.p + 1, &bad)) return r;
-    HIPCHK(hipGetLastError());
-    if (bad) { g_err = std::string(who) + ": a loop vertex with a non-finite component"; return MVS_ERR_ARG; }
-    const int64_t nv = n_v + nv_add, nt = n_t + nt_add;
-    if (nv > MESH_ATTR_MAX || nt > MESH_ATTR_MAX) { g_err = std::string(who) + ": the filled mesh has more than 2^30 vertices or triangles"; return MVS_ERR_CAPACITY; }
-    *n_v_out = nv; *n_t_out = nt;
-    if (n_filled) *n_filled = (int64_t)hc[3];
-    if ((out_verts && cap_v < nv) || (out_tris && cap_t < nt)) { g_err = std::string(who) + ": a cap is smaller than the filled mesh (*n_v_out, *n_t_out)"; return MVS_ERR_CAPACITY; }
-    if (!out_verts || !out_tris) return MVS_OK;
-    if (nt_add > 0) {
-        if (acc.ensure(3 * n_v) || add_tris.ensure(3 * nt_add) || add_verts.ensure(3 * nv_add)) return MVS_ERR_HIP;
-        HIPCHK(hipMemsetAsync(acc.p, 0, (size_t)n_v * 3 * sizeof(long long), st));
-        mvsk_mfill_emit(n_v, d_verts.p, b.loop.p, b.length.p, f->max_edges, b.next.p, tbase.p, vbase.p, b.flags.p, acc.p, add_tris.p, nt_add, add_verts.p, nv_add, st);
-        HIPCHK(hipStreamSynchronize(st));  // a failure is known before anything is written
-        HIPCHK(hipGetLastError());
-    }
-    if (n_v > 0) HIPCHK(hipMemcpyAsync(out_verts, d_verts.p, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
-    if (n_t > 0) HIPCHK(hipMemcpyAsync(out_tris, b.d_tris.p, (size_t)n_t * 3 * sizeof(int32_t), hipMemcpyDefault, st));
-    if (nv_add > 0) HIPCHK(hipMemcpyAsync(out_verts + 3 * n_v, add_verts.p, (size_t)nv_add * 3 * sizeof(float), hipMemcpyDefault, st));
-    if (nt_add > 0) HIPCHK(hipMemcpyAsync(out_tris + 3 * n_t, add_tris.p, (size_t)nt_add * 3 * sizeof(int32_t), hipMemcpyDefault, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
     return MVS_OK;
 }
 

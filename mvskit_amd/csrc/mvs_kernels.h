@@ -163,6 +163,8 @@ void mvsk_mesh_colours(const DParams& prm, const MapsArgs& a, const MeshColourAr
 void mvsk_mesh_check_ids(int64_t n_v, int64_t n_t, const int32_t* tris, uint32_t* bad, hipStream_t st);
 // parent[i] = the smallest id of i's component, size[i] = the triangles of that component, *ncomp += the components with a triangle
 void mvsk_mesh_components(int64_t n_v, int64_t n_t, const int32_t* tris, int32_t* parent, int32_t* size, unsigned long long* ncomp, hipStream_t st);
+// parent[i] = the root of i in a union-find whose unions are done (the third launch of mvsk_mesh_components; mvs_mesh_fill.hip's too)
+void mvsk_mesh_flatten(int64_t n_v, int32_t* parent, hipStream_t st);
 // *best = max over the components with a triangle of (size << 32) | (0xffffffff - label) (zero before the launch)
 void mvsk_mesh_largest(int64_t n_v, const int32_t* parent, const int32_t* size, unsigned long long* best, hipStream_t st);
 // tflag[t] = triangle t is kept; vflag[i] = 1 where a kept triangle names vertex i (vflag zero before the launch); best is read with largest_only
