@@ -709,6 +709,68 @@ int mvs_engine_mesh_fill(mvs_engine* e, const mvs_mesh_filling* f, int64_t n_v, 
                          int64_t cap_v, float* out_verts, int64_t cap_t, int32_t* out_tris, int64_t* n_v_out, int64_t* n_t_out,
                          int64_t* n_filled /* or NULL */);
 
+/* Mesh render (no reference counterpart): a triangle mesh SEEN FROM THE VIEWS -- per view the z-buffer depth and triangle row of every
+ * pixel, per vertex the views that see it, and the colouring call that takes that visibility.  mvs_engine_mesh_colours decides occlusion
+ * against the dense maps; after fill, smooth and decimate (or for a caller's own mesh) the maps say nothing where the vertices are, and
+ * this is the occlusion test against the mesh itself.  verts: n_v x 3 floats, tris: n_t x 3 int32 vertex ids.  The three calls are
+ * stateless and only read the engine; mesh_render and mesh_visibility need views but no pool; all pointers may be host or device memory
+ * (hipMemcpyDefault; the array `out` itself is host memory).  Masks play no part in the render: the caller combines them.  Every result is
+ * integer arithmetic or an fp64 chain without contraction behind an associative minimum: the same bytes in any triangle order and across
+ * two calls.  A refused call writes nothing.
+ * Per view v at level L = m_level (W x H = the view's size there):
+ *     VERTEX        r0, r1, r2 = the three fp32 fma chains of Camera::project on P_L; inv = the correctly rounded 1 / r2; x = r0 inv,
+ *                   y = r1 inv, each clamped to +-2^31 as Camera::project does (a NaN becomes +2^31).  d = r2 is the depth along the optical
+ *                   axis under mvs_view_desc's precondition |P[2,:3]| = 1.  sx = llrint((double)x * 256), sy alike: the product is exact,
+ *                   the rounding half-to-even.  The vertex is USABLE when d > 0, d is finite and |sx|, |sy| <= 2^24 (a NaN fails).
+ *                   screen and vdepth return (sx, sy) -- saturated to int32 where the vertex is not usable -- and d for every vertex.
+ *     TRIANGLE      one with an unusable vertex is SKIPPED and counted in n_skipped[v]: THERE IS NO NEAR-PLANE CLIPPING, a triangle that
+ *                   crosses the camera plane is not drawn at all.  area = (x1-x0)(y2-y0) - (y1-y0)(x2-x0) in int64; area == 0 covers
+ *                   nothing (and is not skipped); area < 0 swaps vertices 1 and 2.  Both faces render: there is no culling.
+ *     COVERAGE      the centre of the integer pixel (px, py) inside the image is q = (256 px, 256 py).  For each directed edge a -> b with
+ *                   (dx, dy) = b - a: E = dx (qy - ay) - dy (qx - ax), below 2^51 and exact.  The pixel is covered when every E > 0, or
+ *                   E == 0 on a top-left edge (dy < 0, or dy == 0 and dx > 0): a pixel on a shared edge belongs to one triangle.
+ *     DEPTH         in fp64, left to right, without contraction: w_i = 1.0 / (double)d_i; inv = ((double)E0 w0 + (double)E1 w1 +
+ *                   (double)E2 w2) / (double)area with E_i the edge opposite vertex i; depth = (float)(1.0 / inv).  A depth that is
+ *                   not finite is not written.
+ *     Z-BUFFER      the pixel keeps the smallest 64-bit key (bits(depth) << 32) | t: the nearest depth, and on an exact tie the smallest
+ *                   triangle row t.  n_covered[v] = the pixels with a key.
+ * mvs_engine_mesh_render: out[v].depth (quiet NaN where no triangle covers the centre) and out[v].tri (-1 there), H x W each; out, either
+ * pointer of a view, screen, vdepth, n_covered and n_skipped may be NULL: not wanted.
+ * mvs_engine_mesh_visibility: bit v of visible[i] is set when vertex i is usable in view v, its nearest pixel ((sx + 128) >> 8,
+ * (sy + 128) >> 8) (arithmetic shift) lies inside the image, and that pixel is empty or (double)d <= (double)z * (1.0 + (double)tol) for
+ * its rendered depth z.  Bits at and above nviews are 0.
+ * mvs_engine_mesh_colours_visible: mvs_engine_mesh_colours with one more gate -- view v takes part for vertex i only when bit v of
+ * visible[i] is set.  With visible == NULL it is mvs_engine_mesh_colours, byte for byte; its checks and errors are that call's.
+ * LIMITS: n_v, n_t in 0 .. 2^30.  Device memory for a render or visibility call: 16 bytes a vertex (and the 12 of the input), 12 a triangle
+ * plus 4 for the list of the large ones, per pixel of the largest view 8 for the keys and 8 for the two maps; 8 a vertex more for the
+ * visibility.  A triangle whose clipped bounding box holds more than 32 pixel centres is rasterised by a wave of its own, in tiles of
+ * 8 x 8 pixels: one that spans the image costs that wave W H / 64 steps.  MVS_MRENDER_SMALL=<n> in the environment (read at every call of
+ * the render, the visibility and the list counts; n >= 1) puts another number in the place of the 32: a tuning switch of
+ * tools/mesh_render_probe.py.  No map, count or visibility bit depends on it.
+ * mvs_engine_mesh_render_lists: n_listed[v] = the triangles of view v that went to the wave-per-triangle kernel (usable, area != 0, a
+ * clipped box of more than 32 pixel centres), counted by the device as it renders; the maps are not made.  It is how a caller, the tests
+ * and the probe see which of the two rasterising kernels a mesh runs on.  Arguments, state and errors as mvs_engine_mesh_render's, and
+ * n_listed NULL is MVS_ERR_ARG behind the arrays.
+ * MVS_ERR_ARG, checked in this order before the handle is read: (visibility: tol not finite or negative;) a negative count or a count
+ * over the limit; verts NULL with n_v > 0; tris NULL with n_t > 0; (visibility: visible NULL with n_v > 0;) no engine.  MVS_ERR_STATE: the
+ * views are not set, or a pass is waiting for its commit.  Then MVS_ERR_ARG after one validating pass on the device: an id outside
+ * 0 .. n_v - 1.  MVS_ERR_HIP: an allocation or copy failed.
+ * WHAT THE RENDER DOES NOT DO: near-plane clipping, back-face culling, masks, interpolation of attributes other than depth, a texture
+ * atlas, a variant sharded over GPUs. */
+typedef struct mvs_mesh_view_render {
+    float* depth; /* H_L*W_L: depth of the nearest triangle at the pixel centre; quiet NaN where none covers it */
+    int32_t* tri; /* H_L*W_L: that triangle's row in tris; -1 */
+} mvs_mesh_view_render; /* 16 bytes */
+int mvs_engine_mesh_render(mvs_engine* e, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris,
+                           mvs_mesh_view_render* out /* [nviews] or NULL; either pointer NULL: not wanted */,
+                           int32_t* screen /* [nviews][n_v][2] or NULL */, float* vdepth /* [nviews][n_v] or NULL */,
+                           int64_t* n_covered /* [nviews] or NULL */, int64_t* n_skipped /* [nviews] or NULL */);
+int mvs_engine_mesh_render_lists(mvs_engine* e, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, int64_t* n_listed /* [nviews] */);
+int mvs_engine_mesh_visibility(mvs_engine* e, float tol, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris,
+                               uint64_t* visible /* [n_v] */);
+int mvs_engine_mesh_colours_visible(mvs_engine* e, const mvs_maps_config* c, const mvs_mesh_colouring* m, int64_t n_v, const float* verts,
+                                    const float* normals, const uint64_t* visible /* [n_v] or NULL */, uint8_t* rgb, uint8_t* used);
+
 /* Propagate::run(iter), propagate.cpp:28-64: two colour passes, each = index build + sweep + commit */
 int mvs_engine_propagate(mvs_engine* e, int iter, mvs_counters* out);
 

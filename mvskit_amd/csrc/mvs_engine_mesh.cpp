@@ -1,9 +1,11 @@
 // mvs_engine_mesh.cpp -- the mesh calls of the C ABI in include/mvskit_engine.h: the TSDF volume over the dense maps and its extraction
 // (mvs_mesh.hip), vertex normals and colours (mvs_mesh_attr.hip), components, pruning and smoothing (mvs_mesh_clean.hip), decimation
-// (mvs_mesh_decimate.hip), boundary loops and hole filling (mvs_mesh_fill.hip).  The maps they start from come from
+// (mvs_mesh_decimate.hip), boundary loops and hole filling (mvs_mesh_fill.hip), the mesh rendered into the views and the vertex
+// visibility (mvs_mesh_render.hip).  The maps they start from come from
 // mvs_engine_output.cpp (render_usable).  Every entry point is stateless: its working arrays live in buffers of the call, the caller's
 // arrays come into them from wherever they lie, and nothing of the engine's state changes.
 #include <cmath>
+#include <cstdlib>
 
 #include "mvs_engine_impl.h"
 
@@ -208,9 +210,10 @@ void mvs_default_mesh_colouring(mvs_mesh_colouring* m) {
     m->occl_tol = 0.01f; m->min_cos = 0.1f;
 }
 
-int mvs_engine_mesh_colours(mvs_engine* e, const mvs_maps_config* c, const mvs_mesh_colouring* m, int64_t n_v, const float* verts, const float* normals,
-                            uint8_t* rgb, uint8_t* used) {
-    const char* who = "mvs_engine_mesh_colours";
+namespace {
+// both colouring calls; visible (host or device memory) may be null: no gate then, and k_mattr_colours runs as it always did
+int mesh_colours(mvs_engine* e, const mvs_maps_config* c, const mvs_mesh_colouring* m, int64_t n_v, const float* verts, const float* normals,
+                 const uint64_t* visible, uint8_t* rgb, uint8_t* used, const char* who) {
     if (int r = maps_args(c, who)) return r;
     if (!m) { g_err = std::string(who) + ": colouring null"; return MVS_ERR_ARG; }
     if (!std::isfinite(m->occl_tol) || !(m->occl_tol > 0.0f)) { g_err = std::string(who) + ": occl_tol not finite or <= 0"; return MVS_ERR_ARG; }
@@ -224,6 +227,7 @@ int mvs_engine_mesh_colours(mvs_engine* e, const mvs_maps_config* c, const mvs_m
     hipStream_t st = e->stream;
     DevBuf<float> d_verts, d_normals;
     DevBuf<uint8_t> d_rgb, d_used;
+    DevBuf<unsigned long long> d_visible;
     if (d_rgb.ensure(3 * n_v) || d_used.ensure(n_v)) return MVS_ERR_HIP;
     int64_t alive = 0;
     if (int r = mvs_engine_num_patches(e, &alive)) return r;
@@ -236,14 +240,32 @@ int mvs_engine_mesh_colours(mvs_engine* e, const mvs_maps_config* c, const mvs_m
         if (d_verts.ensure(3 * n_v) || (normals && d_normals.ensure(3 * n_v))) return MVS_ERR_HIP;
         if (int r = upload_rows(e, d_verts.p, verts, n_v)) return r;
         if (normals) HIPCHK(hipMemcpyAsync(d_normals.p, normals, (size_t)n_v * 3 * sizeof(float), hipMemcpyDefault, st));
-        mvsk_mesh_colours(current_params(e), b.args, MeshColourArgs{m->occl_tol, m->min_cos}, n_v, d_verts.p, normals ? d_normals.p : nullptr, b.ids.p,
-                          b.flag8.p, d_rgb.p, d_used.p, st);
+        if (visible) {
+            if (d_visible.ensure(n_v)) return MVS_ERR_HIP;
+            HIPCHK(hipMemcpyAsync(d_visible.p, visible, (size_t)n_v * sizeof(uint64_t), hipMemcpyDefault, st));
+            mvsk_mesh_colours_visible(current_params(e), b.args, MeshColourArgs{m->occl_tol, m->min_cos}, n_v, d_verts.p, normals ? d_normals.p : nullptr,
+                                      b.ids.p, b.flag8.p, d_visible.p, d_rgb.p, d_used.p, st);
+        } else {
+            mvsk_mesh_colours(current_params(e), b.args, MeshColourArgs{m->occl_tol, m->min_cos}, n_v, d_verts.p, normals ? d_normals.p : nullptr, b.ids.p,
+                              b.flag8.p, d_rgb.p, d_used.p, st);
+        }
     }
     HIPCHK(hipMemcpyAsync(rgb, d_rgb.p, (size_t)n_v * 3, hipMemcpyDefault, st));
     if (used) HIPCHK(hipMemcpyAsync(used, d_used.p, (size_t)n_v, hipMemcpyDefault, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
     return MVS_OK;
+}
+}  // namespace
+
+int mvs_engine_mesh_colours(mvs_engine* e, const mvs_maps_config* c, const mvs_mesh_colouring* m, int64_t n_v, const float* verts, const float* normals,
+                            uint8_t* rgb, uint8_t* used) {
+    return mesh_colours(e, c, m, n_v, verts, normals, nullptr, rgb, used, "mvs_engine_mesh_colours");
+}
+
+int mvs_engine_mesh_colours_visible(mvs_engine* e, const mvs_maps_config* c, const mvs_mesh_colouring* m, int64_t n_v, const float* verts, const float* normals,
+                                    const uint64_t* visible, uint8_t* rgb, uint8_t* used) {
+    return mesh_colours(e, c, m, n_v, verts, normals, visible, rgb, used, "mvs_engine_mesh_colours_visible");
 }
 
 // Mesh clean-up (mvs_mesh_clean.hip; the definitions are in mvskit_engine.h): components, pruning, smoothing.  Stateless like the
@@ -595,6 +617,136 @@ int mvs_engine_mesh_fill(mvs_engine* e, const mvs_mesh_filling* f, int64_t n_v, 
     if (nt_add > 0) HIPCHK(hipMemcpyAsync(out_tris + 3 * n_t, add_tris.p, (size_t)nt_add * 3 * sizeof(int32_t), hipMemcpyDefault, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
+    return MVS_OK;
+}
+
+// Mesh render (mvs_mesh_render.hip; the definitions are in mvskit_engine.h): a z-buffer of the mesh in every view and the vertex
+// visibility from it.  Stateless like the clean-up calls, but with views: they stream through one set of per-view buffers, as the maps do.
+static_assert(sizeof(mvs_mesh_view_render) == 16, "mvs_mesh_view_render is 16 bytes");
+namespace {
+// the triangles a lane of k_mrender_small rasterises itself: a clipped box of at most this many pixel centres.  MVS_MRENDER_SMALL in the
+// environment (mvskit_engine.h), read at every call, sets another value: the maps do not depend on it, mvs_engine_mesh_render_lists does
+#define MRENDER_SMALL 32
+int mrender_small_max() {
+    const char* s = getenv("MVS_MRENDER_SMALL");
+    const int v = s ? atoi(s) : 0;
+    return v > 0 ? v : MRENDER_SMALL;
+}
+struct MrenderBufs {
+    DevBuf<int32_t> d_tris, scr, list, tri;
+    DevBuf<uint32_t> words, ok;
+    DevBuf<float> d_verts, vd, depth;
+    DevBuf<unsigned long long> keys, counts, visible;  // counts: a view's [0] listed triangles, [1] skipped triangles, [2] covered pixels
+};
+// the caller's mesh checked and on the device, the per-view buffers allocated; the stream is idle on return
+int mrender_take(mvs_engine* e, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, MrenderBufs& b, const char* who) {
+    if (int r = mesh_take_tris(e, n_v, n_t, tris, b.d_tris, b.words, who)) return r;
+    int64_t max_pix = 0;
+    for (int v = 0; v < e->cfg.nviews; ++v) max_pix = std::max(max_pix, maps_npix(e, v));
+    if (b.d_verts.ensure(3 * n_v) || b.scr.ensure(2 * n_v) || b.vd.ensure(n_v) || b.ok.ensure(n_v) || b.list.ensure(n_t) || b.keys.ensure(max_pix) ||
+        b.depth.ensure(max_pix) || b.tri.ensure(max_pix) || b.counts.ensure(3 * (int64_t)MVS_MAXVIEWS))
+        return MVS_ERR_HIP;
+    if (int r = upload_rows(e, b.d_verts.p, verts, n_v)) return r;
+    HIPCHK(hipMemsetAsync(b.counts.p, 0, 3 * (size_t)MVS_MAXVIEWS * sizeof(unsigned long long), e->stream));
+    return MVS_OK;
+}
+// view v's vertices projected and its z-buffer filled: b.scr, b.vd, b.ok, b.keys and counts[3 v], counts[3 v + 1] (launched, not waited for)
+int mrender_view(mvs_engine* e, const DParams& p, int v, int64_t n_v, int64_t n_t, int small_max, MrenderBufs& b) {
+    hipStream_t st = e->stream;
+    const int W = e->hviews[v].W[e->cfg.level], H = e->hviews[v].H[e->cfg.level];
+    mvsk_mrender_project(p, v, n_v, b.d_verts.p, b.scr.p, b.vd.p, b.ok.p, st);
+    HIPCHK(hipMemsetAsync(b.keys.p, 0xff, (size_t)W * H * sizeof(unsigned long long), st));
+    mvsk_mrender_raster(n_t, b.d_tris.p, b.scr.p, b.vd.p, b.ok.p, W, H, small_max, b.keys.p, b.list.p, b.counts.p + 3 * v, st);
+    return MVS_OK;
+}
+}  // namespace
+
+int mvs_engine_mesh_render(mvs_engine* e, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, mvs_mesh_view_render* out, int32_t* screen,
+                           float* vdepth, int64_t* n_covered, int64_t* n_skipped) {
+    const char* who = "mvs_engine_mesh_render";
+    if (int r = mesh_in_args(n_v, verts, n_t, tris, who)) return r;
+    if (int r = need_state(e, NEED_IDLE, who)) return r;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:mesh_render");
+    hipStream_t st = e->stream;
+    const int nviews = e->cfg.nviews, small_max = mrender_small_max();
+    MrenderBufs b;
+    if (int r = mrender_take(e, n_v, verts, n_t, tris, b, who)) return r;
+    const DParams p = current_params(e);
+    std::vector<unsigned long long> hc(3 * (size_t)nviews, 0ull);
+    for (int v = 0; v < nviews; ++v) {
+        const int64_t npix = maps_npix(e, v);
+        const mvs_mesh_view_render o = out ? out[v] : mvs_mesh_view_render{nullptr, nullptr};
+        if (int r = mrender_view(e, p, v, n_v, n_t, small_max, b)) return r;
+        mvsk_mrender_resolve(npix, b.keys.p, o.depth ? b.depth.p : nullptr, o.tri ? b.tri.p : nullptr, b.counts.p + 3 * v + 2, st);
+        if (o.depth) HIPCHK(hipMemcpyAsync(o.depth, b.depth.p, (size_t)npix * sizeof(float), hipMemcpyDefault, st));
+        if (o.tri) HIPCHK(hipMemcpyAsync(o.tri, b.tri.p, (size_t)npix * sizeof(int32_t), hipMemcpyDefault, st));
+        if (screen && n_v > 0) HIPCHK(hipMemcpyAsync(screen + 2 * n_v * v, b.scr.p, (size_t)n_v * 2 * sizeof(int32_t), hipMemcpyDefault, st));
+        if (vdepth && n_v > 0) HIPCHK(hipMemcpyAsync(vdepth + n_v * v, b.vd.p, (size_t)n_v * sizeof(float), hipMemcpyDefault, st));
+        HIPCHK(hipStreamSynchronize(st));  // the buffers are reused by the next view
+        HIPCHK(hipGetLastError());
+    }
+    if (n_covered || n_skipped) {
+        HIPCHK(hipMemcpyAsync(hc.data(), b.counts.p, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        std::vector<int64_t> cov(nviews), skip(nviews);
+        for (int v = 0; v < nviews; ++v) { skip[v] = (int64_t)hc[3 * v + 1]; cov[v] = (int64_t)hc[3 * v + 2]; }
+        if (n_covered) HIPCHK(hipMemcpyAsync(n_covered, cov.data(), (size_t)nviews * sizeof(int64_t), hipMemcpyDefault, st));
+        if (n_skipped) HIPCHK(hipMemcpyAsync(n_skipped, skip.data(), (size_t)nviews * sizeof(int64_t), hipMemcpyDefault, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return MVS_OK;
+}
+
+int mvs_engine_mesh_render_lists(mvs_engine* e, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, int64_t* n_listed) {
+    const char* who = "mvs_engine_mesh_render_lists";
+    if (int r = mesh_in_args(n_v, verts, n_t, tris, who)) return r;
+    if (!n_listed) { g_err = std::string(who) + ": n_listed null"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_IDLE, who)) return r;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:mesh_render_lists");
+    hipStream_t st = e->stream;
+    const int nviews = e->cfg.nviews, small_max = mrender_small_max();
+    MrenderBufs b;
+    if (int r = mrender_take(e, n_v, verts, n_t, tris, b, who)) return r;
+    const DParams p = current_params(e);
+    for (int v = 0; v < nviews; ++v)
+        if (int r = mrender_view(e, p, v, n_v, n_t, small_max, b)) return r;  // the views' counts are apart: no wait between them
+    std::vector<unsigned long long> hc(3 * (size_t)nviews, 0ull);
+    HIPCHK(hipMemcpyAsync(hc.data(), b.counts.p, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));  // a failure is known before anything is written
+    HIPCHK(hipGetLastError());
+    std::vector<int64_t> listed(nviews);
+    for (int v = 0; v < nviews; ++v) listed[v] = (int64_t)hc[3 * v];
+    HIPCHK(hipMemcpyAsync(n_listed, listed.data(), (size_t)nviews * sizeof(int64_t), hipMemcpyDefault, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MVS_OK;
+}
+
+int mvs_engine_mesh_visibility(mvs_engine* e, float tol, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, uint64_t* visible) {
+    const char* who = "mvs_engine_mesh_visibility";
+    if (!std::isfinite(tol) || !(tol >= 0.0f)) { g_err = std::string(who) + ": tol not finite or negative"; return MVS_ERR_ARG; }
+    if (int r = mesh_in_args(n_v, verts, n_t, tris, who)) return r;
+    if (!visible && n_v > 0) { g_err = std::string(who) + ": visible null"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_IDLE, who)) return r;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:mesh_visibility");
+    hipStream_t st = e->stream;
+    const int nviews = e->cfg.nviews, small_max = mrender_small_max();
+    MrenderBufs b;
+    if (int r = mrender_take(e, n_v, verts, n_t, tris, b, who)) return r;
+    if (n_v == 0) return MVS_OK;
+    if (b.visible.ensure(n_v)) return MVS_ERR_HIP;
+    HIPCHK(hipMemsetAsync(b.visible.p, 0, (size_t)n_v * sizeof(unsigned long long), st));
+    const DParams p = current_params(e);
+    for (int v = 0; v < nviews; ++v) {
+        if (int r = mrender_view(e, p, v, n_v, n_t, small_max, b)) return r;
+        mvsk_mrender_visible(v, tol, n_v, b.scr.p, b.vd.p, b.ok.p, e->hviews[v].W[e->cfg.level], e->hviews[v].H[e->cfg.level], b.keys.p, b.visible.p, st);
+    }
+    HIPCHK(hipStreamSynchronize(st));  // a failure is known before anything is written
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(visible, b.visible.p, (size_t)n_v * sizeof(uint64_t), hipMemcpyDefault, st));
+    HIPCHK(hipStreamSynchronize(st));
     return MVS_OK;
 }
 

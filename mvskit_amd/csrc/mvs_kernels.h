@@ -157,6 +157,23 @@ void mvsk_mesh_normals_finish(int64_t n_v, const long long* acc, float* normals,
 struct MeshColourArgs { float occl_tol, min_cos; };
 void mvsk_mesh_colours(const DParams& prm, const MapsArgs& a, const MeshColourArgs& m, int64_t n_v, const float* verts, const float* normals,
                        const int32_t* ids, const uint8_t* usable, uint8_t* rgb, uint8_t* used, hipStream_t st);
+// the same with one more gate: view v takes part for vertex i only when bit v of visible[i] is set (k_mattr_colours_visible)
+void mvsk_mesh_colours_visible(const DParams& prm, const MapsArgs& a, const MeshColourArgs& m, int64_t n_v, const float* verts, const float* normals,
+                               const int32_t* ids, const uint8_t* usable, const unsigned long long* visible, uint8_t* rgb, uint8_t* used, hipStream_t st);
+// mvs_engine_mesh_render / mvs_engine_mesh_visibility (mvs_mesh_render.hip): a z-buffer of the mesh per view and the vertex visibility
+// from it, one view at a time.  Every launcher wants valid ids.
+// scr[2 i ..] = vertex i in 1/256 pixel of `view` at prm.level (saturated to int32), vd[i] = its depth, ok[i] = 1 where it is usable
+void mvsk_mrender_project(const DParams& prm, int view, int64_t n_v, const float* verts, int32_t* scr, float* vd, uint32_t* ok, hipStream_t st);
+// keys (W H words, all ones before) take the minimum of (bits(depth) << 32) | row over the triangles that cover each pixel centre; a
+// triangle whose clipped box holds more than small_max pixels goes through list (n_t slots); counts (zero before): [0] the listed
+// triangles, [1] the skipped ones
+void mvsk_mrender_raster(int64_t n_t, const int32_t* tris, const int32_t* scr, const float* vd, const uint32_t* ok, int W, int H, int small_max,
+                         unsigned long long* keys, int32_t* list, unsigned long long* counts, hipStream_t st);
+// depth[p], tri[p] (either may be null) from keys[p], NaN and -1 where it is all ones; *covered (zero before) += the pixels with a key
+void mvsk_mrender_resolve(int64_t npix, const unsigned long long* keys, float* depth, int32_t* tri, unsigned long long* covered, hipStream_t st);
+// visible[i] |= 1 << view where vertex i is usable, its nearest pixel lies inside W x H and is empty or not nearer than d / (1 + tol)
+void mvsk_mrender_visible(int view, float tol, int64_t n_v, const int32_t* scr, const float* vd, const uint32_t* ok, int W, int H, const unsigned long long* keys,
+                          unsigned long long* visible, hipStream_t st);
 // mvs_engine_mesh_components / mvs_engine_mesh_prune / mvs_engine_mesh_smooth (mvs_mesh_clean.hip): connected components by union-find,
 // pruning behind two scans, Taubin smoothing as an order-free integer sum.  verts: 3 floats a vertex, tris: 3 ids a triangle.
 // *bad != 0 when an id of a triangle lies outside 0 .. n_v - 1 (zero before the launch); every launcher below wants valid ids

@@ -37,6 +37,7 @@ EXPORTS = [
     "mvs_default_mesh_pruning", "mvs_default_mesh_smoothing", "mvs_engine_mesh_components", "mvs_engine_mesh_prune", "mvs_engine_mesh_smooth",
     "mvs_default_mesh_decimation", "mvs_engine_mesh_decimate",
     "mvs_default_mesh_filling", "mvs_engine_mesh_boundaries", "mvs_engine_mesh_fill",
+    "mvs_engine_mesh_render", "mvs_engine_mesh_render_lists", "mvs_engine_mesh_visibility", "mvs_engine_mesh_colours_visible",
 ]
 PLY_ASCII, PLY_BINARY_LE = 0, 1  # mvs_ply_format
 #: one vertex of the binary PLY file (mvs_engine_export_ply): 27 packed bytes
@@ -126,6 +127,11 @@ class MeshDecimation(C.Structure):
 class MeshFilling(C.Structure):
     """mvs_mesh_filling: the longest loop mvs_engine_mesh_fill closes, 8 bytes."""
     _fields_ = [("max_edges", C.c_int32), ("pad", C.c_int32)]
+
+
+class MeshViewRender(C.Structure):
+    """mvs_mesh_view_render: where one view's rendered depth and triangle rows go (host or device pointers, either null), 16 bytes."""
+    _fields_ = [("depth", C.c_void_p), ("tri", C.c_void_p)]
 
 
 class Counters(C.Structure):
@@ -271,6 +277,11 @@ def load_library(cap32: bool = False, cap: int = 0):
         L.mvs_engine_mesh_boundaries.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.mvs_engine_mesh_fill.argtypes = [vp, C.POINTER(MeshFilling), C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp,
                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    if hasattr(L, "mvs_engine_mesh_render"):
+        L.mvs_engine_mesh_render.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, C.POINTER(MeshViewRender), vp, vp, vp, vp]
+        L.mvs_engine_mesh_render_lists.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp]
+        L.mvs_engine_mesh_visibility.argtypes = [vp, C.c_float, C.c_int64, vp, C.c_int64, vp, vp]
+        L.mvs_engine_mesh_colours_visible.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(MeshColouring), C.c_int64, vp, vp, vp, vp, vp]
     _libs[LIB_PATH] = L
     return L
 
@@ -616,13 +627,14 @@ class Engine:
         self._check(self.L.mvs_engine_mesh_normals(self.h, verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), _ptr(out)))
         return out
 
-    def mesh_colours(self, verts, normals=None, source=0, min_consistent=1, depth_tol=0.01, normal_cos=0.9, occl_tol=0.01, min_cos=0.1):
+    def mesh_colours(self, verts, normals=None, source=0, min_consistent=1, depth_tol=0.01, normal_cos=0.9, occl_tol=0.01, min_cos=0.1, visible=None):
         """A colour per vertex from the views that see it (include/mvskit_engine.h, mvs_engine_mesh_colours): (rgb [n, 3] uint8, used [n]
         uint8).  A view counts when the vertex projects into its sampling window (and foreground), faces it (normal . ray >= min_cos; no
         test without normals or for a zero normal) and is not contradicted by the view's dense map (a usable pixel whose plane lies more
         than occl_tol, relative, before or behind the vertex).  Views whose map confirms the vertex are blended if there are any (used =
         their number | 0x80), otherwise the views whose map says nothing there (used = their number); grey and 0 with no view at all.
-        Reads engine state only."""
+        visible: a uint64 per vertex (mesh_visibility's, or the caller's); view v then counts for vertex i only when bit v of visible[i]
+        is set (mvs_engine_mesh_colours_visible).  Reads engine state only."""
         verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
         if normals is not None:
             normals = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
@@ -631,8 +643,70 @@ class Engine:
         c = self._maps_config(source, min_consistent, depth_tol, normal_cos, 0)
         m = MeshColouring(float(occl_tol), float(min_cos))
         rgb, used = np.zeros((verts.shape[0], 3), np.uint8), np.zeros(verts.shape[0], np.uint8)
-        self._check(self.L.mvs_engine_mesh_colours(self.h, C.byref(c), C.byref(m), verts.shape[0], _ptr(verts), _ptr(normals), _ptr(rgb), _ptr(used)))
+        if visible is None:
+            self._check(self.L.mvs_engine_mesh_colours(self.h, C.byref(c), C.byref(m), verts.shape[0], _ptr(verts), _ptr(normals), _ptr(rgb), _ptr(used)))
+            return rgb, used
+        visible = np.ascontiguousarray(visible, dtype=np.uint64).reshape(-1)
+        if visible.shape[0] != verts.shape[0]:
+            raise ValueError("mesh_colours: one visibility word per vertex")
+        self._check(self.L.mvs_engine_mesh_colours_visible(self.h, C.byref(c), C.byref(m), verts.shape[0], _ptr(verts), _ptr(normals), _ptr(visible), _ptr(rgb),
+                                                           _ptr(used)))
         return rgb, used
+
+    # ---- the mesh seen from the views
+    def render_mesh(self, verts, tris, views=None):
+        """The mesh rasterised into the views at the engine's level (include/mvskit_engine.h, mvs_engine_mesh_render): (maps, covered,
+        skipped) -- maps a list with one (depth [H, W] float32, tri [H, W] int32) per view, the depth of the nearest triangle at each
+        pixel centre and its row in tris (NaN and -1 where none covers it), or None for a view that `views` (default: all) does not list;
+        covered [nviews] int64, the pixels with a triangle; skipped [nviews] int64, the triangles with a vertex behind the camera, not
+        finite or beyond 2^16 pixels (there is no near-plane clipping).  Both faces render, masks play no part.  An order-free minimum:
+        the same bytes whatever order the triangles are listed in.  Needs views but no pool."""
+        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        n = self.cfg.nviews
+        want = range(n) if views is None else [int(v) for v in views]
+        if any(v < 0 or v >= n for v in want):
+            raise ValueError(f"render_mesh: views must lie in 0..{n - 1}")
+        slots = (MeshViewRender * n)()
+        maps = [None] * n
+        for v in want:
+            h, w = self.level_shape(v)
+            maps[v] = (np.zeros((h, w), np.float32), np.zeros((h, w), np.int32))
+            slots[v].depth, slots[v].tri = maps[v][0].ctypes.data, maps[v][1].ctypes.data
+        covered, skipped = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        self._check(self.L.mvs_engine_mesh_render(self.h, verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), slots, None, None, _ptr(covered),
+                                                  _ptr(skipped)))
+        return maps, covered, skipped
+
+    def mesh_screen(self, verts, tris):
+        """What the render sees of every vertex (mvs_engine_mesh_render's screen and vdepth): (screen [nviews, n, 2] int32, the position
+        in 1/256 pixel; vdepth [nviews, n] float32, the depth along the optical axis).  A vertex is usable in a view when its depth is
+        positive and finite and |screen| <= 2^24."""
+        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        n = self.cfg.nviews
+        screen, vdepth = np.zeros((n, verts.shape[0], 2), np.int32), np.zeros((n, verts.shape[0]), np.float32)
+        self._check(self.L.mvs_engine_mesh_render(self.h, verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), None, _ptr(screen), _ptr(vdepth), None, None))
+        return screen, vdepth
+
+    def mesh_render_lists(self, verts, tris):
+        """Per view the triangles of the mesh that the render hands to its wave-per-triangle kernel, a clipped bounding box of more than
+        32 pixel centres (mvs_engine_mesh_render_lists): int64 [nviews], counted on the device.  The others are rasterised a lane each."""
+        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        out = np.zeros(self.cfg.nviews, np.int64)
+        self._check(self.L.mvs_engine_mesh_render_lists(self.h, verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), _ptr(out)))
+        return out
+
+    def mesh_visibility(self, verts, tris, tol=0.01):
+        """The views that see each vertex of the mesh (include/mvskit_engine.h, mvs_engine_mesh_visibility): uint64 [n], bit v set when the
+        vertex is usable in view v, its nearest pixel lies inside the image and the mesh rendered there is not nearer than the vertex by
+        more than `tol`, relative (an empty pixel hides nothing).  What mesh_colours(visible=) takes.  Needs views but no pool."""
+        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        out = np.zeros(verts.shape[0], np.uint64)
+        self._check(self.L.mvs_engine_mesh_visibility(self.h, float(tol), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), _ptr(out)))
+        return out
 
     # ---- mesh clean-up
     def mesh_components(self, n_v, tris):
@@ -733,13 +807,16 @@ class Engine:
         return out_v, out_t, nf.value
 
     def coloured_mesh(self, volume, source=0, min_consistent=1, depth_tol=0.01, normal_cos=0.9, occl_tol=0.01, min_cos=0.1, cap_v=0, cap_t=0,
-                      min_triangles=0, largest_only=False, smooth_iterations=0, decimate_cell=0.0, decimate_placement="mean", fill_max_edges=0):
+                      min_triangles=0, largest_only=False, smooth_iterations=0, decimate_cell=0.0, decimate_placement="mean", fill_max_edges=0,
+                      mesh_occlusion=False, visibility_tol=0.01):
         """mesh, mesh_normals and mesh_colours chained: (verts, tris, normals, rgb, used), what write_mesh_ply takes.  Every step renders
         the maps it needs itself.  With min_triangles >= 1 or largest_only the mesh is pruned (prune_mesh), with fill_max_edges >= 3 its
         holes of up to that many edges are filled (fill_holes: the floaters are gone first, and the smoothing relaxes the fans), with
         smooth_iterations > 0 it is smoothed (smooth_mesh with its default steps), with decimate_cell > 0 decimated (decimate_mesh), in
         that order, before the normals and colours are taken.  The decimation grid starts at volume.origin - voxel / 2: marching tetrahedra leaves lattice coordinates in
-        two of a vertex's three components, and with a cell that is a multiple of the voxel none of them sits on a cell boundary."""
+        two of a vertex's three components, and with a cell that is a multiple of the voxel none of them sits on a cell boundary.
+        mesh_occlusion: the colours also take the visibility of the final mesh (mesh_visibility with visibility_tol, behind the
+        decimation) -- a view that looks at a vertex through the front of the mesh no longer colours it; False calls nothing new."""
         kw = dict(source=source, min_consistent=min_consistent, depth_tol=depth_tol, normal_cos=normal_cos)
         verts, tris = self.mesh(volume, cap_v=cap_v, cap_t=cap_t, **kw)
         if min_triangles > 0 or largest_only:
@@ -751,7 +828,8 @@ class Engine:
         if decimate_cell > 0:
             verts, tris, _ = self.decimate_mesh(verts, tris, decimate_cell, decimation_origin(volume), decimate_placement)
         normals = self.mesh_normals(verts, tris)
-        rgb, used = self.mesh_colours(verts, normals, occl_tol=occl_tol, min_cos=min_cos, **kw)
+        visible = self.mesh_visibility(verts, tris, visibility_tol) if mesh_occlusion else None
+        rgb, used = self.mesh_colours(verts, normals, occl_tol=occl_tol, min_cos=min_cos, visible=visible, **kw)
         return verts, tris, normals, rgb, used
 
     # ---- the hot path
