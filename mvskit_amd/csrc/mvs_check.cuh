@@ -78,7 +78,7 @@ DEV int is_neighbor_h(const DParams& prm, const PGeo& l, const PGeo& r, float hu
     const float f0 = dot4(l.normal, diff), f1 = dot4(r.normal, diff);
     float ftmp = (fabsf(f0) + fabsf(f1)) / 2.0f;
     ftmp = div_rn(ftmp, vunit);  // two seeds without a depth scale (vunit 0): infinity or NaN either way, and neither is < thr
-    const F4 h = add4(sub4(diff, mul4(l.normal, f0)), sub4(diff, mul4(r.normal, f1)));
+    const F4 h = add4(sub4(diff, scl4(l.normal, f0)), sub4(diff, scl4(r.normal, f1)));
     const float hsize = div_rn(norm4(h) / 2.0f, hunit);
     if (1.0f < hsize) ftmp = div_rn(ftmp, fminf(2.0f, hsize));
     return ftmp < thr ? 1 : 0;
@@ -95,7 +95,7 @@ DEV int is_neighbor_radius(const DParams& prm, const PGeo& l, const PGeo& r, flo
     const float f0 = dot4(l.normal, diff), f1 = dot4(r.normal, diff);
     float ftmp = (fabsf(f0) + fabsf(f1)) / 2.0f;
     ftmp = div_rn(ftmp, vunit);
-    const F4 h = sub4(sub4(mul4(diff, 2.0f), mul4(l.normal, f0)), mul4(r.normal, f1));
+    const F4 h = sub4(sub4(scl4(diff, 2.0f), scl4(l.normal, f0)), scl4(r.normal, f1));
     const float hsize = div_rn(norm4(h) / 2.0f, hunit);
     if (div_rn(radius, hunit) < hsize) return 0;
     if (1.0f < hsize) ftmp = div_rn(ftmp, fminf(2.0f, hsize));

@@ -2,6 +2,7 @@
 // and the per-cell maps derived from the pool (m_dpgrids, the best-NCC map, their extraction); kernels first, their launchers behind them.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include "mvs_camera.cuh"
 #include "mvs_common.cuh"
 #include "mvs_kernels.h"
 

@@ -12,6 +12,7 @@
 // validity or agreement is written so that a NaN fails it.  Stores are plain vector stores.
 #include <hip/hip_runtime.h>
 
+#include "mvs_camera.cuh"
 #include "mvs_common.cuh"
 #include "mvs_kernels.h"
 

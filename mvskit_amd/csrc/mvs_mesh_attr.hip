@@ -18,6 +18,7 @@
 // fails it.  Stores are plain vector stores.
 #include <hip/hip_runtime.h>
 
+#include "mvs_camera.cuh"
 #include "mvs_mesh_common.cuh"
 #include "mvs_kernels.h"
 

@@ -8,6 +8,7 @@
 // k_mfill_classify), the sum of a first_group in the wave (k_mdec_sum, k_mfill_sum), finite3 in k_mdec_member.
 #pragma once
 #include "mvs_common.cuh"
+#include "mvs_wave.cuh"
 
 #define MESH_BLOCK 256
 #define MESH_EMPTY 0xffffffffffffffffull  // the key of a free table slot, and of an item without a key

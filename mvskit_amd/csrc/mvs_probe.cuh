@@ -2,7 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include "mvs_common.cuh"
+#include "mvs_patch_common.cuh"
 #include "mvs_check.cuh"
 #include "mvs_kernels.h"
 

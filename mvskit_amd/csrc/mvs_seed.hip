@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mvs_common.cuh"
+#include "mvs_wave.cuh"
 #include "mvs_kernels.h"
 
 using namespace mvsdev;

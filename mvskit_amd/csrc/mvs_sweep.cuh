@@ -3,7 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include "mvs_common.cuh"
+#include "mvs_patch_common.cuh"
 #include "mvs_check.cuh"
 #include "mvs_kernels.h"
 
@@ -455,7 +455,7 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WC& wc, SweepAcc* ac
 // chunk to itself spreads the 384 waves of an XCD over 384 chunks: sweep 333 ms per step against 281 for one block per cell;
 // takes of 64 / 16 / 4 / 1 jobs (of unlisted jobs, a lane per job testing for a source): 309 / 285 / 273.5 / 270.4 ms
 // (profiles/r09_resident_ab.txt).  The cursor's atomic is one per listed job: a round trip in ~430 us of work per cell.
-// WC: the wave context of the instantiation -- plain WaveCtx, or a WaveCtxT for a full window and / or the narrow samplers (mvs_device.cuh)
+// WC: the wave context of the instantiation -- plain WaveCtx, or a WaveCtxT for a full window and / or the narrow samplers (mvs_sample.cuh)
 template <bool SIMPLEX, class WC>
 DEV void sweep_resident(const DParams& prm, const SweepArgs& a, int* s_scratch, int* s_pend, float* s_texs, int max_evals, float xtol) {
     WC wc;
@@ -491,7 +491,7 @@ DEV void sweep_retry_cell(const DParams& prm, const SweepArgs& a, const int64_t 
 // the kernels compile to other code -- profiles/r24_codeobj_kernel_split.txt.)
 #define SWEEP_LDS                                                                                                                  \
     __shared__ int s_scratch[192];                                                                                                 \
-    __shared__ __attribute__((aligned(16))) int s_pend[MVS_PEND_INTS]; /* a waiting candidate, the working block of a pair (mvs_device.cuh) */ \
+    __shared__ __attribute__((aligned(16))) int s_pend[MVS_PEND_INTS]; /* a waiting candidate, the working block of a pair (mvs_refine.cuh) */ \
     extern __shared__ float s_texs[];
 __global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep(DParams prm, SweepArgs a) { SWEEP_LDS sweep_resident<false, WaveCtx>(prm, a, s_scratch, s_pend, s_texs, 0, 0.0f); }
 // for a launch whose window fills every slot of every lane (cls_full_window: the default 7x7)

@@ -1,6 +1,7 @@
 // mvs_types.h -- device-side data layout of the MI355X PatchMatch-MVS engine (internal).
 #pragma once
 #include <stdint.h>
+#include <hip/hip_vector_types.h>  // float4
 
 #define MVS_WAVE 64
 #define MVS_MAXLEV 7       // level (<=4) + 3 pyramid levels (pmmvps.cpp:36)

@@ -911,7 +911,7 @@ double cost_func(const Scene& s, const RefineCtx& rc, const int* idx, int n, con
     return ans / denom;
 }
 
-/* ---- class-lane arithmetic of the engine's refinement steps (mvs_device.cuh, eval_steps3) --------------------------------
+/* ---- class-lane arithmetic of the engine's refinement steps (mvs_sample.cuh, eval_steps3) --------------------------------
  * The 7x7 samples of one (proposal, view) are dealt over 16 lanes: lane c walks samples c, c + 16, c + 32 (as far as they
  * exist) and the few samples beyond the last full 16 ("extras": sample 48 of a 7x7 window) sit in a lane of their own,
  * whose sums are added to lane e.  Colours are taken relative to a pivot p per view, c' = colour - p, and normalize /

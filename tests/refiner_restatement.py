@@ -1,4 +1,4 @@
-"""A numpy restatement, in float32, of the engine's CONVERGED refiner (refine_patch_simplex, mvskit_amd/csrc/mvs_device.cuh):
+"""A numpy restatement, in float32, of the engine's CONVERGED refiner (refine_patch_simplex, mvskit_amd/csrc/mvs_refine.cuh):
 a bounded Nelder-Mead over Optim::refinePatch's three variables whose iterations make one four-proposal pass each.
 
 `cost(x)` is Optim::cost_func at x (float32[3]) -> float (double); the tests pass the oracle's orc_cost.  Every vertex update

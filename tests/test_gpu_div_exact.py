@@ -1,4 +1,4 @@
-"""rcp_rn / div_rn of mvs_device.cuh -- v_rcp_f32 + one Newton step in fma; Markstein's quotient correction on top -- stand in for
+"""rcp_rn / div_rn of mvs_math.cuh -- v_rcp_f32 + one Newton step in fma; Markstein's quotient correction on top -- stand in for
 IEEE-754 division in the hot geometry (projection, ray normalisation, units, 1 / msd, robust INCC, isNeighbor): 3 and 6 instructions
 where the compiler's expansion takes 11.  They must return the very bits `1.0f / x` and `a / b` return, or the engine would leave
 the oracle's arithmetic.  tools/microbench/div_exact.hip checks that on the device: the reciprocal EXHAUSTIVELY -- every float with

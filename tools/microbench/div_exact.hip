@@ -1,4 +1,4 @@
-// tools/microbench/div_exact.hip -- does the short reciprocal / division of mvs_device.cuh (rcp_rn, div_rn) return the IEEE-754
+// tools/microbench/div_exact.hip -- does the short reciprocal / division of mvs_math.cuh (rcp_rn, div_rn) return the IEEE-754
 // round-to-nearest result?  EXHAUSTIVE for the reciprocal: every float bit pattern with a biased exponent in [7, 247] (|x| in
 // 2^-120 .. 2^120, both signs: 2 x 241 x 2^23 inputs) against the compiler's IEEE division 1.0f / x.  The division: Markstein's
 // theorem (q' = RN(q + (a - b q) y) is a / b correctly rounded when y = RN(1 / b) and q is a faithful quotient, barring over- and
