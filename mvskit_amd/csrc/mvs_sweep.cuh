@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cstddef>
+#include <type_traits>
 #include "mvs_patch_common.cuh"
 #include "mvs_check.cuh"
 #include "mvs_kernels.h"
@@ -197,49 +199,82 @@ DEV void sweep_acc_flush(const SweepArgs& a, const SweepAcc& acc, unsigned slot)
     atomicAdd(&C->stage[14], acc.stage[14]); atomicAdd(&C->stage[15], acc.stage[15]);  // inside postProcess: setRefImage's pair sums and choice
 #endif
 }
+// The ONE argument of every sweep kernel, and how the sweep reads it.  DParams and SweepArgs are ~230 dwords against 104 scalar
+// registers: taken by value and read as plain kernel arguments, every field is fetched once at kernel entry and lives across the
+// whole cell loop -- 336 scalars spilled into vector lanes, 779 v_readlane_b32 to bring them back, most of them in the stages around
+// the refinement (profiles/r26_codeobj_stage_args.txt).  The sweep instead reads the fields where it uses them, from the
+// kernel-argument segment itself (constant address space: a uniform read is a scalar load, which takes no vector issue slot), through
+// a pointer that stage_args makes opaque at a stage boundary: a load cannot be hoisted above the empty asm that defines the
+// pointer it reads through, so a field's live range ends with the stage that read it.  The shared device functions still take
+// `const DParams&`; inlined, their reads resolve to the constant address space behind the reference.
+struct SweepKArgs {
+    DParams prm;
+    SweepArgs a;
+    int32_t nretry;     // k_sweep_retry, k_sweep_retry_simplex: the cells handed to the second tier
+    int32_t max_evals;  // the CONVERGED refiner (k_sweep_simplex, k_sweep_retry_simplex)
+    float xtol;
+};
+// the kernel-argument segment IS this struct: one argument, at offset 0, in its C++ layout
+static_assert(std::is_standard_layout<SweepKArgs>::value && std::is_trivially_copyable<SweepKArgs>::value, "SweepKArgs is read from the kernel-argument segment as it lies in memory");
+static_assert(offsetof(SweepKArgs, prm) == 0 && offsetof(SweepKArgs, a) == sizeof(DParams) && sizeof(DParams) % 8 == 0, "DParams, then SweepArgs");
+static_assert(sizeof(SweepKArgs) <= 4096, "a kernel-argument segment holds at most 4 KiB");
+typedef const __attribute__((address_space(4))) SweepKArgs* SweepKPtr;
+DEV SweepKPtr sweep_kargs() { return (SweepKPtr)__builtin_amdgcn_kernarg_segment_ptr(); }
+// the arguments for ONE stage: what is read through the result is loaded after this point and is dead when the stage is
+DEV const SweepKArgs& stage_args(SweepKPtr p) {
+    asm volatile("" : "+s"(p));
+    return *(const SweepKArgs*)p;
+}
+// ... and without a boundary: the stages of a trial up to and including the refinement read through the kernel's own pointer.  Their
+// loads stay where the fields are used all the same (nothing proves the segment dereferenceable, so nothing is hoisted), and with a
+// boundary around each of them the pair step loop reloads 9 spilled scalars instead of 2.  With no boundary anywhere the kernel spills
+// 22 VGPRs where the parent spilled 20; with the boundaries of sweep_cell, sweep_resident and the retry loops 15
+// (profiles/r26_codeobj_stage_args.txt: the three granularities side by side).
+DEV const SweepKArgs& kernel_args(SweepKPtr p) { return *(const SweepKArgs*)p; }
 // One destination cell: `job` has a cell and a source entry that starts a trial (it is listed: k_job_list), job_nstage[job] is 0.  The wave comes here cell after cell
 // (the LDS of the previous cell is dead: the caller puts a barrier in between): everything a cell keeps is set up here, and what it
 // counted goes into `acc` when it is done -- nothing of a cell that gives up.
 // SIMPLEX = true: the refinement is refine_patch_simplex with max_evals / xtol (k_sweep_simplex, k_sweep_retry_simplex: the CONVERGED
-// refiner of mvs_engine_set_refiner); the default kernels keep the halving search and never see the two arguments.
+// refiner of mvs_engine_set_refiner); the default kernels keep the halving search and never read the two fields.
 template <bool BIG, bool SIMPLEX = false, class WC>
-DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WC& wc, SweepAcc* acc, const int64_t job, int* s_scratch, int* s_pend, float* s_texs,
-                    int* big_table, int max_evals = 0, float xtol = 0.0f) {
+DEV void sweep_cell(const SweepKPtr kp, WC& wc, SweepAcc* acc, const int64_t job, int* s_scratch, int* s_pend, float* s_texs, int* big_table) {
 #ifdef MVS_STAGE_TIMING
     unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const unsigned long long st_begin = ST_NOW();
     unsigned long long st_t = st_begin;
     for (int k = 0; k < 8; ++k) wc.st_acc[k] = 0;
 #endif
-    int v, cx, cy;
-    job_cell(prm, a, job, v, cx, cy);
-    const DView* vw = prm.views + v;
-    const int gw = vw->gw, gh = vw->gh;
-    wc.evals = 0; wc.view_evals = 0;
-    const int cell = cy * gw + cx;
-    const int inc = a.inc;
-    const int sxs[2] = {cx, cx - inc}, sys[2] = {cy - inc, cy};
-
-    const int tstride = prm.wsz;  // odd for 7x7 / 5x5 windows: the lane-per-pair reads of setRefImage fall in distinct banks
-    unsigned n_cand = 0, n_pref = 0, n_patch = 0, n_f0 = 0, n_f1 = 0, n_ins = 0, n_rep = 0;
+    // ---- stage: the cell's prologue.  What the cell keeps of the arguments: its place (v, cx, cy, the grid), inc, the number of sources.
+    int v, cx, cy, gw, gh, cell, inc, nsrc;
+    const DView* vw;
+    float icx, icy;
     // live list of this cell as view-lane arrays: lane k holds entry k (sorted: ncc desc, id asc)
     int L_id = -1;
     float L_ncc = 0.0f;
     int L_n = 0;
     {
+        const SweepKArgs& K = stage_args(kp);
+        const DParams& prm = K.prm;
+        job_cell(prm, K.a, job, v, cx, cy);
+        vw = prm.views + v;
+        gw = vw->gw; gh = vw->gh;
+        cell = cy * gw + cx;
+        inc = K.a.inc;
         const int g = vw->cell_base + cell;
         const csr_off_t fb = prm.csr_start[g];
         L_n = min(prm.csr_cnt[g], MVS_CAPMAX);
         if (wc.lane < L_n) { L_id = pgrid_id(prm, fb + wc.lane); L_ncc = pgrid_ncc(prm, fb + wc.lane); }
+        icx = (float)(prm.csize * (2 * cx + 1) - 1) / 2.0f; icy = (float)(prm.csize * (2 * cy + 1) - 1) / 2.0f;
+        // sources: the cell above/below, the cell beside (propagate.cpp:104-108), and -- view propagation, the branch the
+        // reference keeps commented out (propagate.cpp:110-120) -- this cell's own list: a patch of another reference view
+        // that is listed here proposes itself with view v as the reference
+        nsrc = prm.view_propagation ? 3 : 2;
     }
+    wc.evals = 0; wc.view_evals = 0;
+    const int sxs[2] = {cx, cx - inc}, sys[2] = {cy - inc, cy};
+    unsigned n_cand = 0, n_pref = 0, n_patch = 0, n_f0 = 0, n_f1 = 0, n_ins = 0, n_rep = 0;
     int ns = 0;  // staged records of this job
     bool gave_up = false;
-    const float icx = (float)(prm.csize * (2 * cx + 1) - 1) / 2.0f, icy = (float)(prm.csize * (2 * cy + 1) - 1) / 2.0f;
-
-    // sources: the cell above/below, the cell beside (propagate.cpp:104-108), and -- view propagation, the branch the
-    // reference keeps commented out (propagate.cpp:110-120) -- this cell's own list: a patch of another reference view
-    // that is listed here proposes itself with view v as the reference
-    const int nsrc = prm.view_propagation ? 3 : 2;
     // Two consecutive trials of the cell are refined TOGETHER where the second is certain to find room (refine_patch_pair): a candidate that
     // has passed preProcess waits in s_pend for the next one that does.  Everything after the refinement -- postProcess, Optim::check, the
     // staging slot, the live list -- then runs candidate by candidate in trial order, as if each had been refined in its turn.  When the
@@ -258,7 +293,8 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WC& wc, SweepAcc* ac
         // per entry, six in seven of them only to find another reference view); then the sources in list order
         int E_id = 0;
         bool E_take = false;
-        if (!flush) {
+        if (!flush) {  // ---- stage: a source list
+            const DParams& prm = kernel_args(kp).prm;
             const int g = vw->cell_base + scy * gw + scx;
             const csr_off_t sb = prm.csr_start[g];
             const int sn = min(prm.csr_cnt[g], MVS_CAPMAX);  // a trimmed list: at most MAX_NUM_OF_PATCHES <= 32 entries
@@ -268,14 +304,19 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WC& wc, SweepAcc* ac
         while (todo) {
             const int n = __ffs((int)todo) - 1;
             todo &= todo - 1u;
-            const DPatch* sp = prm.pool + rli(E_id, n);
-            const int srcslot = sidx * prm.cap + n;
-            // ---- Propagate::propagatePatch, propagate.cpp:153-213
-            const int ntrial = flush ? 1 : prm.max_propag;
+            const DPatch* sp;
+            int srcslot, ntrial;
+            {
+                const DParams& prm = kernel_args(kp).prm;
+                sp = prm.pool + rli(E_id, n);
+                srcslot = sidx * prm.cap + n;
+                // ---- Propagate::propagatePatch, propagate.cpp:153-213
+                ntrial = flush ? 1 : prm.max_propag;
+            }
             for (int it = 0; it < ntrial; ++it) {
                 ST_ADD(7, st_t)
                 const int np = L_n;
-                const uint32_t k0 = (uint32_t)a.iter, k1 = (uint32_t)v, k2 = (uint32_t)cell;
+                const uint32_t k1 = (uint32_t)v, k2 = (uint32_t)cell;  // (k0, the iteration, is read where a stage draws)
                 uint32_t k3 = (uint32_t)(srcslot * 16 + it);
                 Cand c;
                 float keep_w = 0.0f;  // computeWeights of refinePatch, for the m_ncc postProcess takes from its first evaluation
@@ -284,40 +325,48 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WC& wc, SweepAcc* ac
                 if (!flush) {
                     float worst_ncc = 0.0f;
                     F3 ic;
-                    if (np < prm.cap) {
-                        const float ra = rng_uniform(prm.seed, k0, k1, k2, k3, 0) * (float)prm.csize;
-                        const float rb = rng_uniform(prm.seed, k0, k1, k2, k3, 1) * (float)prm.csize;
-                        ic = {icx + ra, icy + rb, 1.0f};
-                    } else {
-                        worst = rli(L_id, prm.cap - 1);
-                        worst_ncc = rlf(L_ncc, prm.cap - 1);
-                        const DPatch* wp = worst >= MVS_NEWBASE ? a.staging + (worst - MVS_NEWBASE) : prm.pool + worst;
-                        ic = project(vw, ld4(wp->coord), prm.level);
+                    bool full;  // the trial goes into a full cell
+                    {   // ---- stage: the trial's image point
+                        const SweepKArgs& K = kernel_args(kp);
+                        const DParams& prm = K.prm;
+                        full = np >= prm.cap;
+                        if (!full) {
+                            const uint32_t k0 = (uint32_t)K.a.iter;
+                            const float ra = rng_uniform(prm.seed, k0, k1, k2, k3, 0) * (float)prm.csize;
+                            const float rb = rng_uniform(prm.seed, k0, k1, k2, k3, 1) * (float)prm.csize;
+                            ic = {icx + ra, icy + rb, 1.0f};
+                        } else {
+                            worst = rli(L_id, prm.cap - 1);
+                            worst_ncc = rlf(L_ncc, prm.cap - 1);
+                            const DPatch* wp = worst >= MVS_NEWBASE ? K.a.staging + (worst - MVS_NEWBASE) : prm.pool + worst;
+                            ic = project(vw, ld4(wp->coord), prm.level);
+                        }
                     }
                     // A trial into a FULL cell draws nothing before the refinement: what follows, up to and including preProcess, is a function
                     // of the source record, the worst patch and the index.  If it ends there it has staged nothing, the live list is what it
                     // was, and the `rest` trials of this source entry still to come would compute the same and end the same way: their counts
                     // (the evaluations included) are added here and they are not run.  (Nothing waits in such a cell: `pend` is false.)
-                    const unsigned rest = np >= prm.cap ? (unsigned)(ntrial - 1 - it) : 0u;
+                    const unsigned rest = full ? (unsigned)(ntrial - 1 - it) : 0u;
                     const unsigned ev0 = wc.evals, vev0 = wc.view_evals;
                     auto skip_rest = [&]() {
                         n_skip += rest;
                         wc.evals += rest * (wc.evals - ev0); wc.view_evals += rest * (wc.view_evals - vev0);
                         it += (int)rest;
                     };
-                    {
+                    {   // ---- stage: generate
                         Cand src;  // loaded per trial: its registers are free again during the refinement
                         load_cand(sp, wc, src);
-                        const bool gen_ok = generate_patch(prm, wc, s_scratch, src, ic, c, as_view, np >= prm.cap);
+                        const bool gen_ok = generate_patch(kernel_args(kp).prm, wc, s_scratch, src, ic, c, as_view, full);
                         ST_ADD(1, st_t)
                         if (!gen_ok) { pend_failed |= pend; skip_rest(); continue; }
                     }
                     ++n_cand;
-                    if (np >= prm.cap && c.ncc < worst_ncc) { ++n_pref; n_cand += rest; n_pref += rest; skip_rest(); continue; }
+                    if (full && c.ncc < worst_ncc) { ++n_pref; n_cand += rest; n_pref += rest; skip_rest(); continue; }
                     ++n_patch;
-                    const int pre_r = pre_process(prm, wc, s_scratch, c);
+                    const int pre_r = pre_process(kernel_args(kp).prm, wc, s_scratch, c);  // ---- stage: preProcess
                     ST_ADD(2, st_t)
                     if (pre_r == -1) { ++n_f0; pend_failed |= pend; n_cand += rest; n_patch += rest; n_f0 += rest; skip_rest(); continue; }
+                    const DParams& prm = kernel_args(kp).prm;
                     if (!pend && np + 1 < prm.cap) {
                         // Room for this trial AND the next: the next one, whatever becomes of this one, still takes the np < cap branch above and
                         // reads nothing of the live list before Optim::check -- it may be generated first and refined together with this one.
@@ -333,14 +382,16 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WC& wc, SweepAcc* ac
                     if (pend_failed) ++n_lost; else ++n_last;
                 }
                 bool paired = false;
-                if (nfin == 2) {
+                if (nfin == 2) {  // ---- stage: the refinement of a pair
                     // the waiting candidate is the earlier trial: it is finished first, this one takes its place in the stash meanwhile
+                    const SweepKArgs& K = kernel_args(kp);
+                    const DParams& prm = K.prm;
                     const bool fits = pend_sz <= 8 && min(prm.tau, c.nimg) <= 8;
                     if (!fits) n_long += 2;
                     else n_elig += 2;
                     if constexpr (!SIMPLEX) {
-                        if (fits && a.pair) {
-                            refine_patch_pair(prm, wc, s_pend, c, k0, k1, k2, pend_k3, k3, keep_w);
+                        if (fits && K.a.pair) {
+                            refine_patch_pair(prm, wc, s_pend, c, (uint32_t)K.a.iter, k1, k2, pend_k3, k3, keep_w);
                             paired = true;
                             n_pair += 2;
                         }
@@ -355,28 +406,42 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WC& wc, SweepAcc* ac
                 pend = false;
                 for (int fi = 0; fi < nfin; ++fi) {
                     if (fi == 1) { pend_load(s_pend, wc, c, keep_w); k3 = pend_k3; }
-                    if (!paired) {
-                        if constexpr (SIMPLEX) (void)refine_patch_simplex(prm, wc, c, max_evals, xtol, &keep_w);
-                        else refine_patch(prm, wc, c, k0, k1, k2, k3, &keep_w);
+                    if (!paired) {  // ---- stage: the refinement of one candidate
+                        const SweepKArgs& K = kernel_args(kp);
+                        if constexpr (SIMPLEX) (void)refine_patch_simplex(K.prm, wc, c, K.max_evals, K.xtol, &keep_w);
+                        else refine_patch(K.prm, wc, c, (uint32_t)K.a.iter, k1, k2, k3, &keep_w);
                     }
                     ST_ADD(3, st_t)
-                    const int post_r = post_process(prm, wc, s_scratch, s_texs, tstride, c, keep_w, true);
+                    int post_r;
+                    {   // ---- stage: postProcess
+                        const DParams& prm = stage_args(kp).prm;
+                        const int tstride = prm.wsz;  // odd for 7x7 / 5x5 windows: the lane-per-pair reads of setRefImage fall in distinct banks
+                        post_r = post_process(prm, wc, s_scratch, s_texs, tstride, c, keep_w, true);
+                    }
                     ST_ADD(4, st_t)
                     if (post_r == -1) { ++n_f1; continue; }
-                    if (prm.depth >= 2 && prm.enable_check) {  // Optim::check, optim.cpp:292
-                        __syncthreads();
-                        if (wc.lane < MVS_CAPMAX) s_scratch[wc.lane] = L_id;  // publish the live list of this cell
-                        __syncthreads();
-                        #ifdef MVS_STAGE_TIMING
-                        const CheckCtx cx{a.staging, v, cell, L_n, s_scratch, st_acc};
+                    {   // ---- stage: Optim::check, optim.cpp:292
+                        const SweepKArgs& K = stage_args(kp);
+                        const DParams& prm = K.prm;
+                        if (prm.depth >= 2 && prm.enable_check) {
+                            __syncthreads();
+                            if (wc.lane < MVS_CAPMAX) s_scratch[wc.lane] = L_id;  // publish the live list of this cell
+                            __syncthreads();
+#ifdef MVS_STAGE_TIMING
+                            const CheckCtx cx{K.a.staging, v, cell, L_n, s_scratch, st_acc};
 #else
-                        const CheckCtx cx{a.staging, v, cell, L_n, s_scratch, nullptr};
+                            const CheckCtx cx{K.a.staging, v, cell, L_n, s_scratch, nullptr};
 #endif
-                        const int chk_r = check_patch<BIG>(prm, wc, cx, c, s_texs, a.error_flag, big_table);
-                        ST_ADD(5, st_t)
-                        if (!BIG && chk_r < 0) { gave_up = true; break; }  // the neighbourhood does not fit LDS: this cell goes to k_sweep_retry
-                        if (chk_r) { ++n_f1; continue; }
+                            const int chk_r = check_patch<BIG>(prm, wc, cx, c, s_texs, K.a.error_flag, big_table);
+                            ST_ADD(5, st_t)
+                            if (!BIG && chk_r < 0) { gave_up = true; break; }  // the neighbourhood does not fit LDS: this cell goes to k_sweep_retry
+                            if (chk_r) { ++n_f1; continue; }
+                        }
                     }
+                    // ---- stage: staging and insert
+                    const SweepKArgs& K = stage_args(kp);
+                    const DParams& prm = K.prm;
+                    const SweepArgs& a = K.a;
                     // staging slot for the accepted patch
                     unsigned long long slot64 = 0;
                     if (wc.lane == 0) slot64 = atomicAdd(a.stage_counter, 1ull);
@@ -415,6 +480,7 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WC& wc, SweepAcc* ac
         }
         if (gave_up) break;
     }
+    const SweepArgs& a = stage_args(kp).a;  // ---- stage: the cell's end
     if (!BIG && gave_up) {
         if (wc.lane == 0) { a.job_nstage[job] = 0; a.retry_jobs[atomicAdd(a.nretry, 1)] = (int32_t)job; }
         return;
@@ -457,34 +523,40 @@ DEV void sweep_cell(const DParams& prm, const SweepArgs& a, WC& wc, SweepAcc* ac
 // (profiles/r09_resident_ab.txt).  The cursor's atomic is one per listed job: a round trip in ~430 us of work per cell.
 // WC: the wave context of the instantiation -- plain WaveCtx, or a WaveCtxT for a full window and / or the narrow samplers (mvs_sample.cuh)
 template <bool SIMPLEX, class WC>
-DEV void sweep_resident(const DParams& prm, const SweepArgs& a, int* s_scratch, int* s_pend, float* s_texs, int max_evals, float xtol) {
+DEV void sweep_resident(const SweepKPtr kp, int* s_scratch, int* s_pend, float* s_texs) {
     WC wc;
-    static_cast<WaveCtx&>(wc) = make_wave_ctx(prm);
+    static_cast<WaveCtx&>(wc) = make_wave_ctx(stage_args(kp).prm);
     SweepAcc acc = sweep_acc_zero();
     for (unsigned step = 0; step < MVS_SWEEP_QUEUES; ++step) {
         const unsigned q = (blockIdx.x + step) & (MVS_SWEEP_QUEUES - 1u);
-        const int32_t qbegin = a.list_bounds[q];
-        const unsigned ntake = (unsigned)(a.list_bounds[q + 1] - qbegin);
+        int32_t qbegin;
+        unsigned ntake;
+        {
+            const SweepArgs& a = stage_args(kp).a;
+            qbegin = a.list_bounds[q];
+            ntake = (unsigned)(a.list_bounds[q + 1] - qbegin);
+        }
         if (ntake == 0u) continue;
         for (;;) {
+            const SweepArgs& a = stage_args(kp).a;  // a take: the queue's cursor and the list
             unsigned k = 0;
             if (wc.lane == 0) k = atomicAdd(a.cursors + q * MVS_SWEEP_CURSOR_STRIDE, 1u);
             k = (unsigned)rfl((int)k);
             if (k >= ntake) break;  // drained: on to the next queue
             const int64_t job = a.job_list[qbegin + (int32_t)k];
             __syncthreads();  // the LDS scratch, frames, pivots and kept textures of the previous cell are dead
-            sweep_cell<false, SIMPLEX>(prm, a, wc, &acc, job, s_scratch, s_pend, s_texs, nullptr, max_evals, xtol);
+            sweep_cell<false, SIMPLEX>(kp, wc, &acc, job, s_scratch, s_pend, s_texs, nullptr);
         }
     }
-    if (wc.lane == 0) sweep_acc_flush(a, acc, blockIdx.x & (MVS_COUNTER_SLOTS - 1));
+    if (wc.lane == 0) sweep_acc_flush(stage_args(kp).a, acc, blockIdx.x & (MVS_COUNTER_SLOTS - 1));
 }
 // the second tier: block b runs the cells retry_jobs[b], retry_jobs[b + gridDim.x], ... with big_tables slot b
 template <bool SIMPLEX>
-DEV void sweep_retry_cell(const DParams& prm, const SweepArgs& a, const int64_t job, int* s_scratch, int* s_pend, float* s_texs, int* big_table, int max_evals, float xtol) {
-    WaveCtx wc = make_wave_ctx(prm);
+DEV void sweep_retry_cell(const SweepKPtr kp, const int64_t job, int* s_scratch, int* s_pend, float* s_texs, int* big_table) {
+    WaveCtx wc = make_wave_ctx(stage_args(kp).prm);
     SweepAcc acc = sweep_acc_zero();
-    sweep_cell<true, SIMPLEX>(prm, a, wc, &acc, job, s_scratch, s_pend, s_texs, big_table, max_evals, xtol);
-    if (wc.lane == 0) sweep_acc_flush(a, acc, (unsigned)(job & (MVS_COUNTER_SLOTS - 1)));
+    sweep_cell<true, SIMPLEX>(kp, wc, &acc, job, s_scratch, s_pend, s_texs, big_table);
+    if (wc.lane == 0) sweep_acc_flush(stage_args(kp).a, acc, (unsigned)(job & (MVS_COUNTER_SLOTS - 1)));
 }
 // The kernels: the block's LDS, then sweep_resident or the retry loop on what varies (refiner, wave context); mvsk_sweep's table chooses
 // among the first four.  (The LDS is declared, and the retry loop written, in the kernel itself: with either in a shared device function
@@ -493,27 +565,30 @@ DEV void sweep_retry_cell(const DParams& prm, const SweepArgs& a, const int64_t 
     __shared__ int s_scratch[192];                                                                                                 \
     __shared__ __attribute__((aligned(16))) int s_pend[MVS_PEND_INTS]; /* a waiting candidate, the working block of a pair (mvs_refine.cuh) */ \
     extern __shared__ float s_texs[];
-__global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep(DParams prm, SweepArgs a) { SWEEP_LDS sweep_resident<false, WaveCtx>(prm, a, s_scratch, s_pend, s_texs, 0, 0.0f); }
+// (The argument is never named: the kernels read it in place, through sweep_kargs().)
+__global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep(SweepKArgs) { SWEEP_LDS sweep_resident<false, WaveCtx>(sweep_kargs(), s_scratch, s_pend, s_texs); }
 // for a launch whose window fills every slot of every lane (cls_full_window: the default 7x7)
-__global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep_full(DParams prm, SweepArgs a) { SWEEP_LDS sweep_resident<false, WaveCtxT<true, false>>(prm, a, s_scratch, s_pend, s_texs, 0, 0.0f); }
+__global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep_full(SweepKArgs) { SWEEP_LDS sweep_resident<false, WaveCtxT<true, false>>(sweep_kargs(), s_scratch, s_pend, s_texs); }
 // ... with the narrow samplers (32-bit texel offsets from DParams::pyr32) where the pyramid block is below 4 GiB; k_sweep_full itself,
 // with a 64-bit address per lane, serves the larger ones
-__global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep_full_ofs(DParams prm, SweepArgs a) { SWEEP_LDS sweep_resident<false, WaveCtxT<true, true>>(prm, a, s_scratch, s_pend, s_texs, 0, 0.0f); }
-__global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep_simplex(DParams prm, SweepArgs a, int max_evals, float xtol) { SWEEP_LDS sweep_resident<true, WaveCtx>(prm, a, s_scratch, s_pend, s_texs, max_evals, xtol); }
-__global__ __launch_bounds__(64, 1) void k_sweep_retry(DParams prm, SweepArgs a, int nretry) {
+__global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep_full_ofs(SweepKArgs) { SWEEP_LDS sweep_resident<false, WaveCtxT<true, true>>(sweep_kargs(), s_scratch, s_pend, s_texs); }
+__global__ __launch_bounds__(64, MVS_SWEEP_WAVES) void k_sweep_simplex(SweepKArgs) { SWEEP_LDS sweep_resident<true, WaveCtx>(sweep_kargs(), s_scratch, s_pend, s_texs); }
+__global__ __launch_bounds__(64, 1) void k_sweep_retry(SweepKArgs) {
     SWEEP_LDS
-    int* big_table = a.big_tables + (size_t)blockIdx.x * MVS_FILTER2_HASH_CAP;
-    for (int k = blockIdx.x; k < nretry; k += gridDim.x) {
+    const SweepKPtr kp = sweep_kargs();
+    int* big_table = stage_args(kp).a.big_tables + (size_t)blockIdx.x * MVS_FILTER2_HASH_CAP;
+    for (int k = blockIdx.x; k < stage_args(kp).nretry; k += gridDim.x) {
         __syncthreads();
-        sweep_retry_cell<false>(prm, a, (int64_t)a.retry_jobs[k], s_scratch, s_pend, s_texs, big_table, 0, 0.0f);
+        sweep_retry_cell<false>(kp, (int64_t)stage_args(kp).a.retry_jobs[k], s_scratch, s_pend, s_texs, big_table);
     }
 }
-__global__ __launch_bounds__(64, 1) void k_sweep_retry_simplex(DParams prm, SweepArgs a, int nretry, int max_evals, float xtol) {
+__global__ __launch_bounds__(64, 1) void k_sweep_retry_simplex(SweepKArgs) {
     SWEEP_LDS
-    int* big_table = a.big_tables + (size_t)blockIdx.x * MVS_FILTER2_HASH_CAP;
-    for (int k = blockIdx.x; k < nretry; k += gridDim.x) {
+    const SweepKPtr kp = sweep_kargs();
+    int* big_table = stage_args(kp).a.big_tables + (size_t)blockIdx.x * MVS_FILTER2_HASH_CAP;
+    for (int k = blockIdx.x; k < stage_args(kp).nretry; k += gridDim.x) {
         __syncthreads();
-        sweep_retry_cell<true>(prm, a, (int64_t)a.retry_jobs[k], s_scratch, s_pend, s_texs, big_table, max_evals, xtol);
+        sweep_retry_cell<true>(kp, (int64_t)stage_args(kp).a.retry_jobs[k], s_scratch, s_pend, s_texs, big_table);
     }
 }
 
@@ -570,15 +645,22 @@ KernelVariant mvsk_kernel_variant(const DParams& prm) {
 }
 // The sweep's kernels, the most particular first: a launch goes to the first row of its refiner that asks for nothing the launch lacks
 // (mvsk_kernel_variant), and what mvsk_sweep reports is that row.  A new instantiation is a wrapper above and a row here.
+// A launch's argument block is built here, per launch, and passed by value: the runtime copies it into the launch's own kernel-argument
+// segment, so two launches in flight -- of one engine or of two -- never share a parameter.
+static SweepKArgs sweep_kargs_of(const DParams& prm, const SweepArgs& a, int nretry, const RefineSel& rs) {
+    SweepKArgs k;
+    k.prm = prm; k.a = a; k.nretry = nretry; k.max_evals = rs.max_evals; k.xtol = rs.xtol;
+    return k;
+}
 typedef void (*SweepLaunch)(unsigned nblocks, size_t lds, hipStream_t st, const DParams& prm, const SweepArgs& a, const RefineSel& rs);
 #define SWEEP_ROW(simplex, full_window, narrow, ...) \
     {simplex, full_window, narrow, [](unsigned nblocks, size_t lds, hipStream_t st, const DParams& prm, const SweepArgs& a, const RefineSel& rs) { \
-         (void)rs; hipLaunchKernelGGL(__VA_ARGS__); }}
+         hipLaunchKernelGGL(__VA_ARGS__); }}
 static const struct { bool simplex, full_window, narrow; SweepLaunch launch; } sweep_table[] = {
-    SWEEP_ROW(true, false, false, k_sweep_simplex, dim3(nblocks), dim3(64), lds, st, prm, a, rs.max_evals, rs.xtol),
-    SWEEP_ROW(false, true, true, k_sweep_full_ofs, dim3(nblocks), dim3(64), lds, st, prm, a),
-    SWEEP_ROW(false, true, false, k_sweep_full, dim3(nblocks), dim3(64), lds, st, prm, a),
-    SWEEP_ROW(false, false, false, k_sweep, dim3(nblocks), dim3(64), lds, st, prm, a),
+    SWEEP_ROW(true, false, false, k_sweep_simplex, dim3(nblocks), dim3(64), lds, st, sweep_kargs_of(prm, a, 0, rs)),
+    SWEEP_ROW(false, true, true, k_sweep_full_ofs, dim3(nblocks), dim3(64), lds, st, sweep_kargs_of(prm, a, 0, rs)),
+    SWEEP_ROW(false, true, false, k_sweep_full, dim3(nblocks), dim3(64), lds, st, sweep_kargs_of(prm, a, 0, rs)),
+    SWEEP_ROW(false, false, false, k_sweep, dim3(nblocks), dim3(64), lds, st, sweep_kargs_of(prm, a, 0, rs)),
 };
 KernelVariant mvsk_sweep(const DParams& prm, const SweepArgs& a, const RefineSel& rs, hipStream_t st) {
     KernelVariant v = mvsk_kernel_variant(prm);
@@ -632,8 +714,8 @@ void mvsk_sweep_retry(const DParams& prm, const SweepArgs& a, int nretry, const 
     const dim3 grid((unsigned)std::min(nretry, MVS_BIG_SLOTS));
     SweepArgs b = a;
     b.pair = mvsk_kernel_variant(prm).pair ? 1 : 0;
-    if (rs.simplex) hipLaunchKernelGGL(k_sweep_retry_simplex, grid, dim3(64), mvsk_sweep_lds_bytes(prm), st, prm, b, nretry, rs.max_evals, rs.xtol);
-    else hipLaunchKernelGGL(k_sweep_retry, grid, dim3(64), mvsk_sweep_lds_bytes(prm), st, prm, b, nretry);
+    if (rs.simplex) hipLaunchKernelGGL(k_sweep_retry_simplex, grid, dim3(64), mvsk_sweep_lds_bytes(prm), st, sweep_kargs_of(prm, b, nretry, rs));
+    else hipLaunchKernelGGL(k_sweep_retry, grid, dim3(64), mvsk_sweep_lds_bytes(prm), st, sweep_kargs_of(prm, b, nretry, rs));
 }
 void mvsk_commit_count(const SweepArgs& a, int32_t* cnt, hipStream_t st) { hipLaunchKernelGGL(k_commit_count, dim3(nblk(a.njobs, 256)), dim3(256), 0, st, a, cnt); }
 void mvsk_commit_copy(const SweepArgs& a, const int32_t* base, DPatch* dst, int64_t dst_cap, int32_t* per_view, int keep_key, hipStream_t st) {
