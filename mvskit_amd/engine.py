@@ -5,289 +5,34 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 
 import numpy as np
 
-from . import build
 from . import synth
+from .abi import *  # noqa: F401,F403  (abi.__all__: the constants, dtypes, structs, SIGNATURES, EngineError and load_library)
 from .synth import MAX_IMAGES, PATCH_DTYPE  # noqa: F401  (PATCH_DTYPE mirrors mvs_patch at 32 list slots)
-
-PROBE_NCC, PROBE_PREPROCESS, PROBE_REFINE, PROBE_POSTPROCESS, PROBE_COST, PROBE_MATH, PROBE_REFINE_X = range(7)
-REFINE_HALVING, REFINE_CONVERGED = 0, 1  # mvs_refine_mode
-MVS_OK, MVS_ERR_ARG, MVS_ERR_STATE, MVS_ERR_HIP, MVS_ERR_CAPACITY, MVS_ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5  # mvs_status
-
-#: every symbol include/mvskit_engine.h declares
-EXPORTS = [
-    "mvs_last_error", "mvs_device_count", "mvs_default_config", "mvs_engine_create", "mvs_engine_destroy",
-    "mvs_engine_set_views", "mvs_engine_grid_dims", "mvs_engine_get_pyramid", "mvs_engine_set_thresholds",
-    "mvs_engine_get_thresholds", "mvs_engine_update_threshold", "mvs_engine_upload_patches",
-    "mvs_engine_clear_patches", "mvs_engine_num_patches", "mvs_engine_download_patches", "mvs_engine_propagate",
-    "mvs_engine_pass", "mvs_engine_export_counts", "mvs_engine_export_device", "mvs_engine_commit_device",
-    "mvs_engine_commit_local", "mvs_engine_depth_normal_map", "mvs_engine_probe", "mvs_engine_last_timing",
-    "mvs_engine_filter", "mvs_comm_unique_id", "mvs_engine_comm_init", "mvs_engine_comm_attach", "mvs_engine_comm_release",
-    "mvs_engine_exchange", "mvs_list_cap", "mvs_engine_filter_stats", "mvs_patch_bytes", "mvs_engine_reserve", "mvs_engine_comm_info",
-    "mvs_default_refiner", "mvs_engine_set_refiner", "mvs_engine_export_ply", "mvs_engine_seed_patches",
-    "mvs_default_seed_random", "mvs_engine_seed_random", "mvs_engine_seed_random_hypotheses",
-    "mvs_default_seed_points", "mvs_engine_seed_points", "mvs_engine_seed_points_hypotheses", "mvs_engine_depth_ranges",
-    "mvs_default_maps_config", "mvs_engine_render_maps", "mvs_engine_fused_points",
-    "mvs_engine_tsdf", "mvs_engine_extract_mesh", "mvs_engine_mesh", "mvs_engine_sweep_pairs", "mvs_engine_sweep_repeats", "mvs_engine_sweep_kernels",
-    "mvs_engine_sampler_launches",
-    "mvs_default_mesh_colouring", "mvs_engine_mesh_normals", "mvs_engine_mesh_colours",
-    "mvs_default_mesh_pruning", "mvs_default_mesh_smoothing", "mvs_engine_mesh_components", "mvs_engine_mesh_prune", "mvs_engine_mesh_smooth",
-    "mvs_default_mesh_decimation", "mvs_engine_mesh_decimate",
-    "mvs_default_mesh_filling", "mvs_engine_mesh_boundaries", "mvs_engine_mesh_fill",
-    "mvs_engine_mesh_render", "mvs_engine_mesh_render_lists", "mvs_engine_mesh_visibility", "mvs_engine_mesh_colours_visible",
-]
-PLY_ASCII, PLY_BINARY_LE = 0, 1  # mvs_ply_format
-#: one vertex of the binary PLY file (mvs_engine_export_ply): 27 packed bytes
-PLY_VERTEX_DTYPE = np.dtype([("xyz", "<f4", (3,)), ("normal", "<f4", (3,)), ("rgb", "u1", (3,))])
-#: mvs_fused_point: one record of mvs_engine_fused_points, 32 bytes
-FUSED_POINT_DTYPE = np.dtype([("xyz", "<f4", (3,)), ("normal", "<f4", (3,)), ("conf", "<f4"), ("rgb", "u1", (3,)), ("view", "u1")])
-
-
-class Config(C.Structure):
-    _fields_ = [("nviews", C.c_int32), ("level", C.c_int32), ("csize", C.c_int32), ("wsize", C.c_int32),
-                ("minImageNum", C.c_int32), ("max_propag", C.c_int32), ("nccThreshold", C.c_float),
-                ("maxAngleThreshold", C.c_float), ("quadThreshold", C.c_float), ("depth", C.c_int32),
-                ("seed", C.c_uint32), ("refine_steps", C.c_int32), ("refine_rd0", C.c_float), ("refine_ra0", C.c_float),
-                ("enable_check", C.c_int32), ("view_begin", C.c_int32), ("view_stride", C.c_int32),
-                ("device", C.c_int32), ("view_propagation", C.c_int32), ("shard_index", C.c_int32), ("shard_count", C.c_int32),
-                ("literal_groups", C.c_int32), ("max_patches", C.c_int64)]
-
-
-class Refiner(C.Structure):
-    """mvs_refiner: which refiner Optim::refinePatch runs (mvs_engine_set_refiner)."""
-    _fields_ = [("mode", C.c_int32), ("max_evals", C.c_int32), ("xtol", C.c_float)]
-
-
-class ViewDesc(C.Structure):
-    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("P", C.c_float * 12), ("rgb", C.c_void_p),
-                ("mask", C.c_void_p)]
-
-
-class SeedView(C.Structure):
-    """mvs_seed_view: one view's world-space normal map and level-0 mask (mvs_engine_seed_patches)."""
-    _fields_ = [("normals", C.c_void_p), ("mask", C.c_void_p)]
-
-
-class SeedRandom(C.Structure):
-    """mvs_seed_random: the parameters of a cold start (mvs_engine_seed_random); depth_min / depth_max point at one float per view."""
-    _fields_ = [("hypotheses", C.c_int32), ("seed", C.c_uint32), ("max_tilt", C.c_float), ("min_ncc", C.c_float),
-                ("depth_min", C.c_void_p), ("depth_max", C.c_void_p)]
-
-
-class SeedPoints(C.Structure):
-    """mvs_seed_points: the parameters of a warm start (mvs_engine_seed_points)."""
-    _fields_ = [("hypotheses", C.c_int32), ("min_ncc", C.c_float)]
-
-
-class MapsConfig(C.Structure):
-    """mvs_maps_config: the parameters of mvs_engine_render_maps / mvs_engine_fused_points."""
-    _fields_ = [("source", C.c_int32), ("min_consistent", C.c_int32), ("depth_tol", C.c_float), ("normal_cos", C.c_float),
-                ("dedupe", C.c_int32), ("pad", C.c_int32)]
-
-
-class ViewMaps(C.Structure):
-    """mvs_view_maps: where one view's maps go (host or device pointers, any of them null)."""
-    _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("conf", C.c_void_p), ("ids", C.c_void_p), ("agree", C.c_void_p)]
-
-
-class Volume(C.Structure):
-    """mvs_volume: the lattice of mvs_engine_tsdf / mvs_engine_extract_mesh / mvs_engine_mesh, 40 bytes."""
-    _fields_ = [("origin", C.c_float * 3), ("voxel", C.c_float), ("dims", C.c_int32 * 3), ("trunc", C.c_float), ("min_count", C.c_int32),
-                ("pad", C.c_int32)]
-
-    @property
-    def shape(self):
-        """(nz, ny, nx): the shape of the volume's arrays"""
-        return self.dims[2], self.dims[1], self.dims[0]
-
-
-class MeshColouring(C.Structure):
-    """mvs_mesh_colouring: the two thresholds of mvs_engine_mesh_colours, 8 bytes."""
-    _fields_ = [("occl_tol", C.c_float), ("min_cos", C.c_float)]
-
-
-class MeshPruning(C.Structure):
-    """mvs_mesh_pruning: what mvs_engine_mesh_prune keeps, 16 bytes."""
-    _fields_ = [("min_triangles", C.c_int64), ("largest_only", C.c_int32), ("pad", C.c_int32)]
-
-
-class MeshSmoothing(C.Structure):
-    """mvs_mesh_smoothing: the steps of mvs_engine_mesh_smooth, 16 bytes."""
-    _fields_ = [("iterations", C.c_int32), ("lam", C.c_float), ("mu", C.c_float), ("pad", C.c_int32)]
-
-
-class MeshDecimation(C.Structure):
-    """mvs_mesh_decimation: the grid and the placement of mvs_engine_mesh_decimate, 24 bytes."""
-    _fields_ = [("origin", C.c_float * 3), ("cell", C.c_float), ("placement", C.c_int32), ("pad", C.c_int32)]
-
-
-class MeshFilling(C.Structure):
-    """mvs_mesh_filling: the longest loop mvs_engine_mesh_fill closes, 8 bytes."""
-    _fields_ = [("max_edges", C.c_int32), ("pad", C.c_int32)]
-
-
-class MeshViewRender(C.Structure):
-    """mvs_mesh_view_render: where one view's rendered depth and triangle rows go (host or device pointers, either null), 16 bytes."""
-    _fields_ = [("depth", C.c_void_p), ("tri", C.c_void_p)]
-
-
-class Counters(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ("candidates", "prefiltered", "patches", "fail0", "fail1", "inserted",
-                                         "replaced", "evals", "view_evals", "trimmed")]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_}
-
-
-class Timing(C.Structure):
-    _fields_ = [("index_ms", C.c_float), ("sweep_ms", C.c_float), ("commit_ms", C.c_float), ("sweep_launches", C.c_int32),
-                ("exchange_ms", C.c_float), ("sweep_jobs_listed", C.c_int32), ("exchange_bytes", C.c_int64), ("check_retried_cells", C.c_int64)]
-
-
-class FilterStats(C.Structure):
-    _fields_ = [(n, C.c_float) for n in ("outside_ms", "exact_ms", "neighbor_ms", "groups_ms", "rebuild_ms", "total_ms")] + \
-               [(n, C.c_int64) for n in ("patches_in", "exact_patches", "exact_view_evals", "neighbor_patches", "neighbor_tasks", "neighbor_entries",
-                                         "neighbor_visited", "neighbor_accepted", "neighbor_retried", "exchange_bytes")]
-
-
-class EngineError(RuntimeError):
-    """A call of the C ABI returned a negative mvs_status (`status`; include/mvskit_engine.h)."""
-
-    def __init__(self, msg, status=None):
-        super().__init__(msg)
-        self.status = status
-
-
-_libs = {}
-
-
-def load_library(cap32: bool = False, cap: int = 0):
-    """Loads libmvskit_engine.so (view lists of 16) -- or libmvskit_engine_cap32.so / _cap64.so, the same sources built with
-    -DMVS_LISTCAP=32 / 64 (the latter with 192-byte records) -- built in-tree by mvskit_amd.build / __graft_entry__.build."""
-    cap = cap or (32 if cap32 else 16)
-    default = build.ENGINE_LIBS[cap]
-    LIB_PATH = os.environ.get({16: "MVS_ENGINE_LIB", 32: "MVS_ENGINE_LIB32", 64: "MVS_ENGINE_LIB64"}[cap], default)  # development: A/B timing of two builds on one box
-    if LIB_PATH in _libs:
-        return _libs[LIB_PATH]
-    if not os.path.exists(LIB_PATH):
-        raise EngineError(f"{LIB_PATH} is missing: run `python -m mvskit_amd.build` (the engine has no CPU fallback)")
-    try:
-        # torch bundles its own libamdhip64.so.7; two HIP runtimes in one process cannot both open the GPU.
-        # Loaded first, torch's copy satisfies this library's NEEDED entry (same SONAME), so both share one.
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    L = C.CDLL(LIB_PATH)
-    vp = C.c_void_p
-    L.mvs_last_error.restype = C.c_char_p
-    L.mvs_device_count.restype = C.c_int
-    L.mvs_default_config.argtypes = [C.POINTER(Config)]
-    L.mvs_engine_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
-    L.mvs_engine_destroy.argtypes = [vp]
-    L.mvs_engine_set_views.argtypes = [vp, C.c_int, C.POINTER(ViewDesc)]
-    L.mvs_engine_grid_dims.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.mvs_engine_get_pyramid.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.mvs_engine_set_thresholds.argtypes = [vp, C.c_float, C.c_float, C.c_int]
-    L.mvs_engine_get_thresholds.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    L.mvs_engine_update_threshold.argtypes = [vp]
-    L.mvs_engine_upload_patches.argtypes = [vp, C.c_int64, vp]
-    L.mvs_engine_clear_patches.argtypes = [vp]
-    L.mvs_engine_num_patches.argtypes = [vp, C.POINTER(C.c_int64)]
-    L.mvs_engine_download_patches.argtypes = [vp, C.c_int64, vp, C.POINTER(C.c_int64)]
-    L.mvs_engine_propagate.argtypes = [vp, C.c_int, C.POINTER(Counters)]
-    L.mvs_engine_pass.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Counters)]
-    L.mvs_engine_export_counts.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]
-    L.mvs_engine_export_device.argtypes = [vp, vp, C.c_int64, vp, C.c_int64]
-    L.mvs_engine_commit_device.argtypes = [vp, vp, C.c_int64, vp, C.c_int64]
-    L.mvs_engine_commit_local.argtypes = [vp]
-    L.mvs_engine_depth_normal_map.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
-    L.mvs_engine_probe.argtypes = [vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp]
-    L.mvs_engine_last_timing.argtypes = [vp, C.POINTER(Timing)]
-    L.mvs_engine_filter.argtypes = [vp, vp]
-    L.mvs_comm_unique_id.argtypes = [vp]
-    L.mvs_engine_comm_init.argtypes = [vp, vp, C.c_int, C.c_int]
-    L.mvs_engine_comm_attach.argtypes = [vp, vp, C.c_int, C.c_int]
-    L.mvs_engine_comm_release.argtypes = [vp]
-    L.mvs_engine_exchange.argtypes = [vp]
-    L.mvs_list_cap.restype = C.c_int
-    L.mvs_patch_bytes.restype = C.c_int
-    L.mvs_engine_reserve.argtypes = [vp, C.c_int64]
-    L.mvs_engine_filter_stats.argtypes = [vp, C.POINTER(FilterStats)]
-    if hasattr(L, "mvs_engine_set_refiner"):  # absent from a build of an older revision (tools/build_variant.sh, A/B timing)
-        L.mvs_default_refiner.argtypes = [C.POINTER(Refiner)]
-        L.mvs_default_refiner.restype = None
-        L.mvs_engine_set_refiner.argtypes = [vp, C.POINTER(Refiner)]
-    if hasattr(L, "mvs_engine_export_ply"):
-        L.mvs_engine_export_ply.argtypes = [vp, C.c_int, C.c_int64, vp, C.POINTER(C.c_int64)]
-    if hasattr(L, "mvs_engine_seed_patches"):
-        L.mvs_engine_seed_patches.argtypes = [vp, C.c_int64, vp, C.POINTER(SeedView), C.POINTER(C.c_int64)]
-    if hasattr(L, "mvs_engine_seed_random"):
-        L.mvs_default_seed_random.argtypes = [C.POINTER(SeedRandom)]
-        L.mvs_default_seed_random.restype = None
-        L.mvs_engine_seed_random.argtypes = [vp, C.POINTER(SeedRandom), C.POINTER(C.c_int64)]
-        L.mvs_engine_seed_random_hypotheses.argtypes = [vp, C.POINTER(SeedRandom), C.c_int, C.c_int64, vp, vp]
-    if hasattr(L, "mvs_engine_seed_points"):
-        L.mvs_default_seed_points.argtypes = [C.POINTER(SeedPoints)]
-        L.mvs_default_seed_points.restype = None
-        L.mvs_engine_seed_points.argtypes = [vp, C.POINTER(SeedPoints), C.c_int64, vp, C.POINTER(C.c_int64)]
-        L.mvs_engine_seed_points_hypotheses.argtypes = [vp, C.POINTER(SeedPoints), C.c_int64, vp, vp, vp]
-        L.mvs_engine_depth_ranges.argtypes = [vp, C.c_int64, vp, C.c_float, vp, vp, vp]
-    if hasattr(L, "mvs_engine_render_maps"):
-        L.mvs_default_maps_config.argtypes = [C.POINTER(MapsConfig)]
-        L.mvs_default_maps_config.restype = None
-        L.mvs_engine_render_maps.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(ViewMaps), vp]
-        L.mvs_engine_fused_points.argtypes = [vp, C.POINTER(MapsConfig), C.c_int64, vp, C.POINTER(C.c_int64)]
-    if hasattr(L, "mvs_engine_sweep_pairs"):
-        L.mvs_engine_sweep_pairs.argtypes = [vp, C.POINTER(C.c_int64)]
-    if hasattr(L, "mvs_engine_sweep_repeats"):
-        L.mvs_engine_sweep_repeats.argtypes = [vp, C.POINTER(C.c_int64)]
-    if hasattr(L, "mvs_engine_sweep_kernels"):
-        L.mvs_engine_sweep_kernels.argtypes = [vp, C.POINTER(C.c_int64)]
-    if hasattr(L, "mvs_engine_sampler_launches"):
-        L.mvs_engine_sampler_launches.argtypes = [vp, C.POINTER(C.c_int64)]
-    if hasattr(L, "mvs_engine_tsdf"):
-        L.mvs_engine_tsdf.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(Volume), vp, vp]
-        L.mvs_engine_extract_mesh.argtypes = [vp, C.POINTER(Volume), vp, vp, C.c_int64, vp, C.c_int64, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.mvs_engine_mesh.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(Volume), C.c_int64, vp, C.c_int64, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    if hasattr(L, "mvs_engine_mesh_normals"):
-        L.mvs_default_mesh_colouring.argtypes = [C.POINTER(MeshColouring)]
-        L.mvs_default_mesh_colouring.restype = None
-        L.mvs_engine_mesh_normals.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp]
-        L.mvs_engine_mesh_colours.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(MeshColouring), C.c_int64, vp, vp, vp, vp]
-    if hasattr(L, "mvs_engine_mesh_components"):
-        L.mvs_default_mesh_pruning.argtypes = [C.POINTER(MeshPruning)]
-        L.mvs_default_mesh_pruning.restype = None
-        L.mvs_default_mesh_smoothing.argtypes = [C.POINTER(MeshSmoothing)]
-        L.mvs_default_mesh_smoothing.restype = None
-        L.mvs_engine_mesh_components.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp, C.POINTER(C.c_int64)]
-        L.mvs_engine_mesh_prune.argtypes = [vp, C.POINTER(MeshPruning), C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp,
-                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.mvs_engine_mesh_smooth.argtypes = [vp, C.POINTER(MeshSmoothing), C.c_int64, vp, C.c_int64, vp, vp]
-    if hasattr(L, "mvs_engine_mesh_decimate"):
-        L.mvs_default_mesh_decimation.argtypes = [C.POINTER(MeshDecimation)]
-        L.mvs_default_mesh_decimation.restype = None
-        L.mvs_engine_mesh_decimate.argtypes = [vp, C.POINTER(MeshDecimation), C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp,
-                                               C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    if hasattr(L, "mvs_engine_mesh_fill"):
-        L.mvs_default_mesh_filling.argtypes = [C.POINTER(MeshFilling)]
-        L.mvs_default_mesh_filling.restype = None
-        L.mvs_engine_mesh_boundaries.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.mvs_engine_mesh_fill.argtypes = [vp, C.POINTER(MeshFilling), C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp,
-                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    if hasattr(L, "mvs_engine_mesh_render"):
-        L.mvs_engine_mesh_render.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, C.POINTER(MeshViewRender), vp, vp, vp, vp]
-        L.mvs_engine_mesh_render_lists.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp]
-        L.mvs_engine_mesh_visibility.argtypes = [vp, C.c_float, C.c_int64, vp, C.c_int64, vp, vp]
-        L.mvs_engine_mesh_colours_visible.argtypes = [vp, C.POINTER(MapsConfig), C.POINTER(MeshColouring), C.c_int64, vp, vp, vp, vp, vp]
-    _libs[LIB_PATH] = L
-    return L
 
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _verts(a):
+    """[n, 3] float32, C order: mesh vertices, and the world points of the seed calls"""
+    return np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+
+
+_points = _verts
+
+
+def _tris(a):
+    """[m, 3] int32, C order"""
+    return np.ascontiguousarray(a, dtype=np.int32).reshape(-1, 3)
+
+
+def _record(s):
+    """a struct of numbers as a dictionary: int for the integer fields, float for the float fields"""
+    return {n: getattr(s, n) for n, _ in s._fields_}
 
 
 class Engine:
@@ -310,7 +55,6 @@ class Engine:
             setattr(self.cfg, k, v)
         self.h = C.c_void_p()
         self._check(self.L.mvs_engine_create(C.byref(self.cfg), C.byref(self.h)))
-        self._keep = None
 
     def _check(self, status):
         if status != 0:
@@ -398,10 +142,10 @@ class Engine:
         n = self.cfg.nviews
         if len(normal_maps) != n or (masks is not None and len(masks) != n):
             raise ValueError(f"seed_patches: {n} views, one normal map (and mask) each")
-        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        pts = _points(points)
         shapes = getattr(self, "_view_shapes", None)
         views = (SeedView * n)()
-        keep = [pts]
+        keep = []  # the maps and masks, until the call has returned
         for v in range(n):
             views[v].normals = views[v].mask = None
             shape = shapes[v] if shapes is not None else None
@@ -434,20 +178,18 @@ class Engine:
         [depth_min, depth_max] along the view's optical axis and within max_tilt of the direction to the camera, the best-scoring one
         refined and post-processed on the device; the patches that pass are appended to the pool in (view, cell) order.  Ranges:
         one value per view or a scalar for all.  min_ncc None: the engine's nccThresholdBefore.  Returns how many were appended."""
-        s, keep = self._seed_random_args(depth_min, depth_max, hypotheses, seed, max_tilt, min_ncc)
+        s, _ranges = self._seed_random_args(depth_min, depth_max, hypotheses, seed, max_tilt, min_ncc)
         added = C.c_int64()
         self._check(self.L.mvs_engine_seed_random(self.h, C.byref(s), C.byref(added)))
-        del keep
         return added.value
 
     def seed_random_hypotheses(self, view, cells, depth_min, depth_max, hypotheses=8, seed=1, max_tilt=math.pi / 3, min_ncc=None):
         """The hypotheses seed_random scores, as records: `hypotheses` per listed cell (cy * gw + cx) of `view`, hypothesis k of cells[i]
         at [i * hypotheses + k].  Reads engine state only."""
-        s, keep = self._seed_random_args(depth_min, depth_max, hypotheses, seed, max_tilt, min_ncc)
+        s, _ranges = self._seed_random_args(depth_min, depth_max, hypotheses, seed, max_tilt, min_ncc)
         cells = np.ascontiguousarray(cells, dtype=np.int32).ravel()
         out = np.zeros(cells.shape[0] * max(int(hypotheses), 0), dtype=self.dtype)
         self._check(self.L.mvs_engine_seed_random_hypotheses(self.h, C.byref(s), int(view), cells.shape[0], _ptr(cells), _ptr(out)))
-        del keep
         return out
 
     def seed_points(self, points, hypotheses=4, min_ncc=None):
@@ -455,7 +197,7 @@ class Engine:
         points of structure-from-motion) at most `hypotheses` reference views, nearest first, each with the normal turned towards its
         camera; the best-scoring one refined and post-processed on the device; the patches that pass are appended to the pool in point
         order.  min_ncc None: the engine's nccThresholdBefore.  Returns how many were appended."""
-        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        pts = _points(points)
         s = SeedPoints(int(hypotheses), -1.0 if min_ncc is None else float(min_ncc))
         added = C.c_int64()
         self._check(self.L.mvs_engine_seed_points(self.h, C.byref(s), pts.shape[0], _ptr(pts), C.byref(added)))
@@ -464,7 +206,7 @@ class Engine:
     def seed_points_hypotheses(self, points, hypotheses=4, min_ncc=None):
         """The hypotheses seed_points scores -> (records, count): count[i] hypotheses of point i at records[i * hypotheses ...], zero
         records in the slots behind.  Reads engine state only."""
-        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        pts = _points(points)
         s = SeedPoints(int(hypotheses), -1.0 if min_ncc is None else float(min_ncc))
         out = np.zeros(pts.shape[0] * max(int(hypotheses), 0), dtype=self.dtype)
         count = np.zeros(pts.shape[0], np.int32)
@@ -474,7 +216,7 @@ class Engine:
     def depth_ranges(self, points, margin=0.1):
         """Per view the depth range of the points that pass its gate, widened by `margin` -> (depth_min, depth_max, count): float32
         arrays that seed_random takes as they are, and the number of qualifying points per view (a view with none: 0, 0)."""
-        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        pts = _points(points)
         n = self.cfg.nviews
         lo, hi, count = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int64)
         self._check(self.L.mvs_engine_depth_ranges(self.h, pts.shape[0], _ptr(pts), float(margin), _ptr(lo), _ptr(hi), _ptr(count)))
@@ -581,9 +323,10 @@ class Engine:
         self._check(self.L.mvs_engine_tsdf(self.h, C.byref(c), C.byref(volume), _ptr(tsdf), _ptr(count)))
         return tsdf, count
 
-    def _mesh(self, call, cap_v=0, cap_t=0):
+    def _mesh(self, call, cap_v=0, cap_t=0, always=False):
         """-> (verts [n, 3] float32, tris [m, 3] int32).  With estimated caps the full call comes first, and only a mesh that does not fit
-        them (MVS_ERR_CAPACITY leaves the exact counts) is run again; without, the size call comes first."""
+        them (MVS_ERR_CAPACITY leaves the exact counts) is run again; without, the size call comes first.  An empty mesh is not asked for
+        a second time unless `always`."""
         nv, nt = C.c_int64(), C.c_int64()
         if cap_v > 0 and cap_t > 0:
             verts, tris = np.zeros((cap_v, 3), np.float32), np.zeros((cap_t, 3), np.int32)
@@ -595,9 +338,16 @@ class Engine:
         else:
             self._check(call(0, None, 0, None, C.byref(nv), C.byref(nt)))
         verts, tris = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
-        if nv.value or nt.value:
+        if always or nv.value or nt.value:
             self._check(call(nv.value, _ptr(verts), nt.value, _ptr(tris), C.byref(nv), C.byref(nt)))
         return verts, tris
+
+    def _mesh_vmap(self, fn, params, verts, tris):
+        """prune_mesh / decimate_mesh -> (verts, tris, vmap): the size call without vmap, then always the full call, vmap preset to -1"""
+        vmap = np.full(verts.shape[0], -1, np.int32)
+        head = (self.h, C.byref(params), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris))
+        out_v, out_t = self._mesh(lambda cap_v, pv, cap_t, pt, *n: fn(*head, cap_v, pv, cap_t, pt, None if pv is None else _ptr(vmap), *n), always=True)
+        return out_v, out_t, vmap
 
     def extract_mesh(self, volume, tsdf, count=None):
         """Marching tetrahedra over a volume (include/mvskit_engine.h, mvs_engine_extract_mesh): (verts [n, 3] float32, tris [m, 3] int32),
@@ -621,8 +371,7 @@ class Engine:
         """Area-weighted vertex normals of the mesh verts [n, 3], tris [m, 3] (include/mvskit_engine.h, mvs_engine_mesh_normals): float32
         [n, 3], unit length, zero for a vertex that no triangle with an area uses.  An order-free integer sum: the same bytes whatever
         order the triangles are listed in.  Needs no views."""
-        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        verts, tris = _verts(verts), _tris(tris)
         out = np.zeros((verts.shape[0], 3), np.float32)
         self._check(self.L.mvs_engine_mesh_normals(self.h, verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), _ptr(out)))
         return out
@@ -635,9 +384,9 @@ class Engine:
         their number | 0x80), otherwise the views whose map says nothing there (used = their number); grey and 0 with no view at all.
         visible: a uint64 per vertex (mesh_visibility's, or the caller's); view v then counts for vertex i only when bit v of visible[i]
         is set (mvs_engine_mesh_colours_visible).  Reads engine state only."""
-        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        verts = _verts(verts)
         if normals is not None:
-            normals = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+            normals = _verts(normals)
             if normals.shape != verts.shape:
                 raise ValueError("mesh_colours: one normal per vertex")
         c = self._maps_config(source, min_consistent, depth_tol, normal_cos, 0)
@@ -661,8 +410,7 @@ class Engine:
         covered [nviews] int64, the pixels with a triangle; skipped [nviews] int64, the triangles with a vertex behind the camera, not
         finite or beyond 2^16 pixels (there is no near-plane clipping).  Both faces render, masks play no part.  An order-free minimum:
         the same bytes whatever order the triangles are listed in.  Needs views but no pool."""
-        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        verts, tris = _verts(verts), _tris(tris)
         n = self.cfg.nviews
         want = range(n) if views is None else [int(v) for v in views]
         if any(v < 0 or v >= n for v in want):
@@ -682,8 +430,7 @@ class Engine:
         """What the render sees of every vertex (mvs_engine_mesh_render's screen and vdepth): (screen [nviews, n, 2] int32, the position
         in 1/256 pixel; vdepth [nviews, n] float32, the depth along the optical axis).  A vertex is usable in a view when its depth is
         positive and finite and |screen| <= 2^24."""
-        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        verts, tris = _verts(verts), _tris(tris)
         n = self.cfg.nviews
         screen, vdepth = np.zeros((n, verts.shape[0], 2), np.int32), np.zeros((n, verts.shape[0]), np.float32)
         self._check(self.L.mvs_engine_mesh_render(self.h, verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), None, _ptr(screen), _ptr(vdepth), None, None))
@@ -692,8 +439,7 @@ class Engine:
     def mesh_render_lists(self, verts, tris):
         """Per view the triangles of the mesh that the render hands to its wave-per-triangle kernel, a clipped bounding box of more than
         32 pixel centres (mvs_engine_mesh_render_lists): int64 [nviews], counted on the device.  The others are rasterised a lane each."""
-        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        verts, tris = _verts(verts), _tris(tris)
         out = np.zeros(self.cfg.nviews, np.int64)
         self._check(self.L.mvs_engine_mesh_render_lists(self.h, verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), _ptr(out)))
         return out
@@ -702,8 +448,7 @@ class Engine:
         """The views that see each vertex of the mesh (include/mvskit_engine.h, mvs_engine_mesh_visibility): uint64 [n], bit v set when the
         vertex is usable in view v, its nearest pixel lies inside the image and the mesh rendered there is not nearer than the vertex by
         more than `tol`, relative (an empty pixel hides nothing).  What mesh_colours(visible=) takes.  Needs views but no pool."""
-        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        verts, tris = _verts(verts), _tris(tris)
         out = np.zeros(verts.shape[0], np.uint64)
         self._check(self.L.mvs_engine_mesh_visibility(self.h, float(tol), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), _ptr(out)))
         return out
@@ -713,7 +458,7 @@ class Engine:
         """The connected components of the mesh's vertex graph (include/mvskit_engine.h, mvs_engine_mesh_components): (label [n_v] int32,
         the smallest vertex id of each vertex's component; ntris [n_v] int32, the triangles of that component; the number of components
         with a triangle).  Needs no views."""
-        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        tris = _tris(tris)
         label, ntris, n = np.zeros(int(n_v), np.int32), np.zeros(int(n_v), np.int32), C.c_int64()
         self._check(self.L.mvs_engine_mesh_components(self.h, int(n_v), tris.shape[0], _ptr(tris), _ptr(label), _ptr(ntris), C.byref(n)))
         return label, ntris, n.value
@@ -722,27 +467,14 @@ class Engine:
         """The mesh without the components of fewer than min_triangles triangles (largest_only: without all but the largest) and without
         the vertices that no kept triangle names (include/mvskit_engine.h, mvs_engine_mesh_prune): (verts, tris, vmap [n] int32, the new
         id of every input vertex or -1).  What stays keeps its order and its bytes.  The size call comes first.  Needs no views."""
-        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
-        p = MeshPruning(int(min_triangles), int(bool(largest_only)), 0)
-        nv, nt = C.c_int64(), C.c_int64()
-
-        def call(cap_v, out_v, cap_t, out_t, vmap):
-            return self.L.mvs_engine_mesh_prune(self.h, C.byref(p), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), cap_v, _ptr(out_v), cap_t,
-                                                _ptr(out_t), _ptr(vmap), C.byref(nv), C.byref(nt))
-
-        self._check(call(0, None, 0, None, None))
-        out_v, out_t = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
-        vmap = np.full(verts.shape[0], -1, np.int32)
-        self._check(call(nv.value, out_v, nt.value, out_t, vmap))
-        return out_v, out_t, vmap
+        verts, tris = _verts(verts), _tris(tris)
+        return self._mesh_vmap(self.L.mvs_engine_mesh_prune, MeshPruning(int(min_triangles), int(bool(largest_only)), 0), verts, tris)
 
     def smooth_mesh(self, verts, tris, iterations=10, lam=0.5, mu=-0.53):
         """Taubin smoothing of the positions (include/mvskit_engine.h, mvs_engine_mesh_smooth): float32 [n, 3].  Every iteration moves
         each vertex by lam towards the mean of its triangles' other corners and then, unless mu is 0, by mu away from it again; an
         order-free integer sum, the same bytes whatever order the triangles are listed in.  Boundaries are not pinned.  Needs no views."""
-        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        verts, tris = _verts(verts), _tris(tris)
         s = MeshSmoothing(int(iterations), float(lam), float(mu), 0)
         out = np.zeros((verts.shape[0], 3), np.float32)
         self._check(self.L.mvs_engine_mesh_smooth(self.h, C.byref(s), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), _ptr(out)))
@@ -755,22 +487,11 @@ class Engine:
         the cell's vertices (placement "mean") or at the one of them nearest to that mean ("member"); triangles that no longer join
         three cells go, and of those that join the same three only the first stays.  The result of a closed surface need not be closed.
         The same bytes whatever order the hardware meets the triangles in.  The size call comes first.  Needs no views."""
-        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        verts, tris = _verts(verts), _tris(tris)
         if placement not in ("mean", "member"):
             raise ValueError("decimate_mesh: placement is 'mean' or 'member'")
         d = MeshDecimation((C.c_float * 3)(*[float(o) for o in origin]), float(cell), 1 if placement == "member" else 0, 0)
-        nv, nt = C.c_int64(), C.c_int64()
-
-        def call(cap_v, out_v, cap_t, out_t, vmap):
-            return self.L.mvs_engine_mesh_decimate(self.h, C.byref(d), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), cap_v, _ptr(out_v), cap_t,
-                                                   _ptr(out_t), _ptr(vmap), C.byref(nv), C.byref(nt))
-
-        self._check(call(0, None, 0, None, None))
-        out_v, out_t = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
-        vmap = np.full(verts.shape[0], -1, np.int32)
-        self._check(call(nv.value, out_v, nt.value, out_t, vmap))
-        return out_v, out_t, vmap
+        return self._mesh_vmap(self.L.mvs_engine_mesh_decimate, d, verts, tris)
 
     # ---- mesh hole filling
     def mesh_boundaries(self, n_v, tris):
@@ -778,7 +499,7 @@ class Engine:
         of each vertex's boundary component or -1; length [n_v] int32, the half-edges of that component, negated when it is no simple
         loop; the numbers of loops, of complex components and of irregular edges).  A mesh is a closed edge-manifold exactly when the
         three counts are 0.  Needs no views."""
-        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        tris = _tris(tris)
         loop, length = np.zeros(int(n_v), np.int32), np.zeros(int(n_v), np.int32)
         nl, nc, ni = C.c_int64(), C.c_int64(), C.c_int64()
         self._check(self.L.mvs_engine_mesh_boundaries(self.h, int(n_v), tris.shape[0], _ptr(tris), _ptr(loop), _ptr(length), C.byref(nl), C.byref(nc),
@@ -791,19 +512,11 @@ class Engine:
         it.  The input rows stay where they are, the new ones follow them; ids do not change.  The rim of an open surface is a loop too:
         max_edges keeps it open.  The same bytes whatever order the hardware meets the triangles in.  The size call comes first.  Needs
         no views."""
-        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        verts, tris = _verts(verts), _tris(tris)
         f = MeshFilling(int(max_edges), 0)
-        nv, nt, nf = C.c_int64(), C.c_int64(), C.c_int64()
-
-        def call(cap_v, out_v, cap_t, out_t):
-            return self.L.mvs_engine_mesh_fill(self.h, C.byref(f), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), cap_v, _ptr(out_v), cap_t,
-                                               _ptr(out_t), C.byref(nv), C.byref(nt), C.byref(nf))
-
-        self._check(call(0, None, 0, None))
-        out_v, out_t = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32)
-        if nv.value or nt.value:
-            self._check(call(nv.value, out_v, nt.value, out_t))
+        nf = C.c_int64()
+        out_v, out_t = self._mesh(lambda *a: self.L.mvs_engine_mesh_fill(self.h, C.byref(f), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), *a,
+                                                                         C.byref(nf)))
         return out_v, out_t, nf.value
 
     def coloured_mesh(self, volume, source=0, min_consistent=1, depth_tol=0.01, normal_cos=0.9, occl_tol=0.01, min_cos=0.1, cap_v=0, cap_t=0,
@@ -846,7 +559,7 @@ class Engine:
     def filter_stats(self):
         f = FilterStats()
         self._check(self.L.mvs_engine_filter_stats(self.h, C.byref(f)))
-        return {n: getattr(f, n) for n, _ in f._fields_}
+        return _record(f)
 
     def engine_pass(self, it, p):
         c = Counters()
@@ -884,7 +597,6 @@ class Engine:
     def comm_info(self):
         """rank / world the engine holds and what its communicator reports (ncclCommCount / ncclCommUserRank; -1 if it cannot be asked)"""
         r, w, cc, cr = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-        self.L.mvs_engine_comm_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
         self._check(self.L.mvs_engine_comm_info(self.h, C.byref(r), C.byref(w), C.byref(cc), C.byref(cr)))
         return {"rank": r.value, "world": w.value, "comm_count": cc.value, "comm_rank": cr.value}
 
@@ -897,41 +609,37 @@ class Engine:
     def timing(self):
         t = Timing()
         self._check(self.L.mvs_engine_last_timing(self.h, C.byref(t)))
-        return {"index_ms": t.index_ms, "sweep_ms": t.sweep_ms, "commit_ms": t.commit_ms, "sweep_launches": t.sweep_launches,
-                "exchange_ms": t.exchange_ms, "exchange_bytes": int(t.exchange_bytes), "check_retried_cells": int(t.check_retried_cells),
-                "sweep_jobs_listed": int(t.sweep_jobs_listed)}
+        return _record(t)
+
+    def _counts(self, fn, keys):
+        """the `int64_t out[N]` counters of fn under their keys"""
+        out = (C.c_int64 * len(keys))()
+        self._check(fn(self.h, out))
+        return dict(zip(keys, (int(x) for x in out)))
 
     #: mvs_engine_sweep_pairs: the sweep's trials by how they were refined, since the engine was created
     SWEEP_PAIR_KEYS = ("paired", "alone_no_partner", "alone_no_room", "alone_partner_failed", "alone_long_list", "can_pair")
 
     def sweep_pairs(self):
-        out = (C.c_int64 * 6)()
-        self._check(self.L.mvs_engine_sweep_pairs(self.h, out))
-        return dict(zip(self.SWEEP_PAIR_KEYS, (int(x) for x in out)))
+        return self._counts(self.L.mvs_engine_sweep_pairs, self.SWEEP_PAIR_KEYS)
 
     #: mvs_engine_sweep_repeats: the trials of full cells that did not run again what the trial before them had computed
     SWEEP_REPEAT_KEYS = ("skipped", "from_stash")
 
     def sweep_repeats(self):
-        out = (C.c_int64 * 2)()
-        self._check(self.L.mvs_engine_sweep_repeats(self.h, out))
-        return dict(zip(self.SWEEP_REPEAT_KEYS, (int(x) for x in out)))
+        return self._counts(self.L.mvs_engine_sweep_repeats, self.SWEEP_REPEAT_KEYS)
 
     #: mvs_engine_sweep_kernels: sweep launches by the kernel the launcher chose, since the engine was created
     SWEEP_KERNEL_KEYS = ("generic", "full_window")
 
     def sweep_kernels(self):
-        out = (C.c_int64 * 2)()
-        self._check(self.L.mvs_engine_sweep_kernels(self.h, out))
-        return dict(zip(self.SWEEP_KERNEL_KEYS, (int(x) for x in out)))
+        return self._counts(self.L.mvs_engine_sweep_kernels, self.SWEEP_KERNEL_KEYS)
 
     #: mvs_engine_sampler_launches: sweep launches and refine probes by the form of their texture samplers, since the engine was created
     SAMPLER_LAUNCH_KEYS = ("sweep_wide", "sweep_narrow", "refine_wide", "refine_narrow")
 
     def sampler_launches(self):
-        out = (C.c_int64 * 4)()
-        self._check(self.L.mvs_engine_sampler_launches(self.h, out))
-        return dict(zip(self.SAMPLER_LAUNCH_KEYS, (int(x) for x in out)))
+        return self._counts(self.L.mvs_engine_sampler_launches, self.SAMPLER_LAUNCH_KEYS)
 
     def depth_normal_map(self, view, kind):
         gw, gh = self.grid_dims(view)
