@@ -755,8 +755,9 @@ int mvs_engine_mesh_fill(mvs_engine* e, const mvs_mesh_filling* f, int64_t n_v, 
  * over the limit; verts NULL with n_v > 0; tris NULL with n_t > 0; (visibility: visible NULL with n_v > 0;) no engine.  MVS_ERR_STATE: the
  * views are not set, or a pass is waiting for its commit.  Then MVS_ERR_ARG after one validating pass on the device: an id outside
  * 0 .. n_v - 1.  MVS_ERR_HIP: an allocation or copy failed.
- * WHAT THE RENDER DOES NOT DO: near-plane clipping, back-face culling, masks, interpolation of attributes other than depth, a texture
- * atlas, a variant sharded over GPUs. */
+ * WHAT THE RENDER DOES NOT DO: near-plane clipping, back-face culling, masks, interpolation of attributes other than depth, a variant
+ * sharded over GPUs.  A texture atlas is not the render's either: mvs_engine_mesh_face_views and mvs_engine_mesh_texture in
+ * mvskit_texture.h build one from the render's vertices and this visibility. */
 typedef struct mvs_mesh_view_render {
     float* depth; /* H_L*W_L: depth of the nearest triangle at the pixel centre; quiet NaN where none covers it */
     int32_t* tri; /* H_L*W_L: that triangle's row in tris; -1 */

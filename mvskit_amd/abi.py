@@ -1,5 +1,7 @@
 """What mirrors include/mvskit_engine.h, once: the constants, the record dtypes, the structs, the signature of every entry point, and
-the loader that applies them.  tests/test_abi.py holds SIGNATURES and STRUCTS against the header itself."""
+the loader that applies them.  tests/test_abi.py holds SIGNATURES and STRUCTS against the header itself.  The textured-mesh calls of
+include/mvskit_texture.h have a table of their own, TEXTURE_SIGNATURES and TEXTURE_STRUCTS, which tests/test_mesh_texture_abi.py holds
+against that header in the same way."""
 from __future__ import annotations
 
 import ctypes as C
@@ -13,7 +15,8 @@ __all__ = ["PROBE_NCC", "PROBE_PREPROCESS", "PROBE_REFINE", "PROBE_POSTPROCESS",
            "REFINE_CONVERGED", "MVS_OK", "MVS_ERR_ARG", "MVS_ERR_STATE", "MVS_ERR_HIP", "MVS_ERR_CAPACITY", "MVS_ERR_NO_DEVICE", "PLY_ASCII",
            "PLY_BINARY_LE", "PLY_VERTEX_DTYPE", "FUSED_POINT_DTYPE", "Config", "Refiner", "ViewDesc", "SeedView", "SeedRandom", "SeedPoints",
            "MapsConfig", "ViewMaps", "Volume", "MeshColouring", "MeshPruning", "MeshSmoothing", "MeshDecimation", "MeshFilling", "MeshViewRender",
-           "Counters", "Timing", "FilterStats", "STRUCTS", "SIGNATURES", "EXPORTS", "EngineError", "load_library"]
+           "MeshTexturing", "TEXTURE_STRUCTS", "TEXTURE_SIGNATURES", "Counters", "Timing", "FilterStats", "STRUCTS", "SIGNATURES", "EXPORTS",
+           "EngineError", "load_library"]
 
 PROBE_NCC, PROBE_PREPROCESS, PROBE_REFINE, PROBE_POSTPROCESS, PROBE_COST, PROBE_MATH, PROBE_REFINE_X = range(7)
 REFINE_HALVING, REFINE_CONVERGED = 0, 1  # mvs_refine_mode
@@ -111,6 +114,11 @@ class MeshFilling(C.Structure):
 class MeshViewRender(C.Structure):
     """mvs_mesh_view_render: where one view's rendered depth and triangle rows go (host or device pointers, either null), 16 bytes."""
     _fields_ = [("depth", C.c_void_p), ("tri", C.c_void_p)]
+
+
+class MeshTexturing(C.Structure):
+    """mvs_mesh_texturing (include/mvskit_texture.h): the atlas of mvs_engine_mesh_face_views / mvs_engine_mesh_texture, 16 bytes."""
+    _fields_ = [("res", C.c_int32), ("width", C.c_int32), ("front_only", C.c_int32), ("pad", C.c_int32)]
 
 
 class Counters(C.Structure):
@@ -229,6 +237,24 @@ SIGNATURES = _signatures()
 EXPORTS = list(SIGNATURES)
 
 
+#: include/mvskit_texture.h: its struct, and its entry points in its order
+TEXTURE_STRUCTS = {"mvs_mesh_texturing": MeshTexturing}
+
+
+def _texture_signatures():
+    P, vp, i, i64 = C.POINTER, C.c_void_p, C.c_int, C.c_int64
+    tex, pi64 = P(MeshTexturing), P(C.c_int64)
+    mesh_in = [i64, vp, i64, vp]               # n_v, verts, n_t, tris
+    return {
+        "mvs_default_mesh_texturing": (None, [tex]),
+        "mvs_engine_mesh_face_views": (i, [vp, tex] + mesh_in + [vp, vp, vp, vp]),
+        "mvs_engine_mesh_texture": (i, [vp, tex] + mesh_in + [vp, i64, vp, vp, pi64, pi64]),
+    }
+
+
+TEXTURE_SIGNATURES = _texture_signatures()
+
+
 class EngineError(RuntimeError):
     """A call of the C ABI returned a negative mvs_status (`status`; include/mvskit_engine.h)."""
 
@@ -257,7 +283,7 @@ def load_library(cap32: bool = False, cap: int = 0):
     except ImportError:
         pass
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **TEXTURE_SIGNATURES}.items():
         # a build of an older revision (tools/build_variant.sh, A/B timing) lacks the newer symbols: the method that needs one raises AttributeError
         fn = getattr(L, name, None)
         if fn is not None:

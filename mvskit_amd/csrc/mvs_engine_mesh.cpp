@@ -1,13 +1,15 @@
 // mvs_engine_mesh.cpp -- the mesh calls of the C ABI in include/mvskit_engine.h: the TSDF volume over the dense maps and its extraction
 // (mvs_mesh.hip), vertex normals and colours (mvs_mesh_attr.hip), components, pruning and smoothing (mvs_mesh_clean.hip), decimation
 // (mvs_mesh_decimate.hip), boundary loops and hole filling (mvs_mesh_fill.hip), the mesh rendered into the views and the vertex
-// visibility (mvs_mesh_render.hip).  The maps they start from come from
+// visibility (mvs_mesh_render.hip), the view of each triangle and the texture atlas (mvs_mesh_texture.hip; declared in
+// include/mvskit_texture.h).  The maps they start from come from
 // mvs_engine_output.cpp (render_usable).  Every entry point is stateless: its working arrays live in buffers of the call, the caller's
 // arrays come into them from wherever they lie, and nothing of the engine's state changes.
 #include <cmath>
 #include <cstdlib>
 
 #include "mvs_engine_impl.h"
+#include "mvskit_texture.h"
 
 using namespace mvseng;
 
@@ -746,6 +748,131 @@ int mvs_engine_mesh_visibility(mvs_engine* e, float tol, int64_t n_v, const floa
     HIPCHK(hipStreamSynchronize(st));  // a failure is known before anything is written
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(visible, b.visible.p, (size_t)n_v * sizeof(uint64_t), hipMemcpyDefault, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MVS_OK;
+}
+
+// Textured mesh (mvs_mesh_texture.hip; the definitions are in mvskit_engine.h): the view that textures each triangle, then the atlas and
+// the texture coordinates.  Stateless like the render, and the views stream through the render's per-vertex buffers.
+static_assert(sizeof(mvs_mesh_texturing) == 16, "mvs_mesh_texturing is 16 bytes");
+namespace {
+int mtex_args(const mvs_mesh_texturing* x, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, const int32_t* label, const char* who) {
+    if (!x) { g_err = std::string(who) + ": texturing null"; return MVS_ERR_ARG; }
+    if (x->res < 1 || x->res > 256) { g_err = std::string(who) + ": res outside 1..256"; return MVS_ERR_ARG; }
+    if (x->width < x->res + 3 || x->width > 32768) { g_err = std::string(who) + ": width outside res + 3 .. 32768"; return MVS_ERR_ARG; }
+    if (int r = mesh_in_args(n_v, verts, n_t, tris, who)) return r;
+    if (!label && n_t > 0) { g_err = std::string(who) + ": label null"; return MVS_ERR_ARG; }
+    return MVS_OK;
+}
+struct MtexBufs {
+    DevBuf<int32_t> d_tris, scr, label, win, flag, base, scan, list, uv;
+    DevBuf<uint32_t> words, ok;
+    DevBuf<float> d_verts, vd;
+    DevBuf<long long> area;
+    DevBuf<unsigned long long> visible, counts;
+    DevBuf<uint8_t> rgb;
+};
+// the caller's mesh checked and on the device, the per-vertex buffers of a view allocated; the stream is idle on return
+int mtex_take_mesh(mvs_engine* e, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, MtexBufs& b, const char* who) {
+    if (int r = mesh_take_tris(e, n_v, n_t, tris, b.d_tris, b.words, who)) return r;
+    if (b.d_verts.ensure(3 * n_v) || b.scr.ensure(2 * n_v) || b.vd.ensure(n_v) || b.ok.ensure(n_v) || b.label.ensure(n_t)) return MVS_ERR_HIP;
+    return upload_rows(e, b.d_verts.p, verts, n_v);
+}
+// f_v: the sign of a triangle's area in view v when its face vector points to the camera centre, -sign(det M) for P_L = [M | p]; 0 for a
+// camera without an orientation
+int mtex_front_sign(const mvs_engine* e, int v) {
+    const float* P = e->hviews[v].P[e->cfg.level];
+    const double a = P[0], b = P[1], c = P[2], d = P[4], f = P[5], g = P[6], h = P[8], i = P[9], j = P[10];
+    const double det = a * (f * j - g * i) - b * (d * j - g * h) + c * (d * i - f * h);
+    return det > 0.0 ? -1 : (det < 0.0 ? 1 : 0);
+}
+}  // namespace
+
+void mvs_default_mesh_texturing(mvs_mesh_texturing* x) {
+    if (!x) return;
+    x->res = 8; x->width = 4096; x->front_only = 1; x->pad = 0;
+}
+
+int mvs_engine_mesh_face_views(mvs_engine* e, const mvs_mesh_texturing* x, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris,
+                               const uint64_t* visible, int32_t* label, int64_t* area, int64_t* n_faces) {
+    const char* who = "mvs_engine_mesh_face_views";
+    if (int r = mtex_args(x, n_v, verts, n_t, tris, label, who)) return r;
+    if (int r = need_state(e, NEED_IDLE, who)) return r;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:mesh_face_views");
+    hipStream_t st = e->stream;
+    const int nviews = e->cfg.nviews, level = e->cfg.level;
+    MtexBufs b;
+    if (int r = mtex_take_mesh(e, n_v, verts, n_t, tris, b, who)) return r;
+    if (b.area.ensure(n_t) || b.counts.ensure(MVS_MAXVIEWS) || (visible && b.visible.ensure(n_v))) return MVS_ERR_HIP;
+    if (visible && n_v > 0) HIPCHK(hipMemcpyAsync(b.visible.p, visible, (size_t)n_v * sizeof(uint64_t), hipMemcpyDefault, st));
+    if (n_t > 0) {
+        HIPCHK(hipMemsetAsync(b.area.p, 0, (size_t)n_t * sizeof(long long), st));
+        HIPCHK(hipMemsetAsync(b.label.p, 0xff, (size_t)n_t * sizeof(int32_t), st));
+    }
+    HIPCHK(hipMemsetAsync(b.counts.p, 0, (size_t)MVS_MAXVIEWS * sizeof(unsigned long long), st));
+    const DParams p = current_params(e);
+    for (int v = 0; v < nviews; ++v) {  // one stream: a view's kernels run behind those of the view before, through the same buffers
+        const int want = x->front_only ? mtex_front_sign(e, v) : 0;
+        if (x->front_only && want == 0) continue;
+        mvsk_mrender_project(p, v, n_v, b.d_verts.p, b.scr.p, b.vd.p, b.ok.p, st);
+        mvsk_mtex_best(v, want, n_t, b.d_tris.p, b.scr.p, b.ok.p, visible ? b.visible.p : nullptr, e->hviews[v].W[level], e->hviews[v].H[level], b.area.p,
+                       b.label.p, st);
+    }
+    mvsk_mtex_count(n_t, b.label.p, nviews, b.counts.p, st);
+    std::vector<unsigned long long> hc((size_t)nviews, 0ull);
+    HIPCHK(hipMemcpyAsync(hc.data(), b.counts.p, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));  // a failure is known before anything is written
+    HIPCHK(hipGetLastError());
+    std::vector<int64_t> faces(hc.begin(), hc.end());
+    if (n_t > 0) HIPCHK(hipMemcpyAsync(label, b.label.p, (size_t)n_t * sizeof(int32_t), hipMemcpyDefault, st));
+    if (area && n_t > 0) HIPCHK(hipMemcpyAsync(area, b.area.p, (size_t)n_t * sizeof(int64_t), hipMemcpyDefault, st));
+    if (n_faces) HIPCHK(hipMemcpyAsync(n_faces, faces.data(), (size_t)nviews * sizeof(int64_t), hipMemcpyDefault, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MVS_OK;
+}
+
+int mvs_engine_mesh_texture(mvs_engine* e, const mvs_mesh_texturing* x, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, const int32_t* label,
+                            int64_t cap_h, uint8_t* rgb, int32_t* uv, int64_t* height, int64_t* n_textured) {
+    const char* who = "mvs_engine_mesh_texture";
+    if (int r = mtex_args(x, n_v, verts, n_t, tris, label, who)) return r;
+    if (!height || !n_textured) { g_err = std::string(who) + ": height or n_textured null"; return MVS_ERR_ARG; }
+    if (cap_h < 0) { g_err = std::string(who) + ": a negative cap_h"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_IDLE, who)) return r;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:mesh_texture");
+    hipStream_t st = e->stream;
+    const int nviews = e->cfg.nviews;
+    MtexBufs b;
+    if (int r = mtex_take_mesh(e, n_v, verts, n_t, tris, b, who)) return r;
+    if (n_t > 0) HIPCHK(hipMemcpyAsync(b.label.p, label, (size_t)n_t * sizeof(int32_t), hipMemcpyDefault, st));
+    mvsk_mtex_check_labels(n_t, b.label.p, nviews, b.words.p + 1, st);  // mesh_take_tris left both words zero
+    uint32_t bad = 0;
+    if (int r = read_back(e, b.words.p + 1, &bad)) return r;
+    HIPCHK(hipGetLastError());
+    if (bad) { g_err = std::string(who) + ": a label outside -1 .. nviews - 1"; return MVS_ERR_ARG; }
+    if (b.win.ensure(9 * n_t) || b.flag.ensure(n_t) || b.base.ensure(n_t + 1) || b.scan.ensure(n_t / 256 + 4096)) return MVS_ERR_HIP;
+    if (n_t > 0) HIPCHK(hipMemsetAsync(b.flag.p, 0, (size_t)n_t * sizeof(int32_t), st));
+    const DParams p = current_params(e);
+    for (int v = 0; v < nviews && n_t > 0; ++v) {
+        mvsk_mrender_project(p, v, n_v, b.d_verts.p, b.scr.p, b.vd.p, b.ok.p, st);
+        mvsk_mtex_take(v, n_t, b.d_tris.p, b.label.p, b.scr.p, b.vd.p, b.ok.p, b.win.p, b.flag.p, st);
+    }
+    int64_t nt = 0;
+    if (int r = scan_total(e, b.flag.p, b.base.p, b.scan.p, n_t, &nt)) return r;
+    const int64_t B = x->res + 3, cpr = x->width / B, n_cells = 1 + (nt + 1) / 2, h = (n_cells + cpr - 1) / cpr * B;
+    *height = h; *n_textured = nt;
+    if (h > 32768 || (int64_t)x->width * h > ((int64_t)1 << 30)) { g_err = std::string(who) + ": the atlas is higher than 32768 or holds more than 2^30 texels (*height)"; return MVS_ERR_CAPACITY; }
+    if (!rgb) return MVS_OK;
+    if (cap_h < h) { g_err = std::string(who) + ": cap_h is smaller than the atlas (*height)"; return MVS_ERR_CAPACITY; }
+    const int64_t total = (int64_t)x->width * h;
+    if (b.list.ensure(nt) || b.rgb.ensure((total + 3) / 4 * 12) || (uv && b.uv.ensure(6 * n_t))) return MVS_ERR_HIP;
+    mvsk_mtex_layout(n_t, b.flag.p, b.base.p, b.list.p, nt, x->res, (int)cpr, uv ? b.uv.p : nullptr, st);
+    mvsk_mtex_texels(p, x->res, x->width, h, nt, b.list.p, b.label.p, b.win.p, b.rgb.p, st);
+    HIPCHK(hipStreamSynchronize(st));  // a failure is known before anything is written
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(rgb, b.rgb.p, (size_t)total * 3, hipMemcpyDefault, st));
+    if (uv && n_t > 0) HIPCHK(hipMemcpyAsync(uv, b.uv.p, (size_t)n_t * 6 * sizeof(int32_t), hipMemcpyDefault, st));
     HIPCHK(hipStreamSynchronize(st));
     return MVS_OK;
 }

@@ -174,6 +174,26 @@ void mvsk_mrender_resolve(int64_t npix, const unsigned long long* keys, float* d
 // visible[i] |= 1 << view where vertex i is usable, its nearest pixel lies inside W x H and is empty or not nearer than d / (1 + tol)
 void mvsk_mrender_visible(int view, float tol, int64_t n_v, const int32_t* scr, const float* vd, const uint32_t* ok, int W, int H, const unsigned long long* keys,
                           unsigned long long* visible, hipStream_t st);
+// mvs_engine_mesh_face_views / mvs_engine_mesh_texture (mvs_mesh_texture.hip): the view that textures each triangle, and the atlas.  The
+// views stream through mvsk_mrender_project's buffers.  Every launcher wants valid ids.
+// *bad |= 1 when a label lies outside -1 .. nviews - 1 (zero before the launch)
+void mvsk_mtex_check_labels(int64_t n_t, const int32_t* label, int nviews, uint32_t* bad, hipStream_t st);
+// one view: where triangle t is a candidate of `view` (W x H) with |area| > best_area[t], both slots take the view's; want: the sign the
+// area must have, 0 = either; visible may be null.  best_area 0 and best_label -1 before the first view, the views in ascending order
+void mvsk_mtex_best(int view, int want, int64_t n_t, const int32_t* tris, const int32_t* scr, const uint32_t* ok, const unsigned long long* visible, int W, int H,
+                    long long* best_area, int32_t* best_label, hipStream_t st);
+// counts[v] += the triangles labelled v (zero before the launch)
+void mvsk_mtex_count(int64_t n_t, const int32_t* label, int nviews, unsigned long long* counts, hipStream_t st);
+// one view: for the triangles labelled `view` whose label is honoured, win[9 t ..] = (sx, sy, bits(d)) x 3 and flag[t] = 1 (flag zero
+// before the first view)
+void mvsk_mtex_take(int view, int64_t n_t, const int32_t* tris, const int32_t* label, const int32_t* scr, const float* vd, const uint32_t* ok, int32_t* win,
+                    int32_t* flag, hipStream_t st);
+// with base = the exclusive scan of flag: list[base[t]] = t for the n_textured flagged triangles; uv[6 t ..] (or null) = the corner texels
+void mvsk_mtex_layout(int64_t n_t, const int32_t* flag, const int32_t* base, int32_t* list, int64_t n_textured, int res, int cpr, int32_t* uv, hipStream_t st);
+// the atlas of `width` x `height` texels, three bytes each, from the level prm.level of the labelled views; rgb holds the bytes rounded
+// up to a multiple of twelve
+void mvsk_mtex_texels(const DParams& prm, int res, int width, int64_t height, int64_t n_textured, const int32_t* list, const int32_t* label, const int32_t* win,
+                      uint8_t* rgb, hipStream_t st);
 // mvs_engine_mesh_components / mvs_engine_mesh_prune / mvs_engine_mesh_smooth (mvs_mesh_clean.hip): connected components by union-find,
 // pruning behind two scans, Taubin smoothing as an order-free integer sum.  verts: 3 floats a vertex, tris: 3 ids a triangle.
 // *bad != 0 when an id of a triangle lies outside 0 .. n_v - 1 (zero before the launch); every launcher below wants valid ids

@@ -1,6 +1,6 @@
 // mvs_mesh_common.cuh -- what the mesh units behind the extraction (mvs_mesh_attr.hip, mvs_mesh_clean.hip, mvs_mesh_decimate.hip,
-// mvs_mesh_fill.hip and mvs_mesh_render.hip) share: the block and launch of a lane-per-item kernel, the 64-bit wave shuffles, the
-// open-addressing table of 64-bit keys, the lanes of a wave that share the first one's key, and the order-free fixed-point sum (a
+// mvs_mesh_fill.hip, mvs_mesh_render.hip and mvs_mesh_texture.hip) share: the block and launch of a lane-per-item kernel, the 64-bit
+// wave shuffles, the open-addressing table of 64-bit keys, the lanes of a wave that share the first one's key, and the order-free fixed-point sum (a
 // power-of-two scale from the bits of the largest component, three 31-bit integers a position, the block maximum that finds the scale).
 // No other unit includes this file, the sweep's (which includes mvs_common.cuh) least of all: nothing here can reach its code.
 // Every function is force-inlined, and every kernel that uses one holds the machine code it held with the helper's lines written into

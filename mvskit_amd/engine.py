@@ -1,10 +1,13 @@
-"""ctypes binding of the C ABI in include/mvskit_engine.h.
+"""ctypes binding of the C ABI in include/mvskit_engine.h and include/mvskit_texture.h.
 
 There is no CPU path: if the HIP library is missing or no GPU is visible, creating an Engine raises."""
 from __future__ import annotations
 
 import ctypes as C
 import math
+import os
+import struct
+import zlib
 
 import numpy as np
 
@@ -453,6 +456,62 @@ class Engine:
         self._check(self.L.mvs_engine_mesh_visibility(self.h, float(tol), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), _ptr(out)))
         return out
 
+    # ---- textured mesh
+    def mesh_face_views(self, verts, tris, visible=None, front_only=True):
+        """The view that textures each triangle (include/mvskit_texture.h, mvs_engine_mesh_face_views): (label [m] int32, the view in
+        which the triangle projects largest among those where its three vertices are usable and inside the bilinear window, it has an
+        area, faces the camera (front_only) and -- with visible, mesh_visibility's words -- all three vertices are seen; -1 when there
+        is none, the lowest view among equals; area [m] int64, the winner's |area| in 1/65536 pixel^2; n_faces [nviews] int64, the
+        triangles per label).  Needs views but no pool."""
+        verts, tris = _verts(verts), _tris(tris)
+        if visible is not None:
+            visible = np.ascontiguousarray(visible, dtype=np.uint64).reshape(-1)
+            if visible.shape[0] != verts.shape[0]:
+                raise ValueError("mesh_face_views: one visibility word per vertex")
+        x = MeshTexturing(8, 4096, int(bool(front_only)), 0)
+        label, area, faces = np.zeros(tris.shape[0], np.int32), np.zeros(tris.shape[0], np.int64), np.zeros(self.cfg.nviews, np.int64)
+        self._check(self.L.mvs_engine_mesh_face_views(self.h, C.byref(x), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), _ptr(visible), _ptr(label),
+                                                      _ptr(area), _ptr(faces)))
+        return label, area, faces
+
+    def texture_mesh(self, verts, tris, label, res=8, width=4096):
+        """The texture atlas of the mesh under `label` (include/mvskit_texture.h, mvs_engine_mesh_texture): (atlas [H, width, 3] uint8,
+        uv [m, 3, 2] int32, the (column, row) of the texel under each corner; the number of textured triangles).  Every triangle whose
+        label is honoured (its vertices usable in that view, an area there) gets half a cell of res + 3 texels, sampled from the view at
+        the engine's level at the perspective-correct position; the others point at the grey cell 0.  The size call comes first."""
+        verts, tris = _verts(verts), _tris(tris)
+        label = np.ascontiguousarray(label, dtype=np.int32).reshape(-1)
+        if label.shape[0] != tris.shape[0]:
+            raise ValueError("texture_mesh: one label per triangle")
+        x = MeshTexturing(int(res), int(width), 1, 0)
+        h, n = C.c_int64(), C.c_int64()
+        head = (self.h, C.byref(x), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), _ptr(label))
+        self._check(self.L.mvs_engine_mesh_texture(*head, 0, None, None, C.byref(h), C.byref(n)))
+        atlas, uv = np.zeros((h.value, int(width), 3), np.uint8), np.zeros((tris.shape[0], 3, 2), np.int32)
+        self._check(self.L.mvs_engine_mesh_texture(*head, h.value, _ptr(atlas), _ptr(uv), C.byref(h), C.byref(n)))
+        return atlas, uv, n.value
+
+    def textured_mesh(self, volume, source=0, min_consistent=1, depth_tol=0.01, normal_cos=0.9, cap_v=0, cap_t=0, min_triangles=0, largest_only=False,
+                      smooth_iterations=0, decimate_cell=0.0, decimate_placement="mean", fill_max_edges=0, res=8, atlas_width=4096, front_only=True,
+                      visibility_tol=0.01):
+        """mesh, the clean-up steps of coloured_mesh in its order (prune, fill, smooth, decimate), mesh_normals, mesh_visibility,
+        mesh_face_views and texture_mesh chained: (verts, tris, normals, atlas, uv, label), what write_mesh_obj takes."""
+        kw = dict(source=source, min_consistent=min_consistent, depth_tol=depth_tol, normal_cos=normal_cos)
+        verts, tris = self.mesh(volume, cap_v=cap_v, cap_t=cap_t, **kw)
+        if min_triangles > 0 or largest_only:
+            verts, tris, _ = self.prune_mesh(verts, tris, max(1, int(min_triangles)), largest_only)
+        if fill_max_edges >= 3:
+            verts, tris, _ = self.fill_holes(verts, tris, fill_max_edges)
+        if smooth_iterations > 0:
+            verts = self.smooth_mesh(verts, tris, smooth_iterations)
+        if decimate_cell > 0:
+            verts, tris, _ = self.decimate_mesh(verts, tris, decimate_cell, decimation_origin(volume), decimate_placement)
+        normals = self.mesh_normals(verts, tris)
+        visible = self.mesh_visibility(verts, tris, visibility_tol)
+        label, _, _ = self.mesh_face_views(verts, tris, visible=visible, front_only=front_only)
+        atlas, uv, _ = self.texture_mesh(verts, tris, label, res=res, width=atlas_width)
+        return verts, tris, normals, atlas, uv, label
+
     # ---- mesh clean-up
     def mesh_components(self, n_v, tris):
         """The connected components of the mesh's vertex graph (include/mvskit_engine.h, mvs_engine_mesh_components): (label [n_v] int32,
@@ -728,3 +787,57 @@ def write_mesh_ply(path, verts, tris, binary=True, normals=None, colours=None):
             lists = [c.tolist() for c in cols]
             f.write("".join(" ".join(f"{x:.9g}" if isinstance(x, float) else str(x) for c in row for x in c) + "\n" for row in zip(*lists)).encode("ascii"))
             f.write("".join(f"3 {a} {b} {c}\n" for a, b, c in tris.tolist()).encode("ascii"))
+
+
+def encode_png_rgb(image):
+    """image [H, W, 3] uint8 as the bytes of an 8-bit RGB PNG: one zlib stream, filter 0 on every row"""
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    if image.ndim != 3 or image.shape[2] != 3 or image.shape[0] < 1 or image.shape[1] < 1:
+        raise ValueError("encode_png_rgb: an image of H x W x 3 bytes, H and W at least 1")
+    h, w = image.shape[:2]
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+    rows = np.zeros((h, 1 + 3 * w), np.uint8)  # the filter byte, 0, in front of every row
+    rows[:, 1:] = image.reshape(h, 3 * w)
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6))
+            + chunk(b"IEND", b""))
+
+
+def write_mesh_obj(path, verts, tris, atlas, uv, normals=None):
+    """The textured mesh as a Wavefront OBJ at `path`, with a material file and the atlas as an 8-bit RGB PNG beside it (the path's
+    stem with .mtl and .png).  atlas [H, W, 3] uint8 and uv [m, 3, 2] int32 texels (column, row) as texture_mesh returns them.  One vt
+    per corner, ((column + 0.5) / W, 1 - (row + 0.5) / H): the centre of the texel, v upwards; faces v/vt or, with normals [n, 3],
+    v/vt/vn, 1-based."""
+    verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    tris = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    atlas = np.ascontiguousarray(atlas, dtype=np.uint8)
+    uv = np.ascontiguousarray(uv, dtype=np.int32).reshape(-1, 3, 2)
+    if uv.shape[0] != tris.shape[0]:
+        raise ValueError("write_mesh_obj: three texels per triangle")
+    if normals is not None:
+        normals = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if normals.shape != verts.shape:
+            raise ValueError("write_mesh_obj: one normal per vertex")
+    stem = os.path.splitext(path)[0]
+    name = os.path.basename(stem)
+    with open(stem + ".png", "wb") as f:
+        f.write(encode_png_rgb(atlas))
+    with open(stem + ".mtl", "w") as f:
+        f.write(f"newmtl {name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {name}.png\n")
+    H, W = atlas.shape[:2]
+    vt = np.stack([(uv[..., 0].astype(np.float64) + 0.5) / W, 1.0 - (uv[..., 1].astype(np.float64) + 0.5) / H], axis=-1).reshape(-1, 2)
+    out = [f"mtllib {name}.mtl\n"]
+    out += [f"v {x:.9g} {y:.9g} {z:.9g}\n" for x, y, z in verts.tolist()]
+    if normals is not None:
+        out += [f"vn {x:.9g} {y:.9g} {z:.9g}\n" for x, y, z in normals.tolist()]
+    out += [f"vt {u:.17g} {v:.17g}\n" for u, v in vt.tolist()]
+    out.append(f"usemtl {name}\n")
+    ids = (tris + 1).tolist()
+    if normals is None:
+        out += [f"f {a}/{3 * t + 1} {b}/{3 * t + 2} {c}/{3 * t + 3}\n" for t, (a, b, c) in enumerate(ids)]
+    else:
+        out += [f"f {a}/{3 * t + 1}/{a} {b}/{3 * t + 2}/{b} {c}/{3 * t + 3}/{c}\n" for t, (a, b, c) in enumerate(ids)]
+    with open(path, "w") as f:
+        f.write("".join(out))
