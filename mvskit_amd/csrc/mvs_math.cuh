@@ -15,10 +15,13 @@ struct F4 { float x, y, z, w; };
 DEV float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 DEV float dot4(F4 a, F4 b) { return fma_(a.w, b.w, fma_(a.z, b.z, fma_(a.y, b.y, a.x * b.x))); }
 DEV float dot3(F3 a, F3 b) { return fma_(a.z, b.z, fma_(a.y, b.y, a.x * b.x)); }
-// Correctly rounded square root (== the oracle's sqrtf) for zero, normal and infinite arguments: v_sqrt_f32 is within one
+// Correctly rounded square root (== the oracle's sqrtf) for +-0, +inf and every argument from 2^-96 up: v_sqrt_f32 is within one
 // ulp, and the residuals of its two neighbours (one fma each) decide which of the three is the rounded root.  This is
 // the compiler's own IEEE expansion without the rescaling of arguments below 2^-96, which this path never produces
-// (squared lengths and texture variances), and at half its instruction count.
+// (squared lengths and texture variances), and at half its instruction count.  tools/microbench/math_exact.hip runs it against
+// (float)sqrt((double)x) for EVERY float from 2^-96 to +inf (1.88 * 10^9 inputs: no difference).  Measured below that: right down
+// to 2^-104; the largest float at which it differs is 0x0b6e9372 = 4.5948e-32 (3.95 * 10^6 normal floats differ, and every
+// subnormal).
 DEV float sqrt_rn(float x) {
     float s = __builtin_amdgcn_sqrtf(x);
     const float dn = __int_as_float(__float_as_int(s) - 1), up = __int_as_float(__float_as_int(s) + 1);
@@ -58,6 +61,12 @@ DEV F3 ld3(const float* p) { return {p[0], p[1], p[2]}; }
 
 // ------------------------------------------------------------------ deterministic libm subset
 // (same kernels, constants and evaluation order as the oracle's pm_* functions)
+// Largest |pm_f(x) - f(x)| against fp64 over EVERY float of the domain (tools/microbench/math_exact.hip, section c), in rad:
+//   pm_sinf  1.0636e-07 at 0x40274eb8, pm_cosf 1.3457e-07 at 0x40170bc5   (|x| <= MVS_PI)
+//   pm_asinf 1.6525e-07 at 0x3f5db809, pm_acosf 3.0491e-07 at 0xbf003df1   (|x| <= 1)
+//   pm_atanf 1.7068e-07 at 0x403f4d05                                      (every finite float, +-inf)
+// Beyond the domains: pm_asinf clamps |x| > 1 to 1; pm_acosf is NaN there (its callers clamp); pm_sinf / pm_cosf are not reduced
+// beyond pi.  pm_sincosf returns the bits of pm_sinf and pm_cosf for all 2^32 arguments (section b).
 #define MVS_PIO2_HI 1.57079625129699707031f
 #define MVS_PIO2_LO 7.54978941586159635335e-08f
 #define MVS_PIO4 0.78539816339744830962f

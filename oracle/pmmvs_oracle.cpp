@@ -2410,6 +2410,14 @@ float orc_cosf(float x) { return pm_cosf(x); }
 float orc_asinf(float x) { return pm_asinf(x); }
 float orc_acosf(float x) { return pm_acosf(x); }
 float orc_atanf(float x) { return pm_atanf(x); }
+void orc_math_batch(int fn, int64_t n, const float* in, float* out) {
+    float (*const f[5])(float) = {pm_sinf, pm_cosf, pm_asinf, pm_acosf, pm_atanf};
+    if (fn < 0 || fn > 4) return;
+    for (int64_t i = 0; i < n; ++i) out[i] = f[fn](in[i]);
+}
+void orc_rng_batch(uint32_t seed, int64_t n, const uint32_t* keys, float* out) {
+    for (int64_t i = 0; i < n; ++i) out[i] = rng_uniform(seed, keys[5 * i], keys[5 * i + 1], keys[5 * i + 2], keys[5 * i + 3], keys[5 * i + 4]);
+}
 int orc_is_neighbor(orc_scene* h, const orc_patch* a, const orc_patch* b, float thr) {
     Patch p, q; prep_probe(h->s, a, p); prep_probe(h->s, b, q); return is_neighbor(h->s, p, q, thr);
 }

@@ -176,6 +176,8 @@ float orc_cosf(float x);
 float orc_asinf(float x);
 float orc_acosf(float x);
 float orc_atanf(float x);
+void orc_math_batch(int fn, int64_t n, const float* in, float* out);  /* fn 0..4 = sin, cos, asin, acos, atan: out[i] = orc_*f(in[i]) */
+void orc_rng_batch(uint32_t seed, int64_t n, const uint32_t* keys /* 5 a draw */, float* out);  /* out[i] = orc_rng_uniform(seed, keys[5 i .. 5 i + 4]) */
 int orc_is_neighbor(orc_scene* s, const orc_patch* a, const orc_patch* b, float thr);            /* pmmvps.cpp:117-147 */
 float orc_compute_gain(orc_scene* s, const orc_patch* p);                                        /* filter.cpp:108-146 */
 int orc_check(orc_scene* s, orc_patch* p);                                                        /* optim.cpp:300-323 */

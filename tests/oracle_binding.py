@@ -146,6 +146,10 @@ def lib(wide=False):
     for fn in ("orc_sinf", "orc_cosf", "orc_asinf", "orc_acosf", "orc_atanf"):
         getattr(L, fn).argtypes = [C.c_float]
         getattr(L, fn).restype = C.c_float
+    L.orc_math_batch.argtypes = [C.c_int, C.c_int64, vp, vp]
+    L.orc_math_batch.restype = None
+    L.orc_rng_batch.argtypes = [C.c_uint32, C.c_int64, vp, vp]
+    L.orc_rng_batch.restype = None
     L.orc_is_neighbor.argtypes = [vp, vp, vp, C.c_float]
     L.orc_compute_gain.argtypes = [vp, vp]
     L.orc_compute_gain.restype = C.c_float
@@ -161,6 +165,26 @@ def _ptr(a):
 
 def f4(*v):
     return np.asarray(v, dtype=np.float32)
+
+
+MATH_FNS = ("sin", "cos", "asin", "acos", "atan")  # orc_math_batch's fn, the columns of the engine's MVS_PROBE_MATH
+
+
+def math_batch(fn, x):
+    """orc_math_batch: the oracle's pm_* function number fn (MATH_FNS) of every float32 of x"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty_like(x)
+    lib().orc_math_batch(int(fn), x.size, _ptr(x), _ptr(out))
+    return out
+
+
+def rng_batch(seed, keys):
+    """orc_rng_batch: the counter RNG's draw for every row (a, b, c, d, e) of keys [n, 5] uint32"""
+    keys = np.ascontiguousarray(keys, dtype=np.uint32)
+    assert keys.ndim == 2 and keys.shape[1] == 5
+    out = np.empty(keys.shape[0], np.float32)
+    lib().orc_rng_batch(int(seed) & 0xffffffff, keys.shape[0], _ptr(keys), _ptr(out))
+    return out
 
 
 class Oracle:

@@ -4,21 +4,13 @@
 // theorem (q' = RN(q + (a - b q) y) is a / b correctly rounded when y = RN(1 / b) and q is a faithful quotient, barring over- and
 // underflow) makes it follow from the reciprocal; checked here on 2^33 pseudo-random pairs with exponents in [-40, 40] and on
 // mantissa patterns that are hard for division (all ones, one, alternating).
-//   hipcc --offload-arch=gfx950 -O2 -ffp-contract=off -o div_exact div_exact.hip && ./div_exact
+//   hipcc <mvskit_amd.build.FLAGS without -shared -fPIC> -o div_exact div_exact.hip && ./div_exact
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
-__device__ __forceinline__ float rcp_rn(float x) {
-    const float r = __builtin_amdgcn_rcpf(x);
-    const float e = __builtin_fmaf(-x, r, 1.0f);
-    return __builtin_fmaf(e, r, r);
-}
-__device__ __forceinline__ float div_rn(float a, float b) {
-    const float y = rcp_rn(b);
-    const float q = a * y;
-    const float e = __builtin_fmaf(-b, q, a);
-    return __builtin_fmaf(e, y, q);
-}
+#include "../../mvskit_amd/csrc/mvs_math.cuh"  // rcp_rn, div_rn: the engine's own, not a copy
+using mvsdev::rcp_rn;
+using mvsdev::div_rn;
 __global__ void k_rcp(unsigned long long* bad, unsigned* first_bad) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // 2 signs x 241 exponents x 2^23 mantissas
     const uint32_t mant = (uint32_t)(i & 0x7fffffu);
