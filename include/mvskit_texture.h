@@ -65,8 +65,8 @@
  * (mvs_engine_mesh_texture: height or n_textured NULL; a negative cap_h;) no engine.  MVS_ERR_STATE: the views are not set, or a pass is
  * waiting for its commit.  Then MVS_ERR_ARG after a validating pass on the device: an id outside 0 .. n_v - 1, or (mvs_engine_mesh_texture)
  * a label outside -1 .. nviews - 1.  MVS_ERR_HIP: an allocation or copy failed.
- * WHAT THE TEXTURING DOES NOT DO: seam-aware labelling (an MRF over neighbouring triangles); colour levelling across seams;
- * per-triangle size classes or chart packing (res is one number per call; the meshes made here are near-uniform); level-0 texels when
+ * WHAT THE TEXTURING DOES NOT DO: seam-aware labelling (an MRF over neighbouring triangles) (since f-14: mvskit_seams.h); colour
+ * levelling across seams (since f-14: mvskit_seams.h); per-triangle size classes or chart packing (res is one number per call; the meshes made here are near-uniform); level-0 texels when
  * m_level > 0; masks; per-pixel occlusion inside a triangle (visibility is per vertex, as in the render); a variant sharded over GPUs. */
 #ifndef MVSKIT_TEXTURE_H
 #define MVSKIT_TEXTURE_H

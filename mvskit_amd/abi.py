@@ -1,7 +1,8 @@
 """What mirrors include/mvskit_engine.h, once: the constants, the record dtypes, the structs, the signature of every entry point, and
 the loader that applies them.  tests/test_abi.py holds SIGNATURES and STRUCTS against the header itself.  The textured-mesh calls of
 include/mvskit_texture.h have a table of their own, TEXTURE_SIGNATURES and TEXTURE_STRUCTS, which tests/test_mesh_texture_abi.py holds
-against that header in the same way."""
+against that header in the same way; the seam calls of include/mvskit_seams.h a third, SEAM_SIGNATURES and SEAM_STRUCTS, held by
+tests/test_mesh_seams_abi.py."""
 from __future__ import annotations
 
 import ctypes as C
@@ -15,7 +16,7 @@ __all__ = ["PROBE_NCC", "PROBE_PREPROCESS", "PROBE_REFINE", "PROBE_POSTPROCESS",
            "REFINE_CONVERGED", "MVS_OK", "MVS_ERR_ARG", "MVS_ERR_STATE", "MVS_ERR_HIP", "MVS_ERR_CAPACITY", "MVS_ERR_NO_DEVICE", "PLY_ASCII",
            "PLY_BINARY_LE", "PLY_VERTEX_DTYPE", "FUSED_POINT_DTYPE", "Config", "Refiner", "ViewDesc", "SeedView", "SeedRandom", "SeedPoints",
            "MapsConfig", "ViewMaps", "Volume", "MeshColouring", "MeshPruning", "MeshSmoothing", "MeshDecimation", "MeshFilling", "MeshViewRender",
-           "MeshTexturing", "TEXTURE_STRUCTS", "TEXTURE_SIGNATURES", "Counters", "Timing", "FilterStats", "STRUCTS", "SIGNATURES", "EXPORTS",
+           "MeshTexturing", "TEXTURE_STRUCTS", "TEXTURE_SIGNATURES", "MeshSeams", "SEAM_STRUCTS", "SEAM_SIGNATURES", "Counters", "Timing", "FilterStats", "STRUCTS", "SIGNATURES", "EXPORTS",
            "EngineError", "load_library"]
 
 PROBE_NCC, PROBE_PREPROCESS, PROBE_REFINE, PROBE_POSTPROCESS, PROBE_COST, PROBE_MATH, PROBE_REFINE_X = range(7)
@@ -119,6 +120,11 @@ class MeshViewRender(C.Structure):
 class MeshTexturing(C.Structure):
     """mvs_mesh_texturing (include/mvskit_texture.h): the atlas of mvs_engine_mesh_face_views / mvs_engine_mesh_texture, 16 bytes."""
     _fields_ = [("res", C.c_int32), ("width", C.c_int32), ("front_only", C.c_int32), ("pad", C.c_int32)]
+
+
+class MeshSeams(C.Structure):
+    """mvs_mesh_seams (include/mvskit_seams.h): the smoothing of the view labels and the levelling on the seams, 16 bytes."""
+    _fields_ = [("keep", C.c_int32), ("iterations", C.c_int32), ("max_shift", C.c_int32), ("samples", C.c_int32)]
 
 
 class Counters(C.Structure):
@@ -255,6 +261,27 @@ def _texture_signatures():
 TEXTURE_SIGNATURES = _texture_signatures()
 
 
+#: include/mvskit_seams.h: its struct, and its entry points in its order
+SEAM_STRUCTS = {"mvs_mesh_seams": MeshSeams}
+
+
+def _seam_signatures():
+    P, vp, i, i64 = C.POINTER, C.c_void_p, C.c_int, C.c_int64
+    seams, tex, pi64 = P(MeshSeams), P(MeshTexturing), P(C.c_int64)
+    mesh_in = [i64, vp, i64, vp]               # n_v, verts, n_t, tris
+    return {
+        "mvs_default_mesh_seams": (None, [seams]),
+        "mvs_engine_mesh_adjacency": (i, [vp, i64, i64, vp, vp, pi64]),
+        "mvs_engine_mesh_face_quality": (i, [vp, tex] + mesh_in + [vp, vp]),
+        "mvs_engine_mesh_smooth_labels": (i, [vp, seams, i64, i64, vp, i, vp, vp, vp, vp]),
+        "mvs_engine_mesh_seam_levels": (i, [vp, seams, tex] + mesh_in + [vp, vp, vp, pi64]),
+        "mvs_engine_mesh_texture_levelled": (i, [vp, tex] + mesh_in + [vp, vp, i64, vp, vp, pi64, pi64]),
+    }
+
+
+SEAM_SIGNATURES = _seam_signatures()
+
+
 class EngineError(RuntimeError):
     """A call of the C ABI returned a negative mvs_status (`status`; include/mvskit_engine.h)."""
 
@@ -283,7 +310,7 @@ def load_library(cap32: bool = False, cap: int = 0):
     except ImportError:
         pass
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**SIGNATURES, **TEXTURE_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **TEXTURE_SIGNATURES, **SEAM_SIGNATURES}.items():
         # a build of an older revision (tools/build_variant.sh, A/B timing) lacks the newer symbols: the method that needs one raises AttributeError
         fn = getattr(L, name, None)
         if fn is not None:

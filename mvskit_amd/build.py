@@ -17,11 +17,12 @@ ENGINE_LIBS = {16: LIB_PATH, 32: LIB32_PATH, 64: LIB64_PATH}
 FAULT_LIB_PATH = os.path.join(LIB_DIR, "libmvskit_engine_faultinj.so")
 CAP_FLAGS = {16: [], 32: ["-DMVS_LISTCAP=32"], 64: ["-DMVS_LISTCAP=64", "-DMVS_MAX_IMAGES=64"]}
 SOURCES = ["mvs_image.hip", "mvs_index.hip", "mvs_patch.hip", "mvs_ply.hip", "mvs_seed.hip", "mvs_seed_random.hip", "mvs_seed_points.hip",
-           "mvs_maps.hip", "mvs_mesh.hip", "mvs_mesh_attr.hip", "mvs_mesh_clean.hip", "mvs_mesh_decimate.hip", "mvs_mesh_fill.hip", "mvs_mesh_render.hip", "mvs_mesh_texture.hip", "mvs_engine.cpp", "mvs_engine_pass.cpp", "mvs_engine_comm.cpp",
+           "mvs_maps.hip", "mvs_mesh.hip", "mvs_mesh_attr.hip", "mvs_mesh_clean.hip", "mvs_mesh_decimate.hip", "mvs_mesh_fill.hip", "mvs_mesh_render.hip", "mvs_mesh_texture.hip", "mvs_mesh_seams.hip", "mvs_engine.cpp", "mvs_engine_pass.cpp", "mvs_engine_comm.cpp",
            "mvs_engine_filter.cpp", "mvs_engine_seed.cpp", "mvs_engine_output.cpp", "mvs_engine_mesh.cpp"]
 # what a library is rebuilt for: its sources, every header next to them, and the public header
 DEPS = SOURCES + sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".cuh"))) + [os.path.join(ROOT, "include", "mvskit_engine.h"),
-                                                                                                 os.path.join(ROOT, "include", "mvskit_texture.h")]
+                                                                                                 os.path.join(ROOT, "include", "mvskit_texture.h"),
+                                                                                                 os.path.join(ROOT, "include", "mvskit_seams.h")]
 
 # -ffp-contract=off: the explicit fmaf chains in the source are the only fused operations (DESIGN.md,
 # "engine arithmetic"), which is what lets the CPU oracle reproduce the results bit for bit.

@@ -2,14 +2,15 @@
 // (mvs_mesh.hip), vertex normals and colours (mvs_mesh_attr.hip), components, pruning and smoothing (mvs_mesh_clean.hip), decimation
 // (mvs_mesh_decimate.hip), boundary loops and hole filling (mvs_mesh_fill.hip), the mesh rendered into the views and the vertex
 // visibility (mvs_mesh_render.hip), the view of each triangle and the texture atlas (mvs_mesh_texture.hip; declared in
-// include/mvskit_texture.h).  The maps they start from come from
+// include/mvskit_texture.h), the adjacency of triangles, the smoothed view labels and the levels on the seams (mvs_mesh_seams.hip and
+// mvs_mesh_texture.hip; declared in include/mvskit_seams.h).  The maps they start from come from
 // mvs_engine_output.cpp (render_usable).  Every entry point is stateless: its working arrays live in buffers of the call, the caller's
 // arrays come into them from wherever they lie, and nothing of the engine's state changes.
 #include <cmath>
 #include <cstdlib>
 
 #include "mvs_engine_impl.h"
-#include "mvskit_texture.h"
+#include "mvskit_seams.h"
 
 using namespace mvseng;
 
@@ -832,9 +833,10 @@ int mvs_engine_mesh_face_views(mvs_engine* e, const mvs_mesh_texturing* x, int64
     return MVS_OK;
 }
 
-int mvs_engine_mesh_texture(mvs_engine* e, const mvs_mesh_texturing* x, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, const int32_t* label,
-                            int64_t cap_h, uint8_t* rgb, int32_t* uv, int64_t* height, int64_t* n_textured) {
-    const char* who = "mvs_engine_mesh_texture";
+namespace {
+// mvs_engine_mesh_texture, and with offset (host or device, or null) mvs_engine_mesh_texture_levelled
+int mtex_texture(mvs_engine* e, const mvs_mesh_texturing* x, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, const int32_t* label,
+                 const int32_t* offset, int64_t cap_h, uint8_t* rgb, int32_t* uv, int64_t* height, int64_t* n_textured, const char* who) {
     if (int r = mtex_args(x, n_v, verts, n_t, tris, label, who)) return r;
     if (!height || !n_textured) { g_err = std::string(who) + ": height or n_textured null"; return MVS_ERR_ARG; }
     if (cap_h < 0) { g_err = std::string(who) + ": a negative cap_h"; return MVS_ERR_ARG; }
@@ -868,7 +870,14 @@ int mvs_engine_mesh_texture(mvs_engine* e, const mvs_mesh_texturing* x, int64_t 
     const int64_t total = (int64_t)x->width * h;
     if (b.list.ensure(nt) || b.rgb.ensure((total + 3) / 4 * 12) || (uv && b.uv.ensure(6 * n_t))) return MVS_ERR_HIP;
     mvsk_mtex_layout(n_t, b.flag.p, b.base.p, b.list.p, nt, x->res, (int)cpr, uv ? b.uv.p : nullptr, st);
-    mvsk_mtex_texels(p, x->res, x->width, h, nt, b.list.p, b.label.p, b.win.p, b.rgb.p, st);
+    if (offset) {
+        DevBuf<int32_t>& d_off = b.scan;  // the scan is over
+        if (d_off.ensure(3 * (int64_t)nviews)) return MVS_ERR_HIP;
+        HIPCHK(hipMemcpyAsync(d_off.p, offset, 3 * (size_t)nviews * sizeof(int32_t), hipMemcpyDefault, st));
+        mvsk_mtex_texels_levelled(p, x->res, x->width, h, nt, b.list.p, b.label.p, b.win.p, d_off.p, b.rgb.p, st);
+    } else {
+        mvsk_mtex_texels(p, x->res, x->width, h, nt, b.list.p, b.label.p, b.win.p, b.rgb.p, st);
+    }
     HIPCHK(hipStreamSynchronize(st));  // a failure is known before anything is written
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(rgb, b.rgb.p, (size_t)total * 3, hipMemcpyDefault, st));
@@ -876,5 +885,259 @@ int mvs_engine_mesh_texture(mvs_engine* e, const mvs_mesh_texturing* x, int64_t 
     HIPCHK(hipStreamSynchronize(st));
     return MVS_OK;
 }
+}  // namespace
 
+int mvs_engine_mesh_texture(mvs_engine* e, const mvs_mesh_texturing* x, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris, const int32_t* label,
+                            int64_t cap_h, uint8_t* rgb, int32_t* uv, int64_t* height, int64_t* n_textured) {
+    return mtex_texture(e, x, n_v, verts, n_t, tris, label, nullptr, cap_h, rgb, uv, height, n_textured, "mvs_engine_mesh_texture");
+}
+
+// Seams of the textured mesh (mvs_mesh_seams.hip and, for what needs the gates or a view's texels, mvs_mesh_texture.hip; the contract is in
+// include/mvskit_seams.h): the adjacency of triangles, the quality table, the smoothed labels, the levels on the seams and the levelled
+// atlas.  Stateless like the texture calls.
+static_assert(sizeof(mvs_mesh_seams) == 16, "mvs_mesh_seams is 16 bytes");
+namespace {
+int mseam_args(const mvs_mesh_seams* s, const char* who) {
+    if (!s) { g_err = std::string(who) + ": seams null"; return MVS_ERR_ARG; }
+    if (s->keep < 1 || s->keep > 255) { g_err = std::string(who) + ": keep outside 1..255"; return MVS_ERR_ARG; }
+    if (s->iterations < 0 || s->iterations > 4096) { g_err = std::string(who) + ": iterations outside 0..4096"; return MVS_ERR_ARG; }
+    if (s->max_shift < 0 || s->max_shift > 255) { g_err = std::string(who) + ": max_shift outside 0..255"; return MVS_ERR_ARG; }
+    if (s->samples < 1 || s->samples > 16) { g_err = std::string(who) + ": samples outside 1..16"; return MVS_ERR_ARG; }
+    return MVS_OK;
+}
+struct MseamBufs {
+    DevBuf<int32_t> d_tris, tval, town, nbr;
+    DevBuf<uint32_t> words;
+    DevBuf<unsigned long long> tkey, counts;  // counts: [0] irregular edges, [1] seams before, [2] seams after, [3] seam edges
+};
+// nbr of the triangles in d_tris (checked ids) and counts zeroed, counts[0] the irregular edges when wanted; the stream is idle on return
+int mseam_adjacency(mvs_engine* e, int64_t n_t, const int32_t* d_tris, MseamBufs& b, bool irregular, const char* who) {
+    hipStream_t st = e->stream;
+    const int64_t slots = table_slots(3 * n_t);
+    if (b.counts.ensure(4) || b.words.ensure(2) || b.nbr.ensure(3 * n_t) || (n_t > 0 && (b.tkey.ensure(slots) || b.tval.ensure(slots) || b.town.ensure(slots))))
+        return MVS_ERR_HIP;
+    HIPCHK(hipMemsetAsync(b.counts.p, 0, 4 * sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(b.words.p, 0, 2 * sizeof(uint32_t), st));
+    if (n_t > 0) if (int r = table_reset(e, b.tkey.p, b.tval.p, slots, 0)) return r;
+    mvsk_mseam_adjacency(n_t, d_tris, b.tkey.p, b.tval.p, b.town.p, slots, b.nbr.p, irregular ? b.counts.p : nullptr, b.words.p, st);
+    uint32_t fail = 0;
+    if (int r = read_back(e, b.words.p, &fail)) return r;
+    HIPCHK(hipGetLastError());
+    if (fail) { g_err = std::string(who) + ": the edge table found no slot"; return MVS_ERR_HIP; }
+    return MVS_OK;
+}
+// offset[v][ch] from the mirrored pair table: the header's OFFSETS, in its order of operations (this file is built without contraction)
+void mseam_offsets(int n, const std::vector<int64_t>& pairs, int max_shift, std::vector<int32_t>& offset) {
+    std::vector<double> A((size_t)n * n), rhs(n), g(n);
+    const double lim = 16.0 * (double)max_shift;
+    for (int ch = 0; ch < 3; ++ch) {
+        for (int a = 0; a < n; ++a) {
+            double diag = 1.0, s = 0.0;
+            for (int b = 0; b < n; ++b) {
+                if (b == a) continue;
+                const int64_t* pr = &pairs[((size_t)a * n + b) * 4];
+                diag = diag + (double)pr[0];
+                s = s + (double)pr[1 + ch];
+                A[(size_t)a * n + b] = -(double)pr[0];
+            }
+            A[(size_t)a * n + a] = diag;
+            rhs[a] = -s;
+        }
+        for (int i = 0; i < n; ++i)
+            for (int r = i + 1; r < n; ++r) {
+                const double f = A[(size_t)r * n + i] / A[(size_t)i * n + i];
+                for (int c = i; c < n; ++c) A[(size_t)r * n + c] = A[(size_t)r * n + c] - f * A[(size_t)i * n + c];
+                rhs[r] = rhs[r] - f * rhs[i];
+            }
+        for (int i = n - 1; i >= 0; --i) {
+            double s = rhs[i];
+            for (int c = i + 1; c < n; ++c) s = s - A[(size_t)i * n + c] * g[c];
+            g[i] = s / A[(size_t)i * n + i];
+        }
+        for (int a = 0; a < n; ++a) offset[(size_t)a * 3 + ch] = (int32_t)std::floor(std::fmin(std::fmax(g[a], -lim), lim) + 0.5);
+    }
+}
+}  // namespace
+
+void mvs_default_mesh_seams(mvs_mesh_seams* s) {
+    if (!s) return;
+    s->keep = 192; s->iterations = 64; s->max_shift = 32; s->samples = 4;
+}
+
+int mvs_engine_mesh_adjacency(mvs_engine* e, int64_t n_v, int64_t n_t, const int32_t* tris, int32_t* nbr, int64_t* n_irregular) {
+    const char* who = "mvs_engine_mesh_adjacency";
+    if (int r = mesh_counts(n_v, n_t, who)) return r;
+    if (!tris && n_t > 0) { g_err = std::string(who) + ": tris null"; return MVS_ERR_ARG; }
+    if (!nbr && n_t > 0) { g_err = std::string(who) + ": nbr null"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
+    unsigned long long nirr = 0;
+    if (n_t > 0) {
+        HIPCHK(hipSetDevice(e->cfg.device));
+        Range rg("mvs:mesh_adjacency");
+        hipStream_t st = e->stream;
+        MseamBufs b;
+        if (int r = mesh_take_tris(e, n_v, n_t, tris, b.d_tris, b.words, who)) return r;
+        if (int r = mseam_adjacency(e, n_t, b.d_tris.p, b, n_irregular != nullptr, who)) return r;
+        if (int r = read_back(e, b.counts.p, &nirr)) return r;  // a failure is known before anything is written
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(nbr, b.nbr.p, (size_t)n_t * 3 * sizeof(int32_t), hipMemcpyDefault, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    if (n_irregular) *n_irregular = (int64_t)nirr;
+    return MVS_OK;
+}
+
+int mvs_engine_mesh_face_quality(mvs_engine* e, const mvs_mesh_texturing* x, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris,
+                                 const uint64_t* visible, uint8_t* quality) {
+    const char* who = "mvs_engine_mesh_face_quality";
+    const int32_t no_label = -1;  // this call takes none
+    if (int r = mtex_args(x, n_v, verts, n_t, tris, &no_label, who)) return r;
+    if (!quality && n_t > 0) { g_err = std::string(who) + ": quality null"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_IDLE, who)) return r;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:mesh_face_quality");
+    hipStream_t st = e->stream;
+    const int nviews = e->cfg.nviews, level = e->cfg.level;
+    MtexBufs b;
+    if (int r = mtex_take_mesh(e, n_v, verts, n_t, tris, b, who)) return r;
+    if (n_t == 0) return MVS_OK;
+    if (b.area.ensure(n_t) || b.rgb.ensure(n_t * nviews) || (visible && b.visible.ensure(n_v))) return MVS_ERR_HIP;
+    if (visible && n_v > 0) HIPCHK(hipMemcpyAsync(b.visible.p, visible, (size_t)n_v * sizeof(uint64_t), hipMemcpyDefault, st));
+    HIPCHK(hipMemsetAsync(b.area.p, 0, (size_t)n_t * sizeof(long long), st));
+    HIPCHK(hipMemsetAsync(b.label.p, 0xff, (size_t)n_t * sizeof(int32_t), st));
+    HIPCHK(hipMemsetAsync(b.rgb.p, 0, (size_t)n_t * nviews, st));
+    const DParams p = current_params(e);
+    for (int pass = 0; pass < 2; ++pass)  // the best |area| over all views, then every view against it
+        for (int v = 0; v < nviews; ++v) {
+            const int want = x->front_only ? mtex_front_sign(e, v) : 0;
+            if (x->front_only && want == 0) continue;
+            const int W = e->hviews[v].W[level], H = e->hviews[v].H[level];
+            mvsk_mrender_project(p, v, n_v, b.d_verts.p, b.scr.p, b.vd.p, b.ok.p, st);
+            if (pass == 0) mvsk_mtex_best(v, want, n_t, b.d_tris.p, b.scr.p, b.ok.p, visible ? b.visible.p : nullptr, W, H, b.area.p, b.label.p, st);
+            else mvsk_mtex_quality(v, want, n_t, b.d_tris.p, b.scr.p, b.ok.p, visible ? b.visible.p : nullptr, W, H, b.area.p, nviews, b.rgb.p, st);
+        }
+    HIPCHK(hipStreamSynchronize(st));  // a failure is known before anything is written
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(quality, b.rgb.p, (size_t)n_t * nviews, hipMemcpyDefault, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MVS_OK;
+}
+
+int mvs_engine_mesh_smooth_labels(mvs_engine* e, const mvs_mesh_seams* s, int64_t n_v, int64_t n_t, const int32_t* tris, int nviews_q, const uint8_t* quality,
+                                  const int32_t* label_in, int32_t* label_out, int64_t* stats) {
+    const char* who = "mvs_engine_mesh_smooth_labels";
+    if (int r = mseam_args(s, who)) return r;
+    if (int r = mesh_counts(n_v, n_t, who)) return r;
+    if (!tris && n_t > 0) { g_err = std::string(who) + ": tris null"; return MVS_ERR_ARG; }
+    if (nviews_q < 1 || nviews_q > MVS_MAXVIEWS) { g_err = std::string(who) + ": nviews_q outside 1..64"; return MVS_ERR_ARG; }
+    if (!quality && n_t > 0) { g_err = std::string(who) + ": quality null"; return MVS_ERR_ARG; }
+    if (!label_in && n_t > 0) { g_err = std::string(who) + ": label_in null"; return MVS_ERR_ARG; }
+    if (!label_out && n_t > 0) { g_err = std::string(who) + ": label_out null"; return MVS_ERR_ARG; }
+    if (!stats) { g_err = std::string(who) + ": stats null"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_ENGINE, who)) return r;
+    int64_t hs[4] = {0, 0, 0, 0};
+    HIPCHK(hipSetDevice(e->cfg.device));
+    if (n_t > 0) {
+        Range rg("mvs:mesh_smooth_labels");
+        hipStream_t st = e->stream;
+        MseamBufs b;
+        DevBuf<int32_t> label, prop, score;
+        DevBuf<uint8_t> d_quality;
+        DevBuf<unsigned long long> moved;
+        const int iters = s->iterations;
+        if (int r = mesh_take_tris(e, n_v, n_t, tris, b.d_tris, b.words, who)) return r;
+        if (label.ensure(n_t) || prop.ensure(n_t) || score.ensure(n_t) || d_quality.ensure(n_t * nviews_q) || moved.ensure(iters + 1)) return MVS_ERR_HIP;
+        HIPCHK(hipMemcpyAsync(label.p, label_in, (size_t)n_t * sizeof(int32_t), hipMemcpyDefault, st));
+        mvsk_mtex_check_labels(n_t, label.p, nviews_q, b.words.p + 1, st);  // mesh_take_tris left both words zero
+        uint32_t bad = 0;
+        if (int r = read_back(e, b.words.p + 1, &bad)) return r;
+        HIPCHK(hipGetLastError());
+        if (bad) { g_err = std::string(who) + ": a label outside -1 .. nviews_q - 1"; return MVS_ERR_ARG; }
+        if (int r = mseam_adjacency(e, n_t, b.d_tris.p, b, false, who)) return r;
+        HIPCHK(hipMemcpyAsync(d_quality.p, quality, (size_t)n_t * nviews_q, hipMemcpyDefault, st));
+        HIPCHK(hipMemsetAsync(moved.p, 0, (size_t)(iters + 1) * sizeof(unsigned long long), st));
+        mvsk_mseam_count(n_t, b.nbr.p, label.p, b.counts.p + 1, st);
+        std::vector<unsigned long long> hm((size_t)iters + 1, 0ull);
+        for (int it = 0; it < iters; ++it) {
+            mvsk_mseam_iteration(it, moved.p, n_t, b.d_tris.p, b.nbr.p, nviews_q, d_quality.p, s->keep, prop.p, score.p, label.p, st);
+            if (it % 8 == 7) {  // a look every eight iterations: the launches behind a still iteration do nothing anyway
+                if (int r = read_back(e, moved.p + it, &hm[it])) return r;
+                if (hm[it] == 0ull) break;
+            }
+        }
+        mvsk_mseam_count(n_t, b.nbr.p, label.p, b.counts.p + 2, st);
+        unsigned long long hc[4] = {0, 0, 0, 0};
+        HIPCHK(hipMemcpyAsync(hm.data(), moved.p, hm.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hc, b.counts.p, sizeof(hc), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));  // a failure is known before anything is written
+        HIPCHK(hipGetLastError());
+        hs[0] = (int64_t)hc[1]; hs[1] = (int64_t)hc[2];
+        for (int it = 0; it < iters; ++it) { hs[2] += (int64_t)hm[it]; hs[3] += hm[it] != 0ull ? 1 : 0; }
+        HIPCHK(hipMemcpyAsync(label_out, label.p, (size_t)n_t * sizeof(int32_t), hipMemcpyDefault, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    HIPCHK(hipMemcpy(stats, hs, sizeof(hs), hipMemcpyDefault));
+    return MVS_OK;
+}
+
+int mvs_engine_mesh_seam_levels(mvs_engine* e, const mvs_mesh_seams* s, const mvs_mesh_texturing* x, int64_t n_v, const float* verts, int64_t n_t,
+                                const int32_t* tris, const int32_t* label, int32_t* offset, int64_t* pairs, int64_t* n_seam_edges) {
+    const char* who = "mvs_engine_mesh_seam_levels";
+    if (!s) { g_err = std::string(who) + ": seams null"; return MVS_ERR_ARG; }
+    if (!x) { g_err = std::string(who) + ": texturing null"; return MVS_ERR_ARG; }
+    if (int r = mseam_args(s, who)) return r;
+    if (int r = mtex_args(x, n_v, verts, n_t, tris, label, who)) return r;
+    if (!offset) { g_err = std::string(who) + ": offset null"; return MVS_ERR_ARG; }
+    if (!pairs) { g_err = std::string(who) + ": pairs null"; return MVS_ERR_ARG; }
+    if (int r = need_state(e, NEED_IDLE, who)) return r;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    Range rg("mvs:mesh_seam_levels");
+    hipStream_t st = e->stream;
+    const int nviews = e->cfg.nviews;
+    MtexBufs b;
+    MseamBufs m;
+    DevBuf<long long> d_pairs;
+    std::vector<int64_t> hp((size_t)nviews * nviews * 4, 0);
+    unsigned long long nedges = 0;
+    if (int r = mtex_take_mesh(e, n_v, verts, n_t, tris, b, who)) return r;
+    if (n_t > 0) {
+        HIPCHK(hipMemcpyAsync(b.label.p, label, (size_t)n_t * sizeof(int32_t), hipMemcpyDefault, st));
+        mvsk_mtex_check_labels(n_t, b.label.p, nviews, b.words.p + 1, st);  // mesh_take_tris left both words zero
+        uint32_t bad = 0;
+        if (int r = read_back(e, b.words.p + 1, &bad)) return r;
+        HIPCHK(hipGetLastError());
+        if (bad) { g_err = std::string(who) + ": a label outside -1 .. nviews - 1"; return MVS_ERR_ARG; }
+        if (b.win.ensure(9 * n_t) || b.flag.ensure(n_t) || d_pairs.ensure((int64_t)hp.size())) return MVS_ERR_HIP;
+        if (int r = mseam_adjacency(e, n_t, b.d_tris.p, m, false, who)) return r;
+        HIPCHK(hipMemsetAsync(b.flag.p, 0, (size_t)n_t * sizeof(int32_t), st));
+        HIPCHK(hipMemsetAsync(d_pairs.p, 0, hp.size() * sizeof(long long), st));
+        const DParams p = current_params(e);
+        for (int v = 0; v < nviews; ++v) {
+            mvsk_mrender_project(p, v, n_v, b.d_verts.p, b.scr.p, b.vd.p, b.ok.p, st);
+            mvsk_mtex_take(v, n_t, b.d_tris.p, b.label.p, b.scr.p, b.vd.p, b.ok.p, b.win.p, b.flag.p, st);
+        }
+        mvsk_mtex_seam_samples(p, nviews, s->samples, n_t, b.d_tris.p, m.nbr.p, b.label.p, b.flag.p, b.win.p, d_pairs.p, m.counts.p + 3, st);
+        HIPCHK(hipMemcpyAsync(hp.data(), d_pairs.p, hp.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
+        if (int r = read_back(e, m.counts.p + 3, &nedges)) return r;  // a failure is known before anything is written
+        HIPCHK(hipGetLastError());
+    }
+    for (int a = 0; a < nviews; ++a)  // the device filled [min][max]: the mirror
+        for (int c = a + 1; c < nviews; ++c) {
+            const int64_t* up = &hp[((size_t)a * nviews + c) * 4];
+            int64_t* lo = &hp[((size_t)c * nviews + a) * 4];
+            lo[0] = up[0]; lo[1] = -up[1]; lo[2] = -up[2]; lo[3] = -up[3];
+        }
+    std::vector<int32_t> ho((size_t)nviews * 3, 0);
+    mseam_offsets(nviews, hp, s->max_shift, ho);
+    HIPCHK(hipMemcpyAsync(offset, ho.data(), ho.size() * sizeof(int32_t), hipMemcpyDefault, st));
+    HIPCHK(hipMemcpyAsync(pairs, hp.data(), hp.size() * sizeof(int64_t), hipMemcpyDefault, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (n_seam_edges) *n_seam_edges = (int64_t)nedges;
+    return MVS_OK;
+}
+
+int mvs_engine_mesh_texture_levelled(mvs_engine* e, const mvs_mesh_texturing* x, int64_t n_v, const float* verts, int64_t n_t, const int32_t* tris,
+                                     const int32_t* label, const int32_t* offset, int64_t cap_h, uint8_t* rgb, int32_t* uv, int64_t* height, int64_t* n_textured) {
+    return mtex_texture(e, x, n_v, verts, n_t, tris, label, offset, cap_h, rgb, uv, height, n_textured, "mvs_engine_mesh_texture_levelled");
+}
 }  // extern "C"

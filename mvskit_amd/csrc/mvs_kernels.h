@@ -194,6 +194,28 @@ void mvsk_mtex_layout(int64_t n_t, const int32_t* flag, const int32_t* base, int
 // up to a multiple of twelve
 void mvsk_mtex_texels(const DParams& prm, int res, int width, int64_t height, int64_t n_textured, const int32_t* list, const int32_t* label, const int32_t* win,
                       uint8_t* rgb, hipStream_t st);
+// The seam calls of include/mvskit_seams.h.  In mvs_mesh_texture.hip, with the gates and the texel chain:
+// one view, behind mvsk_mtex_best over all views: quality[t * nviews + view] = max(1, 255 |area| / best_area[t]) where t is a candidate
+// (quality zero before the first view)
+void mvsk_mtex_quality(int view, int want, int64_t n_t, const int32_t* tris, const int32_t* scr, const uint32_t* ok, const unsigned long long* visible, int W, int H,
+                       const long long* best_area, int nviews, uint8_t* quality, hipStream_t st);
+// mvsk_mtex_texels with offset[3 v ..], view v's levels in 1/16 grey level, added before the rounding
+void mvsk_mtex_texels_levelled(const DParams& prm, int res, int width, int64_t height, int64_t n_textured, const int32_t* list, const int32_t* label,
+                               const int32_t* win, const int32_t* offset, uint8_t* rgb, hipStream_t st);
+// pairs[(min * nviews + max) * 4 ..] += (N, S_r, S_g, S_b) of the seam edges between two views, *n_edges += the seam edges (both zero
+// before the launch); nbr from mvsk_mseam_adjacency, flag and win from mvsk_mtex_take over all views
+void mvsk_mtex_seam_samples(const DParams& prm, int nviews, int samples, int64_t n_t, const int32_t* tris, const int32_t* nbr, const int32_t* label,
+                            const int32_t* flag, const int32_t* win, long long* pairs, unsigned long long* n_edges, hipStream_t st);
+// In mvs_mesh_seams.hip: the edge table (tkey all ones, tval zero before; slots a power of two), nbr[3 t + k] = the triangle across edge
+// k or -1, *nirr (or null) += the irregular edges; *fail != 0: a probe ran out
+void mvsk_mseam_adjacency(int64_t n_t, const int32_t* tris, unsigned long long* tkey, int32_t* tval, int32_t* town, int64_t slots, int32_t* nbr,
+                          unsigned long long* nirr, uint32_t* fail, hipStream_t st);
+// *seams += the adjacent pairs whose labels are both >= 0 and differ
+void mvsk_mseam_count(int64_t n_t, const int32_t* nbr, const int32_t* label, unsigned long long* seams, hipStream_t st);
+// iteration `it` of the smoothing, a propose and an apply launch: moved[it] += the triangles that moved (moved zero before the first);
+// nothing happens when moved[it - 1] == 0.  Labels in -1 .. nviews_q - 1
+void mvsk_mseam_iteration(int it, unsigned long long* moved, int64_t n_t, const int32_t* tris, const int32_t* nbr, int nviews_q, const uint8_t* quality, int keep,
+                          int32_t* prop, int32_t* score, int32_t* label, hipStream_t st);
 // mvs_engine_mesh_components / mvs_engine_mesh_prune / mvs_engine_mesh_smooth (mvs_mesh_clean.hip): connected components by union-find,
 // pruning behind two scans, Taubin smoothing as an order-free integer sum.  verts: 3 floats a vertex, tris: 3 ids a triangle.
 // *bad != 0 when an id of a triangle lies outside 0 .. n_v - 1 (zero before the launch); every launcher below wants valid ids

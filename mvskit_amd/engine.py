@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/mvskit_engine.h and include/mvskit_texture.h.
+"""ctypes binding of the C ABI in include/mvskit_engine.h, include/mvskit_texture.h and include/mvskit_seams.h.
 
 There is no CPU path: if the HIP library is missing or no GPU is visible, creating an Engine raises."""
 from __future__ import annotations
@@ -491,11 +491,90 @@ class Engine:
         self._check(self.L.mvs_engine_mesh_texture(*head, h.value, _ptr(atlas), _ptr(uv), C.byref(h), C.byref(n)))
         return atlas, uv, n.value
 
+    # ---- seams of the textured mesh
+    def mesh_adjacency(self, n_v, tris):
+        """The triangle across each edge (include/mvskit_seams.h, mvs_engine_mesh_adjacency): (nbr [m, 3] int32, nbr[t][k] the row of the
+        triangle that has the reverse of t's edge from vertex k to vertex (k + 1) % 3 when both directed edges occur once, else -1; the
+        number of irregular edges, as mesh_boundaries counts them).  Needs no views."""
+        tris = _tris(tris)
+        nbr, ni = np.zeros((tris.shape[0], 3), np.int32), C.c_int64()
+        self._check(self.L.mvs_engine_mesh_adjacency(self.h, int(n_v), tris.shape[0], _ptr(tris), _ptr(nbr), C.byref(ni)))
+        return nbr, ni.value
+
+    def mesh_face_quality(self, verts, tris, visible=None, front_only=True):
+        """How well each view shows each triangle (include/mvskit_seams.h, mvs_engine_mesh_face_quality): uint8 [m, nviews], 0 where the
+        view is no candidate under mesh_face_views' gates, else max(1, 255 |area| // the triangle's largest |area|): mesh_face_views'
+        winner has 255.  Needs views but no pool."""
+        verts, tris = _verts(verts), _tris(tris)
+        if visible is not None:
+            visible = np.ascontiguousarray(visible, dtype=np.uint64).reshape(-1)
+            if visible.shape[0] != verts.shape[0]:
+                raise ValueError("mesh_face_quality: one visibility word per vertex")
+        x = MeshTexturing(8, 4096, int(bool(front_only)), 0)
+        quality = np.zeros((tris.shape[0], self.cfg.nviews), np.uint8)
+        self._check(self.L.mvs_engine_mesh_face_quality(self.h, C.byref(x), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), _ptr(visible),
+                                                        _ptr(quality)))
+        return quality
+
+    def smooth_face_views(self, tris, quality, label, keep=192, iterations=64):
+        """The view labels with fewer changes of view across edges (include/mvskit_seams.h, mvs_engine_mesh_smooth_labels): (label [m]
+        int32, stats [4] int64 = seams before, seams after, moves, iterations that moved something).  A triangle moves to the label of
+        its neighbours that agrees with more of them than its own, among the views whose quality for it is at least `keep`; the movers
+        of an iteration are an independent set.  Needs no views."""
+        tris = _tris(tris)
+        quality = np.ascontiguousarray(quality, dtype=np.uint8)
+        label = np.ascontiguousarray(label, dtype=np.int32).reshape(-1)
+        if quality.ndim != 2 or quality.shape[0] != tris.shape[0] or label.shape[0] != tris.shape[0]:
+            raise ValueError("smooth_face_views: one row of quality and one label per triangle")
+        s = MeshSeams(int(keep), int(iterations), 32, 4)
+        out, stats = np.zeros(tris.shape[0], np.int32), np.zeros(4, np.int64)
+        n_v = int(tris.max()) + 1 if tris.size else 0
+        self._check(self.L.mvs_engine_mesh_smooth_labels(self.h, C.byref(s), max(n_v, 0), tris.shape[0], _ptr(tris), quality.shape[1], _ptr(quality),
+                                                         _ptr(label), _ptr(out), _ptr(stats)))
+        return out, stats
+
+    def seam_levels(self, verts, tris, label, max_shift=32, samples=4):
+        """The views' colour levels from the seams (include/mvskit_seams.h, mvs_engine_mesh_seam_levels): (offset [nviews, 3] int32 in
+        1/16 grey level, what texture_mesh_levelled adds to a view's texels; pairs [nviews, nviews, 4] int64, per pair of views the
+        samples on the seam edges between them and the summed differences of the three channels in 1/16 grey level; the number of seam
+        edges).  Needs views but no pool."""
+        verts, tris = _verts(verts), _tris(tris)
+        label = np.ascontiguousarray(label, dtype=np.int32).reshape(-1)
+        if label.shape[0] != tris.shape[0]:
+            raise ValueError("seam_levels: one label per triangle")
+        n = self.cfg.nviews
+        s, x = MeshSeams(192, 64, int(max_shift), int(samples)), MeshTexturing(8, 4096, 1, 0)
+        offset, pairs, ne = np.zeros((n, 3), np.int32), np.zeros((n, n, 4), np.int64), C.c_int64()
+        self._check(self.L.mvs_engine_mesh_seam_levels(self.h, C.byref(s), C.byref(x), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), _ptr(label),
+                                                       _ptr(offset), _ptr(pairs), C.byref(ne)))
+        return offset, pairs, ne.value
+
+    def texture_mesh_levelled(self, verts, tris, label, offset, res=8, width=4096):
+        """texture_mesh with `offset` [nviews, 3] (seam_levels'; None: zeros) added to the texels of each view before they are rounded
+        (include/mvskit_seams.h, mvs_engine_mesh_texture_levelled): (atlas, uv, the number of textured triangles)."""
+        verts, tris = _verts(verts), _tris(tris)
+        label = np.ascontiguousarray(label, dtype=np.int32).reshape(-1)
+        if label.shape[0] != tris.shape[0]:
+            raise ValueError("texture_mesh_levelled: one label per triangle")
+        if offset is not None:
+            offset = np.ascontiguousarray(offset, dtype=np.int32)
+            if offset.shape != (self.cfg.nviews, 3):
+                raise ValueError("texture_mesh_levelled: offset is [nviews, 3]")
+        x = MeshTexturing(int(res), int(width), 1, 0)
+        h, n = C.c_int64(), C.c_int64()
+        head = (self.h, C.byref(x), verts.shape[0], _ptr(verts), tris.shape[0], _ptr(tris), _ptr(label), _ptr(offset))
+        self._check(self.L.mvs_engine_mesh_texture_levelled(*head, 0, None, None, C.byref(h), C.byref(n)))
+        atlas, uv = np.zeros((h.value, int(width), 3), np.uint8), np.zeros((tris.shape[0], 3, 2), np.int32)
+        self._check(self.L.mvs_engine_mesh_texture_levelled(*head, h.value, _ptr(atlas), _ptr(uv), C.byref(h), C.byref(n)))
+        return atlas, uv, n.value
+
     def textured_mesh(self, volume, source=0, min_consistent=1, depth_tol=0.01, normal_cos=0.9, cap_v=0, cap_t=0, min_triangles=0, largest_only=False,
                       smooth_iterations=0, decimate_cell=0.0, decimate_placement="mean", fill_max_edges=0, res=8, atlas_width=4096, front_only=True,
-                      visibility_tol=0.01):
+                      visibility_tol=0.01, seam_keep=0, level_colours=False):
         """mesh, the clean-up steps of coloured_mesh in its order (prune, fill, smooth, decimate), mesh_normals, mesh_visibility,
-        mesh_face_views and texture_mesh chained: (verts, tris, normals, atlas, uv, label), what write_mesh_obj takes."""
+        mesh_face_views and texture_mesh chained: (verts, tris, normals, atlas, uv, label), what write_mesh_obj takes.  seam_keep in
+        1..255: the labels go through mesh_face_quality and smooth_face_views(keep=seam_keep) first; level_colours: the atlas is
+        texture_mesh_levelled's under seam_levels' offsets."""
         kw = dict(source=source, min_consistent=min_consistent, depth_tol=depth_tol, normal_cos=normal_cos)
         verts, tris = self.mesh(volume, cap_v=cap_v, cap_t=cap_t, **kw)
         if min_triangles > 0 or largest_only:
@@ -509,7 +588,14 @@ class Engine:
         normals = self.mesh_normals(verts, tris)
         visible = self.mesh_visibility(verts, tris, visibility_tol)
         label, _, _ = self.mesh_face_views(verts, tris, visible=visible, front_only=front_only)
-        atlas, uv, _ = self.texture_mesh(verts, tris, label, res=res, width=atlas_width)
+        if seam_keep > 0:
+            quality = self.mesh_face_quality(verts, tris, visible=visible, front_only=front_only)
+            label, _ = self.smooth_face_views(tris, quality, label, keep=seam_keep)
+        if level_colours:
+            offset, _, _ = self.seam_levels(verts, tris, label)
+            atlas, uv, _ = self.texture_mesh_levelled(verts, tris, label, offset, res=res, width=atlas_width)
+        else:
+            atlas, uv, _ = self.texture_mesh(verts, tris, label, res=res, width=atlas_width)
         return verts, tris, normals, atlas, uv, label
 
     # ---- mesh clean-up
